@@ -15,6 +15,12 @@ gathered on rank 0 over RCCL/xGMI -- the path's only exchange step.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line (the headline figure, the stage times and the
+live roofline of the timed steps).  `--full` adds everything else after the timed region: the check of the timed
+codestreams against libopenjp2's hash (or an idle-chip re-encode), the DWT launches alone and replayed, the host
+path, rate control, decode and the CPU baseline (each of the last four can be left out with its --no-* option).
+`--dump-outputs DIR` writes the codestream of the last timed step as .npy arrays (dump_codestream).
 """
 from __future__ import annotations
 
@@ -27,8 +33,11 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 # one hardware queue per stream of an encoder handle (main + 4 coder streams); more queues measurably slow the
-# chains of short dependent launches (DWT levels) on this ROCm release.  Must be set before HIP starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
+# chains of short dependent launches (DWT levels) on this ROCm release.  Must be set before HIP starts.  A smaller value
+# already in the environment is raised: the band-pipelined host call (host_path) fails when its streams share queues.
+_q = os.environ.get("GPU_MAX_HW_QUEUES", "")
+if not _q.isdigit() or int(_q) < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -44,6 +53,25 @@ class DevView:
 
     def __init__(self, ptr: int, nbytes: int):
         self.__cuda_array_interface__ = dict(shape=(nbytes,), typestr="|u1", data=(ptr, False), version=2)
+
+
+def dump_codestream(out_dir: str, cs: np.ndarray, sample: int = 1 << 23, head: int = 1 << 20, seed: int = 0):
+    """What the timed path hands its caller -- the codestream of the last timed step -- as float32 .npy files, small enough
+    to compare two builds output for output (~36 MB for the metric frame's 325 MB codestream):
+      codestream_length.npy  [length] (float64)
+      codestream_head.npy    the first `head` bytes (main header, tile header, the first packets)
+      codestream_sample.npy  one byte out of each of `sample` equal slices of the codestream, at a seeded position in its
+                             slice (fixed for a given length); the whole codestream when it is no longer than `sample`"""
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(cs.size)
+    if n <= sample:
+        pos = np.arange(n, dtype=np.int64)
+    else:
+        edges = np.arange(sample + 1, dtype=np.int64) * n // sample
+        pos = edges[:-1] + (np.random.default_rng(seed).random(sample) * (edges[1:] - edges[:-1])).astype(np.int64)
+    np.save(os.path.join(out_dir, "codestream_length.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(out_dir, "codestream_head.npy"), cs[:head].astype(np.float32))
+    np.save(os.path.join(out_dir, "codestream_sample.npy"), cs[pos].astype(np.float32))
 
 
 def pmc_traffic(size, prec, levels):
@@ -549,19 +577,28 @@ def main():
     ap.add_argument("--size", type=int, default=8192, help="frame side (default: the metric's 8192)")
     ap.add_argument("--prec", type=int, default=16)
     ap.add_argument("--levels", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive plug-in-boundary measurement")
-    ap.add_argument("--no-decode", action="store_true", help="skip the decode of the timed codestream (reported beside value)")
-    ap.add_argument("--no-rate-control", action="store_true", help="skip the rate-controlled encode of the same frame (reported beside value)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the PCIe-inclusive plug-in-boundary measurement")
+    ap.add_argument("--no-decode", action="store_true", help="with --full: skip the decode of the timed codestream (reported beside value)")
+    ap.add_argument("--no-rate-control", action="store_true", help="with --full: skip the rate-controlled encode of the same frame (reported beside value)")
     ap.add_argument("--no-dwt-replay", action="store_true",
-                    help="skip the replays of the DWT launches after the timed region (roofline.phase.sum_kernel / alone_back_to_back): "
+                    help="with --full: skip the replays of the DWT launches after the timed region (roofline.phase.sum_kernel / alone_back_to_back): "
                          "tools/profile_round.sh passes it so that rocprofv3 --stats averages the launches of the timed region only")
     ap.add_argument("--mode", choices=["c3", "c4", "c5"], default="c3",
                     help="c3 (default): the metric's frame, weak scaling; c4 / c5: the multi-GPU configurations of BASELINE.json, strong scaling")
     ap.add_argument("--inflight", type=int, default=3,
                     help="frames in flight per GPU: independent encoder handles driven by host threads, so that one frame's "
                          "MQ-coder tail and host Tier-2 overlap the next frame's DWT/modelling (image-sequence path)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also verify the timed codestreams, time the DWT launches alone and replayed, and run "
+                         "the host path, rate control, decode and CPU baseline legs (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the codestream of the last timed step to DIR as .npy arrays (see dump_codestream)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.mode != "c3" or args.gpus != 1):
+        ap.error("--dump-outputs is implemented for the default mode on one GPU")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -682,49 +719,52 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
     # ---- after the timed region (none of this is inside `value`) ------------------------------------
-    # (1) every handle's last codestream of the timed region -- produced by the timed configuration itself:
-    # frames in flight, two coder groups, held-back and yielding coder launches -- is hashed and compared with
-    # libopenjp2's codestream for this workload (tests/golden/golden.json; same seed, no COM segment).  Other
-    # workloads (other sizes, tile-sharded ranks) are compared with a re-encode on an idle chip instead.
-    import hashlib
-    timed_hashes = [hashlib.sha256(encs[k].d2h(outs[k][0].value, outs[k][1].value)).hexdigest()
-                    for k in range(min(nfl, args.steps))]
+    if args.dump_outputs:  # the last timed step is frame steps - 1, which handle (steps - 1) % nfl encoded
+        last = (args.steps - 1) % nfl
+        dump_codestream(args.dump_outputs, encs[last].d2h(outs[last][0].value, outs[last][1].value))
     verified, verified_against = None, None
-    if world == 1 and (S, prec, args.levels) == (8192, 16, 5):
-        with open(os.path.join(ROOT, "tests", "golden", "golden.json")) as f:
-            gold = json.load(f)["c3_8192_rgb16_97_5lvl"]
-        verified = all(h == gold["sha256"] for h in timed_hashes) and int(outs[0][1].value) == gold["length"]
-        verified_against = "tests/golden/golden.json c3_8192_rgb16_97_5lvl (libopenjp2 %s, sha256)" % "2.4.0/2.5.4"
-    # (2) the same DWT launches with nothing else on the chip (one frame at a time, one handle), reported
-    # beside the live figure as roofline.alone
-    alone_lv = []
-    if exchange:
-        exchange.reset()
-    for k in range(3):
-        step(0, k)
+    alone_lv, alone_replay, level_kernel_ms, alone_cs = [], None, None, None
+    if args.full:
+        # (1) every handle's last codestream of the timed region -- produced by the timed configuration itself:
+        # frames in flight, two coder groups, held-back and yielding coder launches -- is hashed and compared with
+        # libopenjp2's codestream for this workload (tests/golden/golden.json; same seed, no COM segment).  Other
+        # workloads (other sizes, tile-sharded ranks) are compared with a re-encode on an idle chip instead.
+        import hashlib
+        timed_hashes = [hashlib.sha256(encs[k].d2h(outs[k][0].value, outs[k][1].value)).hexdigest()
+                        for k in range(min(nfl, args.steps))]
+        if world == 1 and (S, prec, args.levels) == (8192, 16, 5):
+            with open(os.path.join(ROOT, "tests", "golden", "golden.json")) as f:
+                gold = json.load(f)["c3_8192_rgb16_97_5lvl"]
+            verified = all(h == gold["sha256"] for h in timed_hashes) and int(outs[0][1].value) == gold["length"]
+            verified_against = "tests/golden/golden.json c3_8192_rgb16_97_5lvl (libopenjp2 %s, sha256)" % "2.4.0/2.5.4"
+        # (2) the same DWT launches with nothing else on the chip (one frame at a time, one handle), reported
+        # beside the live figure as roofline.alone
         if exchange:
-            exchange.drain(k + 1)
-        alone_lv.append(encs[0].dwt_level_ms())
-    fence()
-    # the whole DWT phase alone: the frame's launches replayed back to back between two events (an event between
-    # two dependent launches costs ~20 us of queue time, which the 7-25 us launches of levels 3-5 would carry)
-    alone_replay, level_kernel_ms = None, None
-    if not args.no_dwt_replay and alone_lv and len(alone_lv[0]) > 0:
-        alone_replay = (encs[0].dwt_time(0, 1, 20), encs[0].dwt_time(0, len(alone_lv[0]), 20))
-        # SURVEY 8d's phase figure is Sigma bytes / Sigma KERNEL time: every level's launch replayed 20 times back to back on its own
-        # (no event packet between dependent launches, no queue latency inside the bracket)
-        level_kernel_ms = [encs[0].dwt_time(l, 1, 20) for l in range(len(alone_lv[0]))]
-    alone_cs = encs[0].d2h(outs[0][0].value, outs[0][1].value).tobytes()  # (kept: the decode leg reads this very codestream back)
-    alone_hash = hashlib.sha256(alone_cs).hexdigest()
-    if verified is None:
-        verified = all(h == alone_hash for h in timed_hashes)
-        verified_against = "re-encode of the same input on an idle chip (no golden for this workload)"
-    if world > 1:
-        v = torch.tensor([1 if verified else 0], dtype=torch.int32, device="cuda" if backend == "nccl" else "cpu")
-        dist.all_reduce(v, op=dist.ReduceOp.MIN)
-        verified = bool(v.item())
-    if not verified:
-        print(f"rank {rank}: codestream of the timed configuration differs: {timed_hashes} vs {alone_hash}", file=sys.stderr, flush=True)
+            exchange.reset()
+        for k in range(3):
+            step(0, k)
+            if exchange:
+                exchange.drain(k + 1)
+            alone_lv.append(encs[0].dwt_level_ms())
+        fence()
+        # the whole DWT phase alone: the frame's launches replayed back to back between two events (an event between
+        # two dependent launches costs ~20 us of queue time, which the 7-25 us launches of levels 3-5 would carry)
+        if not args.no_dwt_replay and alone_lv and len(alone_lv[0]) > 0:
+            alone_replay = (encs[0].dwt_time(0, 1, 20), encs[0].dwt_time(0, len(alone_lv[0]), 20))
+            # SURVEY 8d's phase figure is Sigma bytes / Sigma KERNEL time: every level's launch replayed 20 times back to back on its own
+            # (no event packet between dependent launches, no queue latency inside the bracket)
+            level_kernel_ms = [encs[0].dwt_time(l, 1, 20) for l in range(len(alone_lv[0]))]
+        alone_cs = encs[0].d2h(outs[0][0].value, outs[0][1].value).tobytes()  # (kept: the decode leg reads this very codestream back)
+        alone_hash = hashlib.sha256(alone_cs).hexdigest()
+        if verified is None:
+            verified = all(h == alone_hash for h in timed_hashes)
+            verified_against = "re-encode of the same input on an idle chip (no golden for this workload)"
+        if world > 1:
+            v = torch.tensor([1 if verified else 0], dtype=torch.int32, device="cuda" if backend == "nccl" else "cpu")
+            dist.all_reduce(v, op=dist.ReduceOp.MIN)
+            verified = bool(v.item())
+        if not verified:
+            print(f"rank {rank}: codestream of the timed configuration differs: {timed_hashes} vs {alone_hash}", file=sys.stderr, flush=True)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -740,13 +780,12 @@ def main():
         phase_ms = float(np.mean([sum(x) for x in dwt_ms])) if nl else 0.0
         gbps = lambda nbytes, ms: nbytes / (ms * 1e-3) / 1e9 if ms > 0 else 0.0
         traffic, traffic_src = pmc_traffic(S, prec, args.levels)
-        a1 = float(np.median([x[0] for x in alone_lv])) if nl else 0.0
-        ap = float(np.median([sum(x) for x in alone_lv])) if nl else 0.0
         out = {
             "metric": "Mpixels/s encode, 8Kx8K 16-bit RGB, 5 DWT levels; DWT HBM GB/s vs roofline",
             "value": round(value, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic", "verified": bool(verified), "verified_against": verified_against,
+            "dtype": "f32", "data": "synthetic",
+            **({"verified": bool(verified), "verified_against": verified_against} if args.full else {}),
             "config": {"workload": f"{S}x{S} {prec}-bit RGB per GPU, 9/7 irreversible + ICT, {args.levels} DWT levels, "
                                    f"64x64 code-blocks, AE ARGB64 frame resident in HBM -> codestream assembled in HBM"
                                    + ("" if world == 1 else f"; image {W}x{H}, one {S}x{S} tile per rank, tile-parts gathered on rank 0 over RCCL"),
@@ -757,30 +796,34 @@ def main():
                          "achieved": round(gbps(l1_bytes, l1_ms), 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": round(gbps(l1_bytes, l1_ms) / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_src,
                          "bytes_per_launch": l1_bytes, "mean_launch_ms": round(l1_ms, 4),
-                         "alone": {"achieved": round(gbps(l1_bytes, a1), 1), "frac": round(gbps(l1_bytes, a1) / HBM_PEAK_GBPS, 4),
-                                   "mean_launch_ms": round(a1, 4)},
                          "phase": {"launches": nl, "bytes": dwt_bytes, "ms": round(phase_ms, 4),
-                                   "achieved": round(gbps(dwt_bytes, phase_ms), 1), "frac": round(gbps(dwt_bytes, phase_ms) / HBM_PEAK_GBPS, 4),
-                                   "alone": {"ms": round(ap, 4), "achieved": round(gbps(dwt_bytes, ap), 1),
-                                             "frac": round(gbps(dwt_bytes, ap) / HBM_PEAK_GBPS, 4)},
-                                   "sum_kernel": None if not level_kernel_ms else {
-                                       "per_launch_ms": [round(x, 4) for x in level_kernel_ms], "ms": round(sum(level_kernel_ms), 4),
-                                       "achieved": round(gbps(dwt_bytes, sum(level_kernel_ms)), 1),
-                                       "frac": round(gbps(dwt_bytes, sum(level_kernel_ms)) / HBM_PEAK_GBPS, 4),
-                                       "note": "Sigma bytes / Sigma kernel time (SURVEY 8d): each level's launch replayed back to back on an idle chip "
-                                               "(j2k_hip_debug_dwt_time), so no queue latency of event packets is inside"},
-                                   "alone_back_to_back": None if not alone_replay else {
-                                       "level1_ms": round(alone_replay[0], 4), "ms": round(alone_replay[1], 4),
-                                       "achieved": round(gbps(dwt_bytes, alone_replay[1]), 1),
-                                       "frac": round(gbps(dwt_bytes, alone_replay[1]) / HBM_PEAK_GBPS, 4)}},
+                                   "achieved": round(gbps(dwt_bytes, phase_ms), 1), "frac": round(gbps(dwt_bytes, phase_ms) / HBM_PEAK_GBPS, 4)},
                          "note": ("achieved/frac are live values from the timed region with %d frames in flight (the DWT of one "
-                                  "frame runs beside the MQ coder waves of the others); 'alone' = the same launches on an idle "
+                                  "frame runs beside the MQ coder waves of the others); 'alone' (--full) = the same launches on an idle "
                                   "chip after the timed region; 'phase' = all %d DWT launches of a frame together.  The dominant "
                                   "launch is timed by HIP events attached to its own dispatch (hipExtLaunchKernelGGL start / stop: the "
                                   "kernel's begin and end on its stream, what rocprofv3 --kernel-trace reports), the phase by event "
                                   "records around its launches" % (nfl, nl))},
             "stages_ms": {k: round(v, 3) for k, v in stage.items()},  # per frame, as seen by one handle (ms_total = frame latency)
         }
+        if args.full:
+            a1 = float(np.median([x[0] for x in alone_lv])) if nl else 0.0
+            ap = float(np.median([sum(x) for x in alone_lv])) if nl else 0.0
+            out["roofline"]["alone"] = {"achieved": round(gbps(l1_bytes, a1), 1), "frac": round(gbps(l1_bytes, a1) / HBM_PEAK_GBPS, 4),
+                                        "mean_launch_ms": round(a1, 4)}
+            out["roofline"]["phase"].update({
+                "alone": {"ms": round(ap, 4), "achieved": round(gbps(dwt_bytes, ap), 1),
+                          "frac": round(gbps(dwt_bytes, ap) / HBM_PEAK_GBPS, 4)},
+                "sum_kernel": None if not level_kernel_ms else {
+                    "per_launch_ms": [round(x, 4) for x in level_kernel_ms], "ms": round(sum(level_kernel_ms), 4),
+                    "achieved": round(gbps(dwt_bytes, sum(level_kernel_ms)), 1),
+                    "frac": round(gbps(dwt_bytes, sum(level_kernel_ms)) / HBM_PEAK_GBPS, 4),
+                    "note": "Sigma bytes / Sigma kernel time (SURVEY 8d): each level's launch replayed back to back on an idle chip "
+                            "(j2k_hip_debug_dwt_time), so no queue latency of event packets is inside"},
+                "alone_back_to_back": None if not alone_replay else {
+                    "level1_ms": round(alone_replay[0], 4), "ms": round(alone_replay[1], 4),
+                    "achieved": round(gbps(dwt_bytes, alone_replay[1]), 1),
+                    "frac": round(gbps(dwt_bytes, alone_replay[1]) / HBM_PEAK_GBPS, 4)}})
         # Tier-1 work (no roofline fraction is claimed for the serial, integer Tier-1 -- its rate of work is reported)
         st0 = per_frame[-1][0] if per_frame else None
         if st0:
@@ -794,7 +837,7 @@ def main():
                          "valu_source": None if not valu else valu[1],
                          "note": "coded bits = bits of the finished codestream; valu_frac = VALU wave-instructions of the modeller + coder per frame "
                                  "(SQ_INSTS_VALU, replayed from the committed PMC run) x 4 cycles / (1024 SIMDs x 2.4 GHz) x frames per second per GPU"}
-        if world == 1 and not args.no_host_path:
+        if args.full and world == 1 and not args.no_host_path:
             for e in encs[1:]:
                 e.close()
             hp = synth.planes(S, S, 3, prec, 23456)
@@ -802,15 +845,15 @@ def main():
             del hp
             out["host_path"] = host_path(api, hframe, hlay, params, S)
             del hframe
-        if world == 1 and not args.no_rate_control:  # (after the host path: its handles and arenas are gone again by then)
+        if args.full and world == 1 and not args.no_rate_control:  # (after the host path: its handles and arenas are gone again by then)
             for e in encs:  # the timed region's handles too: their streams would share the hardware queues with the new ones
                 e.close()
             out["rate_control"] = rate_control_path(api, planes, S, prec, numres, local_rank)
-        if world == 1 and not args.no_decode:
+        if args.full and world == 1 and not args.no_decode:
             for e in encs:  # (already closed above unless the other legs were skipped)
                 e.close()
             out["decode"] = decode_path(api, alone_cs, synth.planes(S, S, 3, prec, seed), S, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(S, prec, numres, 23456)
         print(json.dumps(out), flush=True)
     if exchange:

@@ -10,8 +10,11 @@ if ROOT not in sys.path:
 
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 # one hardware queue per stream of the handles in flight (a deployment knob of the HIP runtime; bench.py and the
-# tools set it the same way): must be in the environment before HIP starts
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
+# tools set it the same way): must be in the environment before HIP starts.  A smaller value already in the environment is
+# raised: the band-pipelined encode fails (Tier-1 error 4) when its streams share queues
+_q = os.environ.get("GPU_MAX_HW_QUEUES", "")
+if not _q.isdigit() or int(_q) < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"
 
 
 def pytest_configure(config):
