@@ -17,9 +17,11 @@
 //            (Table D.1), sign contexts and predictions (Tables D.2/D.3) and the run-length flags
 //            of the cleanup pass are evaluated bit-sliced on 32-row halves of those masks (boolean
 //            expressions of the neighbour masks, no table, no LDS).  A stripe then costs a few
-//            bit-field extracts to form its decision bytes, which are scattered in scan order (DPP
-//            scan of the per-lane counts, SWAR prefix sum of the per-row counts) into a linear LDS
-//            stage and leave in coalesced 1 KiB stores.  With rate control (DIST) the per-pass distortion
+//            bit-field extracts to form its decision bytes.  In the significance and cleanup passes
+//            a lane's bytes of a stripe are packed in registers (v_perm, selectors from a table by
+//            which rows code something) and ORed as whole words into a zeroed linear LDS stage at
+//            the offset a DPP scan of the per-lane counts gives; the refinement pass scatters its
+//            bytes there.  They leave in coalesced 1 KiB stores.  With rate control (DIST) the per-pass distortion
 //            estimates are weighted population counts of (samples of the pass) & (bit-planes below the
 //            current one): the nmsedec tables are piecewise linear in their index (dist_sum).
 //  t1_mq2_kernel        one LANE per code-block, two waves per 64 blocks: the MQ coder is serial per
@@ -90,6 +92,26 @@ __device__ __forceinline__ int nmsedec_ref(unsigned m, int bp)
     return (((i - 64) * (i - 64) + 32) >> 6) * 128;
 }
 
+// v_perm selectors that compact a stripe column's decision bytes, by presence (entry Vz | N << 4: the rows that code a
+// zero-coding / a sign decision): output byte k = the k-th present one of Z0 S0 Z1 S1 Z2 S2 Z3 S3 (byte r of zsym =
+// selector r, of ssym = selector 4 + r), 0x0c (a zero byte) past the last
+struct PackSel {
+    u64 v[256];
+    constexpr PackSel() : v()
+    {
+        for (int e = 0; e < 256; ++e) {
+            u64 sel = 0x0c0c0c0c0c0c0c0cull;
+            int k = 0;
+            for (int r = 0; r < 4; ++r) {
+                if ((e >> r) & 1) { sel = (sel & ~(0xffull << (8 * k))) | ((u64)r << (8 * k)); ++k; }
+                if ((e >> (4 + r)) & 1) { sel = (sel & ~(0xffull << (8 * k))) | ((u64)(4 + r) << (8 * k)); ++k; }
+            }
+            v[e] = sel;
+        }
+    }
+};
+__constant__ PackSel kPackSel = PackSel();
+
 // one butterfly stage of the 32 x 32 bit-matrix transpose held in 32 registers (m[p] bit r <- m[r] bit p after the five
 // stages J = 16, 8, 4, 2, 1)
 template <int J, unsigned MASK>
@@ -118,6 +140,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
     // look at, wait in LDS (plane q of the magnitudes in slot q % 6; one new plane per bit-plane of the scan).
     __shared__ u64 win[DIST ? 6 * 64 : 1];
     __shared__ __attribute__((aligned(16))) unsigned char stage[kStageBytes];
+    // the selector table kPackSel in LDS (with DIST the distortion window leaves no room for its 2 KiB at 7 waves per
+    // SIMD: that variant reads it from constant memory)
+    __shared__ u64 sel_tab[DIST ? 1 : 256];
 
     const int b = a.first + (int)blockIdx.x;
     const int lane = threadIdx.x;
@@ -126,6 +151,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
     if (a.done_word && blockIdx.x == 0 && lane == 0) __hip_atomic_store(a.done_word, a.done_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const CblkDev cb = a.blks[b];
     const int w = cb.w, h = cb.h, orient = cb.orient;
+    // the stage starts zeroed and stays so beyond what is pending (decisions are ORed into it)
+    for (int i = lane; i < kStageBytes / 16; i += 64) reinterpret_cast<uint4 *>(stage)[i] = make_uint4(0, 0, 0, 0);
+    if constexpr (!DIST)
+        for (int e = lane; e < 256; e += 64) sel_tab[e] = kPackSel.v[e];
 
     // ---- A7: load the block (coalesced rows), scale to sign-magnitude with 6 fractional bits
     u64 chi = 0;
@@ -237,9 +266,30 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
             else overflow = true;
             flushed += kFlush;
             __builtin_amdgcn_wave_barrier();
-            if (lane < 40) *reinterpret_cast<uint4 *>(&stage[lane * 16]) = r;
+            // the remainder moves to the front, and what it leaves behind is zeroed again (the zero is made here: a
+            // constant would be held in four registers through the whole pass loop)
+            unsigned z;
+            asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+            const uint4 zero = make_uint4(z, z, z, z);
+            if (lane < 40) {
+                *reinterpret_cast<uint4 *>(&stage[lane * 16]) = r;
+                *reinterpret_cast<uint4 *>(&stage[kFlush + lane * 16]) = zero;
+            } else *reinterpret_cast<uint4 *>(&stage[lane * 16]) = zero;
             __builtin_amdgcn_wave_barrier();
         }
+    };
+    // A lane's bytes of one stripe, cnt <= 10 of them packed in p0 | p1 << 32 | p2 << 64 and destined for stage[base ..):
+    // they are ORed into the zeroed stage as aligned words (v_alignbyte by the byte offset inside the word), only the
+    // words that hold some of them.  Lanes sharing a word combine by OR, in any order.
+    auto emit = [&](unsigned base, unsigned cnt, unsigned p0, unsigned p1, unsigned p2) {
+        const unsigned t = 0u - base; // (v_alignbyte reads t & 3 = 4 - (base & 3), or 0)
+        const unsigned al = (base + 3u) & ~3u; // the first word boundary at or after base
+        unsigned *const wp = reinterpret_cast<unsigned *>(stage + al);
+        const int e = (int)(base + cnt) - (int)al; // bytes of the lane from there on
+        if (cnt != 0 && al != base) __hip_atomic_fetch_or(wp - 1, __builtin_amdgcn_alignbyte(p0, 0u, t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        if (e > 0) __hip_atomic_fetch_or(wp, __builtin_amdgcn_alignbyte(p1, p0, t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        if (e > 4) __hip_atomic_fetch_or(wp + 1, __builtin_amdgcn_alignbyte(p2, p1, t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        if (e > 8) __hip_atomic_fetch_or(wp + 2, __builtin_amdgcn_alignbyte(0u, p2, t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     };
 
 #ifdef J2K_T1_COUNTERS
@@ -520,6 +570,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                             }
                         }
                     }
+                    // (the selector look-up and the stage offsets first: their latencies hide behind the decision bytes)
+                    const u64 sel = DIST ? kPackSel.v[Vz | (N << 4)] : sel_tab[Vz | (N << 4)];
+                    const unsigned cnt = pc + (unsigned)__builtin_popcount(Vz) + (unsigned)__builtin_popcount(N);
+                    unsigned total;
+                    const unsigned base = reserve(cnt, std::integral_constant<int, 10>(), total);
                     unsigned zsym = 0, ssym = 0; // decision bytes of the four rows: zero coding / sign
                     if (__any(Vz != 0)) // (context << 1) | bit
                         zsym = (spread4((zb0 >> sl) & 0xfu) << 1) | (spread4((zb1 >> sl) & 0xfu) << 2) | (spread4((zb2 >> sl) & 0xfu) << 3) |
@@ -528,25 +583,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                         ssym = 0x12121212u + (spread4((sb0 >> sl) & 0xfu) << 1) + (spread4((sb1 >> sl) & 0xfu) << 2) +
                                (spread4((sb2 >> sl) & 0xfu) << 3) + spread4((sd >> sl) & 0xfu);
                     {
-                        // scatter in coding order: [RL][UNI][UNI] then row by row [ZC][sign]; the stage offset of a
-                        // row's bytes = bytes of the rows above it (SWAR prefix sum of the per-row counts 0..2)
-                        const unsigned cz = spread4(Vz), cb4 = cz + spread4(N);
-                        const unsigned inc = cb4 + (cb4 << 8), inc2 = inc + (inc << 16);
-                        const unsigned zoff = inc2 - cb4, goff = zoff + cz;
-                        unsigned total;
-                        const unsigned cnt = pc + (inc2 >> 24);
-                        const unsigned base = pt == 0 ? reserve(cnt, std::integral_constant<int, 8>(), total)
-                                                      : reserve(cnt, std::integral_constant<int, 10>(), total);
-                        if (pt != 0 && pc) {
-                            stage[base] = (unsigned char)rlsym;
-                            if (pc == 3) { stage[base + 1] = (unsigned char)(rlsym >> 8); stage[base + 2] = (unsigned char)(rlsym >> 16); }
-                        }
-                        const unsigned rb = base + pc;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            if ((Vz >> r) & 1u) stage[rb + ((zoff >> (8 * r)) & 0xffu)] = (unsigned char)(zsym >> (8 * r));
-                            if ((N >> r) & 1u) stage[rb + ((goff >> (8 * r)) & 0xffu)] = (unsigned char)(ssym >> (8 * r));
-                        }
+                        // The lane's bytes in coding order, [RL][UNI][UNI] then row by row [ZC][sign], packed in registers:
+                        // one v_perm per output word picks the present rows' bytes out of zsym / ssym, the run-length prefix
+                        // shifts them up (with a prefix of 1 there are no others; with 3 at most 7)
+                        const unsigned c0 = __builtin_amdgcn_perm(ssym, zsym, (unsigned)sel), c1 = __builtin_amdgcn_perm(ssym, zsym, (unsigned)(sel >> 32));
+                        const u64 d = (((u64)c1 << 32) | c0) << (8 * pc);
+                        emit(base, cnt, (unsigned)d | rlsym, (unsigned)(d >> 32), __builtin_amdgcn_ubfe(c1, 8, 8 * pc));
                         commit(total);
                     }
                 }
