@@ -125,58 +125,30 @@ template <> struct VecOf<float, 2> { using type = float2; };
 template <> struct VecOf<int, 4> { using type = int4; };
 template <> struct VecOf<float, 4> { using type = float4; };
 
-// Software pipeline over the row pairs t = first..last (inclusive) with D register sets: load(t, odd row, even
-// row) issues the fetches of row pair t, step(t, odd, even) consumes them.  At the top of the loop the sets
-// 0..D-2 hold the fetches of t..t+D-2 (in flight); every step is preceded by the issue of the row pair D-1
-// ahead, so the wave always has D-1 row pairs of loads outstanding and never waits on its own stores (the
-// compiler emits counted s_waitcnt vmcnt(N)).  The index arithmetic is compile-time, the sets stay in registers.
-template <int D, int NRAW, typename R, bool SYNC, typename Load, typename Step>
+// The row pairs t = first..last (inclusive), one after the other: load(t, odd row, even row) issues the fetches
+// of row pair t, step(t, odd, even) consumes them; nothing is fetched ahead (the latency is hidden by the other waves of the SIMD: DESIGN.md section 13).
+template <int NRAW, typename R, bool SYNC, typename Load, typename Step>
 __device__ __forceinline__ void pipeline_impl(int first, int last, Load &&load, Step &&step)
 {
-    if constexpr (D == 1) {
-        // two row pairs per round: the vertical state a step leaves is what the next step reads, and with one step per round
-        // every value of it is copied back into "its" register at the back-edge (48 moves per round for three components)
-        int t = first;
+    // two row pairs per round: the vertical state a step leaves is what the next step reads, and with one step per round
+    // every value of it is copied back into "its" register at the back-edge (48 moves per round for three components)
+    int t = first;
 #ifndef J2K_DWT_NO_UNROLL2
-        for (; t + 1 <= last; t += 2) {
-            { R o[NRAW], n[NRAW]; load(t, o, n); step(t, o, n); }
-            if constexpr (SYNC) __builtin_amdgcn_s_barrier(); // (every wave of the workgroup that has a strip runs the same rounds)
-            { R o[NRAW], n[NRAW]; load(t + 1, o, n); step(t + 1, o, n); }
-            if constexpr (SYNC) __builtin_amdgcn_s_barrier();
-        }
-        if (t <= last) { R o[NRAW], n[NRAW]; load(t, o, n); step(t, o, n); }
-#else
-        for (; t <= last; ++t) {
-            R o[NRAW], n[NRAW];
-            load(t, o, n);
-            step(t, o, n);
-            if constexpr (SYNC) __builtin_amdgcn_s_barrier();
-        }
-#endif
-    } else {
-        R so[D][NRAW], sn[D][NRAW];
-#pragma unroll
-        for (int k = 0; k < D - 1; ++k)
-            if (first + k <= last) load(first + k, so[k], sn[k]);
-        int t = first;
-        for (; t + 2 * D - 2 <= last; t += D) { // steady state: every fetch issued in this round is a row pair of the chunk
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                load(t + k + D - 1, so[(k + D - 1) % D], sn[(k + D - 1) % D]);
-                step(t + k, so[k], sn[k]);
-            }
-        }
-        for (; t + D - 1 <= last; t += D) { // the last full round: fetches past the chunk are skipped
-#pragma unroll
-            for (int k = 0; k < D; ++k) {
-                if (t + k + D - 1 <= last) load(t + k + D - 1, so[(k + D - 1) % D], sn[(k + D - 1) % D]);
-                step(t + k, so[k], sn[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < D - 1; ++k) // the last D-1 (or fewer) row pairs: already in flight
-            if (t + k <= last) step(t + k, so[k], sn[k]);
+    for (; t + 1 <= last; t += 2) {
+        { R o[NRAW], n[NRAW]; load(t, o, n); step(t, o, n); }
+        if constexpr (SYNC) __builtin_amdgcn_s_barrier(); // (every wave of the workgroup that has a strip runs the same rounds)
+        { R o[NRAW], n[NRAW]; load(t + 1, o, n); step(t + 1, o, n); }
+        if constexpr (SYNC) __builtin_amdgcn_s_barrier();
     }
+    if (t <= last) { R o[NRAW], n[NRAW]; load(t, o, n); step(t, o, n); }
+#else
+    for (; t <= last; ++t) {
+        R o[NRAW], n[NRAW];
+        load(t, o, n);
+        step(t, o, n);
+        if constexpr (SYNC) __builtin_amdgcn_s_barrier();
+    }
+#endif
 }
 
 // One wave's share of one level: strip of column pairs x chunk of row pairs.
@@ -189,7 +161,7 @@ __device__ __forceinline__ void pipeline_impl(int first, int last, Load &&load, 
 // compile-time, so a sample is one conversion with a sub-word source select (v_cvt_f32_u32 src0_sel:WORD_1, v_cvt_f32_ubyte2)
 // instead of a 64-bit shift by a run-time amount, a mask, a shift and a subtraction.  0: any order, any shift (as before).
 // SYNC: the waves of the workgroup meet at a barrier after every row pair (see kFusedWavesBig).
-template <bool REV, int PAIRS, int DEPTH, bool FAST, int NCOMP, bool FUSED, bool GEN = false, int SPEC = 0, bool SYNC = false>
+template <bool REV, int PAIRS, bool FAST, int NCOMP, bool FUSED, bool GEN = false, int SPEC = 0, bool SYNC = false>
 __device__ __forceinline__ void dwt_wave(const DwtLevelArgs &a, const DwtJob &job, int pairs_per_chunk, int wave, int chunk)
 {
     constexpr int kHaloLanes = Geo<PAIRS>::halo_lanes, kValidPairs = Geo<PAIRS>::valid_pairs, NC = Geo<PAIRS>::ncol;
@@ -250,8 +222,7 @@ __device__ __forceinline__ void dwt_wave(const DwtLevelArgs &a, const DwtJob &jo
                     typedef unsigned U4 __attribute__((ext_vector_type(4)));
                     U4 q0, q1;
                     const U4 *src4 = reinterpret_cast<const U4 *>(row + (long long)(job.px0 + i0) * 8);
-                    if (a.ntl) { q0 = __builtin_nontemporal_load(src4); q1 = __builtin_nontemporal_load(src4 + 1); } // the frame is read once
-                    else { q0 = src4[0]; q1 = src4[1]; }
+                    q0 = src4[0]; q1 = src4[1];
                     v[0] = q0.x; v[1] = q0.y; v[2] = q0.z; v[3] = q0.w; v[4] = q1.x; v[5] = q1.y; v[6] = q1.z; v[7] = q1.w;
                 } else {
 #pragma unroll
@@ -365,19 +336,10 @@ __device__ __forceinline__ void dwt_wave(const DwtLevelArgs &a, const DwtJob &jo
             for (int c = 0; c < NV; ++c) v[c] = raw[c];
         }
     };
-    // nt: the HL/LH/HH bands are read again only by Tier-1, long after this level -- a non-temporal store
-    // keeps them from displacing the LL plane (the next level's input) in the caches
-    const bool nt_bands = a.nt != 0;
-    auto store2 = [&](T *base, long long stride, int y, int x, const T v[PAIRS], bool vecok, const bool ok[PAIRS], bool nt = false) {
+    auto store2 = [&](T *base, long long stride, int y, int x, const T v[PAIRS], bool vecok, const bool ok[PAIRS]) {
         T *p = base + (long long)y * stride + x;
         if constexpr (PAIRS == 2 && FAST) {
-            if (lane_ok) {
-                if (nt) {
-                    typedef T E2 __attribute__((ext_vector_type(2)));
-                    E2 q; q.x = v[0]; q.y = v[1];
-                    __builtin_nontemporal_store(q, reinterpret_cast<E2 *>(p));
-                } else { V2 q; q.x = v[0]; q.y = v[1]; *reinterpret_cast<V2 *>(p) = q; }
-            }
+            if (lane_ok) { V2 q; q.x = v[0]; q.y = v[1]; *reinterpret_cast<V2 *>(p) = q; }
         } else if constexpr (PAIRS == 2) {
             if (vecok) { V2 q; q.x = v[0]; q.y = v[1]; *reinterpret_cast<V2 *>(p) = q; }
             else { if (ok[0]) p[0] = v[0]; if (ok[1]) p[1] = v[1]; }
@@ -401,12 +363,12 @@ __device__ __forceinline__ void dwt_wave(const DwtLevelArgs &a, const DwtJob &jo
             if (!in_chunk) continue;
             T *llc = ll + (long long)c * a.comp_stride, *zc = z + (long long)c * a.comp_stride;
             if (ly >= 0 && ly < sny) {
-                store2(llc, a.ll_stride, ly, lx, l0, vlo_ll, st_lo);          // LL
-                store2(zc, a.z_stride, ly, snx + hx, h0, vhi_z, st_hi, nt_bands);       // HL
+                store2(llc, a.ll_stride, ly, lx, l0, vlo_ll, st_lo);    // LL
+                store2(zc, a.z_stride, ly, snx + hx, h0, vhi_z, st_hi); // HL
             }
             if (hy < dny) {
-                store2(zc, a.z_stride, sny + hy, lx, l1, vlo_z, st_lo, nt_bands);       // LH
-                store2(zc, a.z_stride, sny + hy, snx + hx, h1, vhi_z, st_hi, nt_bands); // HH
+                store2(zc, a.z_stride, sny + hy, lx, l1, vlo_z, st_lo);       // LH
+                store2(zc, a.z_stride, sny + hy, snx + hx, h1, vhi_z, st_hi); // HH
             }
         }
     };
@@ -424,9 +386,7 @@ __device__ __forceinline__ void dwt_wave(const DwtLevelArgs &a, const DwtJob &jo
         return;
     }
 
-    // The row loop is software-pipelined by hand: two register sets (A, B) alternate, the rows of
-    // the next row pair are requested into one set before the other set is consumed, so the wave
-    // always has a full row pair of loads in flight and never waits on its own stores.
+    // The row loop: one row pair per step, two steps per round (pipeline_impl).
     if constexpr (REV) {
         // d[t] = xo[t] - ((xe[t] + xe[t+1]) >> 1);  s[t] = xe[t] + ((d[t-1] + d[t] + 2) >> 2)
         int xe[NV], d[NV];
@@ -445,10 +405,7 @@ __device__ __forceinline__ void dwt_wave(const DwtLevelArgs &a, const DwtJob &jo
 #pragma unroll
             for (int c = 0; c < NV; ++c) { d[c] = nd[c]; xe[c] = rn[c]; }
         };
-        // Row pairs m0-1 .. m1-1 are stepped through with DEPTH register sets: the raw rows of the next DEPTH-1
-        // row pairs are in flight while one is converted and lifted (DEPTH = 1: none -- the latency is hidden
-        // by the other waves of the SIMD only).  Loads past the last row pair are never issued.
-        pipeline_impl<DEPTH, NR, R, SYNC>(m0 - 1, m1 - 1, [&](int t, R o[NR], R n[NR]) { load_raw(2 * t - casy + 1, o); load_raw(2 * t - casy + 2, n); }, step);
+        pipeline_impl<NR, R, SYNC>(m0 - 1, m1 - 1, [&](int t, R o[NR], R n[NR]) { load_raw(2 * t - casy + 1, o); load_raw(2 * t - casy + 2, n); }, step);
     } else {
         // state per column: xe (next even row), d1[t-1], s1[t-1], d2[t-2]
         float xe[NV], d1[NV], s1[NV], d2[NV];
@@ -470,7 +427,7 @@ __device__ __forceinline__ void dwt_wave(const DwtLevelArgs &a, const DwtJob &jo
             }
             store_rows(t - 1, lo, hi);
         };
-        pipeline_impl<DEPTH, NR, R, SYNC>(m0 - 2, m1, [&](int t, R o[NR], R n[NR]) { load_raw(2 * t - casy + 1, o); load_raw(2 * t - casy + 2, n); }, step);
+        pipeline_impl<NR, R, SYNC>(m0 - 2, m1, [&](int t, R o[NR], R n[NR]) { load_raw(2 * t - casy + 1, o); load_raw(2 * t - casy + 2, n); }, step);
     }
 }
 
@@ -496,7 +453,7 @@ __device__ __forceinline__ BlockMap block_map(int nx, int ny, int nz)
     return m;
 }
 
-template <bool REV, int PAIRS, int DEPTH>
+template <bool REV, int PAIRS>
 __global__ __launch_bounds__(64 * kWavesPerBlock) void dwt_level_kernel(DwtLevelArgs a, int pairs_per_chunk, int nx, int ny)
 {
     constexpr int kHaloLanes = Geo<PAIRS>::halo_lanes, kValidPairs = Geo<PAIRS>::valid_pairs, NC = Geo<PAIRS>::ncol;
@@ -517,8 +474,8 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void dwt_level_kernel(DwtLevel
                       ((job.ll_off & 1) == 0) && ((a.ll_stride & 1) == 0) && ((reinterpret_cast<uintptr_t>(a.ll) & 7) == 0) &&
                       ((job.z_off & 1) == 0) && ((a.z_stride & 1) == 0) && ((reinterpret_cast<uintptr_t>(a.z) & 7) == 0) &&
                       ((snx & 1) == 0) && ((job.rw & 1) == 0);
-    if (fast) dwt_wave<REV, PAIRS, DEPTH, true, 1, false>(a, job, pairs_per_chunk, wave, bm.chunk);
-    else dwt_wave<REV, PAIRS, 1, false, 1, false>(a, job, pairs_per_chunk, wave, bm.chunk); // (edge strips: the plain loop)
+    if (fast) dwt_wave<REV, PAIRS, true, 1, false>(a, job, pairs_per_chunk, wave, bm.chunk);
+    else dwt_wave<REV, PAIRS, false, 1, false>(a, job, pairs_per_chunk, wave, bm.chunk); // (edge strips)
 }
 
 // Level 1 with the sample front end fused in: reads the interleaved frame (4*S bytes per pixel)
@@ -549,8 +506,8 @@ __global__ __launch_bounds__(64 * WPB) J2K_FUSED_WAVES_ATTR void dwt_fused_kerne
                       ((job.z_off & 1) == 0) && ((a.z_stride & 1) == 0) && ((reinterpret_cast<uintptr_t>(a.z) & 7) == 0) &&
                       ((a.comp_stride & 1) == 0) && ((snx & 1) == 0) && ((job.rw & 1) == 0);
     // (fast and edge strips of one workgroup run the same rounds of the row loop: the barriers of SYNC pair up)
-    if (fast) dwt_wave<REV, 2, 1, true, NCOMP, true, GEN, SPEC, (WPB > 1)>(a, job, pairs_per_chunk, wave, bm.chunk);
-    else dwt_wave<REV, 2, 1, false, NCOMP, true, GEN, SPEC, (WPB > 1)>(a, job, pairs_per_chunk, wave, bm.chunk);
+    if (fast) dwt_wave<REV, 2, true, NCOMP, true, GEN, SPEC, (WPB > 1)>(a, job, pairs_per_chunk, wave, bm.chunk);
+    else dwt_wave<REV, 2, false, NCOMP, true, GEN, SPEC, (WPB > 1)>(a, job, pairs_per_chunk, wave, bm.chunk);
 }
 
 // ---- bandwidth calibration kernels (diagnostics for the roofline; not part of the product path)
@@ -662,9 +619,7 @@ static dim3 level_grid(int blocks_x, int chunks, int njobs, bool xcd, int &nx, i
     return dim3((unsigned)blocks_x, (unsigned)chunks, (unsigned)njobs);
 }
 
-void launch_dwt_level_tuned(const DwtLevelArgs &a, hipStream_t s, const Tuning &tn);
-
-template <int PAIRS, int DEPTH>
+template <int PAIRS>
 static void launch_variant(const DwtLevelArgs &a, hipStream_t s, const Tuning &tn)
 {
     const int npx = (a.max_rw + 2) >> 1;
@@ -680,8 +635,8 @@ static void launch_variant(const DwtLevelArgs &a, hipStream_t s, const Tuning &t
     const int chunks = (npy + ppc - 1) / ppc;
     int nx, ny;
     const dim3 grid = level_grid(blocks_x, chunks, a.njobs, tn.dwt_xcd != 0, nx, ny);
-    if (a.reversible) J2K_LAUNCH((dwt_level_kernel<true, PAIRS, DEPTH>), grid, dim3(64 * kWavesPerBlock), s, a, ppc, nx, ny);
-    else J2K_LAUNCH((dwt_level_kernel<false, PAIRS, DEPTH>), grid, dim3(64 * kWavesPerBlock), s, a, ppc, nx, ny);
+    if (a.reversible) J2K_LAUNCH((dwt_level_kernel<true, PAIRS>), grid, dim3(64 * kWavesPerBlock), s, a, ppc, nx, ny);
+    else J2K_LAUNCH((dwt_level_kernel<false, PAIRS>), grid, dim3(64 * kWavesPerBlock), s, a, ppc, nx, ny);
 }
 
 template <bool REV, int NCOMP, bool GEN, int SPEC>
@@ -770,23 +725,14 @@ void launch_dwt_level(const DwtLevelArgs &a, hipStream_t s, hipEvent_t start, hi
     }
     tl_bracket_start = start; tl_bracket_stop = start ? stop : nullptr;
     const Tuning tn = tuning();
-    if (tn.dwt_nt || tn.dwt_ntl) { DwtLevelArgs b = a; b.nt = tn.dwt_nt; b.ntl = tn.dwt_ntl; launch_dwt_level_tuned(b, s, tn); return; }
-    launch_dwt_level_tuned(a, s, tn);
-}
-
-void launch_dwt_level_tuned(const DwtLevelArgs &a, hipStream_t s, const Tuning &tn)
-{
     if (a.fused) {
         if (a.fe.ncomp == 1) { if (a.reversible) launch_fused<true, 1>(a, s, tn); else launch_fused<false, 1>(a, s, tn); }
         else if (a.fe.ncomp == 4) { if (a.reversible) launch_fused<true, 4>(a, s, tn); else launch_fused<false, 4>(a, s, tn); }
         else { if (a.reversible) launch_fused<true, 3>(a, s, tn); else launch_fused<false, 3>(a, s, tn); }
         return;
     }
-    if (tn.dwt_pairs == 1) { if (tn.dwt_depth >= 2) launch_variant<1, 2>(a, s, tn); else launch_variant<1, 1>(a, s, tn); }
-    else if (tn.dwt_depth >= 4) launch_variant<2, 4>(a, s, tn);
-    else if (tn.dwt_depth == 3) launch_variant<2, 3>(a, s, tn);
-    else if (tn.dwt_depth == 2) launch_variant<2, 2>(a, s, tn);
-    else launch_variant<2, 1>(a, s, tn);
+    if (tn.dwt_pairs == 1) launch_variant<1>(a, s, tn);
+    else launch_variant<2>(a, s, tn);
 }
 
 } // namespace j2k_hip

@@ -6,7 +6,7 @@
 // src/common/j2k_openjpeg_codec.cpp:589-758):
 //
 //   [H2D frame]  front end (A1,A2,A4,A5; fused into DWT level 1 for the AE layout)  ->  DWT level 1..NL (A6)
-//   -> t1_model (A7 + context modelling)  ||  t1_mq* on the coder streams (A8)
+//   -> t1_model (A7 + context modelling)  ||  t1_mq2 on the coder streams (A8)
 //   -> D2H per-block {numbps,passes,length} [+ per-pass tables and layer allocation: rate control]
 //   -> host Tier-2 plan (A9)  ->  H2D headers  ->  gather (codestream / JP2 file assembled in HBM)
 //   ->  [D2H codestream]
@@ -61,9 +61,6 @@ struct DeviceShared {
     // the event that marks the end of the most recently queued dense phase (guarded by dense): the next
     // frame's stream waits for it on the GPU, so the hand-over costs no host round trip
     hipEvent_t last_dense_done = nullptr;
-    // dwt_ahead: the DWT launches of the previous dense phase have finished (the next frame's DWT may start then,
-    // beside the previous frame's modeller)
-    hipEvent_t last_dwt_done = nullptr;
     unsigned seq = 0;                     // running number of the dense phases (guarded by dense)
     // encode calls in progress on this device (between the entry of the first half and the end of the second):
     // above one, frames are in flight and the next dense phase follows this one at once
@@ -272,81 +269,17 @@ struct EncodeOut {
     size_t len = 0;
 };
 
-// CU masks (hipExtStreamCreateWithCUMask): bit i of the mask is logical CU i; the driver deals logical CUs
-// round-robin over the 8 XCDs (bit i -> XCD i % 8), so the low 8*n bits are n CUs on every XCD.
-void make_streams(j2k_hip_encoder *e)
-{
-    const int want = std::max(0, std::min(28, tuning().coder_cus));
-    if (e->stream && e->stream_cus == want) return;
-    if (e->stream) {
-        (void)hipStreamSynchronize(e->stream);
-        for (auto &v : e->mqs) if (v) { (void)hipStreamSynchronize(v); (void)hipStreamDestroy(v); v = nullptr; }
-        (void)hipStreamDestroy(e->stream);
-        e->stream = nullptr;
-    }
-    if (want == 0) {
-        HIP_CHECK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    } else {
-        uint32_t mask[8];
-        const int split = 8 * want; // logical CUs [0, split) belong to the coder streams
-        for (int w = 0; w < 8; ++w) {
-            uint32_t m = 0;
-            for (int b = 0; b < 32; ++b) if (w * 32 + b >= split) m |= 1u << b;
-            mask[w] = m;
-        }
-        HIP_CHECK(hipExtStreamCreateWithCUMask(&e->stream, 8, mask));
-    }
-    e->stream_cus = want;
-}
-
 } // namespace
 
 hipStream_t j2k_hip::coder_stream(j2k_hip_encoder *e, int i)
 {
     // (created when first used: a handle that only sees small frames needs one, and every stream takes one
     // of the few hardware queues that frames in flight share)
-    if (e->mqs[i]) return e->mqs[i];
-    const int want = e->stream_cus;
-    if (want <= 0) {
-        HIP_CHECK(hipStreamCreateWithFlags(&e->mqs[i], hipStreamNonBlocking));
-    } else {
-        uint32_t mask[8];
-        const int split = 8 * want;
-        for (int w = 0; w < 8; ++w) {
-            uint32_t m = 0;
-            for (int b = 0; b < 32; ++b) if (w * 32 + b < split) m |= 1u << b;
-            mask[w] = m;
-        }
-        HIP_CHECK(hipExtStreamCreateWithCUMask(&e->mqs[i], 8, mask));
-    }
+    if (!e->mqs[i]) HIP_CHECK(hipStreamCreateWithFlags(&e->mqs[i], hipStreamNonBlocking));
     return e->mqs[i];
 }
 
 namespace {
-
-// Upload of a host frame span.  Default: one hipMemcpyAsync from the caller's pageable buffer (the runtime
-// pins the pages in place and DMAs straight from them).  tuning().staging = 1: through two pinned pieces
-// owned by the handle, the host copy of piece k+1 running beside the DMA of piece k.
-void upload_span(j2k_hip_encoder *e, uint8_t *dst, const uint8_t *src, size_t span, hipStream_t s)
-{
-    if (!tuning().staging || span < (8u << 20)) {
-        HIP_CHECK(hipMemcpyAsync(dst, src, span, hipMemcpyHostToDevice, s));
-        return;
-    }
-    const size_t piece = std::max<size_t>(1u << 20, (size_t)tuning().stage_kb << 10);
-    e->h_stage.ensure(2 * piece);
-    for (auto &v : e->stage_ev) if (!v) HIP_CHECK(hipEventCreateWithFlags(&v, hipEventDisableTiming));
-    size_t pos = 0;
-    for (int k = 0; pos < span; ++k) {
-        const size_t n = std::min(piece, span - pos);
-        uint8_t *buf = e->h_stage.as<uint8_t>() + (size_t)(k & 1) * piece;
-        if (k >= 2) HIP_CHECK(hipEventSynchronize(e->stage_ev[k & 1])); // the DMA that last read this piece is done
-        std::memcpy(buf, src + pos, n);
-        HIP_CHECK(hipMemcpyAsync(dst + pos, buf, n, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipEventRecord(e->stage_ev[k & 1], s));
-        pos += n;
-    }
-}
 
 // Launch arguments of DWT level l (0 = full resolution) of frame f of the call: level l reads LL(l-1) and writes LL(l) to
 // the other ping-pong plane (the last level: to Z) and its HL/LH/HH bands to Z.
@@ -423,7 +356,6 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     HIP_CHECK(hipSetDevice(e->device));
     const Tuning tn = tuning(); // one consistent snapshot per call
     DeviceShared &dev = g_dev[e->device];
-    make_streams(e);
     const Coding cod = normalise(params);
     if (cod.dci && !framed) throw Error(J2K_HIP_ERR_PARAM, "a cinema-profile frame is one tile with its TLM in the main header: encode it whole");
     if (framed) { tile_first = 0; tile_count = cod.ntiles(); }
@@ -466,7 +398,8 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
         const size_t span = (size_t)(hi - lo);
         e->in.ensure(span + pad + 16);
         uint8_t *dbase = e->in.as<uint8_t>() + pad;
-        upload_span(e, dbase, lo, span, s);
+        // (from the caller's pageable buffer: the runtime pins the pages in place and DMAs straight from them)
+        HIP_CHECK(hipMemcpyAsync(dbase, lo, span, hipMemcpyHostToDevice, s));
         for (uint32_t c = 0; c < cod.ncomp; ++c)
             dplanes[c].base = dbase + (static_cast<const uint8_t *>(planes[c].base) - lo);
     }
@@ -477,7 +410,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     unsigned *const dwt_word = dev.dwt_done_word;
     // second word of the same allocation (its own 128-byte line): non-zero while a dense phase's DWT launches run
     unsigned *const dwt_busy = (dwt_word && tn.mq_yield && tn.overlap && dev.inflight.load() > 1) ? dwt_word + 32 : nullptr;
-    // ---- Tier-1 arenas: sized and their two control words (error flag, length of the heavy-block list) zeroed here,
+    // ---- Tier-1 arenas: sized and their error flag zeroed here,
     // before this stream starts waiting for the previous frame's dense phase: the fill kernel runs beside that phase and
     // nothing but kernel boundaries sits between the previous modeller, this frame's DWT and this frame's modeller
     const size_t nb1 = g.cblks.size();  // per frame
@@ -486,19 +419,11 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     e->out.ensure(e->out_bytes * F + 64);
     e->meta.ensure((4 * nb + 4) * sizeof(uint32_t));
     e->passes.ensure(std::max<size_t>(1, nb) * kDevMaxPasses * 3 * sizeof(uint32_t));
-    e->heavy.ensure((nb / 8 + 64) * sizeof(uint32_t)); // (the first coder group is an eighth of the table)
-    HIP_CHECK(hipMemsetAsync(e->meta.as<uint32_t>() + 4 * nb, 0, 2 * sizeof(uint32_t), s));
+    HIP_CHECK(hipMemsetAsync(e->meta.as<uint32_t>() + 4 * nb, 0, sizeof(uint32_t), s));
 
     const bool overlap_mq = tn.overlap != 0;
-    // dwt_ahead: this frame's bandwidth-bound DWT only waits for the previous frame's DWT and runs beside that frame's
-    // issue-bound modeller; the modeller launches below wait for the previous modeller
-    const bool dwt_ahead = overlap_mq && tn.dwt_ahead != 0;
-    hipEvent_t prev_dense = (overlap_mq && tn.dense_chain && dev.last_dense_done != e->k1_done) ? dev.last_dense_done : nullptr;
-    if (dwt_ahead) {
-        if (dev.last_dwt_done && dev.last_dwt_done != e->dwt_done) HIP_CHECK(hipStreamWaitEvent(s, dev.last_dwt_done, 0));
-    } else if (prev_dense) {
-        HIP_CHECK(hipStreamWaitEvent(s, prev_dense, 0));
-    }
+    // the dense phases (DWT + modeller) of the frames in flight are chained: the bandwidth-bound launches keep the chip to themselves
+    if (overlap_mq && dev.last_dense_done && dev.last_dense_done != e->k1_done) HIP_CHECK(hipStreamWaitEvent(s, dev.last_dense_done, 0));
     HIP_CHECK(hipEventRecord(e->ev[EV_UPLOAD], s));
 
     // ---- working planes (one set per frame of a sequence)
@@ -564,11 +489,6 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     if (dwt_word && !word_by_modeller) launch_set_word(dwt_word, dense_seq, s, busy_guard.word, 0u);
     busy_guard.word = nullptr;
     HIP_CHECK(hipEventRecord(e->ev[EV_DWT], s));
-    if (dwt_ahead) {
-        HIP_CHECK(hipEventRecord(e->dwt_done, s));
-        dev.last_dwt_done = e->dwt_done;
-        if (prev_dense) HIP_CHECK(hipStreamWaitEvent(s, prev_dense, 0)); // the previous frame's modeller
-    }
 
     // ---- Tier-1: the blocks of all frames in one table (frame f's entries point into its planes and
     // continue the decision / codeword arenas)
@@ -637,14 +557,6 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
         // group g+1 is being modelled on the main stream.
         const int big_groups = std::max(2, std::min(7, tn.groups));
         const int groups = nb >= 8192 ? big_groups : 1; // small frames: one coder launch, two streams per handle in all
-        // decision-stream length from which a block gets its own scalar coder wave (first group only)
-        // The scalar coder was built to shorten the tail of ONE frame (its few longest decision streams get a wave each); with
-        // other frames in flight nobody waits for that tail and its ~100 waves of scalar work are only in the way (four frames
-        // in flight: 6560 Mpixel/s with it, 6820 without), so it is only considered when this call is the only one on the
-        // device -- and since the two-wave coder's loops were trimmed (round 3) that coder is the faster one per decision
-        // too (one frame at a time 17.7 ms without the scalar waves, 20.7 with them): heavy_min defaults to 0, the kernel stays
-        // as a knob under the byte checks.
-        const unsigned heavy_min = (groups > 1 && dev.inflight.load() <= 1) ? (unsigned)std::max(0, tn.heavy_min) : 0u;
         int first = 0;
         for (int gi = 0; gi < groups; ++gi) {
             // first group = the first eighth of the table: packet order puts the low resolutions, whose
@@ -656,26 +568,16 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
             T1Args tg = ta;
             tg.first = first; tg.nblks = last;
             if (gi == 0 && word_by_modeller) { tg.done_word = dwt_word; tg.done_value = dense_seq; }
-            if (gi == 0 && heavy_min) { // the modeller of the first group lists its heavy blocks for the scalar coder
-                tg.heavy_min = heavy_min;
-                tg.heavy_list = e->heavy.as<unsigned>(); tg.heavy_count = ta.err + 1;
-            }
             launch_t1_model(tg, s);
             { // the coder always runs on its own stream: the dense phase of the frame ends with the modeller
                 HIP_CHECK(hipEventRecord(e->gev[gi], s));
                 HIP_CHECK(hipStreamWaitEvent(coder_stream(e, gi), e->gev[gi], 0));
-                if (gi == 0 && heavy_min) {
-                    // the few blocks with the longest decision streams: one scalar coder wave each
-                    HIP_CHECK(hipStreamWaitEvent(coder_stream(e, 7), e->gev[gi], 0));
-                    launch_t1_mq_scalar(tg, e->mqs[7]);
-                    HIP_CHECK(hipEventRecord(e->heavy_done, e->mqs[7]));
-                }
                 // With frames of other handles in flight, the next frame's DWT starts the moment this frame's
                 // modeller ends -- exactly when the bulk of this frame's coder workgroups would be dispatched.
                 // That coder launch therefore waits until the next dense phase's DWT is through (bounded by
                 // mq_wait_us, if no frame follows after all): the bandwidth-bound kernels get in first.
                 // "In flight" is explicit: another encode call is in progress on this device right now.
-                if (tn.mq_wait_us > 0 && dwt_word && overlap_mq && gi == groups - 1 && groups > 1 && dev.inflight.load() > 1 && e->stream_cus <= 0)
+                if (tn.mq_wait_us > 0 && dwt_word && overlap_mq && gi == groups - 1 && groups > 1 && dev.inflight.load() > 1)
                     launch_wait_word(dwt_word, dense_seq + 1, (unsigned)tn.mq_wait_us, e->mqs[gi]);
                 launch_t1_mq(tg, e->mqs[gi]);
                 HIP_CHECK(hipEventRecord(e->mq_done[gi], e->mqs[gi]));
@@ -685,7 +587,6 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
         // the dense phase of this frame ends when its last modeller launch has drained
         HIP_CHECK(hipEventRecord(e->k1_done, s));
         for (int gi = 0; gi < groups; ++gi) HIP_CHECK(hipStreamWaitEvent(s, e->mq_done[gi], 0));
-        if (heavy_min) HIP_CHECK(hipStreamWaitEvent(s, e->heavy_done, 0));
     }
     HIP_CHECK(hipEventRecord(e->ev[EV_T1], s));
 
@@ -1195,9 +1096,9 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     e->gate_state.ensure((NG + (size_t)NS + 8) * sizeof(uint32_t));
     unsigned *const gate_ready = e->gate_state.as<unsigned>(), *const gate_done = gate_ready + NG, *const gate_abort = gate_done + NS;
     HIP_CHECK(hipEventRecord(e->ev[EV_START], s));
-    HIP_CHECK(hipMemsetAsync(meta + 4 * nb, 0, 2 * sizeof(uint32_t), s));
+    HIP_CHECK(hipMemsetAsync(meta + 4 * nb, 0, sizeof(uint32_t), s));
     HIP_CHECK(hipMemsetAsync(gate_ready, 0, (NG + (size_t)NS + 8) * sizeof(uint32_t), s));
-    HIP_CHECK(hipEventRecord(e->heavy_done, s)); // (the counters are zero: the coder launch and the stages' wait kernels may be queued)
+    HIP_CHECK(hipEventRecord(e->gates_zeroed, s)); // (the counters are zero: the coder launch and the stages' wait kernels may be queued)
 
     j2k_hip_plane dplanes[4];
     for (uint32_t c = 0; c < cod.ncomp; ++c) {
@@ -1231,7 +1132,7 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     // workgroups -- further launches follow on the same stream, so that sleeping coder workgroups never take the LDS the
     // modeller's waves need.)
     pd.banded = true; // (from here on a failure leaves sleeping workgroups behind: drain() wakes them through the abort word)
-    HIP_CHECK(hipStreamWaitEvent(s_coder, e->heavy_done, 0));
+    HIP_CHECK(hipStreamWaitEvent(s_coder, e->gates_zeroed, 0));
     for (size_t g0 = 0; g0 < NG; g0 += 1024) launch_t1_mq_gated(ta, (int)g0, (int)std::min<size_t>(1024, NG - g0), s_coder);
     // ---- band by band
     double up_ms = 0;
@@ -1543,12 +1444,11 @@ int j2k_hip_create(j2k_hip_encoder **enc, int device)
         if (device < 0 || device >= n || device >= kMaxDevices) throw Error(J2K_HIP_ERR_DEVICE, "no such HIP device: " + std::to_string(device));
         e->device = device;
         HIP_CHECK(hipSetDevice(device));
-        make_streams(e.get());
+        HIP_CHECK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
         for (auto &v : e->gev) HIP_CHECK(hipEventCreateWithFlags(&v, hipEventDisableTiming));
         for (auto &v : e->mq_done) HIP_CHECK(hipEventCreateWithFlags(&v, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&e->k1_done, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&e->dwt_done, hipEventDisableTiming));
-        HIP_CHECK(hipEventCreateWithFlags(&e->heavy_done, hipEventDisableTiming));
+        HIP_CHECK(hipEventCreateWithFlags(&e->gates_zeroed, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&e->rc_fixed, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&e->rc_tables, hipEventDisableTiming));
         for (auto &v : e->ev) HIP_CHECK(hipEventCreate(&v));
@@ -1579,14 +1479,13 @@ void j2k_hip_destroy(j2k_hip_encoder *e)
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto &v : e->mqs) if (v) (void)hipStreamSynchronize(v);
-    for (DevBuf *b : {&e->in, &e->P, &e->Q, &e->Z, &e->blks, &e->blks_seq, &e->jobs, &e->sym, &e->out, &e->meta, &e->heavy, &e->passes, &e->cs, &e->plan, &e->blks_band, &e->pack_dst, &e->gate_groups, &e->gate_group_of, &e->gate_state,
+    for (DevBuf *b : {&e->in, &e->P, &e->Q, &e->Z, &e->blks, &e->blks_seq, &e->jobs, &e->sym, &e->out, &e->meta, &e->passes, &e->cs, &e->plan, &e->blks_band, &e->pack_dst, &e->gate_groups, &e->gate_group_of, &e->gate_state,
                       &e->d_file, &e->d_cw, &e->d_masks, &e->d_dblk, &e->d_segs, &e->d_outimg}) b->release();
-    for (PinnedBuf *b : {&e->h_meta, &e->h_cs, &e->h_plan, &e->h_passes, &e->h_stage, &e->h_outimg, &e->h_dtab}) b->release();
+    for (PinnedBuf *b : {&e->h_meta, &e->h_cs, &e->h_plan, &e->h_passes, &e->h_outimg, &e->h_dtab}) b->release();
     for (auto &v : e->ev) if (v) (void)hipEventDestroy(v);
     for (auto &v : e->lev) if (v) (void)hipEventDestroy(v);
     for (auto &v : e->gev) if (v) (void)hipEventDestroy(v);
     for (auto &v : e->mq_done) if (v) (void)hipEventDestroy(v);
-    for (auto &v : e->stage_ev) if (v) (void)hipEventDestroy(v);
     if (e->up_stream) (void)hipStreamSynchronize(e->up_stream); // (the device's copy stream: it goes with the device's last handle)
     e->up_stream = e->dl_stream = nullptr;
     for (auto &v : e->band_up) if (v) (void)hipEventDestroy(v);
@@ -1599,12 +1498,7 @@ void j2k_hip_destroy(j2k_hip_encoder *e)
         if (dev.last_dense_done == e->k1_done) dev.last_dense_done = nullptr; // stream already drained above
         (void)hipEventDestroy(e->k1_done);
     }
-    if (e->dwt_done) {
-        std::lock_guard<std::mutex> lk(dev.dense);
-        if (dev.last_dwt_done == e->dwt_done) dev.last_dwt_done = nullptr;
-        (void)hipEventDestroy(e->dwt_done);
-    }
-    if (e->heavy_done) (void)hipEventDestroy(e->heavy_done);
+    if (e->gates_zeroed) (void)hipEventDestroy(e->gates_zeroed);
     if (e->rc_fixed) (void)hipEventDestroy(e->rc_fixed);
     if (e->rc_tables) (void)hipEventDestroy(e->rc_tables);
     for (auto &v : e->mqs) if (v) (void)hipStreamDestroy(v);

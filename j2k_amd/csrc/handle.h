@@ -126,16 +126,14 @@ struct j2k_hip_encoder {
     bool last_fused = false;
     j2k_hip::FrontendArgs last_fa = {};   // of the last call's first frame (j2k_hip_debug_dwt_time replays its DWT launches)
     hipStream_t stream = nullptr;
-    hipStream_t mqs[12] = {};      // MQ coder streams (run beside the context modeller); [7] = scalar coder; a band-pipelined call: one per stage
+    hipStream_t mqs[12] = {};      // MQ coder streams (run beside the context modeller); a band-pipelined call: one per stage
     hipEvent_t gev[12] = {};
     hipEvent_t mq_done[12] = {};
-    hipEvent_t heavy_done = nullptr;
+    hipEvent_t gates_zeroed = nullptr; // band-pipelined call: the gate counters are zero (the gated coder launch may be queued)
     hipEvent_t rc_fixed = nullptr, rc_tables = nullptr; // rate control on the device: pass tables final on the device / copied to the host (side stream)
     hipEvent_t k1_done = nullptr;
-    hipEvent_t dwt_done = nullptr; // this handle's DWT launches have finished (dwt_ahead chaining)
     bool dwt_word_ref = false;
     bool counted_inflight = false;
-    int stream_cus = -1;           // tuning().coder_cus the streams were created with (-1: none yet)
     std::string err;
     hipEvent_t ev[j2k_hip::EV_COUNT] = {};
     hipEvent_t lev[j2k_hip::kMaxLevels + 1] = {};
@@ -146,7 +144,6 @@ struct j2k_hip_encoder {
     j2k_hip::DevBuf in, P, Q, Z, blks, jobs, sym, out, meta, passes, cs, plan;
     std::unique_ptr<j2k_hip::Workers> t2_workers; // host threads of the Tier-2 planner (created with the first big frame)
     std::unique_ptr<j2k_hip::Workers> alloc_workers; // host threads of the layer allocation (rate control), kept from frame to frame
-    j2k_hip::DevBuf heavy;               // work list of the scalar coder (block indices; its length lives behind the error word in meta)
     j2k_hip::PinnedBuf h_meta, h_cs, h_plan, h_passes;
     // rate control on the device (rate.hip): the blocks' weights (per geometry), distortions, bounds; `rc_small` holds the passes
     // of earlier layers, the thresholds ahead with their sums, and a scan's results, mirrored in pinned host memory
@@ -192,9 +189,6 @@ struct j2k_hip_encoder {
     std::vector<std::vector<uint32_t>> job_row_first; // per level: first job of every tile row (+ one past the last)
     std::vector<uint32_t> fused_row_first;            // the same for the fused level-1 jobs (one per tile)
     std::vector<uint8_t> bounce;          // small pieces of the file are handed to the sink in larger writes
-    // pinned staging of host frames (N3): two pieces, the upload of piece k+1 overlaps the host copy of piece k+2
-    j2k_hip::PinnedBuf h_stage;
-    hipEvent_t stage_ev[2] = {};
     // decode path (decoder.cpp): the file on the device, per-block codeword arena, bit-plane masks, block table, output staging
     j2k_hip::DevBuf d_file, d_cw, d_masks, d_dblk, d_segs, d_outimg;
     j2k_hip::PinnedBuf h_outimg, h_dtab;

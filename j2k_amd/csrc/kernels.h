@@ -10,7 +10,7 @@ namespace j2k_hip {
 
 // ------------------------------------------------------------------------------------------------
 // Run-time tuning knobs, process-wide.  Read once from the environment (variable names in tuning.cpp:
-// J2K_NO_OVERLAP, J2K_CODER_CUS, J2K_DWT_PPC ...) and changeable afterwards through
+// J2K_NO_OVERLAP, J2K_GROUPS, J2K_DWT_PPC ...) and changeable afterwards through
 // j2k_hip_debug_tune(), so that one process can sweep variants.  None of them changes a single output
 // byte -- they move work between streams, CUs and launch shapes.
 struct Tuning {
@@ -25,39 +25,23 @@ struct Tuning {
     // by the DWT).
     int mq_yield = 2;
     int groups = 2;         // coder groups of a big frame (2..7)
-    int heavy_min = 0;      // decisions from which a block gets a scalar coder wave of its own when its frame is alone on the device (0: never --
-                            // since the two-wave coder's loops were trimmed it codes a long stream faster than the scalar wave: 17.7 against 20.7 ms per frame)
-    // 1: a frame's DWT waits only for the previous frame's DWT and runs beside that frame's modeller.  Measured on the
-    // metric frame (profiles/r2_live_sweep_ahead.txt): +3 % Mpixel/s (the chip's VALU idles less during the DWT), while
-    // the DWT launches themselves take twice as long (0.52 -> 0.9-1.1 ms: the modeller's 8 waves per SIMD leave them few
-    // wave slots).  Off by default: the bandwidth-bound launches keep the chip to themselves and the coder chains.
-    int dwt_ahead = 0;
     int alloc_threads = 8;  // host threads of one frame's layer allocation (rate control)
     int rate_dev = 0;       // rate control: the per-block work on the device (rate.hip) from this many code-blocks on; 0 = 8192, -1 = never
     int rate_dev_scan = 0;  // ... and the device scans the rounds with at least this many open blocks; 0 = 512
-    int dense_chain = 1;    // 0: the dense phases (DWT + modeller) of frames in flight are not chained (experiment)
     int mq_wait_us = 1500;  // longest time the bulk coder launch of a frame waits for the next frame's DWT phase (0 = never)
-    int mq_single = 0;      // 1: the one-wave MQ coder instead of the producer/consumer pair
-    int coder_cus = 0;      // CUs per XCD reserved for the coder streams (hipExtStreamCreateWithCUMask); the
-                            // main stream (DWT, modeller, assembly) gets the others.  0 = every stream sees the whole chip
     int dwt_pairs = 2;      // column pairs per lane of dwt_level_kernel (1 | 2)
-    int dwt_depth = 1;      // register sets of the row pipeline in dwt_level_kernel (1 = no prefetch, 2, 3, 4)
     int dwt_ppc = 0;        // row pairs per chunk of dwt_level_kernel (0 = chosen per level)
     int dwt_min_waves = 2048; // dwt_level_kernel: chunks are halved until a launch has this many waves
     int fused_wpb = 0;      // waves per workgroup of the fused level-1 kernel: 0 = by launch size (4 for big frames), 1, 4
     int fused_ppc = 0;      // row pairs per chunk of the fused level-1 kernel (0 = default)
     int fused_generic = 0;  // 1: never the variants with compile-time sample positions (A/B; the generic kernel serves every layout)
     int dwt_xcd = 1;        // XCD-aware block -> (strip, chunk) map: the strips of one chunk share an XCD (one L2)
-    int dwt_nt = 0;         // non-temporal stores for the HL/LH/HH bands (read again only by Tier-1)
-    int dwt_ntl = 0;        // non-temporal loads of the interleaved frame in the fused level-1 kernel (read once)
     int t1dec_tail = 1;     // lane-per-block decode: the heaviest blocks go to the wave-per-block kernel on a second stream (0: never)
     int t1dec_lanes = 1;    // decode Tier-1: 2 = a lane per code-block (64 blocks per wave), 0 = a wave per block, 1 = by file size (decoder.cpp)
     // Band-pipelined encode of host frames (bands.h): the frame goes up in row bands, DWT level 1 and the Tier-1 of finished
     // bands run while the next band is on its way, finished stages come down while later ones are coded.  0 = by frame size
     // (off below 16 MiB of frame), -1 = never, n >= 1 = n bands whatever the size (1: the same machinery with one band)
     int bands = 0;
-    int staging = 0;        // 1: upload host frames through two pinned pieces of the handle (0: one copy from the caller's pages)
-    int stage_kb = 16384;       // staging piece size in KiB
 };
 Tuning &tuning();
 int tune(const char *key, int value); // 0 = ok, 1 = unknown key
@@ -116,8 +100,6 @@ struct DwtLevelArgs {
     // words after component 0 in ll / z.  Channel views that are not samples of one interleaved pixel
     // (planar buffers, unequal depths) run unfused.
     int fused;
-    int nt;                            // non-temporal stores for the HL/LH/HH bands (tuning knob dwt_nt)
-    int ntl;                           // non-temporal loads of the interleaved frame (fused level 1; knob dwt_ntl)
     long long comp_stride;
     struct Fused {
         const uint8_t *base;   // first byte of pixel (0,0)
@@ -162,8 +144,6 @@ struct T1Args {
     int want_dist;                      // also produce pass_nmsedec (rate control); 0 = skip that work
     int mq_prio;                        // issue priority of the MQ coder waves: 0 = as launched, 1..3 = s_setprio level (the knob mq_prio = 1 asks for 3)
     int model_prio;                     // the same for the modeller's waves (0 everywhere but in a band-pipelined call's last stages)
-    unsigned heavy_min;                 // blocks with >= heavy_min decisions are coded by t1_mq_scalar (0 = none)
-    unsigned *heavy_list, *heavy_count; // heavy blocks of this launch, appended by the modeller (compact work list of t1_mq_scalar)
 #if defined(J2K_T1_COUNTERS) || defined(J2K_MQ_TIMES)
     unsigned long long *dbg;            // diagnostic builds: counters of the modeller's stripe loops / cycle counts of the coder's two waves
 #endif
@@ -204,8 +184,6 @@ void launch_wait_word(const unsigned *word, unsigned target, unsigned timeout_us
 void launch_set_word(unsigned *word, unsigned value, hipStream_t s, unsigned *word2 = nullptr, unsigned value2 = 0);
 // pass_rate fix-ups of blocks [first, nblks) once their coder has finished (rate control only)
 void launch_t1_rate_fixup(const T1Args &a, hipStream_t s);
-// wave-per-block scalar MQ coder for the few blocks with very long decision streams (>= heavy_min)
-void launch_t1_mq_scalar(const T1Args &a, hipStream_t s);
 
 // Rate control on the device (rate.hip; rate_control.h: RateDevice): a thread per code-block over the Tier-1 results of a frame.
 struct Taken;

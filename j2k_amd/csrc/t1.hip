@@ -27,9 +27,6 @@
 //  t1_mq2_kernel        one LANE per code-block, two waves per 64 blocks: the MQ coder is serial per
 //            block, so blocks are the parallel axis; a producer wave runs the interval/probability
 //            recurrence, a consumer wave the code register and byte output, joined by an LDS queue.
-//  t1_mq_kernel         the same in one wave (A/B knob J2K_MQ_SINGLE).
-//  t1_mq_scalar_kernel  one wave per block, wave-uniform: for the few blocks with very long streams (knob heavy_min,
-//            off by default: the two-wave coder is the faster one per decision).
 //  t1_rate_fixup_kernel the reference's fix-ups of the per-pass byte counts (rate control only).
 #include "kernels.h"
 #include "t1_common.h"
@@ -620,182 +617,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
 #endif
     const bool ovf = __any(overflow);
     if (ovf && lane == 0) a.err[0] = 2u; // decision stream capacity exceeded: the call fails, the coder must not run on it
-    if (lane == 0) {
-        a.numbps[b] = (unsigned)numbps; a.npasses[b] = ovf ? 0u : (unsigned)pass; a.nsym[b] = ovf ? 0u : fill;
-        // blocks with very long decision streams go onto the work list of the scalar coder (order is irrelevant)
-        if (a.heavy_min && a.heavy_list && !ovf && fill >= a.heavy_min) a.heavy_list[atomicAdd(a.heavy_count, 1u)] = (unsigned)b;
-    }
+    if (lane == 0) { a.numbps[b] = (unsigned)numbps; a.npasses[b] = ovf ? 0u : (unsigned)pass; a.nsym[b] = ovf ? 0u : fill; }
     report();
 }
 
 // ------------------------------------------------------------------------------------------------
 // MQ coder (T.800 Annex C); Table C.2 lives in t1_common.h.
-// context state word: qe | index << 16 | mps << 22
-__device__ __forceinline__ unsigned ctx_word(unsigned qe, unsigned idx, unsigned mps) { return qe | (idx << 16) | (mps << 22); }
-// the two-wave coder's state word: Qe in the high half (the interval register lives there too: its leading zeros are the
+// The two-wave coder's state word: Qe in the high half (the interval register lives there too: its leading zeros are the
 // renormalisation shift as they stand), below it the byte offset of the (index, sense) entry in a transition table, and
 // the sense once more in bit 0, where the decision's bit meets it
 __device__ __forceinline__ unsigned ctx_word2(unsigned qe, unsigned idx, unsigned mps) { return (qe << 16) | ((idx | (mps << 6)) << 2) | mps; }
-
-__global__ __launch_bounds__(64) void t1_mq_kernel(T1Args a)
-{
-    // The coder is issue-bound (one wave per SIMD, every lane a different block, one long dependent
-    // chain), so the per-decision instruction count is what matters: the interval update, the
-    // probability-state transition and the first BYTEOUT of a decision are straight-line selects,
-    // codeword bytes are staged in LDS and flushed once per 16 decisions.
-    __shared__ unsigned ctxs[19 * 64];     // [context][lane]: qe | index << 16 | mps << 22
-    __shared__ uint2 trans[47];            // next context word (qe | index<<16) after MPS (x) / LPS (y, bit 22 = SWITCH)
-    __shared__ __attribute__((aligned(16))) unsigned ostage[33 * 64]; // per lane: ring of 128 staged codeword bytes + dummy slot, stride 132 B = 33 banks: lanes never share a bank
-    set_priority(a.mq_prio);
-    const int lane = threadIdx.x;
-    const int b = a.first + (int)blockIdx.x * 64 + lane;
-    if (lane < 47)
-        trans[lane] = make_uint2(ctx_word(kQe[kNmps[lane]], kNmps[lane], 0), ctx_word(kQe[kNlps[lane]], kNlps[lane], kSwitch[lane]));
-#pragma unroll
-    for (int c = 0; c < 19; ++c) {
-        const unsigned idx = c == CTX_UNI ? 46u : (c == CTX_RL ? 3u : (c == 0 ? 4u : 0u));
-        ctxs[c * 64 + lane] = ctx_word(kQe[idx], idx, 0);
-    }
-    __syncthreads();
-
-    const bool live = b < a.nblks;
-    CblkDev cb = {};
-    unsigned nsym = 0, npasses = 0;
-    if (live) { cb = a.blks[b]; nsym = a.nsym[b]; npasses = a.npasses[b]; }
-    const unsigned char *sym = a.sym + cb.sym_off;
-    unsigned char *out = a.out + cb.out_off;
-    const unsigned *pass_nsym = a.pass_nsym + (size_t)(live ? b : 0) * kDevMaxPasses;
-    unsigned *pass_rate = a.pass_rate + (size_t)(live ? b : 0) * kDevMaxPasses;
-    unsigned char *ostage_b = reinterpret_cast<unsigned char *>(ostage);
-
-    // coder registers; B = pending byte, nb = bytes completed (= bp - start, -1 before the first)
-    unsigned A = 0x8000, C = 0, CT = 12, B = 0;
-    int nb = -1;
-    int flushed = 0; // bytes already stored to HBM (multiple of 64)
-    bool overflow = false;
-
-    // BYTEOUT (Figure C.3) for the lanes in `p`, branch-free
-    const unsigned lbase = (unsigned)lane * 132u; // per-lane ring: 128 bytes + dummy slot
-    auto byteout = [&](bool p) {
-        const bool was_ff = B == 0xffu;
-        const unsigned t = was_ff ? 0u : (C >> 27);            // carry into the pending byte
-        const unsigned Bc = B + t;
-        const bool stuff = Bc == 0xffu;                        // the next byte carries only 7 bits
-        const unsigned Cc = C ^ (t << 27);                     // carry consumed
-        const unsigned sh = stuff ? 20u : 19u;
-        // commit Bc at position nb; lanes not in `p` (and the dropped byte before the first code
-        // byte, nb == -1) write into their dummy slot instead of branching
-        ostage_b[lbase + ((p && nb >= 0) ? ((unsigned)nb & 127u) : 128u)] = (unsigned char)Bc;
-        if (p) { B = Cc >> sh; C = Cc & ((1u << sh) - 1u); CT = 27u - sh; ++nb; }
-    };
-
-    unsigned cur_pass = 0;
-    unsigned next_end = npasses ? pass_nsym[0] : 0xffffffffu;
-    auto close_passes = [&](unsigned i) { // record the rate estimate of every pass ending at decision i
-        while (cur_pass < npasses && i == next_end) {
-            pass_rate[cur_pass] = (unsigned)(nb + 3); // numbytes + 3 (numbytes is -1 before the first byte-out)
-            ++cur_pass;
-            next_end = cur_pass < npasses ? pass_nsym[cur_pass] : 0xffffffffu;
-        }
-    };
-
-    unsigned maxsym = nsym;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) maxsym = max(maxsym, (unsigned)__shfl_xor((int)maxsym, o));
-
-    // the stream of the NEXT 16 decisions is fetched while the current 16 are coded (each lane reads
-    // its own stream, so the load is a 64-line gather whose latency must be covered)
-    uint4 next = make_uint4(0, 0, 0, 0);
-    if (nsym) next = *reinterpret_cast<const uint4 *>(sym);
-    for (unsigned base = 0; base < maxsym; base += 16) {
-        const uint4 chunk = next;
-        if (base + 16 < nsym) next = *reinterpret_cast<const uint4 *>(sym + base + 16);
-        const unsigned words[4] = {chunk.x, chunk.y, chunk.z, chunk.w};
-        const int rem = (int)min(nsym - min(base, nsym), 16u);      // decisions of this lane in this chunk
-        int rel = (int)min(next_end - base, 64u);                    // chunk-relative end of the current pass
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            if (j < rem) {
-                const unsigned s = (words[j >> 2] >> (8 * (j & 3))) & 0xffu;
-                const unsigned caddr = (s >> 1) * 64 + lane, d = s & 1u;
-                const unsigned st = ctxs[caddr];
-                const unsigned qe = st & 0xffffu, idx = (st >> 16) & 63u;
-                const uint2 tr = trans[idx];
-                const bool is_mps = d == ((st >> 22) & 1u);
-                const unsigned A1 = A - qe;
-                const bool lt = A1 < qe;
-                const bool use_a1 = is_mps != lt; // MPS: keep A1 unless conditional exchange; LPS: the reverse
-                A = use_a1 ? A1 : qe;
-                C += use_a1 ? qe : 0u;
-                const bool renorm = (A & 0x8000u) == 0;
-                // the probability state moves only when the interval is renormalised; the MPS sense
-                // (bit 22) is kept, or flipped by the SWITCH bit of the LPS transition
-                ctxs[caddr] = renorm ? ((is_mps ? tr.x : tr.y) ^ (st & 0x400000u)) : st;
-                unsigned n = (unsigned)__builtin_clz(A) - 16u; // shifts needed (0 when A >= 0x8000; A != 0)
-                A <<= n;
-                // C <<= n with a BYTEOUT every time CT reaches zero: the first one is straight-line
-                // (some lane of the wave needs it on almost every decision), further ones are rare
-                {
-                    const bool p = n >= CT;
-                    const unsigned k = p ? CT : 0u;
-                    C <<= k; n -= k;
-                    byteout(p);
-                }
-                if (__any(n >= CT)) { // (three at most: see t1_mq2_kernel)
-                    const bool p2 = n >= CT;
-                    const unsigned k2 = p2 ? CT : 0u;
-                    C <<= k2; n -= k2;
-                    byteout(p2);
-                    if (__any(n >= CT)) {
-                        const bool p3 = n >= CT;
-                        const unsigned k3 = p3 ? CT : 0u;
-                        C <<= k3; n -= k3;
-                        byteout(p3);
-                    }
-                }
-                C <<= n; CT -= n;
-                if (rel == j + 1) { close_passes(base + j + 1); rel = (int)min(next_end - base, 64u); }
-            }
-        }
-        // refresh the chunk-relative pass end if it moved, and flush full 64-byte stage halves
-        if (__any(nb - flushed >= 64)) {
-            if (nb - flushed >= 64) {
-                if ((unsigned)(flushed + 64) <= cb.out_cap) {
-                    const unsigned *sp = reinterpret_cast<const unsigned *>(ostage_b + lbase + (flushed & 64));
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) reinterpret_cast<unsigned *>(out + flushed)[q] = sp[q];
-                } else overflow = true;
-                flushed += 64;
-            }
-        }
-    }
-    const bool fin = live && npasses;
-    if (fin) {
-        close_passes(nsym); // passes that coded no decision at the very end
-        // FLUSH (C.2.9): SETBITS, two BYTEOUTs, drop a trailing 0xFF
-        const unsigned tempc = C + A;
-        C |= 0xffffu;
-        if (C >= tempc) C -= 0x8000u;
-    }
-    C <<= CT; byteout(fin);
-    C <<= CT; byteout(fin);
-    if (fin && B != 0xffu) { // the pending byte is part of the codeword unless it is 0xFF
-        ostage_b[lbase + ((unsigned)nb & 127u)] = (unsigned char)B;
-        ++nb;
-    }
-    if (fin) {
-        // drain the stage: bytes [flushed, nb), at most 64 + 48 + 3
-        for (int o = flushed; o < nb; o += 4) {
-            if ((unsigned)(o + 4) <= cb.out_cap) *reinterpret_cast<unsigned *>(out + o) = *reinterpret_cast<const unsigned *>(ostage_b + lbase + (o & 127));
-            else overflow = true;
-        }
-        pass_rate[npasses - 1] = (unsigned)nb; // terminated pass: exact length
-        a.len[b] = (unsigned)nb;
-        if (overflow) a.err[0] = 3u; // codeword segment capacity exceeded
-    } else if (live) {
-        a.len[b] = 0;
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // Two-wave MQ coder.  The coder state splits into two recurrences that only talk one way:
@@ -863,8 +694,6 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
     CblkDev cb = {};
     unsigned nsym = 0, npasses = 0;
     if (live) { cb = a.blks[b]; nsym = a.nsym[b]; npasses = a.npasses[b]; }
-    const bool heavy = a.heavy_min && nsym >= a.heavy_min; // coded by t1_mq_scalar_kernel instead
-    if (heavy) { nsym = 0; npasses = 0; }
     unsigned maxsym = nsym;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) maxsym = max(maxsym, (unsigned)__shfl_xor((int)maxsym, o));
@@ -1098,7 +927,7 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
         pass_rate[npasses - 1] = (unsigned)nb;
         a.len[b] = (unsigned)nb;
         if (overflow) a.err[0] = 3u;
-    } else if (live && !heavy) {
+    } else if (live) {
         a.len[b] = 0;
     } else if (a.gate_groups && lane < (int)gg.count) {
         a.len[b] = 0; // (a group that was never modelled: nothing of it goes into a file -- the call fails -- but the packing must not read garbage)
@@ -1106,136 +935,6 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
     if (a.gate_groups) { // the consumer wave is the workgroup's last: its codewords and lengths are out
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         if (lane == 0) __hip_atomic_fetch_add(a.gate_done + gg.stage, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Scalar MQ coder: ONE wave per code-block, everything wave-uniform.  The lane-parallel coders pay
-// ~450 cycles per decision (every lane's path is executed, state lives in LDS); a handful of blocks
-// (lowest resolutions, most bit-planes) have decision streams twice as long as the rest and would
-// set the critical path.  Here the coder registers are scalars, the 19 context words and the
-// transition table sit in the lanes of three VGPRs (v_readlane / v_writelane instead of LDS) and
-// only the path actually taken is executed, so a decision costs a fraction of that.
-__global__ __launch_bounds__(64) void t1_mq_scalar_kernel(T1Args a)
-{
-    __shared__ unsigned obuf[64]; // 256 codeword bytes, flushed as one coalesced 256-byte store
-    const int lane = threadIdx.x;
-    // work list written by the modeller launch that precedes this one in stream order: entry i -> wave i
-    // (the grid covers the list: the launch is sized for the worst case of launch_t1_mq_scalar)
-    const unsigned count = *a.heavy_count;
-    if (blockIdx.x >= count) return;
-    __builtin_amdgcn_s_setprio(3);
-    for (unsigned entry = blockIdx.x; entry < count; entry += gridDim.x) { // (one round unless the list outgrows the grid)
-    const int b = (int)a.heavy_list[entry];
-    const unsigned nsym = a.nsym[b];
-    const CblkDev cb = a.blks[b];
-    const unsigned npasses = a.npasses[b];
-    const unsigned char *sym = a.sym + cb.sym_off;
-    unsigned char *out = a.out + cb.out_off;
-    const unsigned *pass_nsym = a.pass_nsym + (size_t)b * kDevMaxPasses;
-    unsigned *pass_rate = a.pass_rate + (size_t)b * kDevMaxPasses;
-
-    // tables in registers: lane i = state i (transition words), lane c = context c (state word)
-    const unsigned li = lane < 47 ? lane : 0;
-    const unsigned v_trx = ctx_word(kQe[kNmps[li]], kNmps[li], 0);
-    const unsigned v_try = ctx_word(kQe[kNlps[li]], kNlps[li], kSwitch[li]);
-    const unsigned i0 = lane == CTX_UNI ? 46u : (lane == CTX_RL ? 3u : (lane == 0 ? 4u : 0u));
-    unsigned v_ctx = ctx_word(kQe[i0], i0, 0);
-
-    unsigned A = 0x8000, C = 0, CT = 12, B = 0;
-    int nb = -1;
-    unsigned word = 0;    // bytes [nb & ~3, nb) of the codeword
-    int flushed = 0;
-    bool overflow = false;
-    auto put_byte = [&](unsigned v) { // wave-uniform
-        if (nb >= 0) {
-            word |= (v & 0xffu) << (8 * (nb & 3));
-            if ((nb & 3) == 3) {
-                obuf[(nb >> 2) & 63] = word;
-                word = 0;
-                if (((nb + 1) & 255) == 0) { // 256 staged bytes: coalesced flush
-                    __syncthreads();
-                    if ((unsigned)(flushed + 256) <= cb.out_cap) reinterpret_cast<unsigned *>(out + flushed)[lane] = obuf[lane];
-                    else overflow = true;
-                    flushed += 256;
-                    __syncthreads();
-                }
-            }
-        }
-        ++nb;
-    };
-    auto byteout = [&]() {
-        if (B == 0xff) {
-            put_byte(B); B = C >> 20; C &= 0xfffff; CT = 7;
-        } else {
-            if (C & 0x8000000u) {
-                ++B; C &= 0x7ffffff;
-                if (B == 0xff) { put_byte(B); B = C >> 20; C &= 0xfffff; CT = 7; return; }
-            }
-            put_byte(B); B = (C >> 19) & 0xff; C &= 0x7ffff; CT = 8;
-        }
-    };
-    unsigned cur_pass = 0;
-    unsigned next_end = npasses ? pass_nsym[0] : 0xffffffffu;
-
-    for (unsigned base = 0; base < nsym; base += 256) {
-        // 256 decisions per round: lane l holds decisions base+4l .. base+4l+3
-        const unsigned v_sym = (base + 4 * lane < nsym) ? reinterpret_cast<const unsigned *>(sym + base)[lane] : 0u;
-        const unsigned cntk = min(256u, nsym - base);
-        for (unsigned k = 0; k < cntk; ++k) {
-            const unsigned wsym = (unsigned)__builtin_amdgcn_readlane((int)v_sym, (int)(k >> 2));
-            const unsigned s = (wsym >> (8 * (k & 3))) & 0xffu;
-            const unsigned cx = s >> 1, d = s & 1u;
-            const unsigned st = (unsigned)__builtin_amdgcn_readlane((int)v_ctx, (int)cx);
-            const unsigned qe = st & 0xffffu;
-            const bool is_mps = d == ((st >> 22) & 1u);
-            const unsigned A1 = A - qe;
-            const bool lt = A1 < qe;
-            const bool use_a1 = is_mps != lt;
-            A = use_a1 ? A1 : qe;
-            C += use_a1 ? qe : 0u;
-            if ((A & 0x8000u) == 0) {
-                const unsigned idx = (st >> 16) & 63u;
-                const unsigned tw = is_mps ? (unsigned)__builtin_amdgcn_readlane((int)v_trx, (int)idx)
-                                           : (unsigned)__builtin_amdgcn_readlane((int)v_try, (int)idx);
-                v_ctx = (unsigned)lane == cx ? (tw ^ (st & 0x400000u)) : v_ctx; // "writelane": uniform value into lane cx
-                unsigned n = (unsigned)__builtin_clz(A) - 16u;
-                A <<= n;
-                while (n >= CT) { C <<= CT; n -= CT; byteout(); }
-                C <<= n; CT -= n;
-            }
-            while (cur_pass < npasses && base + k + 1 == next_end) {
-                if (lane == 0) pass_rate[cur_pass] = (unsigned)(nb + 3);
-                ++cur_pass;
-                next_end = cur_pass < npasses ? pass_nsym[cur_pass] : 0xffffffffu;
-            }
-        }
-    }
-    while (cur_pass < npasses && nsym == next_end) { // (cannot happen: the last pass is closed below)
-        if (lane == 0) pass_rate[cur_pass] = (unsigned)(nb + 3);
-        ++cur_pass;
-        next_end = cur_pass < npasses ? pass_nsym[cur_pass] : 0xffffffffu;
-    }
-    // FLUSH
-    const unsigned tempc = C + A;
-    C |= 0xffffu;
-    if (C >= tempc) C -= 0x8000u;
-    C <<= CT; byteout();
-    C <<= CT; byteout();
-    if (B != 0xff) put_byte(B);
-    if (nb & 3) obuf[(nb >> 2) & 63] = word;
-    __syncthreads();
-    // drain: bytes [flushed, nb)
-    if (flushed + 4 * lane < nb) {
-        if ((unsigned)(flushed + 4 * lane + 4) <= cb.out_cap) reinterpret_cast<unsigned *>(out + flushed)[lane] = obuf[lane];
-        else overflow = true;
-    }
-    if (lane == 0) {
-        pass_rate[npasses - 1] = (unsigned)nb;
-        a.len[b] = (unsigned)nb;
-    }
-    if (__any(overflow) && lane == 0) a.err[0] = 3u;
-    __syncthreads(); // obuf is reused by the next entry
     }
 }
 
@@ -1335,21 +1034,7 @@ void launch_t1_mq(const T1Args &a, hipStream_t s)
 {
     const int n = a.nblks - a.first;
     if (n <= 0) return;
-    if (tuning().mq_single) // A/B knob: the one-wave coder
-         hipLaunchKernelGGL(t1_mq_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(t1_mq2_kernel, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, s, a);
+    hipLaunchKernelGGL(t1_mq2_kernel, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, s, a);
 }
 
-} // namespace j2k_hip
-
-namespace j2k_hip {
-constexpr int kScalarWaves = 1024;
-void launch_t1_mq_scalar(const T1Args &a, hipStream_t s)
-{
-    const int n = a.nblks - a.first;
-    if (n <= 0 || !a.heavy_min || !a.heavy_list) return;
-    // One wave per list entry.  Heavy blocks are the few with the most bit-planes (96 of 49,152 on the metric
-    // frame); the launch covers up to kScalarWaves of them, the kernel loops should there ever be more.
-    hipLaunchKernelGGL(t1_mq_scalar_kernel, dim3((unsigned)std::min(n, kScalarWaves)), dim3(64), 0, s, a);
-}
 } // namespace j2k_hip

@@ -419,15 +419,15 @@ def test_timed_configuration_is_byte_exact(golden):
     assert len(hashes) == 9 and set(hashes) == {g["sha256"]}
 
 
-KNOBS = [("mq_yield", 0), ("mq_yield", 1), ("dwt_ahead", 1), ("overlap", 0), ("mq_single", 1), ("heavy_min", 30000),
-         ("groups", 3), ("mq_wait_us", 0), ("dense_chain", 0), ("level1_dispatch_events", 0), ("fused_wpb", 1), ("fused_generic", 1)]
+KNOBS = [("mq_yield", 0), ("mq_yield", 1), ("overlap", 0), ("groups", 3), ("mq_wait_us", 0), ("level1_dispatch_events", 0),
+         ("fused_wpb", 1), ("fused_generic", 1)]
 
 
 @pytest.mark.parametrize("knob,value", KNOBS)
 def test_tuning_knobs_never_change_a_byte(golden, knob, value):
-    """Every scheduling / variant knob of the library (coder yield, DWT ahead of the previous modeller, no overlap,
-    the one-wave coder, a low scalar-coder threshold, three coder groups, no hold-back) with two handles in flight
-    on the metric frame: the codestream stays libopenjp2's."""
+    """Every scheduling / variant knob of the library (coder yield, no overlap, three coder groups, no hold-back, the
+    level-1 launch bracketed by events, the fused kernel's variants) with two handles in flight on the metric frame:
+    the codestream stays libopenjp2's."""
     import threading
     api = _api()
     name = "c3_8192_rgb16_97_5lvl"
@@ -438,8 +438,7 @@ def test_tuning_knobs_never_change_a_byte(golden, knob, value):
     up = api.Encoder(0)
     d = up.upload(frame)
     del frame
-    defaults = {"mq_yield": 2, "dwt_ahead": 0, "overlap": 1, "mq_single": 0, "heavy_min": 0, "groups": 2, "mq_wait_us": 1500, "dense_chain": 1,
-                "level1_dispatch_events": 1, "fused_wpb": 0, "fused_generic": 0}
+    defaults = {"mq_yield": 2, "overlap": 1, "groups": 2, "mq_wait_us": 1500, "level1_dispatch_events": 1, "fused_wpb": 0, "fused_generic": 0}
     hashes, errors = [], []
 
     def worker():
@@ -637,37 +636,11 @@ def test_codestream_equals_oracle_random_block_sizes(enc, oracle):
                 api.tune("rate_dev_scan", 0)
 
 
-@pytest.mark.parametrize("heavy_min", [72000, 30000])
-def test_scalar_coder_for_long_streams_never_changes_a_byte(golden, heavy_min):
-    """The wave-per-block scalar coder (off by default: `heavy_min` = 0) takes the blocks with at least `heavy_min`
-    decisions when a frame is alone on the device: one handle, the metric frame, libopenjp2's hash."""
-    api = _api()
-    name = "c3_8192_rgb16_97_5lvl"
-    g, pl, _, _ = golden_case(golden, name)
-    frame, lay = synth.ae_frame(pl, g["prec"])
-    del pl
-    p = _params_from_golden(g)
-    e = api.Encoder(0)
-    d = e.upload(frame)
-    del frame
-    api.tune("heavy_min", heavy_min)
-    try:
-        for _ in range(2):
-            dptr, n, _ = e.encode_device(d, lay, p, download=False)
-            assert hashlib.sha256(e.d2h(dptr, n)).hexdigest() == g["sha256"]
-    finally:
-        api.tune("heavy_min", 0)
-        e.free(d)
-        e.close()
-
-
 # ------------------------------------------------------------------------------------------------ entry points of the plug-in and the bench
-@pytest.mark.parametrize("staging", [0, 1], ids=["direct", "staged"])
-def test_pipelined_begin_end_is_byte_exact(golden, staging):
+def test_pipelined_begin_end_is_byte_exact(golden):
     """j2k_hip_encode_begin / _end -- the API INTEGRATION.md recommends for an image sequence and bench.py's host_path times:
     one host thread, three handles, begin(h0,f0) begin(h1,f1) end(h0) begin(h2,f2) ... over small goldens and the 4096^2
-    frame (which is large enough for the staged upload, two coder groups and the pieced download).  Also with the pinned
-    double-buffered staging of the upload (`staging` = 1)."""
+    frame (which is large enough for two coder groups and the pieced download)."""
     api = _api()
     jobs = []
     for name in ("g6_300x200_rgb16_97_ict", "g4_300x200_rgb16_53_rct_tile128", "c2_4096_rgb8_97", "g6_300x200_rgb16_97_ict",
@@ -676,8 +649,6 @@ def test_pipelined_begin_end_is_byte_exact(golden, staging):
         frame, lay = synth.ae_frame(pl, g["prec"], row_pad_bytes=0 if name.startswith("c2") else 8)
         jobs.append((name, frame, lay, _params_from_golden(g), cs, g))
     encs = [api.Encoder(0) for _ in range(3)]
-    api.tune("staging", staging)
-    api.tune("stage_kb", 4096)
     got = {}
     try:
         n = len(jobs)
@@ -689,8 +660,6 @@ def test_pipelined_begin_end_is_byte_exact(golden, staging):
                 encs[i % 3].encode_begin_host(frame, lay, p)
                 frame[:] = 0xEE  # the caller's buffer may be reused at once: _begin has taken the frame
     finally:
-        api.tune("staging", 0)
-        api.tune("stage_kb", 16384)
         for e in encs:
             e.close()
     for i, (name, _, _, _, cs, g) in enumerate(jobs):

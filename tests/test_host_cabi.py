@@ -82,6 +82,19 @@ def test_struct_size_guard():
     assert L.j2k_hip_main_header(C.byref(p), None, 0, C.byref(n), C.byref(nt)) == 1
 
 
+def test_removed_tuning_keys_are_refused():
+    """The ten knobs of dropped experiments are gone: a stale sweep script that still sets one fails
+    loudly instead of measuring the default.  A key that stays is still taken."""
+    L = api.load_library()
+    for key in ("heavy_min", "mq_single", "staging", "stage_kb", "coder_cus", "dwt_ahead", "dense_chain", "dwt_nt", "dwt_ntl", "dwt_depth"):
+        assert L.j2k_hip_debug_tune(key.encode(), 0) == 1, key  # J2K_HIP_ERR_PARAM
+        with pytest.raises(KeyError):
+            api.tune(key, 0)
+        with pytest.raises(KeyError):
+            api.get_tune(key)
+    api.tune("groups", api.get_tune("groups"))
+
+
 def test_no_cpu_fallback_without_device():
     import torch
     if torch.cuda.is_available():

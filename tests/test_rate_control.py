@@ -105,9 +105,9 @@ def test_gpu_rate_control_with_the_per_block_work_on_the_device_matches_golden(g
 
 
 @pytest.mark.gpu
-def test_gpu_rate_control_with_scalar_coder_matches_libopenjp2(golden):
-    """Rate control on a frame big enough for two coder groups and deep enough (16 bit) for the scalar coder of
-    the longest decision streams: 4096^2 RGB16 9/7, ratio 20, against libopenjp2's file (hash)."""
+def test_gpu_rate_control_with_two_coder_groups_matches_libopenjp2(golden):
+    """Rate control on a frame big enough for two coder groups, under five thread / device settings of the layer
+    allocation: 4096^2 RGB16 9/7, ratio 20, against libopenjp2's file (hash)."""
     name = "rh1_4096_rgb16_97_r20"
     if name not in golden:
         pytest.skip("full-size golden not generated")
@@ -116,7 +116,6 @@ def test_gpu_rate_control_with_scalar_coder_matches_libopenjp2(golden):
     frame, lay = synth.ae_frame(pl, g["prec"])
     del pl
     enc = api.Encoder(0)
-    api.tune("heavy_min", 72000)  # the scalar coder is off by default
     try:
         # the host allocation cuts its scans and packet walks across this many threads; 12288 blocks: the per-block work is on
         # the device by default (rate_dev -1: all of it on the host; rate_dev_scan 1: every scan on the device)
@@ -133,7 +132,6 @@ def test_gpu_rate_control_with_scalar_coder_matches_libopenjp2(golden):
         api.tune("alloc_threads", 8)
         api.tune("rate_dev", 0)
         api.tune("rate_dev_scan", 0)
-        api.tune("heavy_min", 0)
         enc.close()
 
 

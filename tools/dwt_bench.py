@@ -13,7 +13,7 @@ a = (rng.standard_normal((3, S, S)) * 1000).astype(np.int32 if rev else np.float
 _, ms = enc.stage_dwt(a, levels, rev, repeat=1)
 _, ms = enc.stage_dwt(a, levels, rev, repeat=20)
 nbytes = 8.0 * 3 * S * S * sum(0.25 ** l for l in range(levels))
-print(f"PAIRS={os.environ.get('J2K_DWT_PAIRS','2')} PF={os.environ.get('J2K_DWT_PF','1')} PPC={os.environ.get('J2K_DWT_PPC','auto')} "
+print(f"PAIRS={os.environ.get('J2K_DWT_PAIRS','2')} PPC={os.environ.get('J2K_DWT_PPC','auto')} "
       f"S={S} levels={levels} {'5/3' if rev else '9/7'}: {ms*1e3:.1f} us  {nbytes/ms/1e6:.0f} GB/s")
 if os.environ.get("J2K_COPY_CAL"):
     import torch, time

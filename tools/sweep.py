@@ -3,8 +3,7 @@
 
     python tools/sweep.py membw          copy ceilings of this box (j2k_hip_debug_membw, several shapes and sizes)
     python tools/sweep.py dwt            the DWT launches alone (one frame at a time, per-level hipEvents) under knob variants
-    python tools/sweep.py live           3 frames in flight: Mpixel/s and the live DWT figures under knob variants (CU masks ...)
-    python tools/sweep.py upload         host frame upload: pageable copy vs pinned staging pieces
+    python tools/sweep.py live           3 frames in flight: Mpixel/s and the live DWT figures under knob variants
 
 Knobs go through j2k_hip_debug_tune (no output byte depends on a knob; every variant's codestream hash is checked
 against the first one).  Output: one line per variant, also appended to gpurun_out/sweep_<section>.txt.
@@ -80,8 +79,8 @@ def set_knobs(kn):
         api.tune(k, v)
 
 
-DEFAULTS = dict(dwt_xcd=1, fused_ppc=0, fused_wpb=0, dwt_ppc=0, dwt_min_waves=2048, dwt_pairs=2, dwt_depth=1, coder_cus=0,
-                level_events=0, dwt_nt=0, dwt_ntl=0, mq_wait_us=1500, mq_yield=2, mq_prio=1, dwt_ahead=0, groups=2, heavy_min=0)
+DEFAULTS = dict(dwt_xcd=1, fused_ppc=0, fused_wpb=0, dwt_ppc=0, dwt_min_waves=2048, dwt_pairs=2,
+                level_events=0, mq_wait_us=1500, mq_yield=2, mq_prio=1, groups=2)
 
 
 def dwt():
@@ -128,7 +127,7 @@ def live():
     for kn in variants:
         kn = dict(kn)
         want_nfl = kn.pop("inflight", None)
-        for nfl in ((want_nfl,) if want_nfl else (3, 4) if kn.get("coder_cus") else (3,)):
+        for nfl in ((want_nfl,) if want_nfl else (3,)):
             set_knobs({**DEFAULTS, **kn})
             encs = [api.Encoder(0) for _ in range(nfl)]
             outs = [(C.c_void_p(), C.c_size_t()) for _ in range(nfl)]
@@ -170,37 +169,7 @@ def live():
     boot.close()
 
 
-def upload():
-    enc = api.Encoder(0)
-    pl = synth.planes(S, S, 3, PREC, 23456)
-    frame, lay = synth.ae_frame(pl, PREC)
-    del pl
-    p = params()
-    sink_buf = (C.c_uint8 * frame.nbytes)()
-    pos = [0]
-
-    @api.WRITE_FN
-    def sink(user, ptr, n):
-        C.memmove(C.addressof(sink_buf) + pos[0], ptr, n)
-        pos[0] += n
-        return n
-    planes = api.planes_from_layout(frame.ctypes.data, lay, 3)
-    for kn in (dict(staging=0), dict(staging=1, stage_kb=4096), dict(staging=1, stage_kb=16384), dict(staging=1, stage_kb=65536)):
-        set_knobs(kn)
-        ms = []
-        for it in range(5):
-            pos[0] = 0
-            t0 = time.perf_counter()
-            enc._check(enc.L.j2k_hip_encode(enc.h, C.byref(p), planes, sink, None))
-            ms.append((time.perf_counter() - t0) * 1e3)
-            st = enc.stats()
-        emit("upload", f"{kn}: call {np.median(ms[1:]):.1f} ms, upload {st['ms_upload']:.2f} ms ({frame.nbytes / st['ms_upload'] / 1e6:.1f} GB/s), "
-                       f"download wait {st['ms_download']:.2f} ms")
-    set_knobs(dict(staging=0))
-    enc.close()
-
-
 if __name__ == "__main__":
     for sec in sys.argv[1:] or ["membw", "dwt", "live"]:
         emit(sec, f"# {sec} {time.strftime('%Y-%m-%d %H:%M:%S')} size {S}")
-        dict(membw=membw, dwt=dwt, live=live, upload=upload)[sec]()
+        dict(membw=membw, dwt=dwt, live=live)[sec]()

@@ -15,7 +15,7 @@ for d in ("gpurun_out/pmc_t1a", "gpurun_out/pmc_t1b"):
         print("no counters in", d); continue
     agg = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.defaultdict(set)
     for r in csv.DictReader(open(f[0])):
-        m = re.search(r"(t1_model_kernel|t1_mq2_kernel|t1_mq_scalar_kernel|dwt_fused_kernel|dwt_level_kernel|gather_kernel)", r["Kernel_Name"])
+        m = re.search(r"(t1_model_kernel|t1_mq2_kernel|dwt_fused_kernel|dwt_level_kernel|gather_kernel)", r["Kernel_Name"])
         if m:
             agg[m.group(1)][r["Counter_Name"]] += float(r["Counter_Value"]); n[m.group(1)].add(r["Dispatch_Id"])
     frames = max(1, len(n["dwt_fused_kernel"]))
