@@ -281,6 +281,33 @@ hipStream_t j2k_hip::coder_stream(j2k_hip_encoder *e, int i)
 
 namespace {
 
+#ifdef J2K_T1_COUNTERS
+// diagnostic build: the modeller's loop and path counters (kernels.h: kT1Counters) -- prints the totals of the launches since
+// the last call and hands the zeroed words to the next ones
+void t1_counters(T1Args &ta)
+{
+    static unsigned long long *dbg = nullptr;
+    if (!dbg) { HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dbg), kT1Counters * 8)); }
+    else {
+        unsigned long long h[kT1Counters];
+        HIP_CHECK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
+        std::fprintf(stderr, "t1 counters (previous launches): planes %llu | significance pass: %llu run, %llu decisions, fixed-point rounds %llu, "
+                             "dense halves %llu with %llu stripes written, sparse halves %llu | cleanup pass: %llu run, %llu decisions, dense halves %llu "
+                             "with %llu stripes written, sparse halves %llu | sparse sample rounds %llu, scans over the stage limit %llu | "
+                             "refinement pass: %llu decisions, stripe pairs written %llu, skipped %llu\n",
+                     h[6], h[10], h[14], h[1], h[12], h[0], h[7], h[11], h[15], h[13], h[2], h[8], h[9], h[17], h[16], h[4], h[5]);
+        static const char *const bucket[7] = {"0", "1-2", "3-4", "5-8", "9-16", "17-32", "33-64"};
+        for (int t = 0; t < 2; ++t) {
+            std::fprintf(stderr, "  %s passes by the busiest column's visited samples (passes / stripes holding one):", t ? "cleanup" : "significance");
+            for (int k = 0; k < 7; ++k) std::fprintf(stderr, " %s: %llu / %llu;", bucket[k], h[20 + 14 * t + k], h[27 + 14 * t + k]);
+            std::fprintf(stderr, "\n");
+        }
+    }
+    HIP_CHECK(hipMemset(dbg, 0, kT1Counters * 8));
+    ta.dbg = dbg;
+}
+#endif
+
 // Launch arguments of DWT level l (0 = full resolution) of frame f of the call: level l reads LL(l-1) and writes LL(l) to
 // the other ping-pong plane (the last level: to Z) and its HL/LH/HH bands to Z.
 // tile_row >= 0: the jobs of that tile row only (band-pipelined encode).
@@ -517,10 +544,11 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     ta.pass_nmsedec = reinterpret_cast<int *>(e->passes.as<uint32_t>() + nb * kDevMaxPasses);
     ta.pass_rate = e->passes.as<uint32_t>() + 2 * nb * kDevMaxPasses;
     ta.mq_prio = tn.mq_prio ? 3 : 0;
+    ta.sparse = tn.t1_sparse;
 #ifdef J2K_MQ_TIMES
     { // diagnostic build: where the two waves of the coder spend their cycles (previous frame's totals, at every encode)
         static unsigned long long *dbg = nullptr;
-        if (!dbg) { HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dbg), 12 * 8)); }
+        if (!dbg) { HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dbg), kT1Counters * 8)); }
         else {
             unsigned long long h[12];
             HIP_CHECK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
@@ -528,24 +556,12 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
             std::fprintf(stderr, "coder waves (previous frame): %.0f workgroups, %.0f chunks each; per chunk of 16 decisions, counter ticks: producer work %.1f + barrier %.1f | "
                                  "consumer work %.1f + barrier %.1f\n", wv, ch / wv, h[0] / ch, h[1] / ch, h[2] / ch, h[3] / ch);
         }
-        HIP_CHECK(hipMemset(dbg, 0, 12 * 8));
+        HIP_CHECK(hipMemset(dbg, 0, kT1Counters * 8));
         ta.dbg = dbg;
     }
 #endif
 #ifdef J2K_T1_COUNTERS
-    {
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) { HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dbg), 12 * 8)); }
-        else {
-            unsigned long long h[12];
-            HIP_CHECK(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
-            std::fprintf(stderr, "t1 counters (previous frame): planes %llu | significance pass: stripes written %llu, fixed-point rounds %llu | "
-                                 "cleanup pass: stripes written %llu | refinement pass: stripe pairs written %llu, skipped %llu\n",
-                         h[6], h[0], h[1], h[2], h[4], h[5]);
-        }
-        HIP_CHECK(hipMemset(dbg, 0, 12 * 8));
-        ta.dbg = dbg;
-    }
+    t1_counters(ta);
 #endif
     ta.yield_word = (dwt_word && tn.mq_yield && tn.overlap) ? dwt_word + 32 : nullptr;
     const bool rate_control = cod.rate_control();
@@ -1118,6 +1134,7 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     ta.pass_nmsedec = reinterpret_cast<int *>(e->passes.as<uint32_t>() + nb * kDevMaxPasses);
     ta.pass_rate = e->passes.as<uint32_t>() + 2 * nb * kDevMaxPasses;
     ta.mq_prio = tn.mq_prio ? 3 : 0;
+    ta.sparse = tn.t1_sparse;
     ta.gate_groups = e->gate_groups.as<T1Args::GateGroup>(); ta.gate_group_of = e->gate_group_of.as<unsigned>();
     ta.gate_ready = gate_ready; ta.gate_done = gate_done; ta.gate_abort = gate_abort;
     ta.gate_budget = 1u << 21; // polls of ~4 us: eight seconds, then the workgroup gives up (error 4)
@@ -1905,6 +1922,10 @@ int j2k_hip_stage_t1_passes(j2k_hip_encoder *e, int reversible, void *d_coef, ui
         ta.pass_nmsedec = reinterpret_cast<int *>(e->passes.as<uint32_t>() + nb * kDevMaxPasses);
         ta.pass_rate = e->passes.as<uint32_t>() + 2 * nb * kDevMaxPasses;
         ta.want_dist = pass_dist != nullptr; // the distortion sums cost LDS and issue slots: only on request
+        ta.sparse = tuning().t1_sparse;
+#ifdef J2K_T1_COUNTERS
+        t1_counters(ta);
+#endif
         HIP_CHECK(hipMemsetAsync(ta.err, 0, sizeof(uint32_t), s));
         launch_t1_model(ta, s);
         launch_t1_mq(ta, s);

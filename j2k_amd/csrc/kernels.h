@@ -42,6 +42,9 @@ struct Tuning {
     // bands run while the next band is on its way, finished stages come down while later ones are coded.  0 = by frame size
     // (off below 16 MiB of frame), -1 = never, n >= 1 = n bands whatever the size (1: the same machinery with one band)
     int bands = 0;
+    // debug only (tests, A/B): the modeller's sample-wise path for sparse significance / cleanup passes.  0 = chosen per pass
+    // half by its counts, -1 = never, 1 = whenever the half fits the stage, however dense.  Never changes a byte.
+    int t1_sparse = 0;
 };
 Tuning &tuning();
 int tune(const char *key, int value); // 0 = ok, 1 = unknown key
@@ -136,6 +139,7 @@ struct CblkDev {
     unsigned char pad[2];
 };
 constexpr int kDevMaxPasses = 96;
+constexpr int kT1Counters = 48;         // words behind T1Args::dbg in a J2K_T1_COUNTERS build
 struct T1Args {
     const void *coef; long long stride; // coefficient buffer, words per row
     const CblkDev *blks; int nblks;     // table of all blocks; this launch handles [first, nblks)
@@ -144,6 +148,7 @@ struct T1Args {
     int want_dist;                      // also produce pass_nmsedec (rate control); 0 = skip that work
     int mq_prio;                        // issue priority of the MQ coder waves: 0 = as launched, 1..3 = s_setprio level (the knob mq_prio = 1 asks for 3)
     int model_prio;                     // the same for the modeller's waves (0 everywhere but in a band-pipelined call's last stages)
+    int sparse;                         // t1_model: the sample-wise path of sparse significance / cleanup passes (the knob t1_sparse)
 #if defined(J2K_T1_COUNTERS) || defined(J2K_MQ_TIMES)
     unsigned long long *dbg;            // diagnostic builds: counters of the modeller's stripe loops / cycle counts of the coder's two waves
 #endif

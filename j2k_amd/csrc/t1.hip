@@ -21,7 +21,11 @@
 //            a lane's bytes of a stripe are packed in registers (v_perm, selectors from a table by
 //            which rows code something) and ORed as whole words into a zeroed linear LDS stage at
 //            the offset a DPP scan of the per-lane counts gives; the refinement pass scatters its
-//            bytes there.  They leave in coalesced 1 KiB stores.  With rate control (DIST) the per-pass distortion
+//            bytes there.  A 32-row half of a significance / cleanup pass that visits few samples (and has no
+//            run-length column) is written sample by sample instead: the lanes' bytes per stripe are counted
+//            on the nibbles of the masks, scanned two stripes to a register, and every lane walks its own
+//            visited rows -- the cost follows the samples coded, not the stripes that hold one.
+//            They leave in coalesced 1 KiB stores.  With rate control (DIST) the per-pass distortion
 //            estimates are weighted population counts of (samples of the pass) & (bit-planes below the
 //            current one): the nmsedec tables are piecewise linear in their index (dist_sum).
 //  t1_mq2_kernel        one LANE per code-block, two waves per 64 blocks: the MQ coder is serial per
@@ -75,6 +79,21 @@ __device__ __forceinline__ unsigned prefix_count_dpp(unsigned cnt, unsigned &tot
     return (unsigned)t - cnt;
 }
 
+// population counts of the eight nibbles of a word, each in its nibble
+__device__ __forceinline__ unsigned nibble_counts(unsigned v)
+{
+    const unsigned x = v - ((v >> 1) & 0x55555555u);
+    return (x & 0x33333333u) + ((x >> 2) & 0x33333333u);
+}
+
+// Sample-wise writing of a sparse pass half against its dense stripe loop, in static VALU instructions of the kernel as
+// built (tools/isa.sh, <false,false>, all paths): the stripe loop costs kDenseStripe per stripe that holds a visited
+// sample; the sample-wise path kSparseHead once (nibble counts, four packed scans, stripe bases) and kSparseRound per
+// round, rounds = visited samples of the busiest lane.  The sample-wise path is taken when it is the cheaper one by these.
+// (Stripe costs of 70 and 85 -- nearer to what a stripe executes with its skipped parts left out -- were built and
+//  measured on the metric frame: the kernel's vector instructions and its time moved by less than 0.5 %.)
+constexpr unsigned kDenseStripe = 103, kSparseHead = 64, kSparseRound = 44;
+constexpr unsigned kBurst = 64 * 10; // room of the stage beyond what may be pending
 
 // distortion LUTs of the oracle in closed form (index = 7 bits around the current bit-plane)
 __device__ __forceinline__ int nmsedec_sig(unsigned m, int bp)
@@ -235,7 +254,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
         return;
     }
 
-    const u64 rowmask = lane < w ? (h == 64 ? ~(u64)0 : (((u64)1 << h) - 1)) : 0;
+    // the block's samples of this column as a row mask.  Formed where it is used (the rows are wave-uniform, the column test is
+    // one compare; the width goes through an empty asm so that the mask is not hoisted): held in a register pair through the
+    // pass loops it is one 64-bit value too many there and something spills
+    const u64 rows_of_block = h == 64 ? ~(u64)0 : (((u64)1 << h) - 1);
+    auto rowmask_now = [&]() -> u64 {
+        int wv = w;
+        asm volatile("" : "+s"(wv));
+        return lane < wv ? rows_of_block : 0;
+    };
     const int nstripes = (h + 3) >> 2;
     u64 sigma = 0, mu = 0, pi = 0;
     unsigned fill = 0, flushed = 0; // decisions produced / already stored to HBM (wave-uniform)
@@ -290,10 +317,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
     };
 
 #ifdef J2K_T1_COUNTERS
-    unsigned long long dc[12] = {};
+    unsigned long long dc[kT1Counters] = {};
 #define DCNT(i) (++dc[i])
+#define DADD(i, n) (dc[i] += (n))
 #else
 #define DCNT(i) ((void)0)
+#define DADD(i, n) ((void)0)
 #endif
     // plane q of the magnitudes of this column (stored planes only): two coalesced loads
     auto plane_word = [&](int q) -> u64 {
@@ -378,6 +407,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
             int nm = 0;
             // whole-pass early-out: SPP/CUP code only insignificant samples, MRP only significant ones
             // (the cleanup pass only codes what the significance-propagation pass of this bit-plane left unvisited)
+            const u64 rowmask = rowmask_now();
             const u64 todo = pt == 1 ? sigma : (pt == 0 ? rowmask & ~sigma : rowmask & ~sigma & ~pi);
             const bool pass_work = todo != 0;
             const int ns_eff = __any(pass_work) ? nstripes : 0;
@@ -423,6 +453,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if ((ref8 >> (4 + r)) & 1u) stage[base1 + ((excl[1] >> (8 * r)) & 0xffu)] = (unsigned char)(Wsym[1] >> (8 * r));
+                    DADD(16, total0 + total1);
                     commit(total0 + total1);
                 }
                 mu |= ref64; // every row refined in this pass
@@ -466,6 +497,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
             if constexpr (DIST) nm = dist_sum(N64, bits, bp, false);
             const u64 A = O | N64;
             const u64 LA = from_left64(A), RA = from_right64(A);
+            // (here, not behind the halves, and pinned here: V64 need not outlive them -- sunk to the end of the pass it is
+            //  spilled across the stripe loops)
+            if (pt == 0) pi |= V64;
+            asm volatile("" : "+v"(pi));
             // stripes with anything to code (wave-wide OR of the per-lane nibble occupancy)
             u64 occ = V64 | (V64 >> 1);
             occ = (occ | (occ >> 2)) & M0;
@@ -478,6 +513,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
 #undef J2K_OR_STEP
             const unsigned act[2] = {(unsigned)__builtin_amdgcn_readlane((int)olo, 63), (unsigned)__builtin_amdgcn_readlane((int)ohi, 63)};
             const bool any_n = __any(N64 != 0);
+#ifdef J2K_T1_COUNTERS
+            { // passes by the busiest lane's visited samples, with the stripes that hold one
+                unsigned busiest = (unsigned)__popcll(V64);
+                for (int o = 32; o > 0; o >>= 1) busiest = max(busiest, (unsigned)__shfl_xor((int)busiest, o));
+                const int bucket = busiest == 0 ? 0 : (busiest <= 2 ? 1 : 32 - __clz((int)busiest - 1));
+                const int t0 = pt == 0 ? 20 : 34;
+                DCNT(pt == 0 ? 10 : 11);
+                DCNT(t0 + bucket);
+                DADD(t0 + 7 + bucket, __builtin_popcount(act[0]) + __builtin_popcount(act[1]));
+            }
+#endif
             // The contexts of the pass are formed for 32 rows at a time (rows 0..31, then 32..63): every mask below is the
             // half of a 64-bit row mask, so the bit-sliced tables run on single registers and only one half's planes are alive
             // while its eight stripes are written.
@@ -486,6 +532,54 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                 unsigned active = act[half];
                 if (!active) continue;
                 auto hf = [&](u64 m) { return half ? (unsigned)(m >> 32) : (unsigned)m; };
+                // ---- cleanup pass, run-length mode: a full stripe column with nothing significant in its 3 x 6 neighbourhood
+                // when the scan arrives (flag at the bit of the stripe's first row)
+                unsigned rl = 0;
+                if (pt != 0) {
+                    const u64 in = O | LA | RO; // rows of the stripe: own old, left new, right old
+                    u64 busy = in | (in >> 1);
+                    busy |= busy >> 2;
+                    busy |= ((A | LA | RA) << 1) | ((O | LO | RO) >> 4); // row above the stripe (new), row below it (old)
+                    u64 full = V64 & (V64 >> 1);
+                    full &= full >> 2;
+                    rl = hf(full & ~busy & M0);
+                }
+                const unsigned bitsh = hf(bits), Nh = hf(A) & ~hf(O), Vh = hf(V64); // (N64 = A & ~O: one 64-bit mask less alive through the halves)
+                // ---- sample-wise writing of a sparse half: no stripe loop.  Every lane's bytes per stripe are counted on the
+                // nibbles of V and N, the eight stripes' counts are scanned across the wave two to a register (16-bit fields:
+                // a stripe holds at most 512 bytes), the stripe totals become stripe bases on the scalar unit -- the scan order
+                // is stripe, column, row, [ZC][sign] per row, as the stripe loop writes it -- and then every lane walks its own
+                // visited rows: the contexts are single bits of the planes formed below, the bytes go to its place in the stage.
+                // The busiest lane sets the number of rounds.  A cleanup half with a run-length column stays dense.
+                bool sparse = false;
+                u64 q0 = 0, q1 = 0;
+                unsigned sparse_total = 0;
+                if (a.sparse >= 0 && !__any(rl != 0)) {
+                    // (rounds = the busiest lane's visited samples: no lane may have more than the break-even allows)
+                    const unsigned dense_cost = kDenseStripe * (unsigned)__builtin_popcount(active);
+                    if (a.sparse > 0 || !__any(kSparseHead + kSparseRound * (unsigned)__builtin_popcount(Vh) >= dense_cost)) {
+                        const unsigned c = nibble_counts(Vh) + nibble_counts(Nh); // at most 8 per nibble
+                        // register k: stripes k (low half) and k + 4 (high half)
+                        const unsigned c0 = c & 0x000f000fu, c1 = (c >> 4) & 0x000f000fu, c2 = (c >> 8) & 0x000f000fu, c3 = (c >> 12) & 0x000f000fu;
+                        unsigned t0, t1, t2, t3;
+                        const unsigned e0 = prefix_count_dpp(c0, t0), e1 = prefix_count_dpp(c1, t1), e2 = prefix_count_dpp(c2, t2), e3 = prefix_count_dpp(c3, t3);
+                        // (wave-uniform: the packed totals summed over the registers -- low halves: bytes of the stripes before k,
+                        //  high halves: of the stripes 4 .. 3 + k; the first four stripes together come before every high one)
+                        const unsigned a1 = t0 + t1, a2 = a1 + t2, a3 = a2 + t3;
+                        const unsigned total = (a3 & 0xffffu) + (a3 >> 16);
+                        if (total <= kBurst) {
+                            sparse = true;
+                            sparse_total = total;
+                            DCNT(pt == 0 ? 7 : 8);
+                            DADD(pt == 0 ? 14 : 15, total);
+                            // stage offsets of the lane's first byte in each stripe, four to a 64-bit word: q0 = stripes 0, 4, 1, 5,
+                            // q1 = stripes 2, 6, 3, 7
+                            const unsigned org = (fill - flushed) * 0x10001u + (a3 << 16);
+                            q0 = (u64)(e0 + org) | ((u64)(e1 + org + t0) << 32);
+                            q1 = (u64)(e2 + org + a1) | ((u64)(e3 + org + a2) << 32);
+                        } else DCNT(17);
+                    }
+                }
                 // the eight neighbour masks with the timing of the stripe scan: left column new (its row below the stripe
                 // old), right column old (its row above the stripe new), row above new, row below old
                 const unsigned Wm1 = hf(LA << 1), W0 = hf(LA), Wp1 = hf(((LA >> 1) & ~M3) | (LO >> 1));
@@ -533,19 +627,31 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                     sb0 = (hnz & ~same & ~opp) | (~hnz & vnz);
                     sd = hf(chi) ^ (hn | (~hnz & vn));
                 }
-                // ---- cleanup pass, run-length mode: a full stripe column with nothing significant in its 3 x 6 neighbourhood
-                // when the scan arrives (flag at the bit of the stripe's first row)
-                unsigned rl = 0;
-                if (pt != 0) {
-                    const u64 in = O | LA | RO; // rows of the stripe: own old, left new, right old
-                    u64 busy = in | (in >> 1);
-                    busy |= busy >> 2;
-                    busy |= ((A | LA | RA) << 1) | ((O | LO | RO) >> 4); // row above the stripe (new), row below it (old)
-                    u64 full = V64 & (V64 >> 1);
-                    full &= full >> 2;
-                    rl = hf(full & ~busy & M0);
+                if (sparse) {
+                    unsigned rest = Vh, pos = 0;
+                    int cur = -1; // the stripe pos belongs to
+                    while (__any(rest != 0)) {
+                        DCNT(9);
+                        if (rest) {
+                            const int r = __builtin_ctz(rest);
+                            rest &= rest - 1;
+                            const int st = r >> 2;
+                            if (st != cur) pos = (unsigned)((r & 8 ? q1 : q0) >> (((r & 4) << 3) | (r & 16))) & 0xffffu;
+                            cur = st;
+                            // (context << 1) | bit, one bit of each plane: bit extracts chained by shift-and-or
+                            const auto bit = [&](unsigned plane) { return __builtin_amdgcn_ubfe(plane, (unsigned)r, 1u); };
+                            stage[pos] = (unsigned char)((((((((bit(zb3) << 1) | bit(zb2)) << 1) | bit(zb1)) << 1) | bit(zb0)) << 1) | bit(bitsh));
+                            ++pos;
+                            if (bit(Nh)) {
+                                stage[pos] = (unsigned char)(0x12u + ((((((bit(sb2) << 1) | bit(sb1)) << 1) | bit(sb0)) << 1) | bit(sd)));
+                                ++pos;
+                            }
+                        }
+                    }
+                    commit(sparse_total);
+                    continue;
                 }
-                const unsigned bitsh = hf(bits), Nh = hf(N64), Vh = hf(V64);
+                DCNT(pt == 0 ? 12 : 13);
                 while (active) {
                     const int sl = __builtin_ctz(active) & ~3; // first row of the stripe inside the half
                     active &= active - 1;
@@ -586,11 +692,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                         const unsigned c0 = __builtin_amdgcn_perm(ssym, zsym, (unsigned)sel), c1 = __builtin_amdgcn_perm(ssym, zsym, (unsigned)(sel >> 32));
                         const u64 d = (((u64)c1 << 32) | c0) << (8 * pc);
                         emit(base, cnt, (unsigned)d | rlsym, (unsigned)(d >> 32), __builtin_amdgcn_ubfe(c1, 8, 8 * pc));
+                        DADD(pt == 0 ? 14 : 15, total);
                         commit(total);
                     }
                 }
             }
-            if (pt == 0) pi |= V64;
             sigma = A;
             }
             }
@@ -613,7 +719,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
         } else overflow = true;
     }
 #ifdef J2K_T1_COUNTERS
-    if (lane == 0 && a.dbg) for (int i = 0; i < 12; ++i) atomicAdd(a.dbg + i, dc[i]);
+    if (lane == 0 && a.dbg) for (int i = 0; i < kT1Counters; ++i) if (dc[i]) atomicAdd(a.dbg + i, dc[i]);
 #endif
     const bool ovf = __any(overflow);
     if (ovf && lane == 0) a.err[0] = 2u; // decision stream capacity exceeded: the call fails, the coder must not run on it

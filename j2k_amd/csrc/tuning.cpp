@@ -32,6 +32,7 @@ const Knob kKnobs[] = {
     {"t1dec_lanes", "J2K_T1DEC_LANES", &Tuning::t1dec_lanes},
     {"t1dec_tail", "J2K_T1DEC_TAIL", &Tuning::t1dec_tail},
     {"bands", "J2K_BANDS", &Tuning::bands},
+    {"t1_sparse", "J2K_T1_SPARSE", &Tuning::t1_sparse},
 };
 
 Tuning g_tuning;
