@@ -370,6 +370,39 @@ int j2k_hip_stage_t1_passes(j2k_hip_encoder *enc, int reversible, void *d_coef, 
                             uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
                             void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist);
 
+/* Inverse DWT (the mirror of j2k_hip_stage_dwt): `nplanes` planes of width*height 32-bit words (row stride =
+ * width) in the Mallat layout of the oracle are synthesised from the lowest of `levels` resolutions upwards,
+ * one kernel launch pair per level, the jobs built like a decode builds them.  With nregions == 0 a plane is
+ * one region of origin (x0,y0).  Otherwise every plane holds `nregions` sub-rectangles (the tiles of a tiled
+ * component), each a Mallat layout of its own with its own origin, all of them jobs of the same launches;
+ * they must lie inside the plane and must not overlap; (x0,y0) is ignored.  d_in is preserved, d_out receives
+ * the samples; words outside every region are copied from d_in. */
+typedef struct j2k_hip_idwt_region {
+    uint32_t x, y, w, h; /* the rectangle in the plane */
+    uint32_t x0, y0;     /* its absolute origin (parities of the lifting) */
+} j2k_hip_idwt_region;
+int j2k_hip_stage_idwt(j2k_hip_encoder *enc, int reversible, uint32_t width, uint32_t height,
+                       uint32_t nplanes, uint32_t levels, uint32_t x0, uint32_t y0,
+                       const j2k_hip_idwt_region *regions, uint32_t nregions, const void *d_in,
+                       void *d_out);
+
+/* Tier-1 DECODING of `nblocks` code-blocks (default code-block style) into one coefficient plane of 32-bit
+ * words (row stride `stride` words; int32 for reversible, float32 otherwise).  kernel = 0: a wavefront per
+ * block; 1: a lane per block, the blocks in groups of 64 IN THE ORDER GIVEN.  Codewords are bytes
+ * [cw_off, cw_off + cw_len) of the host buffer `cw`.  npasses is clamped to 3 * numbps - 2; a block with
+ * npasses == 0 or numbps == 0 holds nothing and its rectangle is left as it was -- the rules of a file decode.
+ * Rectangles (1..64 on either edge) must lie inside the stride and must not overlap. */
+typedef struct j2k_hip_dec_block {
+    uint32_t x, y, w, h;
+    uint32_t orient, numbps, npasses, roishift;
+    float half_step;     /* 0.5 x band step size (ignored when reversible) */
+    uint32_t cw_len;
+    uint64_t cw_off;
+} j2k_hip_dec_block;
+int j2k_hip_stage_t1_decode(j2k_hip_encoder *enc, int kernel, int reversible, void *d_coef,
+                            uint32_t stride, uint32_t nblocks, const j2k_hip_dec_block *blocks,
+                            const void *cw, size_t cw_bytes);
+
 /* --- introspection ----------------------------------------------------------------------------- */
 int j2k_hip_get_stats(const j2k_hip_encoder *enc, j2k_hip_stats *stats);
 /* Device-time of the DWT kernels of the last encode call, per level (ms); returns levels. */

@@ -87,8 +87,20 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
            "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
+           "j2k_hip_stage_idwt", "j2k_hip_stage_t1_decode",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink"]
+
+class IdwtRegion(C.Structure):
+    """include/j2k_hip.h: j2k_hip_idwt_region."""
+    _fields_ = [(n, C.c_uint32) for n in ("x", "y", "w", "h", "x0", "y0")]
+
+
+class DecBlock(C.Structure):
+    """include/j2k_hip.h: j2k_hip_dec_block."""
+    _fields_ = [(n, C.c_uint32) for n in ("x", "y", "w", "h", "orient", "numbps", "npasses", "roishift")] + \
+               [("half_step", C.c_float), ("cw_len", C.c_uint32), ("cw_off", C.c_uint64)]
+
 
 class CopySink(C.Structure):
     """include/j2k_hip.h: j2k_hip_copy_sink -- the `user` of j2k_hip_debug_copy_sink."""
@@ -154,6 +166,10 @@ def load_library():
     L.j2k_hip_stage_t1.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, U32P, U32P, U32P, U32P, U32P,
                                    C.POINTER(C.c_float), U32P, U32P, U32P, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t]
     L.j2k_hip_stage_t1_passes.argtypes = L.j2k_hip_stage_t1.argtypes + [U32P, C.POINTER(C.c_int32)]
+    L.j2k_hip_stage_idwt.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.POINTER(IdwtRegion), C.c_uint32, C.c_void_p, C.c_void_p]
+    L.j2k_hip_stage_t1_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DecBlock),
+                                          C.c_void_p, C.c_size_t]
     L.j2k_hip_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.j2k_hip_get_dwt_level_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
     L.j2k_hip_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -549,3 +565,50 @@ class Encoder:
                 o["rates"] = list(rates[i * MP:i * MP + o["npasses"]])
                 o["nmsedec"] = list(dist[i * MP:i * MP + o["npasses"]])
         return out
+
+    def stage_idwt(self, planes: np.ndarray, levels: int, reversible: bool, x0=0, y0=0, regions=None):
+        """planes: (n, h, w) int32 / float32 in Mallat layout -> the synthesised samples.  regions: [(x, y, w, h, x0, y0)]
+        sub-rectangles of every plane, each a Mallat layout of its own (x0, y0 are then ignored); words outside stay."""
+        dt = np.int32 if reversible else np.float32
+        planes = np.ascontiguousarray(planes, dtype=dt)
+        n, h, w = planes.shape
+        nr = len(regions) if regions else 0
+        rg = (IdwtRegion * max(nr, 1))()
+        for i in range(nr):
+            rg[i].x, rg[i].y, rg[i].w, rg[i].h, rg[i].x0, rg[i].y0 = regions[i]
+        d_in = self.upload(planes)
+        d_out = self.malloc(max(planes.nbytes, 16))
+        try:
+            self._check(self.L.j2k_hip_stage_idwt(self.h, int(reversible), w, h, n, levels, x0, y0, rg if nr else None, nr,
+                                                  d_in, d_out))
+            raw = self.d2h(d_out, planes.nbytes)
+        finally:
+            self.free(d_in)
+            self.free(d_out)
+        return raw.view(dt).reshape(n, h, w)
+
+    def stage_t1_decode(self, plane: np.ndarray, blocks, reversible: bool, kernel: str = "wave") -> np.ndarray:
+        """plane: (H, W) int32 / float32 the blocks are decoded into (what it holds elsewhere stays).  blocks: dicts with
+        rect (x, y, w, h), orient, numbps, npasses, data (codeword bytes) and optionally half_step, roishift.
+        kernel: "wave" (a wavefront per block) or "lanes" (a lane per block, groups of 64 in the order given)."""
+        dt = np.int32 if reversible else np.float32
+        plane = np.ascontiguousarray(plane, dtype=dt)
+        H, W = plane.shape
+        nb = len(blocks)
+        arr = (DecBlock * max(nb, 1))()
+        pos = 0
+        for i, b in enumerate(blocks):
+            arr[i].x, arr[i].y, arr[i].w, arr[i].h = b["rect"]
+            arr[i].orient, arr[i].numbps, arr[i].npasses = b["orient"], b["numbps"], b["npasses"]
+            arr[i].roishift, arr[i].half_step = b.get("roishift", 0), b.get("half_step", 1.0)
+            arr[i].cw_off, arr[i].cw_len = pos, len(b["data"])
+            pos += len(b["data"])
+        cw = np.frombuffer(b"".join(b["data"] for b in blocks) + b"\0", dtype=np.uint8)
+        d = self.upload(plane)
+        try:
+            self._check(self.L.j2k_hip_stage_t1_decode(self.h, {"wave": 0, "lanes": 1}[kernel], int(reversible), d, W, nb, arr,
+                                                       cw.ctypes.data, pos))
+            raw = self.d2h(d, plane.nbytes)
+        finally:
+            self.free(d)
+        return raw.view(dt).reshape(H, W)

@@ -611,7 +611,7 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce)
     uint64_t arena = 0;
     for (uint32_t id = 0; id < g.cblks.size(); ++id) {
         const BlockState &bs = st[id];
-        if (!bs.included || !bs.npasses || !bs.numbps || g.cblks[id].res > top_res || g.cblks[id].comp >= 4) continue; // (components beyond the fourth are parsed, not decoded)
+        if (!bs.included || !t1dec_passes(bs.numbps, bs.npasses) || g.cblks[id].res > top_res || g.cblks[id].comp >= 4) continue; // (components beyond the fourth are parsed, not decoded)
         DecBlock db;
         db.cblk = id; db.numbps = bs.numbps; db.npasses = bs.npasses;
         db.roishift = H.roishift[g.cblks[id].comp];
@@ -624,7 +624,7 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce)
             if (pc.len) P.segs.push_back({pc.src, dst, pc.len});
             dst += pc.len;
         }
-        arena = (dst + 2 + 15) & ~(uint64_t)15; // 2 bytes of slack + 16-byte alignment of the next block
+        arena = cw_arena_next(dst);
         if (multiseg) {
             // (a file cut short may have lost bytes the headers had promised: a segment ends where the block's bytes end)
             db.seg_first = (uint32_t)P.cwsegs.size();
@@ -638,7 +638,7 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce)
         }
         P.blocks.push_back(db);
     }
-    P.arena_bytes = arena + 16;
+    P.arena_bytes = cw_arena_bytes(arena);
     return P;
 }
 

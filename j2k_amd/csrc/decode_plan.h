@@ -7,6 +7,8 @@
 // how many bit-planes / coding passes they hold -- the work list of the Tier-1 decode kernel.  O(#code-blocks).
 #pragma once
 
+#include <algorithm>
+
 #include "geometry.h"
 
 namespace j2k_hip {
@@ -61,6 +63,17 @@ struct DecBlock {
     uint32_t seg_first = 0, nsegs = 0;
     uint32_t roishift = 0;      // numbps counts the region-of-interest shift's planes too (H.1); samples at or above 2^roishift come down by it
 };
+// What the Tier-1 decode kernels are given, stated once for the plan, the decode call and the stage hook:
+//  * the coding passes of a block: never more than the 3 numbps - 2 its bit-planes allow; 0 = the block holds nothing
+//    (no pass or no bit-plane) and is NOT handed to the kernels, whose tables (masks, planes) and plane arithmetic
+//    (t1_assemble: npasses - 1) start at one pass of one bit-plane -- its samples stay as the plane was cleared;
+//  * the codeword arena: a block's bytes start 16-byte aligned, 2 bytes of slack follow them, 16 more close the
+//    arena, and the buffer extends kCwArenaTail bytes past that (the wave-per-block kernel loads whole 256-byte windows).
+inline uint32_t t1dec_passes(uint32_t numbps, uint32_t npasses) { return numbps ? std::min<uint32_t>(npasses, 3 * numbps - 2) : 0; }
+inline uint64_t cw_arena_next(uint64_t end) { return (end + 2 + 15) & ~(uint64_t)15; } // where the next block starts after one that ends at `end`
+inline uint64_t cw_arena_bytes(uint64_t next) { return next + 16; }
+constexpr size_t kCwArenaTail = 512;
+
 struct DecodePlan {
     FileHeader hdr;
     Geometry geo;               // all tiles

@@ -49,6 +49,27 @@ template <typename F> void parallel_rows(int rows, size_t work, F &&fn)
     for (auto &t : th) t.join();
 }
 
+// The lane-per-block Tier-1 kernel's tables (t1_dec_lane.h), for decode_impl and the stage hook alike.  Blocks [0, n) form
+// groups of 64 in their order (one wave each); a group's loop bounds are the maxima over its blocks, its output planes
+// ([plane][stripe 16][8][lane 64] words) one more than the planes its longest block reaches.  Returns the words of all planes.
+size_t lane_groups(const DecBlkDev *blk, size_t n, std::vector<DecGroupDev> &groups)
+{
+    size_t plane_words = 0;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        DecGroupDev &G = groups[gi];
+        G.plane_off = plane_words;
+        for (size_t i = gi * 64; i < std::min(n, gi * 64 + 64); ++i) {
+            G.maxpasses = std::max<unsigned>(G.maxpasses, blk[i].npasses);
+            G.maxstripes = std::max<unsigned>(G.maxstripes, (unsigned)(blk[i].h + 3) / 4);
+        }
+        plane_words += (size_t)((G.maxpasses + 1) / 3 + 1) * 16 * 8 * 64;
+    }
+    return plane_words;
+}
+// per group: 16 x 64 x 64 state words + 16 x 4 x 64 edge words (t1lane::kGroupWords per lane), zero before the launch
+size_t lane_state_bytes(size_t ngroups) { return std::max<size_t>(ngroups, 1) * ((16 * 64 + 16 * 4) * 64) * sizeof(uint32_t); }
+size_t lane_planes_bytes(size_t plane_words) { return round_up(std::max<size_t>(plane_words, 64) * sizeof(uint32_t), 64); }
+
 void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_outplane *planes,
                  uint32_t nplanes, bool planes_on_device)
 {
@@ -149,7 +170,7 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     // The tables are built in their final order straight into the pinned staging buffer: the order comes from sorts of
     // small keys (the file is on the device by now and the launches wait for these tables: 3 ms of sorting and copying
     // whole entries for the 49 152 blocks of an 8K frame, 0.6 ms this way).
-    auto passes_of = [](const DecBlock &b) { return std::min<uint32_t>(b.npasses, b.numbps ? 3 * b.numbps - 2 : 0); };
+    auto passes_of = [](const DecBlock &b) { return t1dec_passes(b.numbps, b.npasses); };
     // lane-per-block Tier-1: the blocks of a wave walk their passes in step, so blocks with the same number of coding
     // passes (then of similar codeword length) share a wave -- every lane of it ends at about the same time.
     // All lane waves are resident at once, so the launch lasts as long as its heaviest block (~8 us per codeword byte of
@@ -248,16 +269,7 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
         fill(0, nb / nt);
         for (auto &t : th) t.join();
     } else fill(0, nb);
-    size_t plane_words = 0;
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        DecGroupDev &G = groups[gi];
-        G.plane_off = plane_words;
-        for (size_t i = nheavy + gi * 64; i < nheavy + std::min(nl, gi * 64 + 64); ++i) {
-            G.maxpasses = std::max<unsigned>(G.maxpasses, dblk[i].npasses);
-            G.maxstripes = std::max<unsigned>(G.maxstripes, (unsigned)(dblk[i].h + 3) / 4);
-        }
-        plane_words += (size_t)((G.maxpasses + 1) / 3 + 1) * 16 * 8 * 64;
-    }
+    const size_t plane_words = lane_groups(dblk + nheavy, nl, groups);
     if (!groups.empty()) std::memcpy(ht + grp_base, groups.data(), groups.size() * sizeof(DecGroupDev));
     uint64_t *h_sdst = reinterpret_cast<uint64_t *>(ht + seg_base), *h_ssrc = h_sdst + nseg;
     uint32_t *h_slen = reinterpret_cast<uint32_t *>(h_ssrc + nseg);
@@ -270,7 +282,7 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     HIP_CHECK(hipEventRecord(e->ev[EV_UPLOAD], s));
 
     // ---- codeword arena
-    e->d_cw.ensure(P.arena_bytes + 512);
+    e->d_cw.ensure(P.arena_bytes + kCwArenaTail);
     if (nseg) {
         GatherArgs ga{};
         uint8_t *dt = e->d_dblk.as<uint8_t>();
@@ -296,8 +308,8 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     ta.cwsegs = reinterpret_cast<const unsigned *>(e->d_dblk.as<uint8_t>() + cwseg_base); ta.style = H.cblk_style;
     if (lanes) {
         // per group: 16 x 64 x 64 state words (zero: nothing significant yet) and the planes' output; then the tail's masks
-        const size_t state_bytes = std::max<size_t>(groups.size(), 1) * ((16 * 64 + 16 * 4) * 64) * sizeof(uint32_t); // t1lane::kGroupWords per lane
-        const size_t planes_bytes = round_up(std::max<size_t>(plane_words, 64) * sizeof(uint32_t), 64);
+        const size_t state_bytes = lane_state_bytes(groups.size());
+        const size_t planes_bytes = lane_planes_bytes(plane_words);
         e->d_masks.ensure(state_bytes + planes_bytes + std::max<size_t>(mask_words, 64) * 8);
         HIP_CHECK(hipMemsetAsync(e->d_masks.p, 0, state_bytes, s));
         T1DecArgs tl = ta;
@@ -632,6 +644,163 @@ int j2k_hip_decode_device(j2k_hip_encoder *e, const void *file, size_t len, uint
 {
     if (!e) return J2K_HIP_ERR_PARAM;
     return guarded(e, [&] { decode_impl(e, file, len, subsample, planes, nplanes, true); });
+}
+
+// ---------------------------------------------------------------------------------------- decode stages (tests)
+int j2k_hip_stage_idwt(j2k_hip_encoder *e, int reversible, uint32_t width, uint32_t height, uint32_t nplanes, uint32_t levels,
+                       uint32_t x0, uint32_t y0, const j2k_hip_idwt_region *regions, uint32_t nregions, const void *d_in, void *d_out)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        if (!width || !height || !nplanes || levels > 32 || !d_in || !d_out || (nregions && !regions)) throw Error(J2K_HIP_ERR_PARAM, "bad inverse DWT stage arguments");
+        const j2k_hip_idwt_region whole{0, 0, width, height, x0, y0};
+        const j2k_hip_idwt_region *rg = nregions ? regions : &whole;
+        const uint32_t nr = nregions ? nregions : 1;
+        for (uint32_t i = 0; i < nr; ++i) {
+            if (!rg[i].w || !rg[i].h || (uint64_t)rg[i].x + rg[i].w > width || (uint64_t)rg[i].y + rg[i].h > height ||
+                (uint64_t)rg[i].x0 + rg[i].w > 0x7fffffffu || (uint64_t)rg[i].y0 + rg[i].h > 0x7fffffffu)
+                throw Error(J2K_HIP_ERR_PARAM, "inverse DWT region outside the plane");
+            for (uint32_t j = 0; j < i; ++j)
+                if (rg[i].x < rg[j].x + rg[j].w && rg[j].x < rg[i].x + rg[i].w && rg[i].y < rg[j].y + rg[j].h && rg[j].y < rg[i].y + rg[i].h)
+                    throw Error(J2K_HIP_ERR_PARAM, "inverse DWT regions overlap");
+        }
+        const size_t plane = (size_t)width * height, bytes = plane * nplanes * 4;
+        e->Q.ensure(bytes);
+        e->geo_valid = false; e->seq_valid = false; // the encode path's job table and planes are overwritten
+        // one job per plane, region and level, as a decode builds them per component, tile and resolution: level l of a region
+        // = its resolution `levels - l` (both edges of the area scaled, then subtracted; the parities of the scaled origin)
+        std::vector<IdwtJob> jobs;
+        std::vector<size_t> first(levels + 1, 0);
+        std::vector<int> mrw(levels, 0), mrh(levels, 0);
+        for (uint32_t l = 0; l < levels; ++l) {
+            first[l] = jobs.size();
+            for (uint32_t c = 0; c < nplanes; ++c)
+                for (uint32_t i = 0; i < nr; ++i) {
+                    const int ax0 = ceildivpow2((int)rg[i].x0, (int)l), ax1 = ceildivpow2((int)(rg[i].x0 + rg[i].w), (int)l);
+                    const int ay0 = ceildivpow2((int)rg[i].y0, (int)l), ay1 = ceildivpow2((int)(rg[i].y0 + rg[i].h), (int)l);
+                    IdwtJob j{};
+                    j.rw = ax1 - ax0; j.rh = ay1 - ay0; j.casx = ax0 & 1; j.casy = ay0 & 1;
+                    if (j.rw <= 0 || j.rh <= 0) continue;
+                    j.off = (long long)(c * plane) + (long long)rg[i].y * width + rg[i].x;
+                    jobs.push_back(j);
+                    mrw[l] = std::max(mrw[l], j.rw); mrh[l] = std::max(mrh[l], j.rh);
+                }
+        }
+        first[levels] = jobs.size();
+        HIP_CHECK(hipMemcpyAsync(d_out, d_in, bytes, hipMemcpyDeviceToDevice, s));
+        if (!jobs.empty()) {
+            e->jobs.ensure(jobs.size() * sizeof(IdwtJob));
+            HIP_CHECK(hipMemcpyAsync(e->jobs.p, jobs.data(), jobs.size() * sizeof(IdwtJob), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s)); // `jobs` is a pageable host vector
+            for (uint32_t l = levels; l-- > 0;) { // lowest resolution first
+                IdwtArgs ia{};
+                ia.a = d_out; ia.tmp = e->Q.p; ia.stride = (long long)width;
+                ia.jobs = e->jobs.as<IdwtJob>() + first[l]; ia.njobs = (int)(first[l + 1] - first[l]);
+                ia.max_rw = mrw[l]; ia.max_rh = mrh[l]; ia.reversible = reversible;
+                launch_idwt_level(ia, s);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int j2k_hip_stage_t1_decode(j2k_hip_encoder *e, int kernel, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                            const j2k_hip_dec_block *blocks, const void *cw, size_t cw_bytes)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        if ((kernel != 0 && kernel != 1) || !d_coef || (nblocks && !blocks)) throw Error(J2K_HIP_ERR_PARAM, "bad Tier-1 decode stage arguments");
+        const uint8_t *bytes = static_cast<const uint8_t *>(cw);
+        {
+            // blocks that share a sample would overwrite each other: sweep over the blocks sorted by their top row
+            std::vector<uint32_t> order(nblocks);
+            for (uint32_t i = 0; i < nblocks; ++i) {
+                const j2k_hip_dec_block &b = blocks[i];
+                if (b.w == 0 || b.h == 0 || b.w > 64 || b.h > 64 || b.orient > 3) throw Error(J2K_HIP_ERR_PARAM, "bad code-block rectangle");
+                if ((uint64_t)b.x + b.w > stride) throw Error(J2K_HIP_ERR_PARAM, "code-block rectangle wider than the plane's stride");
+                if (b.numbps > 30 || b.roishift > 30) throw Error(J2K_HIP_ERR_PARAM, "more bit-planes than a 32-bit sample holds");
+                if (b.cw_len && (!bytes || b.cw_off > cw_bytes || b.cw_len > cw_bytes - b.cw_off)) throw Error(J2K_HIP_ERR_PARAM, "codeword bytes outside the buffer");
+                order[i] = i;
+            }
+            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return blocks[a].y < blocks[b].y; });
+            for (size_t i = 0; i < nblocks; ++i)
+                for (size_t j = i + 1; j < nblocks && blocks[order[j]].y < blocks[order[i]].y + blocks[order[i]].h; ++j) {
+                    const j2k_hip_dec_block &a = blocks[order[i]], &b = blocks[order[j]];
+                    if (a.x < b.x + b.w && b.x < a.x + a.w) throw Error(J2K_HIP_ERR_PARAM, "code-block rectangles overlap");
+                }
+        }
+        // the kernels' table: the blocks that hold something, in the order given (t1dec_passes: the plan's rule and the clamp)
+        std::vector<DecBlkDev> tab;
+        std::vector<uint64_t> src;
+        uint64_t arena = 0;
+        size_t mask_words = 0;
+        for (uint32_t i = 0; i < nblocks; ++i) {
+            const j2k_hip_dec_block &b = blocks[i];
+            const uint32_t np = t1dec_passes(b.numbps, b.npasses);
+            if (!np) continue;
+            DecBlkDev d{};
+            d.cw_off = arena; d.cw_len = b.cw_len;
+            d.mask_off = mask_words;
+            d.coef_off = (unsigned long long)b.y * stride + b.x;
+            d.stepsize = b.half_step;
+            d.w = (unsigned short)b.w; d.h = (unsigned short)b.h; d.npasses = (unsigned short)np;
+            d.orient = (unsigned char)b.orient; d.numbps = (unsigned char)b.numbps; d.roishift = (unsigned char)b.roishift;
+            tab.push_back(d);
+            src.push_back(b.cw_off);
+            arena = cw_arena_next(arena + b.cw_len);
+            mask_words += (size_t)(b.numbps + 1) * 64;
+        }
+        const size_t nb = tab.size();
+        if (!nb) return;
+        const size_t arena_bytes = (size_t)cw_arena_bytes(arena) + kCwArenaTail;
+        std::vector<DecGroupDev> groups(kernel == 1 ? (nb + 63) / 64 : 0);
+        const size_t plane_words = lane_groups(tab.data(), nb, groups);
+        // one pinned buffer: block table | groups | codeword arena.  A decode leaves the arena's slack and tail as they were; here
+        // they are zeros, so that a kernel which took a byte from past a block's end (where the decoder is fed 1-bits) shows.
+        const size_t grp_base = round_up(nb * sizeof(DecBlkDev), 16);
+        const size_t tab_bytes = grp_base + round_up(groups.size() * sizeof(DecGroupDev), 16) + 64;
+        const size_t cw_base = round_up(tab_bytes, 16);
+        e->h_dtab.ensure(cw_base + arena_bytes);
+        uint8_t *ht = e->h_dtab.as<uint8_t>();
+        std::memset(ht, 0, cw_base + arena_bytes);
+        std::memcpy(ht, tab.data(), nb * sizeof(DecBlkDev));
+        if (!groups.empty()) std::memcpy(ht + grp_base, groups.data(), groups.size() * sizeof(DecGroupDev));
+        for (size_t k = 0; k < nb; ++k)
+            if (tab[k].cw_len) std::memcpy(ht + cw_base + tab[k].cw_off, bytes + src[k], tab[k].cw_len);
+        e->d_dblk.ensure(tab_bytes);
+        e->d_cw.ensure(arena_bytes);
+        e->geo_valid = false; e->seq_valid = false;
+        HIP_CHECK(hipMemcpyAsync(e->d_dblk.p, ht, tab_bytes, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(e->d_cw.p, ht + cw_base, arena_bytes, hipMemcpyHostToDevice, s));
+        T1DecArgs ta{};
+        ta.cw = e->d_cw.as<uint8_t>();
+        ta.coef = d_coef; ta.stride = (long long)stride;
+        ta.blks = e->d_dblk.as<DecBlkDev>(); ta.nblks = (int)nb; ta.reversible = reversible;
+        ta.cwsegs = reinterpret_cast<const unsigned *>(e->d_dblk.as<uint8_t>() + grp_base); // (no block has segments of its own)
+        ta.style = 0;
+        if (kernel == 1) {
+            const size_t state_bytes = lane_state_bytes(groups.size()), planes_bytes = lane_planes_bytes(plane_words);
+            e->d_masks.ensure(state_bytes + planes_bytes);
+            HIP_CHECK(hipMemsetAsync(e->d_masks.p, 0, state_bytes, s));
+            ta.state = e->d_masks.as<unsigned>();
+            ta.planes = ta.state + state_bytes / sizeof(uint32_t);
+            ta.groups = reinterpret_cast<const DecGroupDev *>(e->d_dblk.as<uint8_t>() + grp_base);
+            launch_t1_decode_lanes(ta, s);
+        } else {
+            e->d_masks.ensure(std::max<size_t>(mask_words, 64) * 8);
+            ta.masks = e->d_masks.as<unsigned long long>();
+            launch_t1_decode(ta, s);
+        }
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
 }
 
 } // extern "C"

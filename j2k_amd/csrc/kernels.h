@@ -249,6 +249,10 @@ struct T1DecArgs {
     unsigned long long *stats; // diagnostic build (-DT1L_STATS): decisions, wave steps, stripe-passes with work, waves, cycles
 #endif
 };
+// Preconditions of both launchers, per block (not checked on the device; decode_plan.h: t1dec_passes is the one place that
+// establishes them): numbps >= 1 and 1 <= npasses <= 3 numbps - 2.  A block without a pass or a bit-plane is not in the
+// table: t1_assemble's plane arithmetic (npasses - 1) and the (numbps + 1) x 64 mask words start at one pass of one plane.
+// cw_off is 16-byte aligned and 256 readable bytes follow a block's last byte (decode_plan.h: the codeword arena).
 void launch_t1_decode(const T1DecArgs &a, hipStream_t s);
 void launch_t1_decode_lanes(const T1DecArgs &a, hipStream_t s);
 

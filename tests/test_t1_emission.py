@@ -8,6 +8,8 @@ are compared with the CPU oracle."""
 import numpy as np
 import pytest
 
+from t1_families import max_stripes as _max_stripes, random_block as _random_block
+
 pytestmark = pytest.mark.gpu
 
 
@@ -17,33 +19,6 @@ def enc():
     e = api.Encoder(0)
     yield e
     e.close()
-
-
-def _max_stripes(rng, w, h, top):
-    """Odd columns of even stripes carry the top bit-plane, with their first 1 in row (column // 2 + stripe // 2) % 5
-    of the stripe (4 = none); all else lies below it.  Nothing around such a stripe column is significant when the
-    cleanup pass of the top plane reaches it, so it is coded in run-length mode: with the first 1 in row 0 that is
-    RL, UNI, UNI, the sign, then ZC + sign for each of the three rows below -- 10 decisions, the most a lane emits."""
-    blk = rng.integers(0, 1 << (top - 2), size=(h, w))
-    for s in range(0, h, 8):
-        for c in range(1, w, 2):
-            r = (c // 2 + s // 8) % 5
-            if r < 4 and s + 4 <= h:
-                rows = slice(s + r, s + 4)
-                blk[rows, c] = (1 << top) | rng.integers(0, 1 << top, size=blk[rows, c].shape)
-    return blk * np.where(rng.random((h, w)) < 0.5, -1, 1)
-
-
-def _random_block(rng, w, h, kind):
-    if kind == 0:  # dense, Laplacian-like
-        v = np.rint(rng.laplace(0, 200, size=(h, w)))
-    elif kind == 1:  # sparse: a few large values among zeros (long runs of run-length decisions)
-        v = np.where(rng.random((h, w)) < 0.05, rng.integers(-4000, 4000, size=(h, w)), 0)
-    elif kind == 2:  # everything at one magnitude: every lane codes the same number of decisions
-        v = np.full((h, w), 1 << 9) * np.where(rng.random((h, w)) < 0.5, -1, 1)
-    else:  # mixed scales by column
-        v = np.rint(rng.standard_normal((h, w)) * (1 << rng.integers(1, 12, size=(1, w))))
-    return v.astype(np.int64)
 
 
 def _cases(seed):
