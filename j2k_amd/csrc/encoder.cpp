@@ -296,6 +296,9 @@ void t1_counters(T1Args &ta)
                              "with %llu stripes written, sparse halves %llu | sparse sample rounds %llu, scans over the stage limit %llu | "
                              "refinement pass: %llu decisions, stripe pairs written %llu, skipped %llu\n",
                      h[6], h[10], h[14], h[1], h[12], h[0], h[7], h[11], h[15], h[13], h[2], h[8], h[9], h[17], h[16], h[4], h[5]);
+        std::fprintf(stderr, "  cleanup stripes that are all run-length-zero over the block's columns (fills): %llu, cleanup halves whose active stripes are all "
+                             "of that kind: %llu | refinement stripe pairs by refined samples: 0: %llu; 1-63: %llu; 64-447: %llu; 448-511: %llu; 512: %llu\n",
+                     h[48], h[49], h[5], h[50], h[51], h[52], h[53]);
         static const char *const bucket[7] = {"0", "1-2", "3-4", "5-8", "9-16", "17-32", "33-64"};
         for (int t = 0; t < 2; ++t) {
             std::fprintf(stderr, "  %s passes by the busiest column's visited samples (passes / stripes holding one):", t ? "cleanup" : "significance");

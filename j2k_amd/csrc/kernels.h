@@ -139,7 +139,7 @@ struct CblkDev {
     unsigned char pad[2];
 };
 constexpr int kDevMaxPasses = 96;
-constexpr int kT1Counters = 48;         // words behind T1Args::dbg in a J2K_T1_COUNTERS build
+constexpr int kT1Counters = 56;         // words behind T1Args::dbg in a J2K_T1_COUNTERS build
 struct T1Args {
     const void *coef; long long stride; // coefficient buffer, words per row
     const CblkDev *blks; int nblks;     // table of all blocks; this launch handles [first, nblks)

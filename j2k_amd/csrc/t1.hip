@@ -20,8 +20,11 @@
 //            bit-field extracts to form its decision bytes.  In the significance and cleanup passes
 //            a lane's bytes of a stripe are packed in registers (v_perm, selectors from a table by
 //            which rows code something) and ORed as whole words into a zeroed linear LDS stage at
-//            the offset a DPP scan of the per-lane counts gives; the refinement pass scatters its
-//            bytes there.  A 32-row half of a significance / cleanup pass that visits few samples (and has no
+//            the offset a DPP scan of the per-lane counts gives; the refinement pass does the same with
+//            the <= 4 bytes of a stripe column (one v_perm, two words, two stripes per scan).  A cleanup
+//            stripe in which every column is in run-length mode and holds no 1 is w identical bytes:
+//            plain stores, and a half made of such stripes forms no contexts.
+//            A 32-row half of a significance / cleanup pass that visits few samples (and has no
 //            run-length column) is written sample by sample instead: the lanes' bytes per stripe are counted
 //            on the nibbles of the masks, scanned two stripes to a register, and every lane walks its own
 //            visited rows -- the cost follows the samples coded, not the stripes that hold one.
@@ -316,6 +319,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
         if (e > 8) __hip_atomic_fetch_or(wp + 2, __builtin_amdgcn_alignbyte(0u, p2, t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     };
 
+    // the two-word form: cnt <= 4 bytes packed in p0 (zero bytes past the last)
+    auto emit4 = [&](unsigned base, unsigned cnt, unsigned p0) {
+        const unsigned t = 0u - base;
+        const unsigned al = (base + 3u) & ~3u;
+        unsigned *const wp = reinterpret_cast<unsigned *>(stage + al);
+        const int e = (int)(base + cnt) - (int)al;
+        if (cnt != 0 && al != base) __hip_atomic_fetch_or(wp - 1, __builtin_amdgcn_alignbyte(p0, 0u, t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        if (e > 0) __hip_atomic_fetch_or(wp, __builtin_amdgcn_alignbyte(0u, p0, t), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+    };
+
 #ifdef J2K_T1_COUNTERS
     unsigned long long dc[kT1Counters] = {};
 #define DCNT(i) (++dc[i])
@@ -416,45 +429,49 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                 // stripe are handled with bit-parallel arithmetic on the 4-bit row nibbles
                 // (model_wc: which rows are refined and which of them have a significant neighbour -- left / right columns
                 //  rows r-1..r+1, own column r-1, r+1 -- for the whole column at once)
+                // (a later refinement has context 16 whatever its neighbours: the neighbour flag is cleared there once per pass, and
+                //  the decision byte of a row is 0x1c + 2 * flag + 4 * later + bit -- 14 + flag or 16, << 1, | bit -- by additions alone)
                 u64 ref64 = 0, nb64 = 0;
                 if (ns_eff) {
                     const u64 LR = from_left64(sigma) | from_right64(sigma);
-                    nb64 = (sigma << 1) | (sigma >> 1) | LR | (LR << 1) | (LR >> 1);
+                    nb64 = ((sigma << 1) | (sigma >> 1) | LR | (LR << 1) | (LR >> 1)) & ~mu;
                     ref64 = sigma & ~pi;
                 }
                 if constexpr (DIST) nm = dist_sum(ref64, bits, bp, true);
-                // two stripes per round: their per-lane byte counts share one prefix scan (16-bit halves of one register)
-                for (int s = 0; s < ns_eff; s += 2) {
-                    const int sh = 4 * s;
-                    const unsigned ref8 = (unsigned)(ref64 >> sh) & 0xffu; // rows of both stripes refined in this pass
-                    if (!__any(ref8 != 0)) { DCNT(5); continue; }
-                    const unsigned nb8 = (unsigned)(nb64 >> sh) & 0xffu, mu8 = (unsigned)(mu >> sh) & 0xffu, bits8 = (unsigned)(bits >> sh) & 0xffu;
-                    unsigned Wsym[2], excl[2], cnt[2];
+                // two stripes per round: their per-lane byte counts share one prefix scan (16-bit halves of one register).  The
+                // rounds run on one 32-row half of the masks at a time: a stripe's rows are 4-bit fields of single registers
+#pragma unroll 1
+                for (int half = 0; 8 * half < ns_eff; ++half) {
+                    auto hf = [&](u64 m) { return half ? (unsigned)(m >> 32) : (unsigned)m; };
+                    const unsigned refh = hf(ref64), nbh = hf(nb64), muh = hf(mu), bitsh = hf(bits);
+                    const int rows = min(4 * ns_eff - 32 * half, 32);
+                    for (int sl = 0; sl < rows; sl += 8) {
+                        const unsigned ref8 = __builtin_amdgcn_ubfe(refh, (unsigned)sl, 8u); // rows of both stripes refined in this pass
+                        if (!__any(ref8 != 0)) { DCNT(5); continue; }
+                        unsigned pk[2], cnt[2];
 #pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const unsigned ref4 = (ref8 >> (4 * k)) & 0xfu;
-                        // decision byte of row r: first refinement (14 + neighbour) << 1, later (16) << 1, | bit
-                        const unsigned M = spread4((mu8 >> (4 * k)) & 0xfu) * 0xffu;
-                        Wsym[k] = (((0x1c1c1c1cu | (spread4((nb8 >> (4 * k)) & 0xfu) << 1)) & ~M) | (0x20202020u & M)) | spread4((bits8 >> (4 * k)) & 0xfu);
-                        const unsigned cb4 = spread4(ref4);
-                        const unsigned inc = cb4 + (cb4 << 8), inc2 = inc + (inc << 16); // inclusive prefix per byte
-                        excl[k] = inc2 - cb4;
-                        cnt[k] = inc2 >> 24;
+                        for (int k = 0; k < 2; ++k) {
+                            // a stripe's four decision bytes are compacted in registers: one v_perm with the low word of the selector
+                            // table's entry (Vz = ref4, N = 0): "the present rows' bytes in order", zero bytes past the last
+                            const unsigned ref4 = k ? ref8 >> 4 : ref8 & 0xfu;
+                            const unsigned at = (unsigned)(sl + 4 * k);
+                            const unsigned sel = (unsigned)(DIST ? kPackSel.v[ref4] : sel_tab[ref4]);
+                            const unsigned W = 0x1c1c1c1cu + (spread4(__builtin_amdgcn_ubfe(nbh, at, 4u)) << 1) + (spread4(__builtin_amdgcn_ubfe(muh, at, 4u)) << 2) +
+                                               spread4(__builtin_amdgcn_ubfe(bitsh, at, 4u));
+                            pk[k] = __builtin_amdgcn_perm(0u, W, sel);
+                            cnt[k] = (unsigned)__builtin_popcount(ref4);
+                        }
+                        DCNT(4);
+                        unsigned totals;
+                        const unsigned offs = prefix_count_dpp(cnt[0] | (cnt[1] << 16), totals); // (sums < 65536: no carry between the halves)
+                        const unsigned total0 = totals & 0xffffu, total1 = totals >> 16;
+                        const unsigned pend = fill - flushed;
+                        emit4(pend + (offs & 0xffffu), cnt[0], pk[0]);
+                        emit4(pend + total0 + (offs >> 16), cnt[1], pk[1]);
+                        DCNT(total0 + total1 < 64 ? 50 : (total0 + total1 < 448 ? 51 : (total0 + total1 < 512 ? 52 : 53)));
+                        DADD(16, total0 + total1);
+                        commit(total0 + total1);
                     }
-                    DCNT(4);
-                    unsigned totals;
-                    const unsigned offs = prefix_count_dpp(cnt[0] | (cnt[1] << 16), totals); // (sums < 65536: no carry between the halves)
-                    const unsigned total0 = totals & 0xffffu, total1 = totals >> 16;
-                    const unsigned pend = fill - flushed;
-                    const unsigned base0 = pend + (offs & 0xffffu), base1 = pend + total0 + (offs >> 16);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if ((ref8 >> r) & 1u) stage[base0 + ((excl[0] >> (8 * r)) & 0xffu)] = (unsigned char)(Wsym[0] >> (8 * r));
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if ((ref8 >> (4 + r)) & 1u) stage[base1 + ((excl[1] >> (8 * r)) & 0xffu)] = (unsigned char)(Wsym[1] >> (8 * r));
-                    DADD(16, total0 + total1);
-                    commit(total0 + total1);
                 }
                 mu |= ref64; // every row refined in this pass
             } else if (ns_eff) {
@@ -545,6 +562,25 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                     rl = hf(full & ~busy & M0);
                 }
                 const unsigned bitsh = hf(bits), Nh = hf(A) & ~hf(O), Vh = hf(V64); // (N64 = A & ~O: one 64-bit mask less alive through the halves)
+                // ---- run-length fills: a cleanup stripe in which every column of the block is in run-length mode and holds no 1
+                // is w bytes CTX_RL << 1, whatever the contexts say.  Columns that are not of that kind raise the flag at the
+                // stripe's first row; the flags are ORed over the wave as act[] is (once per half), what stays clear is a fill.
+                const bool any_rl = __any(rl != 0);
+                unsigned fills = 0;
+                if (any_rl) {
+                    unsigned nof = Nh | (Nh >> 1);
+                    nof = (nof | (nof >> 2) | ~rl) & 0x11111111u;
+                    int wv = w;
+                    asm volatile("" : "+s"(wv));
+                    if (lane >= wv) nof = 0; // (columns outside the block: no say)
+#define J2K_OR_STEP(ctrl, rmask) nof |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)nof, ctrl, rmask, 0xf, false);
+                    J2K_OR_STEP(0x111, 0xf) J2K_OR_STEP(0x112, 0xf) J2K_OR_STEP(0x114, 0xf) J2K_OR_STEP(0x118, 0xf)
+                    J2K_OR_STEP(0x142, 0xa) J2K_OR_STEP(0x143, 0xc)
+#undef J2K_OR_STEP
+                    fills = active & ~(unsigned)__builtin_amdgcn_readlane((int)nof, 63);
+                    DADD(48, __builtin_popcount(fills));
+                    if (fills == active) DCNT(49);
+                }
                 // ---- sample-wise writing of a sparse half: no stripe loop.  Every lane's bytes per stripe are counted on the
                 // nibbles of V and N, the eight stripes' counts are scanned across the wave two to a register (16-bit fields:
                 // a stripe holds at most 512 bytes), the stripe totals become stripe bases on the scalar unit -- the scan order
@@ -554,7 +590,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                 bool sparse = false;
                 u64 q0 = 0, q1 = 0;
                 unsigned sparse_total = 0;
-                if (a.sparse >= 0 && !__any(rl != 0)) {
+                if (a.sparse >= 0 && !any_rl) {
                     // (rounds = the busiest lane's visited samples: no lane may have more than the break-even allows)
                     const unsigned dense_cost = kDenseStripe * (unsigned)__builtin_popcount(active);
                     if (a.sparse > 0 || !__any(kSparseHead + kSparseRound * (unsigned)__builtin_popcount(Vh) >= dense_cost)) {
@@ -580,52 +616,54 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                         } else DCNT(17);
                     }
                 }
-                // the eight neighbour masks with the timing of the stripe scan: left column new (its row below the stripe
-                // old), right column old (its row above the stripe new), row above new, row below old
-                const unsigned Wm1 = hf(LA << 1), W0 = hf(LA), Wp1 = hf(((LA >> 1) & ~M3) | (LO >> 1));
-                const unsigned Em1 = hf((RO << 1) | ((RA << 1) & M0)), E0 = hf(RO), Ep1 = hf(RO >> 1);
-                const unsigned Up = hf(A << 1), Dn = hf(O >> 1);
-                // ---- zero-coding contexts (Table D.1), bit-sliced: counts of significant horizontal / vertical / diagonal
-                // neighbours, then the table of the block's orientation as boolean expressions -> planes of the context 0..8
-                unsigned zb0, zb1, zb2, zb3;
-                {
-                    unsigned h1 = W0 ^ E0, h2 = W0 & E0, v1 = Up ^ Dn, v2 = Up & Dn; // exactly one / both
-                    if (orient == 1) { const unsigned t1 = h1, t2 = h2; h1 = v1; h2 = v2; v1 = t1; v2 = t2; } // HL: swapped
-                    const unsigned p = Wm1 ^ Wp1, q = Wm1 & Wp1, r_ = Em1 ^ Ep1, t = Em1 & Ep1;
-                    const unsigned dodd = p ^ r_, dge1 = p | q | r_ | t, dge2 = (p & r_) | q | t;
-                    const unsigned deq1 = dodd & ~dge2;
-                    const unsigned hz = ~(h1 | h2), vnz = v1 | v2;
-                    if (orient == 3) { // HH: diagonal count first, then min(h + v, 2)
-                        const unsigned dge3 = (q & (r_ | t)) | (t & p);
-                        const unsigned deq2 = dge2 & ~dge3, deq0 = ~dge1;
-                        const unsigned hv0 = hz & ~vnz, hv1 = (h1 & ~vnz) | (hz & v1), hvge2 = ~(hv0 | hv1);
-                        zb3 = dge3;
-                        zb2 = deq2 | (deq1 & ~hv0);
-                        zb1 = deq2 | (deq1 & hv0) | (deq0 & hvge2);
-                        zb0 = (deq2 & ~hv0) | (deq1 & (hv0 | hvge2)) | (deq0 & hv1);
-                    } else {
-                        zb3 = h2;
-                        zb2 = h1 | (hz & v2);
-                        zb1 = (h1 & (vnz | dge1)) | (hz & (v1 | (~vnz & dge2)));
-                        zb0 = (h1 & (vnz | ~dge1)) | (hz & (v1 | (~vnz & deq1)));
+                // (a half whose active stripes are all fills needs none of the context planes)
+                unsigned zb0 = 0, zb1 = 0, zb2 = 0, zb3 = 0, sb0 = 0, sb1 = 0, sb2 = 0, sd = 0;
+                if (fills != active) {
+                    // the eight neighbour masks with the timing of the stripe scan: left column new (its row below the stripe
+                    // old), right column old (its row above the stripe new), row above new, row below old
+                    const unsigned Wm1 = hf(LA << 1), W0 = hf(LA), Wp1 = hf(((LA >> 1) & ~M3) | (LO >> 1));
+                    const unsigned Em1 = hf((RO << 1) | ((RA << 1) & M0)), E0 = hf(RO), Ep1 = hf(RO >> 1);
+                    const unsigned Up = hf(A << 1), Dn = hf(O >> 1);
+                    // ---- zero-coding contexts (Table D.1), bit-sliced: counts of significant horizontal / vertical / diagonal
+                    // neighbours, then the table of the block's orientation as boolean expressions -> planes of the context 0..8
+                    {
+                        unsigned h1 = W0 ^ E0, h2 = W0 & E0, v1 = Up ^ Dn, v2 = Up & Dn; // exactly one / both
+                        if (orient == 1) { const unsigned t1 = h1, t2 = h2; h1 = v1; h2 = v2; v1 = t1; v2 = t2; } // HL: swapped
+                        const unsigned p = Wm1 ^ Wp1, q = Wm1 & Wp1, r_ = Em1 ^ Ep1, t = Em1 & Ep1;
+                        const unsigned dodd = p ^ r_, dge1 = p | q | r_ | t, dge2 = (p & r_) | q | t;
+                        const unsigned deq1 = dodd & ~dge2;
+                        const unsigned hz = ~(h1 | h2), vnz = v1 | v2;
+                        if (orient == 3) { // HH: diagonal count first, then min(h + v, 2)
+                            const unsigned dge3 = (q & (r_ | t)) | (t & p);
+                            const unsigned deq2 = dge2 & ~dge3, deq0 = ~dge1;
+                            const unsigned hv0 = hz & ~vnz, hv1 = (h1 & ~vnz) | (hz & v1), hvge2 = ~(hv0 | hv1);
+                            zb3 = dge3;
+                            zb2 = deq2 | (deq1 & ~hv0);
+                            zb1 = deq2 | (deq1 & hv0) | (deq0 & hvge2);
+                            zb0 = (deq2 & ~hv0) | (deq1 & (hv0 | hvge2)) | (deq0 & hv1);
+                        } else {
+                            zb3 = h2;
+                            zb2 = h1 | (hz & v2);
+                            zb1 = (h1 & (vnz | dge1)) | (hz & (v1 | (~vnz & dge2)));
+                            zb0 = (h1 & (vnz | ~dge1)) | (hz & (v1 | (~vnz & deq1)));
+                        }
                     }
-                }
-                // ---- sign symbols (Tables D.2 / D.3), bit-sliced: contributions h, v in {-1, 0, +1} as two masks each;
-                // code = context - 9 (|h| = 1: 3, +1 if v agrees, -1 if it disagrees; h = 0: 1 if v != 0 else 0), decision bit =
-                // own sign XOR (h < 0 or (h = 0 and v < 0)); the symbol byte is 18 + 2 * code + decision
-                unsigned sb0 = 0, sb1 = 0, sb2 = 0, sd = 0;
-                if (any_n) {
-                    const unsigned cL = hf(from_left64(chi)), cR = hf(from_right64(chi)), cU = hf(chi << 1), cD = hf(chi >> 1);
-                    const unsigned Wp = W0 & ~cL, Wn = W0 & cL, Ep = E0 & ~cR, En = E0 & cR;
-                    const unsigned Upp = Up & ~cU, Upn = Up & cU, Dnp = Dn & ~cD, Dnn = Dn & cD;
-                    const unsigned hp = (Wp & ~En) | (Ep & ~Wn), hn = (Wn & ~Ep) | (En & ~Wp);
-                    const unsigned vp = (Upp & ~Dnn) | (Dnp & ~Upn), vn = (Upn & ~Dnp) | (Dnn & ~Upp);
-                    const unsigned hnz = hp | hn, vnz = vp | vn;
-                    const unsigned same = (hp & vp) | (hn & vn), opp = (hp & vn) | (hn & vp);
-                    sb2 = same;
-                    sb1 = hnz & ~same;
-                    sb0 = (hnz & ~same & ~opp) | (~hnz & vnz);
-                    sd = hf(chi) ^ (hn | (~hnz & vn));
+                    // ---- sign symbols (Tables D.2 / D.3), bit-sliced: contributions h, v in {-1, 0, +1} as two masks each;
+                    // code = context - 9 (|h| = 1: 3, +1 if v agrees, -1 if it disagrees; h = 0: 1 if v != 0 else 0), decision bit =
+                    // own sign XOR (h < 0 or (h = 0 and v < 0)); the symbol byte is 18 + 2 * code + decision
+                    if (any_n) {
+                        const unsigned cL = hf(from_left64(chi)), cR = hf(from_right64(chi)), cU = hf(chi << 1), cD = hf(chi >> 1);
+                        const unsigned Wp = W0 & ~cL, Wn = W0 & cL, Ep = E0 & ~cR, En = E0 & cR;
+                        const unsigned Upp = Up & ~cU, Upn = Up & cU, Dnp = Dn & ~cD, Dnn = Dn & cD;
+                        const unsigned hp = (Wp & ~En) | (Ep & ~Wn), hn = (Wn & ~Ep) | (En & ~Wp);
+                        const unsigned vp = (Upp & ~Dnn) | (Dnp & ~Upn), vn = (Upn & ~Dnp) | (Dnn & ~Upp);
+                        const unsigned hnz = hp | hn, vnz = vp | vn;
+                        const unsigned same = (hp & vp) | (hn & vn), opp = (hp & vn) | (hn & vp);
+                        sb2 = same;
+                        sb1 = hnz & ~same;
+                        sb0 = (hnz & ~same & ~opp) | (~hnz & vnz);
+                        sd = hf(chi) ^ (hn | (~hnz & vn));
+                    }
                 }
                 if (sparse) {
                     unsigned rest = Vh, pos = 0;
@@ -655,6 +693,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                 while (active) {
                     const int sl = __builtin_ctz(active) & ~3; // first row of the stripe inside the half
                     active &= active - 1;
+                    if ((fills >> sl) & 1u) { // plain stores into the zeroed stage, as the sample-wise path does
+                        int wv = w;
+                        asm volatile("" : "+s"(wv));
+                        if (lane < wv) stage[(fill - flushed) + lane] = (unsigned char)(CTX_RL << 1);
+                        DADD(15, w);
+                        commit((unsigned)w);
+                        continue;
+                    }
                     DCNT(pt == 0 ? 0 : 2);
                     const unsigned bits4 = (bitsh >> sl) & 0xfu;
                     const unsigned N = (Nh >> sl) & 0xfu;
