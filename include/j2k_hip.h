@@ -386,6 +386,25 @@ int j2k_hip_stage_idwt(j2k_hip_encoder *enc, int reversible, uint32_t width, uin
                        const j2k_hip_idwt_region *regions, uint32_t nregions, const void *d_in,
                        void *d_out);
 
+/* The decode's output stage alone (decode_output_kernel: inverse RCT / ICT, DC level shift, clamp, replication of
+ * sub-sampled components, CopyChannel's depth conversion), its arguments filled by the function a decode fills them with.
+ * The image is width x height.  Component c is a plane of ceil(width / sub_x) x ceil(height / sub_y) 32-bit words (int32
+ * for reversible, float32 otherwise) at row stride `stride` words, starting `offset` words into the device buffer d_comp of
+ * comp_words words.  planes[i] receives component i as in j2k_hip_decode, except that planes[i].base is a byte OFFSET into
+ * the device buffer d_buf of buf_bytes bytes; only the channels' samples are written.  Refused with J2K_HIP_ERR_PARAM:
+ * what j2k_hip_decode refuses (sample_bits other than 8 / 16, depth outside 1..sample_bits, precisions outside 1..16,
+ * unlike precision or sub-sampling on components 0..2 with mct), a component plane or a channel that leaves its buffer,
+ * and a 16-bit channel with a sample at an odd address. */
+typedef struct j2k_hip_outcomp {
+    uint64_t offset;     /* of the plane's first word in d_comp, in words */
+    uint32_t prec;       /* the component's precision, 1..16 */
+    uint32_t sub_x, sub_y;
+} j2k_hip_outcomp;
+int j2k_hip_stage_decode_output(j2k_hip_encoder *enc, int reversible, int mct, uint32_t width, uint32_t height,
+                                const void *d_comp, size_t comp_words, uint32_t stride,
+                                const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf, size_t buf_bytes,
+                                const j2k_hip_outplane *planes, uint32_t nplanes);
+
 /* Tier-1 DECODING of `nblocks` code-blocks (default code-block style) into one coefficient plane of 32-bit
  * words (row stride `stride` words; int32 for reversible, float32 otherwise).  kernel = 0: a wavefront per
  * block; 1: a lane per block, the blocks in groups of 64 IN THE ORDER GIVEN.  Codewords are bytes

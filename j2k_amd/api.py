@@ -87,7 +87,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
            "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
-           "j2k_hip_stage_idwt", "j2k_hip_stage_t1_decode",
+           "j2k_hip_stage_idwt", "j2k_hip_stage_t1_decode", "j2k_hip_stage_decode_output",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink"]
 
@@ -100,6 +100,11 @@ class DecBlock(C.Structure):
     """include/j2k_hip.h: j2k_hip_dec_block."""
     _fields_ = [(n, C.c_uint32) for n in ("x", "y", "w", "h", "orient", "numbps", "npasses", "roishift")] + \
                [("half_step", C.c_float), ("cw_len", C.c_uint32), ("cw_off", C.c_uint64)]
+
+
+class OutComp(C.Structure):
+    """include/j2k_hip.h: j2k_hip_outcomp."""
+    _fields_ = [("offset", C.c_uint64), ("prec", C.c_uint32), ("sub_x", C.c_uint32), ("sub_y", C.c_uint32)]
 
 
 class CopySink(C.Structure):
@@ -170,6 +175,8 @@ def load_library():
                                      C.POINTER(IdwtRegion), C.c_uint32, C.c_void_p, C.c_void_p]
     L.j2k_hip_stage_t1_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DecBlock),
                                           C.c_void_p, C.c_size_t]
+    L.j2k_hip_stage_decode_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32,
+                                              C.POINTER(OutComp), C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(OutPlane), C.c_uint32]
     L.j2k_hip_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.j2k_hip_get_dwt_level_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
     L.j2k_hip_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -612,3 +619,41 @@ class Encoder:
         finally:
             self.free(d)
         return raw.view(dt).reshape(H, W)
+
+    def stage_decode_output(self, comps, precs, subs, width: int, height: int, reversible: bool, mct: bool, chans, buf: np.ndarray,
+                            stride: int | None = None, gap: int = 0x7fc0dead) -> np.ndarray:
+        """The decode's output stage alone.  comps: one 2-D plane per component, int32 / float32 (irreversible planes may
+        also come as uint32 bit patterns), of ceil(height / sub_y) x ceil(width / sub_x) samples; precs, subs = [(sub_x,
+        sub_y)]: per component.  They go into one device buffer at row stride `stride` words (default: the widest plane's
+        width); the words between a row's end and the stride hold `gap`.  chans: dicts with base (a byte offset into buf),
+        colbytes, rowbytes, sample_bits, depth, width, height.  buf: the uint8 buffer the channels lie in, uploaded as it
+        is.  Returns the whole buffer as the kernel left it."""
+        dt = np.int32 if reversible else np.float32
+        planes = [np.ascontiguousarray(c).view(np.uint32) if np.asarray(c).dtype == np.uint32 else
+                  np.ascontiguousarray(c, dtype=dt).view(np.uint32) for c in comps]
+        stride = stride if stride is not None else max(p.shape[1] for p in planes)
+        rows = [p.shape[0] for p in planes]
+        words = np.full((sum(rows), max(stride, 1)), gap, dtype=np.uint32)
+        oc = (OutComp * len(planes))()
+        y0 = 0
+        for c, p in enumerate(planes):
+            words[y0:y0 + p.shape[0], :min(p.shape[1], stride)] = p[:, :stride]
+            oc[c].offset, oc[c].prec = y0 * stride, precs[c]
+            oc[c].sub_x, oc[c].sub_y = subs[c]
+            y0 += p.shape[0]
+        arr = (OutPlane * len(chans))()
+        for c, ch in enumerate(chans):
+            arr[c].base = ch["base"]
+            arr[c].colbytes, arr[c].rowbytes = ch["colbytes"], ch["rowbytes"]
+            arr[c].sample_bits, arr[c].depth = ch["sample_bits"], ch["depth"]
+            arr[c].width, arr[c].height = ch["width"], ch["height"]
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        d_comp = self.upload(words)
+        d_buf = self.upload(buf)
+        try:
+            self._check(self.L.j2k_hip_stage_decode_output(self.h, int(reversible), int(mct), width, height, d_comp, words.size, stride,
+                                                           oc, len(planes), d_buf, buf.nbytes, arr, len(chans)))
+            return self.d2h(d_buf, buf.nbytes)
+        finally:
+            self.free(d_comp)
+            self.free(d_buf)

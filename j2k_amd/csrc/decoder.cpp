@@ -70,6 +70,47 @@ size_t lane_groups(const DecBlkDev *blk, size_t n, std::vector<DecGroupDev> &gro
 size_t lane_state_bytes(size_t ngroups) { return std::max<size_t>(ngroups, 1) * ((16 * 64 + 16 * 4) * 64) * sizeof(uint32_t); }
 size_t lane_planes_bytes(size_t plane_words) { return round_up(std::max<size_t>(plane_words, 64) * sizeof(uint32_t), 64); }
 
+// The output stage's arguments, for decode_impl and the stage hook alike: everything launch_decode_output reads except
+// dst[] (where the channels lie on the device is the caller's: a decode lays out spans, the hook has one buffer).
+// Enforces kernels.h's preconditions on what it is given; the component planes' and the channels' extents are the caller's.
+struct OutComp { const void *plane; uint32_t prec, sub_x, sub_y; };
+void check_outplane(const j2k_hip_outplane &p)
+{
+    if (p.sample_bits != 8 && p.sample_bits != 16) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8 or 16");
+    if (p.depth < 1 || p.depth > p.sample_bits) throw Error(J2K_HIP_ERR_PARAM, "channel depth does not fit its sample type");
+}
+DecOutArgs decode_output_args(bool reversible, bool mct, int width, int height, long long stride, const OutComp *comps, uint32_t ncomp,
+                              const j2k_hip_outplane *planes, uint32_t nplanes)
+{
+    if (ncomp < 1 || ncomp > 4 || !planes || nplanes < 1 || nplanes > 4) throw Error(J2K_HIP_ERR_PARAM, "1..4 components and destination channels");
+    for (uint32_t c = 0; c < ncomp; ++c) {
+        if (comps[c].prec < 1 || comps[c].prec > 16) throw Error(J2K_HIP_ERR_PARAM, "component precision outside 1..16");
+        if (comps[c].sub_x < 1 || comps[c].sub_x > 255 || comps[c].sub_y < 1 || comps[c].sub_y > 255) throw Error(J2K_HIP_ERR_PARAM, "sub-sampling factor outside 1..255");
+    }
+    if (mct && ncomp < 3) throw Error(J2K_HIP_ERR_PARAM, "component transform on fewer than 3 components");
+    if (mct)
+        for (int c = 1; c < 3; ++c)
+            if (comps[c].prec != comps[0].prec || comps[c].sub_x != comps[0].sub_x || comps[c].sub_y != comps[0].sub_y)
+                throw Error(J2K_HIP_ERR_PARAM, "component transform on components of unlike precision or sub-sampling");
+    DecOutArgs oa{};
+    oa.stride = stride; oa.ncomp = (int)ncomp; oa.width = width; oa.height = height; oa.prec = (int)comps[0].prec;
+    oa.reversible = reversible; oa.mct = mct;
+    for (int c = 0; c < 4; ++c) { oa.cprec[c] = (int)comps[0].prec; oa.sub_x[c] = oa.sub_y[c] = 1; }
+    for (uint32_t c = 0; c < ncomp; ++c) {
+        oa.comp[c] = comps[c].plane;
+        oa.cprec[c] = (int)comps[c].prec; oa.sub_x[c] = (int)comps[c].sub_x; oa.sub_y[c] = (int)comps[c].sub_y;
+    }
+    oa.nout = (int)std::min<uint32_t>(nplanes, ncomp); // reference: min(image->numcomps, channels), :532 and CopyBuffer's loop
+    for (int c = 0; c < oa.nout; ++c) {
+        const j2k_hip_outplane &p = planes[c];
+        check_outplane(p);
+        oa.colbytes[c] = p.colbytes; oa.rowbytes[c] = p.rowbytes;
+        oa.dst_bytes[c] = (int)p.sample_bits / 8; oa.dst_depth[c] = (int)p.depth;
+        oa.dst_w[c] = (int)std::min<uint32_t>(p.width, (uint32_t)width); oa.dst_h[c] = (int)std::min<uint32_t>(p.height, (uint32_t)height);
+    }
+    return oa;
+}
+
 void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_outplane *planes,
                  uint32_t nplanes, bool planes_on_device)
 {
@@ -138,10 +179,8 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     }
     const size_t stride = round_up((size_t)ow, 64), plane_elems = stride * (size_t)oh;
     for (uint32_t c = 0; c < nplanes; ++c) {
-        const j2k_hip_outplane &p = planes[c];
-        if (!p.base) throw Error(J2K_HIP_ERR_PARAM, "destination channel buffer is NULL");
-        if (p.sample_bits != 8 && p.sample_bits != 16) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8 or 16");
-        if (p.depth < 1 || p.depth > p.sample_bits) throw Error(J2K_HIP_ERR_PARAM, "channel depth does not fit its sample type");
+        if (!planes[c].base) throw Error(J2K_HIP_ERR_PARAM, "destination channel buffer is NULL");
+        check_outplane(planes[c]);
     }
 
     // ---- tables to the device
@@ -392,13 +431,9 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     HIP_CHECK(hipEventRecord(e->ev[EV_DWT], s));
 
     // ---- output stage
-    DecOutArgs oa{};
-    for (uint32_t c = 0; c < nd; ++c) oa.comp[c] = e->Z.as<int32_t>() + c * plane_elems;
-    oa.stride = (long long)stride; oa.ncomp = (int)nd; oa.width = ow; oa.height = oh; oa.prec = (int)cod.prec;
-    oa.reversible = cod.reversible; oa.mct = cod.mct;
-    for (int c = 0; c < 4; ++c) { oa.cprec[c] = (int)cod.prec; oa.sub_x[c] = oa.sub_y[c] = 1; }
-    for (uint32_t c = 0; c < nd; ++c) { oa.cprec[c] = cod.cprec[c]; oa.sub_x[c] = cod.cdx[c]; oa.sub_y[c] = cod.cdy[c]; }
-    oa.nout = (int)std::min<uint32_t>(nplanes, nd); // reference: min(image->numcomps, channels), :532 and CopyBuffer's loop
+    OutComp oc[4] = {};
+    for (uint32_t c = 0; c < nd; ++c) oc[c] = OutComp{e->Z.as<int32_t>() + c * plane_elems, cod.cprec[c], cod.cdx[c], cod.cdy[c]};
+    DecOutArgs oa = decode_output_args(cod.reversible, cod.mct, ow, oh, (long long)stride, oc, nd, planes, nplanes);
     // The destination channels' extents in the caller's address space.  Channels whose extents overlap (the samples of
     // interleaved pixels) form one span that keeps its layout on the device; channels that lie apart (planar buffers,
     // wherever they were allocated) are spans of their own.
@@ -410,9 +445,6 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
         int ne = 0;
         for (int c = 0; c < oa.nout; ++c) {
             const j2k_hip_outplane &p = planes[c];
-            oa.colbytes[c] = p.colbytes; oa.rowbytes[c] = p.rowbytes;
-            oa.dst_bytes[c] = (int)p.sample_bits / 8; oa.dst_depth[c] = (int)p.depth;
-            oa.dst_w[c] = (int)std::min<uint32_t>(p.width, (uint32_t)ow); oa.dst_h[c] = (int)std::min<uint32_t>(p.height, (uint32_t)oh);
             if (oa.dst_w[c] <= 0 || oa.dst_h[c] <= 0) continue;
             const uint8_t *b = static_cast<const uint8_t *>(p.base);
             const uint8_t *corners[4] = {b, b + (ptrdiff_t)(oa.dst_h[c] - 1) * p.rowbytes, b + (ptrdiff_t)(oa.dst_w[c] - 1) * p.colbytes,
@@ -704,6 +736,46 @@ int j2k_hip_stage_idwt(j2k_hip_encoder *e, int reversible, uint32_t width, uint3
                 HIP_CHECK(hipGetLastError());
             }
         }
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int j2k_hip_stage_decode_output(j2k_hip_encoder *e, int reversible, int mct, uint32_t width, uint32_t height, const void *d_comp,
+                                size_t comp_words, uint32_t stride, const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf,
+                                size_t buf_bytes, const j2k_hip_outplane *planes, uint32_t nplanes)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        if (!width || !height || width > (1u << 30) || height > (1u << 30) || !stride || !d_comp || !comps || !d_buf || !planes)
+            throw Error(J2K_HIP_ERR_PARAM, "bad output stage arguments");
+        for (uint32_t c = 0; c < nplanes && c < 4; ++c) check_outplane(planes[c]); // (a decode checks the channels beyond its components too)
+        OutComp oc[4] = {};
+        for (uint32_t c = 0; c < ncomp && c < 4; ++c)
+            oc[c] = OutComp{static_cast<const uint32_t *>(d_comp) + comps[c].offset, comps[c].prec, comps[c].sub_x, comps[c].sub_y};
+        DecOutArgs oa = decode_output_args(reversible != 0, mct != 0, (int)width, (int)height, (long long)stride, oc, ncomp, planes, nplanes);
+        // every word the kernel reads lies in the component buffer ...
+        for (uint32_t c = 0; c < ncomp; ++c) {
+            const uint64_t cw = (width + comps[c].sub_x - 1) / comps[c].sub_x, ch = (height + comps[c].sub_y - 1) / comps[c].sub_y;
+            if (cw > stride || comps[c].offset > comp_words || (ch - 1) * (uint64_t)stride + cw > comp_words - comps[c].offset)
+                throw Error(J2K_HIP_ERR_PARAM, "component plane outside the buffer");
+        }
+        // ... and every sample it writes in the channel buffer, 16-bit ones at even addresses
+        for (int c = 0; c < oa.nout; ++c) {
+            if (oa.dst_w[c] <= 0 || oa.dst_h[c] <= 0) continue;
+            const __int128 base = (__int128)reinterpret_cast<uintptr_t>(planes[c].base);
+            const __int128 dx = (__int128)(oa.dst_w[c] - 1) * oa.colbytes[c], dy = (__int128)(oa.dst_h[c] - 1) * oa.rowbytes[c];
+            const __int128 lo = base + std::min<__int128>(dx, 0) + std::min<__int128>(dy, 0);
+            const __int128 hi = base + std::max<__int128>(dx, 0) + std::max<__int128>(dy, 0) + oa.dst_bytes[c];
+            if (lo < 0 || hi > (__int128)buf_bytes) throw Error(J2K_HIP_ERR_PARAM, "destination channel outside the buffer");
+            oa.dst[c] = static_cast<uint8_t *>(d_buf) + (size_t)base;
+            if (oa.dst_bytes[c] == 2 && ((reinterpret_cast<uintptr_t>(oa.dst[c]) & 1) || (oa.dst_w[c] > 1 && (oa.colbytes[c] & 1)) || (oa.dst_h[c] > 1 && (oa.rowbytes[c] & 1))))
+                throw Error(J2K_HIP_ERR_PARAM, "16-bit destination channel at an odd address");
+        }
+        launch_decode_output(oa, s);
+        HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));
     });
 }

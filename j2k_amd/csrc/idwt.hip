@@ -15,6 +15,7 @@
 #include "kernels.h"
 
 #include <algorithm>
+#include <climits>
 #include <type_traits>
 
 namespace j2k_hip {
@@ -192,6 +193,17 @@ __device__ __forceinline__ unsigned depth_out(unsigned v, int src_depth, int dst
     return (t << second) | (t >> ((int)pd - second));
 }
 
+// lrintf with libopenjp2's explicit limits (opj_lrintf behind comparisons against +-2^31): a float below -2^31 and NaN give
+// the lowest value, one at or above 2^31 the highest, everything between rounds to nearest even.  The cast is reached by
+// in-range values only, so no bit pattern's result depends on what the compiler makes of an out-of-range conversion; the
+// clamp behind the DC offset turns the two ends into 0 and 2^prec - 1.
+__device__ __forceinline__ int sat_lrintf(float f)
+{
+    if (!(f >= -2147483648.0f)) return INT_MIN;
+    if (f >= 2147483648.0f) return INT_MAX;
+    return (int)__builtin_rintf(f);
+}
+
 template <bool REV>
 __global__ __launch_bounds__(256) void decode_output_kernel(DecOutArgs a)
 {
@@ -228,7 +240,7 @@ __global__ __launch_bounds__(256) void decode_output_kernel(DecOutArgs a)
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const long long t = (long long)__float2int_rn(f[c]) + (1 << (a.cprec[c] - 1)); // lrintf; out-of-range floats saturate and are clamped below
+            const long long t = (long long)sat_lrintf(f[c]) + (1 << (a.cprec[c] - 1));
             v[c] = (int)min(max(t, 0LL), (long long)((1 << a.cprec[c]) - 1));
         }
     }

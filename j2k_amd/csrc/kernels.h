@@ -281,6 +281,14 @@ struct DecOutArgs {
     uint8_t *dst[4]; long long colbytes[4], rowbytes[4];
     int dst_bytes[4], dst_depth[4], dst_w[4], dst_h[4];
 };
+// Preconditions (not checked on the device; decoder.cpp: decode_output_args is the one place that fills the struct, for a
+// decode and for the stage hook alike):
+//   * 1 <= ncomp <= 4, nout <= ncomp; with mct, ncomp >= 3 and components 0..2 share precision and sub-sampling factors;
+//   * cprec[c] in 1..16, sub_x[c] and sub_y[c] >= 1; comp[c] holds ceil(width / sub_x[c]) x ceil(height / sub_y[c]) words at
+//     row stride `stride` (every component of ncomp is read, whether or not a channel receives it);
+//   * dst_bytes[c] is 1 or 2 and 1 <= dst_depth[c] <= 8 * dst_bytes[c]; dst_w[c] <= width, dst_h[c] <= height;
+//   * dst[c] + y * rowbytes[c] + x * colbytes[c] is writable for x < dst_w[c], y < dst_h[c], and 2-byte aligned where
+//     dst_bytes[c] is 2 (16-bit samples go out as one store).
 void launch_decode_output(const DecOutArgs &a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------

@@ -125,6 +125,10 @@ int j2ko_t1_decode_block(const uint8_t *data, size_t len, int w, int h, int orie
  * the 9/7 synthesis scales the low band by K and the high band by 2/K like libopenjp2's decoder). */
 void j2ko_idwt53(int32_t *a, int w, int h, int stride, int x0, int y0, int levels);
 void j2ko_idwt97(float *a, int w, int h, int stride, int x0, int y0, int levels);
+/* The tail of a tile's decode, in place (what j2ko_decode runs on every tile): inverse RCT / ICT on components 0..2 when
+ * `mct`, DC level shift, saturating float conversion (irreversible; NaN gives the lowest value) and clamp to
+ * [0, 2^prec[c] - 1].  planes[c] = n[c] words, int32 or float32 bit patterns in, int32 samples out. */
+void j2ko_decode_output(int32_t *const planes[], int ncomp, const size_t n[], const int prec[], int reversible, int mct);
 /* Codec::CopyBuffer towards the host's buffer (src/common/j2k_codec.cpp:222-427, DESTTYPE = unsigned char / short). */
 void j2ko_copy_channel_out(uint8_t *dst, int dst_bytes, int dst_depth, ptrdiff_t colbytes, ptrdiff_t rowbytes, int width,
                            int height, const int32_t *src, int src_stride, int src_depth);

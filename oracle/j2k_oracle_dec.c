@@ -674,6 +674,50 @@ static int read_tile_packets(const dhdr_t *H, dres_t **comps, const uint8_t *p, 
     return 0;
 }
 
+/* The tail of a tile's decode, in place: inverse RCT / ICT on components 0..2 (mct; libopenjp2's constants and order of
+ * operations, every product and sum rounded to float), then per component the DC level shift and the clamp to
+ * [0, 2^prec[c] - 1].  planes[c] holds n[c] words: int32 when reversible, float32 bit patterns otherwise, unsigned int32
+ * samples afterwards.  The float conversion is libopenjp2's: above 2^31 - 1 (as a float: 2^31) the highest value, below
+ * -2^31 the lowest, lrintf (to nearest even) between.  NaN compares false with both limits and reaches lrintf there,
+ * whose result for it is the host's; an x86-64 build of libopenjp2 yields the lowest value, which is stated here
+ * explicitly. */
+void j2ko_decode_output(int32_t *const planes[], int ncomp, const size_t n[], const int prec[], int reversible, int mct)
+{
+    if (mct && ncomp >= 3) {
+        if (reversible) {
+            for (size_t i = 0; i < n[0]; i++) {
+                const int32_t y = planes[0][i], u = planes[1][i], v = planes[2][i];
+                const int32_t g = y - ((u + v) >> 2);
+                planes[0][i] = v + g; planes[1][i] = g; planes[2][i] = u + g;
+            }
+        } else {
+            float *c0 = (float *)planes[0], *c1 = (float *)planes[1], *c2 = (float *)planes[2];
+            for (size_t i = 0; i < n[0]; i++) {
+                const float y = c0[i], u = c1[i], v = c2[i];
+                volatile float t1, t2;
+                t1 = v * 1.402f; const float r = y + t1;
+                t1 = u * 0.34413f; t2 = v * 0.71414f; float g = y - t1; g = g - t2;
+                t1 = u * 1.772f; const float b = y + t1;
+                c0[i] = r; c1[i] = g; c2[i] = b;
+            }
+        }
+    }
+    for (int c = 0; c < ncomp; c++) {
+        const int dc = 1 << (prec[c] - 1), vmax = (1 << prec[c]) - 1;
+        for (size_t i = 0; i < n[c]; i++) {
+            int64_t v;
+            if (reversible) v = (int64_t)planes[c][i] + dc;
+            else {
+                float f; memcpy(&f, &planes[c][i], 4);
+                if (f != f) v = 0;
+                else if (f > 2147483647.0f) v = vmax; else if (f < -2147483648.0f) v = 0;
+                else v = (int64_t)lrintf(f) + dc;
+            }
+            planes[c][i] = (int32_t)(v < 0 ? 0 : (v > vmax ? vmax : v));
+        }
+    }
+}
+
 /* decode one tile into out (ncomp planes of ow x oh, the reduced image) */
 static int decode_tile(const dhdr_t *H, int tileno, const uint8_t *data, size_t len, int reduce, int32_t *out, int ow, int oh)
 {
@@ -725,40 +769,14 @@ static int decode_tile(const dhdr_t *H, int tileno, const uint8_t *data, size_t 
         else j2ko_idwt97((float *)planes[c], w, h, w, top->x0, top->y0, R);
     }
     if (rc == 0) {
-        const int dc = 1 << (H->prec - 1), vmax = (1 << H->prec) - 1;
-        const size_t n = (size_t)w * (size_t)h;
-        if (H->mct && H->ncomp >= 3) {
-            if (H->reversible) {
-                for (size_t i = 0; i < n; i++) {
-                    const int32_t y = planes[0][i], u = planes[1][i], v = planes[2][i];
-                    const int32_t g = y - ((u + v) >> 2);
-                    planes[0][i] = v + g; planes[1][i] = g; planes[2][i] = u + g;
-                }
-            } else {
-                float *c0 = (float *)planes[0], *c1 = (float *)planes[1], *c2 = (float *)planes[2];
-                for (size_t i = 0; i < n; i++) {
-                    const float y = c0[i], u = c1[i], v = c2[i];
-                    volatile float t1, t2;
-                    t1 = v * 1.402f; const float r = y + t1;
-                    t1 = u * 0.34413f; t2 = v * 0.71414f; float g = y - t1; g = g - t2;
-                    t1 = u * 1.772f; const float b = y + t1;
-                    c0[i] = r; c1[i] = g; c2[i] = b;
-                }
-            }
-        }
+        const size_t n[4] = {(size_t)w * (size_t)h, (size_t)w * (size_t)h, (size_t)w * (size_t)h, (size_t)w * (size_t)h};
+        const int prec[4] = {H->prec, H->prec, H->prec, H->prec};
+        j2ko_decode_output(planes, H->ncomp, n, prec, H->reversible, H->mct && H->ncomp >= 3);
         const int ox = cdp2(tx0, reduce), oy = cdp2(ty0, reduce);
         for (int c = 0; c < H->ncomp; c++)
             for (int y = 0; y < h && oy + y < oh; y++)
-                for (int x = 0; x < w && ox + x < ow; x++) {
-                    int64_t v;
-                    if (H->reversible) v = (int64_t)planes[c][(size_t)y * w + x] + dc;
-                    else {
-                        float f; memcpy(&f, &planes[c][(size_t)y * w + x], 4);
-                        if (f > 2147483647.0f) v = vmax; else if (f < -2147483648.0f) v = 0;
-                        else v = (int64_t)lrintf(f) + dc;
-                    }
-                    out[((size_t)c * oh + (size_t)(oy + y)) * ow + ox + x] = (int32_t)(v < 0 ? 0 : (v > vmax ? vmax : v));
-                }
+                for (int x = 0; x < w && ox + x < ow; x++)
+                    out[((size_t)c * oh + (size_t)(oy + y)) * ow + ox + x] = planes[c][(size_t)y * w + x];
     }
     for (int c = 0; c < H->ncomp; c++) { free(planes[c]); if (comps[c]) { free_tilecomp(H, comps[c]); free(comps[c]); } }
     return rc;

@@ -108,6 +108,8 @@ class Oracle:
         L.j2ko_copy_channel_out.restype = None
         L.j2ko_copy_channel_out.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_ssize_t, C.c_ssize_t, C.c_int, C.c_int,
                                             C.POINTER(C.c_int32), C.c_int, C.c_int]
+        L.j2ko_decode_output.restype = None
+        L.j2ko_decode_output.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int, C.c_int]
         self.L = L
 
     # -- decode path ------------------------------------------------------------------------------
@@ -146,6 +148,20 @@ class Oracle:
         out = np.empty((h, w), dtype=np.int32)
         self.L.j2ko_t1_decode_block(_u8p(buf), len(data), w, h, orient, numbps, npasses, _i32p(out))
         return out
+
+    def decode_output(self, comps, precs, reversible: bool, mct: bool) -> list:
+        """The tail of a tile's decode (j2ko_decode_output): comps = one 2-D plane per component, int32 (reversible) or
+        float32, each of its own shape (components 0..2 alike when mct); precs = their precisions.  Returns the int32
+        samples, one plane per component."""
+        dt = np.int32 if reversible else np.float32
+        work = [np.array(c, dtype=dt, order="C", copy=True) for c in comps]
+        assert 1 <= len(work) <= 4 and len(precs) == len(work) and all(1 <= p <= 16 for p in precs)
+        if mct:
+            assert len(work) >= 3 and work[0].shape == work[1].shape == work[2].shape
+        ptrs = (C.c_void_p * len(work))(*[w.ctypes.data for w in work])
+        n = (C.c_size_t * len(work))(*[w.size for w in work])
+        self.L.j2ko_decode_output(ptrs, len(work), n, (C.c_int * len(work))(*precs), int(reversible), int(mct))
+        return [w.view(np.int32) for w in work]
 
     def copy_channel_out(self, src: np.ndarray, src_depth: int, dst_bytes: int, dst_depth: int, colbytes: int, rowbytes: int,
                          width: int, height: int) -> np.ndarray:
