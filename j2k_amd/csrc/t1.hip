@@ -145,6 +145,23 @@ __device__ __forceinline__ void transpose_stage(unsigned (&m)[32])
     }
 }
 
+// A coefficient word as the coder sees it: the magnitude of the sample scaled to kFrac fractional bits (9/7: the quotient
+// by the step size, rounded once more to an integer of 1/64 steps, as the oracle's quantiser does; 5/3: the integer
+// shifted up) and its sign as 0 / 1
+template <bool REV>
+__device__ __forceinline__ unsigned scaled_magnitude(unsigned word, float stepsize, unsigned &neg)
+{
+    if constexpr (REV) {
+        const int c = (int)word;
+        neg = (unsigned)c >> 31;
+        return (unsigned)(c < 0 ? -c : c) << kFrac;
+    } else {
+        const int t = __float2int_rn(__fmul_rn(__fdiv_rn(__uint_as_float(word), stepsize), 64.0f));
+        neg = (unsigned)t >> 31;
+        return (unsigned)(t < 0 ? -t : t);
+    }
+}
+
 // (7 waves per SIMD = 72 VGPRs: what the pass loops need; the one-off transposition of the magnitudes would take 98 and
 //  spills a few registers instead -- outside every loop)
 #ifndef J2K_MODEL_WAVES
@@ -153,8 +170,9 @@ __device__ __forceinline__ void transpose_stage(unsigned (&m)[32])
 template <bool REV, bool DIST>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WAVES, J2K_MODEL_WAVES))) void t1_model_kernel(T1Args a)
 {
-    // The block's scaled magnitudes are written back in place (the coefficient buffer is dead after Tier-1) and each
-    // bit-plane is re-read from L2: no 16 KiB of magnitudes in LDS per wave, 2.5x the occupancy.
+    // The block's scaled magnitudes go back into its own area of the coefficient buffer (dead after Tier-1) -- as
+    // transposed bit-planes, or as they are for heights other than 64 and 32 -- and each bit-plane is re-read from L2:
+    // no 16 KiB of magnitudes in LDS per wave, 2.5x the occupancy.
     // DIST (rate control): the six bit-planes below the current one, which the distortion estimates of its passes
     // look at, wait in LDS (plane q of the magnitudes in slot q % 6; one new plane per bit-plane of the scan).
     __shared__ u64 win[DIST ? 6 * 64 : 1];
@@ -178,58 +196,71 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
     // ---- A7: load the block (coalesced rows), scale to sign-magnitude with 6 fractional bits
     u64 chi = 0;
     unsigned mx = 0;
-    // Full 64 x 64 blocks without distortion sums: the magnitudes written back by the loop below are then TRANSPOSED --
-    // 32 rows at a time sit in 32 registers, a 32 x 32 bit-matrix transpose (5 butterfly stages) turns them into one
-    // word per bit-plane (bit r = that plane's bit of row r), and the words of planes kFrac .. kFrac+25 go to rows
-    // 0..25 (upper half of the column) and 32..57 (lower half) of the block's own area.  A bit-plane of the column is
-    // then two coalesced loads instead of 64 loads and 64 bit extractions (and 16 KiB of traffic) per plane.
+    // Rows are addressed as a wave-uniform row pointer (advanced by the stride on the scalar unit) plus the lane: no
+    // per-row address arithmetic on the vector unit.
+    unsigned *const blk0 = const_cast<unsigned *>(reinterpret_cast<const unsigned *>(a.coef)) + cb.coef_off;
+    const long long stride = a.stride;
+    // Blocks of 64 or 32 rows, one 32-row half at a time: the 32 rows of a column are loaded into 32 registers, scaled
+    // there, a 32 x 32 bit-matrix transpose (5 butterfly stages) turns them into one word per bit-plane (bit r = that
+    // plane's bit of row r), and the words of planes kFrac .. kFrac+25 go to rows 0..25 (upper half of the column) and
+    // 32..57 (lower half) of the block's own area (the coefficient buffer is dead after Tier-1).  The magnitudes
+    // themselves are never stored.  A bit-plane of the column is then two coalesced loads: no 16 KiB of magnitudes in
+    // LDS per wave, 2.5x the occupancy.  (Every plane word depends on all 32 rows of its half, so the rows are read
+    // before the first word lands on one of them; lanes beyond w hold other blocks' samples and neither load nor store.)
     // With distortion sums all 32 planes are kept (plane q in rows q and 32 + q): the estimates read the fractional bits.
     constexpr int kPlane0 = DIST ? 0 : kFrac, kPlaneRows = DIST ? 32 : 26;
     // Blocks of 32 rows (the 32 x 32 blocks of the cinema profiles) have one such half: 32 rows, 32 plane words.
     const bool planes_stored = h == 64 || h == 32;
     const int halves = h >> 5;
-    for (int y = 0; y < h; ++y) {
-        unsigned m = 0;
-        bool neg = false;
-        if (lane < w) {
-            const unsigned long long idx = cb.coef_off + (unsigned long long)y * (unsigned long long)a.stride + lane;
-            if (REV) {
-                const int c = reinterpret_cast<const int *>(a.coef)[idx];
-                neg = c < 0;
-                m = (unsigned)(neg ? -c : c) << kFrac;
-            } else {
-                const float f = reinterpret_cast<const float *>(a.coef)[idx];
-                const int t = __float2int_rn(__fmul_rn(__fdiv_rn(f, cb.stepsize), 64.0f));
-                neg = t < 0;
-                m = (unsigned)(neg ? -t : t);
-            }
-        }
-        if (lane < w) // in place: magnitude (bit 31 is never used: |q| < 2^31)
-            const_cast<unsigned *>(reinterpret_cast<const unsigned *>(a.coef))[cb.coef_off + (unsigned long long)y * (unsigned long long)a.stride + lane] = m;
-        chi |= (u64)neg << y;
-        mx = max(mx, m);
-    }
-    if (planes_stored) { // second sweep over the magnitudes just written: 32 rows -> 32 plane words, twice
-        unsigned *const area = const_cast<unsigned *>(reinterpret_cast<const unsigned *>(a.coef)) + cb.coef_off + lane;
+    if (planes_stored) {
+        unsigned mxl = 0;
 #pragma unroll 1
         for (int half = 0; half < halves; ++half) {
-            unsigned m[32];
+            unsigned *const half0 = blk0 + (long long)(32 * half) * stride;
+            unsigned neg = 0;
+            if (lane < w) {
+                unsigned m[32];
+                const unsigned *rp = half0;
 #pragma unroll
-            for (int i = 0; i < 32; ++i) {
-                if ((i & 7) == 0) __builtin_amdgcn_sched_barrier(0); // eight row loads in flight at a time
-                m[i] = lane < w ? area[(unsigned long long)(32 * half + i) * (unsigned long long)a.stride] : 0u;
-            }
-            transpose_stage<16, 0x0000ffffu>(m);
-            transpose_stage<8, 0x00ff00ffu>(m);
-            transpose_stage<4, 0x0f0f0f0fu>(m);
-            transpose_stage<2, 0x33333333u>(m);
-            transpose_stage<1, 0x55555555u>(m);
+                for (int i = 0; i < 32; ++i, rp += stride) {
+                    if ((i & 7) == 0) __builtin_amdgcn_sched_barrier(0); // (the loads leave in row order, all 32 in flight)
+                    m[i] = rp[lane];
+                }
 #pragma unroll
-            for (int q = 0; q < kPlaneRows; ++q) {
-                if ((q & 3) == 0) __builtin_amdgcn_sched_barrier(0); // (keeps the address arithmetic of all stores from piling up in registers)
-                if (lane < w) area[(unsigned long long)(32 * half + q) * (unsigned long long)a.stride] = m[q + kPlane0]; // (beyond w: other blocks' samples)
+                for (int i = 0; i < 32; ++i) {
+                    if ((i & 3) == 0) __builtin_amdgcn_sched_barrier(0); // (a row's sign is folded in before the next rows are scaled: it is not kept beside its magnitude)
+                    unsigned n;
+                    m[i] = scaled_magnitude<REV>(m[i], cb.stepsize, n); // (bit 31 is never used: |q| < 2^31)
+                    neg |= n << i;
+                    mxl = max(mxl, m[i]);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                transpose_stage<16, 0x0000ffffu>(m);
+                transpose_stage<8, 0x00ff00ffu>(m);
+                transpose_stage<4, 0x0f0f0f0fu>(m);
+                transpose_stage<2, 0x33333333u>(m);
+                transpose_stage<1, 0x55555555u>(m);
+                unsigned *wp = half0;
+#pragma unroll
+                for (int q = 0; q < kPlaneRows; ++q, wp += stride) {
+                    if ((q & 3) == 0) __builtin_amdgcn_sched_barrier(0);
+                    wp[lane] = m[q + kPlane0];
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
-            __builtin_amdgcn_sched_barrier(0);
+            chi |= (u64)neg << (32 * half);
+        }
+        mx = mxl;
+    } else { // any other height: the magnitudes are written back in place, and every bit-plane re-reads them from L2
+        unsigned *rp = blk0;
+        for (int y = 0; y < h; ++y, rp += stride) {
+            unsigned m = 0, n = 0;
+            if (lane < w) {
+                m = scaled_magnitude<REV>(rp[lane], cb.stepsize, n);
+                rp[lane] = m;
+            }
+            chi |= (u64)n << y;
+            mx = max(mx, m);
         }
     }
 #pragma unroll
@@ -340,9 +371,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
     // plane q of the magnitudes of this column (stored planes only): two coalesced loads
     auto plane_word = [&](int q) -> u64 {
         if (lane >= w) return 0;
-        const unsigned *mp = reinterpret_cast<const unsigned *>(a.coef) + cb.coef_off + lane;
-        const unsigned lo = mp[(unsigned long long)(q - kPlane0) * (unsigned long long)a.stride];
-        const unsigned hi = halves == 2 ? mp[(unsigned long long)(32 + q - kPlane0) * (unsigned long long)a.stride] : 0u;
+        const unsigned *const rp = blk0 + (long long)(q - kPlane0) * stride; // (wave-uniform: the lane is the load's offset)
+        const unsigned lo = rp[lane];
+        const unsigned hi = halves == 2 ? (rp + 32 * stride)[lane] : 0u;
         return (u64)lo | ((u64)hi << 32);
     };
     if constexpr (DIST) {
@@ -356,10 +387,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
     auto dist_sum = [&](u64 set, u64 cur, int bp, bool refinement) -> int {
         if (!set) return 0;
         if (!planes_stored) { // partial blocks: per sample from the magnitudes in place
-            const unsigned *mp = reinterpret_cast<const unsigned *>(a.coef) + cb.coef_off + lane;
             int sum = 0;
             for (u64 rest = set; rest; rest &= rest - 1) {
-                const unsigned m = mp[(unsigned long long)__builtin_ctzll(rest) * (unsigned long long)a.stride];
+                const unsigned m = blk0[(long long)__builtin_ctzll(rest) * stride + lane];
                 sum += refinement ? nmsedec_ref(m, bp) : nmsedec_sig(m, bp);
             }
             return sum;
@@ -404,16 +434,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
             bits = plane_word(sb);
             if constexpr (DIST) win[(bp % 6) * 64 + lane] = plane_word(bp); // joins the window: planes bp .. bp+5 of the magnitudes
         } else if (lane < w) {
-            const unsigned *mp = reinterpret_cast<const unsigned *>(a.coef) + cb.coef_off + lane;
+            // (row pointers formed from the wave-uniform row number: a scalar multiply, and nothing for the optimiser to
+            //  turn into per-lane pointers that it would keep across the bit-plane loop)
             int y = 0;
             for (; y + 8 <= h; y += 8) { // 8 row loads in flight
+                const unsigned *rp = blk0 + (long long)y * stride;
                 unsigned t[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) t[i] = mp[(unsigned long long)(y + i) * (unsigned long long)a.stride];
+                for (int i = 0; i < 8; ++i, rp += stride) t[i] = rp[lane];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) bits |= (u64)((t[i] >> sb) & 1u) << (y + i);
             }
-            for (; y < h; ++y) bits |= (u64)((mp[(unsigned long long)y * (unsigned long long)a.stride] >> sb) & 1u) << y;
+            for (; y < h; ++y) bits |= (u64)(((blk0 + (long long)y * stride)[lane] >> sb) & 1u) << y;
         }
 
         for (int pt = (bp == numbps - 1 ? 2 : 0); pt < 3; ++pt) {
