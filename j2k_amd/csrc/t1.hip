@@ -34,6 +34,9 @@
 //  t1_mq2_kernel        one LANE per code-block, two waves per 64 blocks: the MQ coder is serial per
 //            block, so blocks are the parallel axis; a producer wave runs the interval/probability
 //            recurrence, a consumer wave the code register and byte output, joined by an LDS queue.
+//            The producer's two table addresses per decision are byte permutes of the symbol word plus one
+//            three-input logic instruction (ctx_word2, mq2_slot); the consumer stores its bytes through a plain
+//            per-lane LDS pointer and moves the lane's remainder to the front of its stage at every flush.
 //  t1_rate_fixup_kernel the reference's fix-ups of the per-pass byte counts (rate control only).
 #include "kernels.h"
 #include "t1_common.h"
@@ -808,9 +811,28 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
 // ------------------------------------------------------------------------------------------------
 // MQ coder (T.800 Annex C); Table C.2 lives in t1_common.h.
 // The two-wave coder's state word: Qe in the high half (the interval register lives there too: its leading zeros are the
-// renormalisation shift as they stand), below it the byte offset of the (index, sense) entry in a transition table, and
-// the sense once more in bit 0, where the decision's bit meets it
-__device__ __forceinline__ unsigned ctx_word2(unsigned qe, unsigned idx, unsigned mps) { return (qe << 16) | ((idx | (mps << 6)) << 2) | mps; }
+// renormalisation shift as they stand), below it the byte offset of the state's entry in the transition table `trans`:
+// the index from bit 2, the MPS sense at bit 8 and once more at bit 9, where the decision's bit meets it.
+// (state ^ bit << 9) & 0x3fc is the address of the entry to take -- one v_bitop3 -- and "less probable symbol" is its top bit:
+// one compare.  (The flag at bit 2, under the index, takes an AND more per decision to test.)
+constexpr unsigned mq2_slot(unsigned idx, unsigned mps, unsigned lps) { return idx | (mps << 6) | (lps << 7); } // word index in `trans`
+constexpr unsigned kMq2LpsBit = 9; // of the entry's byte address
+constexpr bool mq2_slots_ok()
+{
+    bool seen[256] = {};
+    for (unsigned idx = 0; idx < 47; ++idx)
+        for (unsigned mps = 0; mps < 2; ++mps)
+            for (unsigned lps = 0; lps < 2; ++lps) {
+                const unsigned w = mq2_slot(idx, mps, lps), addr = w * 4u;
+                if (w >= 256u || seen[w] || (addr & 3u) || (addr & ~0x3fcu)) return false;
+                // (what the look-up relies on: the lps flag is one bit of the address, and without it the address is the state's own field)
+                if (addr != ((mq2_slot(idx, mps, 0) * 4u) ^ (lps << kMq2LpsBit))) return false;
+                seen[w] = true;
+            }
+    return true;
+}
+static_assert(mq2_slots_ok(), "trans: (index, sense, lps) -> word index must be injective over 47 x 2 x 2, below 256, and a word address within 0x3fc");
+__device__ __forceinline__ unsigned ctx_word2(unsigned qe, unsigned idx, unsigned mps) { return (qe << 16) | (mq2_slot(idx, mps, 0) << 2) | (mps << kMq2LpsBit); }
 
 // ------------------------------------------------------------------------------------------------
 // Two-wave MQ coder.  The coder state splits into two recurrences that only talk one way:
@@ -820,9 +842,9 @@ __device__ __forceinline__ unsigned ctx_word2(unsigned qe, unsigned idx, unsigne
 // different SIMDs, 64 blocks each (lane = block), joined by a double-buffered LDS queue of
 // {addend | n << 16} words that is handed over once per 16 decisions (one barrier).  The serial
 // chain per decision is cut roughly in half.
-// Staged codeword bytes per lane of the two-wave coder.  256 would make the ring index a byte of the count (one SDWA add
-// instead of an AND and an add) and codes a frame alone 1 % sooner, but its 8 KiB more of LDS per workgroup cost 3 % with
-// frames in flight (8020 against 8280 Mpixel/s on one box) and the DWT launches beside the coders a tenth of their rate.
+// Staged codeword bytes per lane of the two-wave coder.  (As a ring of 256 -- the ring index a byte of the count -- it coded a
+// frame alone 1 % sooner, but its 8 KiB more of LDS per workgroup cost 3 % with frames in flight (8020 against 8280 Mpixel/s
+// on one box) and the DWT launches beside the coders a tenth of their rate.  The stage is no ring any more: see the consumer.)
 #ifndef J2K_MQ2_RING
 #define J2K_MQ2_RING 128
 #endif
@@ -830,12 +852,12 @@ constexpr unsigned kRing = J2K_MQ2_RING;
 __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
 {
     __shared__ unsigned ctxs[19 * 64];
-    // [index | mps << 6 | lps << 7]: the context word after an MPS / an LPS out of state (index, mps): MPS sense and SWITCH folded in.
+    // [mq2_slot(index, mps, lps)]: the context word after an MPS / an LPS out of state (index, mps): MPS sense and SWITCH folded in.
     // One 32-bit word per look-up -- the producer knows which of the two it wants before it asks -- instead of the pair:
     // half the LDS bytes of the gather, whose bank conflicts were a third of this kernel's LDS-active cycles (profiles/r2_t1_pmc.txt)
     __shared__ unsigned trans[256];
     __shared__ uint4 queue[2][4][64]; // [buffer][decision / 4][lane]
-    __shared__ __attribute__((aligned(16))) unsigned ostage[(kRing / 4 + 1) * 64]; // per lane a ring of kRing bytes, stride kRing + 4 B (an odd number of banks): conflict-free byte-out stores
+    __shared__ __attribute__((aligned(16))) unsigned ostage[(kRing / 4 + 1) * 64]; // per lane one pad word, then kRing bytes: stride kRing + 4 B (an odd number of banks), conflict-free byte-out stores
     __shared__ unsigned finalA[64];   // the producer's interval register after the last decision (FLUSH needs it)
     const int lane = threadIdx.x & 63;
     const bool producer = threadIdx.x < 64;
@@ -863,10 +885,10 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
     const int b = a.gate_groups ? (int)gg.first + lane : a.first + (int)blockIdx.x * 64 + lane;
     if (producer) {
         if (lane < 47) {
-            trans[lane] = ctx_word2(kQe[kNmps[lane]], kNmps[lane], 0);
-            trans[lane + 64] = ctx_word2(kQe[kNmps[lane]], kNmps[lane], 1);
-            trans[lane + 128] = ctx_word2(kQe[kNlps[lane]], kNlps[lane], kSwitch[lane]);
-            trans[lane + 192] = ctx_word2(kQe[kNlps[lane]], kNlps[lane], 1u ^ kSwitch[lane]);
+            trans[mq2_slot(lane, 0, 0)] = ctx_word2(kQe[kNmps[lane]], kNmps[lane], 0);
+            trans[mq2_slot(lane, 1, 0)] = ctx_word2(kQe[kNmps[lane]], kNmps[lane], 1);
+            trans[mq2_slot(lane, 0, 1)] = ctx_word2(kQe[kNlps[lane]], kNlps[lane], kSwitch[lane]);
+            trans[mq2_slot(lane, 1, 1)] = ctx_word2(kQe[kNlps[lane]], kNlps[lane], 1u ^ kSwitch[lane]);
         }
 #pragma unroll
         for (int c = 0; c < 19; ++c) {
@@ -913,19 +935,25 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
                 const unsigned words[4] = {chunk.x, chunk.y, chunk.z, chunk.w};
                 const int rem = (int)min(nsym - min(base, nsym), 16u);
                 // One decision: the context's word, the transition it may take (asked for as soon as the word is there),
-                // the interval.  Byte offsets into the two tables are put together with ORs -- the tables' own offsets ride
-                // in the instructions -- and what goes to the consumer is {addend | shift << 16} as before.
+                // the interval.  Both table addresses come from byte permutes of values formed once per four symbols: the
+                // context word's is the context number above lane * 4 (both fit a byte), the transition entry's the state
+                // word's low bits xor the decision's bit at bit 9 -- the tables' own offsets ride in the instructions -- and
+                // what goes to the consumer is {addend | shift << 16} as before.
                 unsigned char *const ctx_b = reinterpret_cast<unsigned char *>(ctxs);
                 const unsigned char *const trans_b = reinterpret_cast<const unsigned char *>(trans);
                 const unsigned lane4 = (unsigned)lane * 4u;
-                auto decide = [&](unsigned sb) -> unsigned { // sb: the symbol (context << 1 | bit) in its low byte, anything above
-                    unsigned *const cp = reinterpret_cast<unsigned *>(ctx_b + (((sb << 7) & 0x7f00u) | lane4));
+                // c4: the four symbols' context numbers, one byte each; b4: the symbols (context << 1 | bit < 128) shifted up by
+                // one: a symbol's byte, moved to byte 1, has its bit at bit 9 and nothing else under the mask; jj: which of the four
+                auto decide = [&](unsigned c4, unsigned b4, auto jj_) -> unsigned {
+                    constexpr unsigned jj = decltype(jj_)::value;
+                    unsigned *const cp = reinterpret_cast<unsigned *>(ctx_b + __builtin_amdgcn_perm(c4, lane4, 0x0c0c0400u + (jj << 8)));
                     const unsigned st = *cp;
-                    const unsigned x = (st ^ sb) & 1u; // 1 = the less probable symbol
-                    const unsigned tr = *reinterpret_cast<const unsigned *>(trans_b + ((st & 0x1fcu) | (x << 9)));
+                    const unsigned ta = (st ^ __builtin_amdgcn_perm(b4, 0u, 0x0c0c040cu + (jj << 8))) & 0x3fcu;
+                    const unsigned tr = *reinterpret_cast<const unsigned *>(trans_b + ta);
+                    const bool mps = ta < (1u << kMq2LpsBit); // the more probable symbol
                     const unsigned qe = st & 0xffff0000u;
                     const unsigned A1 = A - qe;
-                    const bool use_a1 = (A1 >= qe) == (x == 0u); // MPS: keep A1 unless conditional exchange; LPS: the reverse
+                    const bool use_a1 = (A1 >= qe) == mps; // MPS: keep A1 unless conditional exchange; LPS: the reverse
                     A = use_a1 ? A1 : qe;
                     const bool renorm = (int)A >= 0;
                     *cp = renorm ? tr : st;
@@ -936,20 +964,23 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
                 if (__all(rem == 16)) { // every lane has a full chunk: no per-decision test for the lane's end
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
+                        const unsigned c4 = (words[g] >> 1) & 0x1f1f1f1fu, b4 = words[g] << 1;
                         unsigned e[4];
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) e[jj] = decide(words[g] >> (8 * jj));
+                        e[0] = decide(c4, b4, std::integral_constant<unsigned, 0>());
+                        e[1] = decide(c4, b4, std::integral_constant<unsigned, 1>());
+                        e[2] = decide(c4, b4, std::integral_constant<unsigned, 2>());
+                        e[3] = decide(c4, b4, std::integral_constant<unsigned, 3>());
                         queue[c & 1][g][lane] = make_uint4(e[0], e[1], e[2], e[3]);
                     }
                 } else
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    unsigned e[4];
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        e[jj] = 0;
-                        if (4 * g + jj < rem) e[jj] = decide(words[g] >> (8 * jj));
-                    }
+                    const unsigned c4 = (words[g] >> 1) & 0x1f1f1f1fu, b4 = words[g] << 1;
+                    unsigned e[4] = {0, 0, 0, 0};
+                    if (4 * g + 0 < rem) e[0] = decide(c4, b4, std::integral_constant<unsigned, 0>());
+                    if (4 * g + 1 < rem) e[1] = decide(c4, b4, std::integral_constant<unsigned, 1>());
+                    if (4 * g + 2 < rem) e[2] = decide(c4, b4, std::integral_constant<unsigned, 2>());
+                    if (4 * g + 3 < rem) e[3] = decide(c4, b4, std::integral_constant<unsigned, 3>());
                     queue[c & 1][g][lane] = make_uint4(e[0], e[1], e[2], e[3]);
                 }
             } else {
@@ -975,12 +1006,17 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
     unsigned *pass_rate = a.pass_rate + (size_t)(live ? b : 0) * kDevMaxPasses;
     unsigned char *ostage_b = reinterpret_cast<unsigned char *>(ostage);
     unsigned C = 0, CT = 12, B = 0;
-    int nb = -1, flushed = 0;
+    int flushed = 0;
     bool overflow = false;
-    const unsigned lbase = (unsigned)lane * (kRing + 4u);
+    // The lane's stage: its data bytes start at dbase, and the byte at dbase is number `flushed` of the codeword.  `pos` is
+    // where the next candidate byte goes -- an offset into ostage: the array's own address rides in the store -- and the byte
+    // count is derived from it where it is needed.  Before the first byte (count -1) it points at the pad word's last byte.
+    const unsigned dbase = (unsigned)lane * (kRing + 4u) + 4u;
+    unsigned pos = dbase - 1u;
+    auto nbytes = [&]() -> int { return (int)(pos - dbase) + flushed; };
     // BYTEOUT (Figure C.3) for the lanes in `p`, by selects.  (An explicit masked block -- `if (p) { ... }` -- was measured
-    // on the same box: 5900 instead of 7050 Mpixel/s.)  Every lane stores its candidate byte at ring position nb -- the next one to become valid: lanes not in `p` only
-    // scribble on a slot that their next committed byte overwrites (nb == -1: the ring's last slot, rewritten before it is read)
+    // on the same box: 5900 instead of 7050 Mpixel/s.)  Every lane stores its candidate byte at `pos` -- the next one to become valid: lanes not in `p` only
+    // scribble on a slot that their next committed byte overwrites (count -1: the pad byte, never read)
     auto byteout = [&](bool p) {
         const bool was_ff = B == 0xffu;
         const unsigned Bc = B + ((C > 0x7ffffffu && !was_ff) ? 1u : 0u); // the carry goes into the byte before -- unless that is a 0xFF
@@ -989,14 +1025,15 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
         // the next byte: ct bits from `sh` up -- the carry above them has gone into Bc -- or, behind a 0xFF, eight: there the
         // carry stays with its byte
         const unsigned bw = was_ff ? 8u : ct;
-        ostage_b[lbase + ((unsigned)nb & (kRing - 1u))] = (unsigned char)Bc;
-        B = p ? __builtin_amdgcn_ubfe(C, sh, bw) : B; C = p ? __builtin_amdgcn_ubfe(C, 0u, sh) : C; CT = p ? ct : CT; nb += p ? 1 : 0;
+        ostage_b[pos] = (unsigned char)Bc;
+        B = p ? __builtin_amdgcn_ubfe(C, sh, bw) : B; C = p ? __builtin_amdgcn_ubfe(C, 0u, sh) : C; CT = p ? ct : CT; pos += p ? 1u : 0u;
+        asm("" : "+v"(pos)); // (one register for the pointer: left to itself the compiler forms it a second time for the next store)
     };
     unsigned cur_pass = 0;
     unsigned next_end = npasses ? pass_nsym[0] : 0xffffffffu;
     auto close_passes = [&](unsigned i) {
         while (cur_pass < npasses && i == next_end) {
-            pass_rate[cur_pass] = (unsigned)(nb + 3);
+            pass_rate[cur_pass] = (unsigned)(nbytes() + 3);
             ++cur_pass;
             next_end = cur_pass < npasses ? pass_nsym[cur_pass] : 0xffffffffu;
         }
@@ -1060,21 +1097,31 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
                 if (ends_here && __any(rel > 4 * g && rel <= 4 * g + 4)) four(std::true_type(), e, g);
                 else four(std::false_type(), e, g);
             }
-            // Codeword bytes leave the ring in 16-byte units, every lane's at once: when some lane has 64 waiting, all lanes send
+            // Codeword bytes leave the stage in 16-byte units, every lane's at once: when some lane has 64 waiting, all lanes send
             // the whole units they have.  (Each lane on its own -- 64 bytes whenever it had them -- ran this code in five chunks
-            // out of six: with 64 lanes somebody is always due.  Together it runs once in thirty.)  A chunk adds fewer than
-            // 48 bytes to a lane: fewer than 112 ever wait in its 128.
-            if (__any(nb - flushed >= 64)) {
-                const int units = (nb - flushed) >> 4; // (nothing yet: nb = -1 -> -1)
+            // out of six: with 64 lanes somebody is always due.  Together it runs once in thirty.)  Then each lane moves what is
+            // left -- fewer than 16 bytes and the candidate's slot: four words -- to the front of its stage and pulls `pos` back.
+            // A chunk adds fewer than 48 bytes to a lane, so fewer than 64 + 48 = 112 ever wait: the candidate's slot is at most
+            // data byte 111 of the lane's kRing = 128, and the move reads no further than byte 6 * 16 + 15.
+            const int waiting = (int)(pos - dbase); // (nothing yet: -1)
+            if (__any(waiting >= 64)) {
+                const int units = waiting >> 4; // (-1 -> -1)
                 for (int u = 0; u < 7; ++u) {
                     if (!__any(u < units)) break;
                     if (u < units) {
                         if ((unsigned)(flushed + 16) <= cb.out_cap) {
-                            const unsigned *sp = reinterpret_cast<const unsigned *>(ostage_b + lbase + ((unsigned)flushed & (kRing - 16u)));
+                            const unsigned *sp = reinterpret_cast<const unsigned *>(ostage_b + dbase + 16 * u);
                             *reinterpret_cast<uint4 *>(out + flushed) = make_uint4(sp[0], sp[1], sp[2], sp[3]);
                         } else overflow = true;
                         flushed += 16;
                     }
+                }
+                if (units > 0) {
+                    const unsigned *sp = reinterpret_cast<const unsigned *>(ostage_b + dbase + 16 * units);
+                    unsigned *dp = reinterpret_cast<unsigned *>(ostage_b + dbase);
+                    const unsigned r0 = sp[0], r1 = sp[1], r2 = sp[2], r3 = sp[3];
+                    dp[0] = r0; dp[1] = r1; dp[2] = r2; dp[3] = r3;
+                    pos -= 16u * (unsigned)units;
                 }
             }
         }
@@ -1100,12 +1147,13 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
     C <<= CT; byteout(fin);
     C <<= CT; byteout(fin);
     if (fin && B != 0xffu) {
-        ostage_b[lbase + ((unsigned)nb & (kRing - 1u))] = (unsigned char)B;
-        ++nb;
+        ostage_b[pos] = (unsigned char)B;
+        ++pos;
     }
+    const int nb = nbytes();
     if (fin) {
         for (int o = flushed; o < nb; o += 4) {
-            if ((unsigned)(o + 4) <= cb.out_cap) *reinterpret_cast<unsigned *>(out + o) = *reinterpret_cast<const unsigned *>(ostage_b + lbase + (o & (kRing - 1u)));
+            if ((unsigned)(o + 4) <= cb.out_cap) *reinterpret_cast<unsigned *>(out + o) = *reinterpret_cast<const unsigned *>(ostage_b + dbase + (o - flushed));
             else overflow = true;
         }
         pass_rate[npasses - 1] = (unsigned)nb;
