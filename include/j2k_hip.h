@@ -123,7 +123,20 @@ typedef struct j2k_hip_params {
     uint32_t dci_profile;
     uint32_t max_cs_size;     /* bytes per frame; 0 or more than 1302083 = 1302083 (24 frames/s at 250 Mbit/s)      */
     uint32_t max_comp_size;   /* bytes per component; 0 or more than 1041666 = 1041666                               */
+    /* ---- code-block style (T.800 Table A.19, D.4 - D.7; opj_compress -M, Kakadu Cmodes).  The COD marker's SPcod code-block
+     * style byte: 0 = none, which is all the reference's WriteFile asks for (CompressionSettings has no such field); otherwise
+     * any combination of J2K_HIP_CBLK_BYPASS, _RESET, _TERMALL, _PTERM and _SEGSYM, byte for byte what OpenJPEG writes for the
+     * same mode.  Vertically causal contexts (bit 8) are not written: J2K_HIP_ERR_PARAM.  A style excludes layer_rates,
+     * layer_psnr and dci_profile (J2K_HIP_ERR_PARAM): the layer allocation does not price codeword segments.
+     * J2K_HIP_ABI_VERSION is still 9: the field was appended, no function changed.  struct_size is the guard against a caller
+     * built with another layout, as for every field before it.  Where the struct ends in alignment padding (LP64: 4 bytes
+     * behind max_comp_size) the field takes that padding and sizeof does not move: a caller of the older header that
+     * zero-initialises the whole struct, as the header has always asked for, passes style 0. */
+    uint32_t cblk_style;
 } j2k_hip_params;
+
+enum { J2K_HIP_CBLK_BYPASS = 1, J2K_HIP_CBLK_RESET = 2, J2K_HIP_CBLK_TERMALL = 4, J2K_HIP_CBLK_VCAUSAL = 8 /* decode only */,
+       J2K_HIP_CBLK_PTERM = 16, J2K_HIP_CBLK_SEGSYM = 32 };
 
 enum { J2K_HIP_FMT_J2K = 0, J2K_HIP_FMT_JP2 = 1 };
 enum { J2K_HIP_CS_UNSPECIFIED = 0, J2K_HIP_CS_SRGB = 1, J2K_HIP_CS_GRAY = 2, J2K_HIP_CS_SYCC = 3,

@@ -34,6 +34,8 @@ struct Coding {
     uint32_t prog = 0;                                 // progression order (J2K_HIP_LRCP ..)
     // digital cinema profile (encode): Rsiz 3 / 4, tile-parts per component, TLM, the 4K progression order change; the cap per component
     uint32_t dci = 0, max_comp_size = 0;
+    // code-block style (COD SPcod; cblk_style.h): encode 0 or bypass / reset / termall / pterm / segsym in any combination
+    uint32_t cblk_style = 0;
     uint32_t dci_tileparts() const { return dci == 4 ? 6u : (dci == 3 ? 3u : 1u); }
     // per component (decode only; the encode path of the reference never sub-samples: SIZ XRsiz = YRsiz = 1, one depth, unsigned):
     // sub-sampling factors on the reference grid, precision, signedness

@@ -112,7 +112,8 @@ bool same_coding(const Coding &a, const Coding &b)
     return a.width == b.width && a.height == b.height && a.ncomp == b.ncomp && a.prec == b.prec &&
            a.reversible == b.reversible && a.mct == b.mct && a.layers == b.layers && a.numres == b.numres &&
            a.cbw == b.cbw && a.cbh == b.cbh && a.tile_w == b.tile_w && a.tile_h == b.tile_h &&
-           std::memcmp(a.ppx, b.ppx, sizeof a.ppx) == 0 && std::memcmp(a.ppy, b.ppy, sizeof a.ppy) == 0 && a.prog == b.prog;
+           std::memcmp(a.ppx, b.ppx, sizeof a.ppx) == 0 && std::memcmp(a.ppy, b.ppy, sizeof a.ppy) == 0 && a.prog == b.prog &&
+           a.cblk_style == b.cblk_style; // (a style changes the codeword capacities)
 }
 
 // Build (or reuse) geometry, code-block table and DWT job lists; upload the device images.
@@ -151,7 +152,12 @@ void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first
         const size_t area = (size_t)c.w * c.h;
         // <= 1.5 decisions per sample and bit-plane (ZC/MR + run-length overhead) + one sign each
         const size_t symcap = round_up(area * 3 * c.Mb / 2 + area + 64, 1024);
-        const size_t outcap = round_up(symcap / 4 + 64, 16);
+        // Under a code-block style every terminated pass adds to the codeword: a FLUSH at most two bytes beyond what the open
+        // segment would have needed anyway, the predictable form at most four, the padding of a raw segment one, and the
+        // four segmentation symbols of a cleanup pass under two.  8 bytes for each of the 3 Mb - 2 passes cover them all;
+        // a raw pass itself takes a bit per decision, less than the quarter byte counted for it.
+        const size_t style_room = cod.cblk_style ? 8 * (size_t)(3 * c.Mb) : 0;
+        const size_t outcap = round_up(symcap / 4 + 64 + style_room, 16);
         d.sym_off = sym_off; d.sym_cap = (unsigned)symcap;
         d.out_off = out_off; d.out_cap = (unsigned)outcap;
         d.stepsize = c.stepsize;
@@ -548,6 +554,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     ta.pass_rate = e->passes.as<uint32_t>() + 2 * nb * kDevMaxPasses;
     ta.mq_prio = tn.mq_prio ? 3 : 0;
     ta.sparse = tn.t1_sparse;
+    ta.style = cod.cblk_style;
 #ifdef J2K_MQ_TIMES
     { // diagnostic build: where the two waves of the coder spend their cycles (previous frame's totals, at every encode)
         static unsigned long long *dbg = nullptr;
@@ -652,7 +659,16 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
             }
             HIP_CHECK(hipMemcpyAsync(e->h_rc_bounds.p, ra.bounds, 3 * nb * sizeof(double), hipMemcpyDeviceToHost, s));
         }
-    } else pd.rc_device = false;
+    } else {
+        pd.rc_device = false;
+        if (cod.cblk_style && nb) { // the per-pass byte counts, after the fix-ups: the codeword segments' lengths for the packet headers
+            T1Args tf = ta;
+            tf.first = 0; tf.nblks = (int)nb;
+            launch_t1_rate_fixup(tf, s);
+            e->h_passes.ensure(nb * kDevMaxPasses * sizeof(uint32_t));
+            HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_rate, nb * kDevMaxPasses * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        }
+    }
     // The dense phase ends when the last modeller launch has drained: the next frame's DWT + modeller
     // then run beside this frame's MQ coder chains, which are latency-bound and leave most issue slots
     // free (+70 % frames/s with 3 frames in flight; the co-running coder waves hold registers and LDS,
@@ -849,6 +865,8 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
         for (size_t f = 0; f < F; ++f) {
             std::vector<CblkResult> res(nb1);
             for (size_t i = 0; i < nb1; ++i) res[i] = CblkResult{hm[f * nb1 + i], hm[nb + f * nb1 + i], hm[2 * nb + f * nb1 + i]};
+            if (cod.cblk_style) // (styled frames: h_passes holds the byte counts per pass alone, [nb][kDevMaxPasses])
+                for (size_t i = 0; i < nb1; ++i) res[i].rates = e->h_passes.as<uint32_t>() + (f * nb1 + i) * kDevMaxPasses;
             LayerAlloc alloc;
             if (rate_control) {
                 const uint32_t *hp = e->h_passes.as<uint32_t>(); // [nmsedec | rate], each [nb][kDevMaxPasses]
@@ -1014,7 +1032,8 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     Pending &pd = e->pend;
     const Geometry &g = e->geo;
     const int NL = (int)cod.levels();
-    if (tn.bands < 0 || NL < 1 || tn.no_fuse || cod.rate_control() || cod.dci || g.cblks.empty()) return false;
+    // (a code-block style: its coder is not the gated two-wave kernel this path is built around)
+    if (tn.bands < 0 || NL < 1 || tn.no_fuse || cod.rate_control() || cod.dci || cod.cblk_style || g.cblks.empty()) return false;
     // Other encode calls in progress on the device (a host that renders on several threads, or pipelines handles with _begin /
     // _end): their frames overlap as wholes -- one frame's upload beside another's coder chains -- and ten more coder launches
     // per frame only get in each other's way (three handles from one thread: 31 -> 50 ms per frame).  The bands are for the call

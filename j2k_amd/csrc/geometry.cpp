@@ -2,6 +2,7 @@
 // B.7 (code-blocks) and E.1 (step sizes), with the parameterisation of the reference's encode call
 // (reference: src/common/j2k_openjpeg_codec.cpp:639-647, 667-670, 703-719).
 #include "geometry.h"
+#include "cblk_style.h"
 
 #include <algorithm>
 #include <cmath>
@@ -108,6 +109,17 @@ Coding normalise(const j2k_hip_params *p)
         c.psnr.assign(p->layer_psnr, p->layer_psnr + c.layers);
         for (float q : c.psnr)
             if (!(q >= 0.0f) || q > 1000.0f) throw Error(J2K_HIP_ERR_PARAM, "layer_psnr must be finite and >= 0");
+    }
+    // code-block style: everything but vertically causal contexts, and not under a layer allocation
+    if (p->cblk_style) {
+        if (p->cblk_style & kStyleVcausal)
+            throw Error(J2K_HIP_ERR_PARAM, "cblk_style: vertically causal contexts (bit 8) are not written");
+        if (p->cblk_style & ~(uint32_t)(kStylesEncoded | kStyleVcausal))
+            throw Error(J2K_HIP_ERR_PARAM, "cblk_style: unknown code-block style bits (bypass 1, reset 2, termall 4, pterm 16, segsym 32 are written)");
+        if (p->dci_profile) throw Error(J2K_HIP_ERR_PARAM, "cblk_style cannot be combined with dci_profile: a digital cinema profile sets style 0");
+        if (p->layer_rates) throw Error(J2K_HIP_ERR_PARAM, "cblk_style cannot be combined with layer_rates: rate control does not price codeword segments");
+        if (p->layer_psnr) throw Error(J2K_HIP_ERR_PARAM, "cblk_style cannot be combined with layer_psnr: rate control does not price codeword segments");
+        c.cblk_style = p->cblk_style;
     }
     // file wrapper
     if (p->file_format != J2K_HIP_FMT_J2K && p->file_format != J2K_HIP_FMT_JP2)

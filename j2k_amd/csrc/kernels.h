@@ -176,9 +176,16 @@ struct T1Args {
     unsigned int *pass_nsym;    // cumulative decisions at the end of each pass
     int *pass_nmsedec;          // distortion LUT sum of each pass
     unsigned int *pass_rate;    // MQ bytes (+3 estimate) at the end of each pass, before fix-ups
+    // Code-block style of the frame (COD SPcod, cblk_style.h; 0 = none).  t1_model: with bypass, the sign decisions of raw passes
+    // carry the sign itself.  launch_t1_mq: a style sends the blocks to the styled coder (t1_mq_styled.hip).
+    unsigned style;
 };
 void launch_t1_model(const T1Args &a, hipStream_t s);
+// blocks [first, nblks): the two-wave coder, or under a style the styled one
 void launch_t1_mq(const T1Args &a, hipStream_t s);
+// the coder of styled blocks (t1_mq_styled.hip): a lane per code-block, interval and code register in the same lane; pass_rate
+// holds libopenjp2's count per pass (exact at a terminated pass) and wants t1_rate_fixup behind it
+void launch_t1_mq_styled(const T1Args &a, hipStream_t s);
 // the gated form: workgroups [group_first, group_first + group_count) of a.gate_groups
 void launch_t1_mq_gated(const T1Args &a, int group_first, int group_count, hipStream_t s);
 // holds a stream until *word >= target (bounded: ~timeout_us microseconds, or *abort != 0); on giving up *err = 5
@@ -187,7 +194,8 @@ void launch_wait_count(const unsigned *word, unsigned target, unsigned timeout_u
 void launch_wait_word(const unsigned *word, unsigned target, unsigned timeout_us, hipStream_t s);
 // agent-scope stores in stream order: *word2 = value2 (if word2) and then *word = value
 void launch_set_word(unsigned *word, unsigned value, hipStream_t s, unsigned *word2 = nullptr, unsigned value2 = 0);
-// pass_rate fix-ups of blocks [first, nblks) once their coder has finished (rate control only)
+// pass_rate fix-ups of blocks [first, nblks) once their coder has finished (rate control, and every styled frame: the
+// segment lengths come from them)
 void launch_t1_rate_fixup(const T1Args &a, hipStream_t s);
 
 // Rate control on the device (rate.hip; rate_control.h: RateDevice): a thread per code-block over the Tier-1 results of a frame.

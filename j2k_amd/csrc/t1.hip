@@ -37,9 +37,12 @@
 //            The producer's two table addresses per decision are byte permutes of the symbol word plus one
 //            three-input logic instruction (ctx_word2, mq2_slot); the consumer stores its bytes through a plain
 //            per-lane LDS pointer and moves the lane's remainder to the front of its stage at every flush.
-//  t1_rate_fixup_kernel the reference's fix-ups of the per-pass byte counts (rate control only).
+//  t1_rate_fixup_kernel the reference's fix-ups of the per-pass byte counts (rate control, and behind the styled coder).
+// Frames with a code-block style are coded by t1_mq_styled.hip (launch_t1_mq chooses); of this file they use the modeller,
+// in its BYPASS instantiation where raw passes exist, and the fix-ups.
 #include "kernels.h"
 #include "t1_common.h"
+#include "cblk_style.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -170,7 +173,11 @@ __device__ __forceinline__ unsigned scaled_magnitude(unsigned word, float stepsi
 #ifndef J2K_MODEL_WAVES
 #define J2K_MODEL_WAVES 7
 #endif
-template <bool REV, bool DIST>
+// BYPASS: an instantiation of its own for frames coded with selective arithmetic-coding bypass (never with DIST: a style
+// excludes rate control).  Its one difference: in a raw significance pass a sign decision carries the sample's sign, not
+// sign XOR prediction -- a raw bit is the sign itself (D.6), and the prediction cannot be taken out again from the context
+// number (Table D.3).  Without it the kernel compiles to the code it was before the parameter existed.
+template <bool REV, bool DIST, bool BYPASS = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WAVES, J2K_MODEL_WAVES))) void t1_model_kernel(T1Args a)
 {
     // The block's scaled magnitudes go back into its own area of the coefficient buffer (dead after Tier-1) -- as
@@ -698,6 +705,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                         sb1 = hnz & ~same;
                         sb0 = (hnz & ~same & ~opp) | (~hnz & vnz);
                         sd = hf(chi) ^ (hn | (~hnz & vn));
+                        if constexpr (BYPASS) {
+                            if (pt == 0 && pass >= 10) sd = hf(chi); // raw pass (wave-uniform): the sign as it is
+                        }
                     }
                 }
                 if (sparse) {
@@ -1171,7 +1181,8 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
 }
 
 // The reference's fix-ups of the per-pass byte counts (OpenJPEG opj_t1_encode_cblk): an estimate never
-// exceeds what follows it, and a pass never ends on 0xFF.  One thread per block, after its coder.
+// exceeds what follows it, and a pass never ends on 0xFF.  One thread per block, after its coder -- either coder: under a
+// code-block style the rules are the same ones (a terminated pass holds its exact count and never ends on 0xFF by itself).
 __global__ void t1_rate_fixup_kernel(T1Args a)
 {
     const int b = a.first + (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -1248,6 +1259,9 @@ void launch_t1_model(const T1Args &a, hipStream_t s)
     if (a.want_dist) {
         if (a.reversible) hipLaunchKernelGGL((t1_model_kernel<true, true>), dim3((unsigned)n), dim3(64), 0, s, a);
         else hipLaunchKernelGGL((t1_model_kernel<false, true>), dim3((unsigned)n), dim3(64), 0, s, a);
+    } else if (a.style & kStyleBypass) {
+        if (a.reversible) hipLaunchKernelGGL((t1_model_kernel<true, false, true>), dim3((unsigned)n), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((t1_model_kernel<false, false, true>), dim3((unsigned)n), dim3(64), 0, s, a);
     } else {
         if (a.reversible) hipLaunchKernelGGL((t1_model_kernel<true, false>), dim3((unsigned)n), dim3(64), 0, s, a);
         else hipLaunchKernelGGL((t1_model_kernel<false, false>), dim3((unsigned)n), dim3(64), 0, s, a);
@@ -1266,6 +1280,7 @@ void launch_t1_mq(const T1Args &a, hipStream_t s)
 {
     const int n = a.nblks - a.first;
     if (n <= 0) return;
+    if (a.style) { launch_t1_mq_styled(a, s); return; } // (a termination at a pass boundary needs interval and code register together)
     hipLaunchKernelGGL(t1_mq2_kernel, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, s, a);
 }
 

@@ -2,6 +2,7 @@
 // parameterisation (no rate target: every coding pass in layer 0, later layers list nothing;
 // pinned by tests/golden g1..g9 through the oracle).
 #include "tier2.h"
+#include "cblk_style.h"
 #include "jp2.h"
 
 #include <algorithm>
@@ -116,7 +117,7 @@ std::vector<uint8_t> main_header(const Coding &c)
     for (uint32_t i = 0; i < c.ncomp; ++i) { o.u8(c.prec - 1); o.u8(1); o.u8(1); }
     o.u16(0xff52); o.u16(c.user_precincts ? 12 + c.numres : 12); o.u8(c.user_precincts ? 1 : 0); // COD; Scod bit 0 = precinct sizes follow
     o.u8(c.prog); o.u16(c.layers); o.u8(c.mct ? 1 : 0);
-    o.u8(c.numres - 1); o.u8(c.cbw - 2); o.u8(c.cbh - 2); o.u8(0); o.u8(c.reversible ? 1 : 0);
+    o.u8(c.numres - 1); o.u8(c.cbw - 2); o.u8(c.cbh - 2); o.u8(c.cblk_style); o.u8(c.reversible ? 1 : 0);
     if (c.user_precincts)
         for (uint32_t r = 0; r < c.numres; ++r) o.u8((unsigned)c.ppx[r] | ((unsigned)c.ppy[r] << 4)); // lowest resolution first
     const uint32_t nbands = 3 * c.numres - 2;
@@ -218,6 +219,30 @@ void for_each_packet(const Coding &cod, const Tile &T, const std::vector<CblkRes
                             if (!np) continue;
                             if (!sofar[li]) { lenbits[li] = 3; tr.imsb.encode(bw, k, 999); }
                             put_numpasses(bw, np);
+                            if (const uint32_t *rates = res[id].rates) {
+                                // Code-block style with several codeword segments (B.10.7.2): one length per terminated segment
+                                // among the passes [first, first + np) of this packet -- the last one closes at the last pass
+                                // included, terminated or not -- each in Lblock + floor(log2(passes of the segment)) bits;
+                                // Lblock rises once, by the largest shortfall over the segments.
+                                const uint32_t first = sofar[li], total = res[id].npasses;
+                                auto segments = [&](auto &&seg) {
+                                    uint32_t nump = 0, start = first ? rates[first - 1] : 0u;
+                                    for (uint32_t p = first; p < first + np; ++p) {
+                                        ++nump;
+                                        if (cblk_pass_terminates(cod.cblk_style, p, total) || p + 1 == first + np) {
+                                            seg(rates[p] - start, nump);
+                                            start = rates[p]; nump = 0;
+                                        }
+                                    }
+                                };
+                                int inc = 0;
+                                segments([&](uint32_t slen, uint32_t nump) { inc = std::max(inc, floorlog2(slen) + 1 - ((int)lenbits[li] + floorlog2(nump))); });
+                                for (int i = 0; i < inc; ++i) bw.bit(1);
+                                bw.bit(0);
+                                lenbits[li] += (uint32_t)inc;
+                                segments([&](uint32_t slen, uint32_t nump) { bw.bits(slen, (int)lenbits[li] + floorlog2(nump)); });
+                                continue;
+                            }
                             const uint32_t len = layer_len(id, l);
                             const int need = floorlog2(len) + 1 - ((int)lenbits[li] + floorlog2(np));
                             const int inc = std::max(0, need);

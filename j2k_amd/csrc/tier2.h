@@ -13,6 +13,10 @@ struct CblkResult { // one per Geometry::cblks entry, produced by the Tier-1 ker
     uint32_t numbps;
     uint32_t npasses;
     uint32_t len;
+    // Under a code-block style (Coding::cblk_style != 0): the block's byte count at the end of each of its passes, after the
+    // fix-ups (t1_rate_fixup_kernel).  Its codeword segments end where cblk_pass_terminates() says (cblk_style.h): segment
+    // boundaries = rates[] at those passes.  Null without a style: one segment of `len` bytes.
+    const uint32_t *rates = nullptr;
 };
 
 struct HeaderSeg { uint64_t dst; uint32_t src; uint32_t len; }; // bytes of `blob` -> codestream
