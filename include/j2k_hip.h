@@ -383,6 +383,19 @@ int j2k_hip_stage_t1_passes(j2k_hip_encoder *enc, int reversible, void *d_coef, 
                             uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
                             void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist);
 
+/* Same as j2k_hip_stage_t1_passes under a code-block style (cblk_style as in j2k_hip_params; no pass_dist: a style excludes
+ * rate control).  The blocks take the way of a styled frame: codeword capacities by the frame's formula, the bypass
+ * instantiation of the modeller, the styled coder, and the fix-ups of pass_rate applied on the device.  pass_rate holds
+ * the exact end of a codeword segment at every pass that terminates one and at the last pass, libopenjp2's estimate at
+ * any other.  Vertically causal contexts (bit 8) and unknown bits: J2K_HIP_ERR_PARAM, as for a frame.  With
+ * cblk_style = 0 the results are those of j2k_hip_stage_t1_passes.
+ * J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
+int j2k_hip_stage_t1_styled(j2k_hip_encoder *enc, int reversible, void *d_coef, uint32_t stride,
+                            uint32_t nblocks, const uint32_t *bx, const uint32_t *by, const uint32_t *bw,
+                            const uint32_t *bh, const uint32_t *orient, const float *stepsize,
+                            uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
+                            void *data, size_t data_cap, uint32_t *pass_rate, uint32_t cblk_style);
+
 /* Inverse DWT (the mirror of j2k_hip_stage_dwt): `nplanes` planes of width*height 32-bit words (row stride =
  * width) in the Mallat layout of the oracle are synthesised from the lowest of `levels` resolutions upwards,
  * one kernel launch pair per level, the jobs built like a decode builds them.  With nregions == 0 a plane is

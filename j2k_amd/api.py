@@ -88,6 +88,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
            "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
+           "j2k_hip_stage_t1_styled",
            "j2k_hip_stage_idwt", "j2k_hip_stage_t1_decode", "j2k_hip_stage_decode_output",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink"]
@@ -172,6 +173,7 @@ def load_library():
     L.j2k_hip_stage_t1.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, U32P, U32P, U32P, U32P, U32P,
                                    C.POINTER(C.c_float), U32P, U32P, U32P, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t]
     L.j2k_hip_stage_t1_passes.argtypes = L.j2k_hip_stage_t1.argtypes + [U32P, C.POINTER(C.c_int32)]
+    L.j2k_hip_stage_t1_styled.argtypes = L.j2k_hip_stage_t1.argtypes + [U32P, C.c_uint32]
     L.j2k_hip_stage_idwt.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.POINTER(IdwtRegion), C.c_uint32, C.c_void_p, C.c_void_p]
     L.j2k_hip_stage_t1_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DecBlock),
@@ -540,8 +542,9 @@ class Encoder:
             self.free(d_out)
         return raw.view(dt).reshape(n, h, w), ms.value
 
-    def stage_t1(self, coef: np.ndarray, rects, orients, stepsizes, reversible: bool, want_passes: bool = False):
-        """coef: (H, W) int32/float32 plane; rects: list of (x, y, w, h). Returns list of dicts."""
+    def stage_t1(self, coef: np.ndarray, rects, orients, stepsizes, reversible: bool, want_passes: bool = False, style=None):
+        """coef: (H, W) int32/float32 plane; rects: list of (x, y, w, h). Returns list of dicts.  style (a code-block style,
+        0 included): through j2k_hip_stage_t1_styled, with `rates` per pass and no `nmsedec`."""
         dt = np.int32 if reversible else np.float32
         coef = np.ascontiguousarray(coef, dtype=dt)
         H, W = coef.shape
@@ -559,7 +562,10 @@ class Encoder:
         rates = (C.c_uint32 * (nb * MP))()
         dist = (C.c_int32 * (nb * MP))()
         try:
-            if want_passes:
+            if style is not None:
+                self._check(self.L.j2k_hip_stage_t1_styled(self.h, int(reversible), d, W, nb, bx, by, bw, bh, ori, ss, numbps,
+                                                           npasses, length, offs, data.ctypes.data, cap, rates, C.c_uint32(style)))
+            elif want_passes:
                 self._check(self.L.j2k_hip_stage_t1_passes(self.h, int(reversible), d, W, nb, bx, by, bw, bh, ori, ss, numbps,
                                                            npasses, length, offs, data.ctypes.data, cap, rates, dist))
             else:
@@ -569,7 +575,10 @@ class Encoder:
             self.free(d)
         out = [dict(numbps=numbps[i], npasses=npasses[i], length=length[i],
                     data=data[offs[i]:offs[i] + length[i]].tobytes()) for i in range(nb)]
-        if want_passes:
+        if style is not None:
+            for i, o in enumerate(out):
+                o["rates"] = list(rates[i * MP:i * MP + o["npasses"]])
+        elif want_passes:
             for i, o in enumerate(out):
                 o["rates"] = list(rates[i * MP:i * MP + o["npasses"]])
                 o["nmsedec"] = list(dist[i * MP:i * MP + o["npasses"]])

@@ -43,6 +43,7 @@
 #include "rate_block.h"
 #include "rate_control.h"
 #include "bands.h"
+#include "cblk_style.h"
 #include "handle.h"
 
 using namespace j2k_hip;
@@ -116,6 +117,23 @@ bool same_coding(const Coding &a, const Coding &b)
            a.cblk_style == b.cblk_style; // (a style changes the codeword capacities)
 }
 
+// Decision-stream and codeword capacities of a code-block of `area` samples with up to Mb bit-planes under code-block style
+// `style`: one rule for the frames (prepare_geometry) and for the Tier-1 stage hooks.  A frame passes the band's own Mb; the
+// hooks know no band and pass 30, so a hook's capacities are a frame's or larger (two to three times at the usual depths):
+// the hooks show that the rule holds the codewords of Mb = 30, not that a frame's smaller Mb does.
+struct CblkCaps { size_t sym, out; };
+CblkCaps cblk_capacities(size_t area, uint32_t Mb, uint32_t style)
+{
+    // <= 1.5 decisions per sample and bit-plane (ZC/MR + run-length overhead) + one sign each
+    const size_t symcap = round_up(area * 3 * Mb / 2 + area + 64, 1024);
+    // Under a code-block style every terminated pass adds to the codeword: a FLUSH at most two bytes beyond what the open
+    // segment would have needed anyway, the predictable form at most four, the padding of a raw segment one, and the
+    // four segmentation symbols of a cleanup pass under two.  8 bytes for each of the 3 Mb - 2 passes cover them all;
+    // a raw pass itself takes a bit per decision, less than the quarter byte counted for it.
+    const size_t style_room = style ? 8 * (size_t)(3 * Mb) : 0;
+    return {symcap, round_up(symcap / 4 + 64 + style_room, 16)};
+}
+
 // Build (or reuse) geometry, code-block table and DWT job lists; upload the device images.
 void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first, uint32_t tile_count)
 {
@@ -150,14 +168,8 @@ void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first
         CblkDev d{};
         d.coef_off = (unsigned long long)c.comp * e->plane_elems + (unsigned long long)(c.py - (uint32_t)by0) * stride + (c.px - (uint32_t)bx0);
         const size_t area = (size_t)c.w * c.h;
-        // <= 1.5 decisions per sample and bit-plane (ZC/MR + run-length overhead) + one sign each
-        const size_t symcap = round_up(area * 3 * c.Mb / 2 + area + 64, 1024);
-        // Under a code-block style every terminated pass adds to the codeword: a FLUSH at most two bytes beyond what the open
-        // segment would have needed anyway, the predictable form at most four, the padding of a raw segment one, and the
-        // four segmentation symbols of a cleanup pass under two.  8 bytes for each of the 3 Mb - 2 passes cover them all;
-        // a raw pass itself takes a bit per decision, less than the quarter byte counted for it.
-        const size_t style_room = cod.cblk_style ? 8 * (size_t)(3 * c.Mb) : 0;
-        const size_t outcap = round_up(symcap / 4 + 64 + style_room, 16);
+        const CblkCaps caps = cblk_capacities(area, c.Mb, cod.cblk_style);
+        const size_t symcap = caps.sym, outcap = caps.out;
         d.sym_off = sym_off; d.sym_cap = (unsigned)symcap;
         d.out_off = out_off; d.out_cap = (unsigned)outcap;
         d.stepsize = c.stepsize;
@@ -1876,10 +1888,11 @@ int j2k_hip_stage_dwt(j2k_hip_encoder *e, int reversible, uint32_t width, uint32
     });
 }
 
-int j2k_hip_stage_t1_passes(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
-                            const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
-                            const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
-                            void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist);
+// the three Tier-1 stage hooks are one function: pass_rate / pass_dist on request, a code-block style or none
+static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                           const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
+                           const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
+                           void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist, uint32_t cblk_style);
 
 int j2k_hip_stage_t1(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
                      const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
@@ -1895,8 +1908,32 @@ int j2k_hip_stage_t1_passes(j2k_hip_encoder *e, int reversible, void *d_coef, ui
                             const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
                             void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist)
 {
+    return stage_t1_blocks(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses, length,
+                           offsets, data, data_cap, pass_rate, pass_dist, 0);
+}
+
+// No pass_dist here, and so no branch that refuses it under bypass: launch_t1_model picks the distortion instantiation
+// (want_dist) before it looks at the bypass bit, and a block modelled that way would hand the raw passes sign XOR
+// prediction.  A style excludes rate control in a frame too (geometry.cpp).
+int j2k_hip_stage_t1_styled(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                            const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
+                            const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
+                            void *data, size_t data_cap, uint32_t *pass_rate, uint32_t cblk_style)
+{
+    return stage_t1_blocks(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses, length,
+                           offsets, data, data_cap, pass_rate, nullptr, cblk_style);
+}
+
+static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                           const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
+                           const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
+                           void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist, uint32_t cblk_style)
+{
     if (!e) return J2K_HIP_ERR_PARAM;
     return guarded(e, [&] {
+        // the styles a frame refuses (geometry.cpp)
+        if (cblk_style & kStyleVcausal) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: vertically causal contexts (bit 8) are not written");
+        if (cblk_style & ~(uint32_t)(kStylesEncoded | kStyleVcausal)) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: unknown code-block style bits");
         HIP_CHECK(hipSetDevice(e->device));
         hipStream_t s = e->stream;
         const size_t nb = nblocks;
@@ -1907,8 +1944,8 @@ int j2k_hip_stage_t1_passes(j2k_hip_encoder *e, int reversible, void *d_coef, ui
             CblkDev d{};
             d.coef_off = (unsigned long long)by[i] * stride + bx[i];
             const size_t area = (size_t)bw[i] * bh[i];
-            const size_t symcap = round_up(area * 3 * 30 / 2 + area + 64, 1024);
-            const size_t outcap = round_up(symcap / 4 + 64, 16);
+            const CblkCaps caps = cblk_capacities(area, 30, cblk_style); // (Mb = 30: no band is known here; a frame's are smaller)
+            const size_t symcap = caps.sym, outcap = caps.out;
             d.sym_off = sym_off; d.sym_cap = (unsigned)symcap; d.out_off = out_off; d.out_cap = (unsigned)outcap;
             d.stepsize = stepsize ? stepsize[i] : 1.0f;
             d.w = (unsigned short)bw[i]; d.h = (unsigned short)bh[i]; d.orient = (unsigned char)orient[i]; d.Mb = 30;
@@ -1945,12 +1982,14 @@ int j2k_hip_stage_t1_passes(j2k_hip_encoder *e, int reversible, void *d_coef, ui
         ta.pass_rate = e->passes.as<uint32_t>() + 2 * nb * kDevMaxPasses;
         ta.want_dist = pass_dist != nullptr; // the distortion sums cost LDS and issue slots: only on request
         ta.sparse = tuning().t1_sparse;
+        ta.style = cblk_style;
 #ifdef J2K_T1_COUNTERS
         t1_counters(ta);
 #endif
         HIP_CHECK(hipMemsetAsync(ta.err, 0, sizeof(uint32_t), s));
         launch_t1_model(ta, s);
         launch_t1_mq(ta, s);
+        if (cblk_style) launch_t1_rate_fixup(ta, s); // as a styled frame has them: on the device, behind the styled coder
         std::vector<uint32_t> hm(4 * nb + 1);
         HIP_CHECK(hipMemcpyAsync(hm.data(), meta, hm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
@@ -1969,13 +2008,15 @@ int j2k_hip_stage_t1_passes(j2k_hip_encoder *e, int reversible, void *d_coef, ui
             for (size_t i = 0; i < nb; ++i) {
                 const uint32_t np = npasses[i];
                 uint32_t *rate = hp.data() + 2 * nb * kDevMaxPasses + i * kDevMaxPasses;
-                // the reference's fix-ups of the per-pass byte counts: an estimate never exceeds what
-                // follows it, and a pass never ends on 0xFF
-                uint32_t last = length[i];
-                for (uint32_t p = np; p > 0;) { --p; if (rate[p] > last) rate[p] = last; else last = rate[p]; }
-                const uint8_t *bytes = static_cast<const uint8_t *>(data) + offsets[i];
-                for (uint32_t p = 0; p < np; ++p)
-                    if (rate[p] > 0 && bytes[rate[p] - 1] == 0xff) --rate[p];
+                if (!cblk_style) {
+                    // the reference's fix-ups of the per-pass byte counts: an estimate never exceeds what
+                    // follows it, and a pass never ends on 0xFF  (under a style the kernel above has applied them)
+                    uint32_t last = length[i];
+                    for (uint32_t p = np; p > 0;) { --p; if (rate[p] > last) rate[p] = last; else last = rate[p]; }
+                    const uint8_t *bytes = static_cast<const uint8_t *>(data) + offsets[i];
+                    for (uint32_t p = 0; p < np; ++p)
+                        if (rate[p] > 0 && bytes[rate[p] - 1] == 0xff) --rate[p];
+                }
                 for (uint32_t p = 0; p < (uint32_t)kDevMaxPasses; ++p) {
                     if (pass_rate) pass_rate[i * kDevMaxPasses + p] = p < np ? rate[p] : 0;
                     if (pass_dist) pass_dist[i * kDevMaxPasses + p] = p < np ? (int32_t)hp[nb * kDevMaxPasses + i * kDevMaxPasses + p] : 0;

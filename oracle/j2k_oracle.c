@@ -283,6 +283,10 @@ typedef struct {
     uint8_t idx[NCTX], mps[NCTX];
     uint8_t *sym; size_t sym_cap, nsym; /* optional symbol trace */
     int overflow;
+    int raw;                 /* the open segment is a raw one (D.6) */
+    uint32_t pk_acc;         /* its bit packer: see bypass_open */
+    int pk_have, pk_room, pk_any, pk_after_ff;
+    j2ko_t1_events ev;       /* what the terminations met (test steering) */
 } mqc_t;
 
 static void mq_init(mqc_t *q, uint8_t *buf, size_t cap)
@@ -295,6 +299,16 @@ static void mq_init(mqc_t *q, uint8_t *buf, size_t cap)
     buf[0] = 0;
     q->start = buf + 1; q->bp = buf; q->end = buf + cap;
     q->overflow = 0;
+    q->raw = 0;
+    memset(&q->ev, 0, sizeof q->ev);
+}
+
+/* D.7 (code-block style RESET): every context back to its initial state */
+static void mq_reset_contexts(mqc_t *q)
+{
+    memset(q->idx, 0, sizeof q->idx);
+    memset(q->mps, 0, sizeof q->mps);
+    q->idx[CTX_UNI] = 46; q->idx[CTX_RL] = 3; q->idx[CTX_ZC] = 4;
 }
 
 static void mq_byteout(mqc_t *q)
@@ -325,7 +339,6 @@ static void mq_renorm(mqc_t *q)
 
 static void mq_encode(mqc_t *q, int ctx, int d)
 {
-    if (q->sym) { if (q->nsym < q->sym_cap) q->sym[q->nsym] = (uint8_t)((ctx << 1) | d); q->nsym++; }
     const mq_state_t *s = &MQ_TABLE[q->idx[ctx]];
     const uint32_t qe = s->qe;
     if (q->mps[ctx] == d) { /* CODEMPS */
@@ -357,6 +370,102 @@ static void mq_flush(mqc_t *q)
 }
 
 static int mq_numbytes(const mqc_t *q) { return (int)(q->bp - q->start); }
+
+/* D.4.2 predictable termination (libopenjp2: opj_mqc_erterm_enc).  The closing byte-out only moves bp behind the
+ * segment's last byte; what it writes there is not counted. */
+static void mq_erterm(mqc_t *q)
+{
+    int k = 11 - (int)q->ct + 1;
+    while (k > 0) {
+        q->c <<= q->ct; q->ct = 0;
+        mq_byteout(q);
+        k -= (int)q->ct;
+    }
+    if (*q->bp != 0xff) mq_byteout(q);
+}
+
+/* A further MQ segment in the same block: INITENC (C.2.8) again, except that the byte pointer moves back one place, so
+ * that the byte which closed the segment before plays the part of the byte in front of the first one.  The first
+ * byte-out overwrites nothing there: the code register is below 2^27 then, so no carry goes into it. */
+static void mq_next_segment(mqc_t *q)
+{
+    q->bp -= 1;
+    q->a = 0x8000; q->c = 0;
+    q->ct = (*q->bp == 0xff) ? 13 : 12;
+    if (q->ct == 13) q->ev.restart_ct13++;
+    q->raw = 0;
+}
+
+/* D.5 segmentation symbol: 1 0 1 0 in the UNIFORM context at the end of a cleanup pass */
+static void mq_segmark(mqc_t *q)
+{
+    for (int i = 1; i < 5; i++) mq_encode(q, CTX_UNI, i % 2);
+}
+
+/* D.6, selective arithmetic-coding bypass: a bit packer on the same byte buffer.  pk_acc gathers the bits of the byte
+ * under construction, most significant first, pk_have counts them, pk_room is how many that byte holds: 8, or 7 when the
+ * byte in front of it is 0xFF (bit stuffing).  pk_any: the segment has received a bit.  Here bp is the place of the byte
+ * under construction. */
+static void bypass_open(mqc_t *q)
+{
+    q->raw = 1;
+    q->pk_acc = 0; q->pk_have = 0; q->pk_room = 8; q->pk_any = 0; q->pk_after_ff = 0;
+}
+
+static void bypass_store(mqc_t *q)
+{
+    if (q->bp + 2 >= q->end) { q->overflow = 1; q->bp = q->start; }
+    *q->bp++ = (uint8_t)q->pk_acc;
+    q->pk_after_ff = q->pk_acc == 0xff;
+    q->pk_room = q->pk_after_ff ? 7 : 8;
+    q->pk_acc = 0; q->pk_have = 0;
+}
+
+static void bypass_bit(mqc_t *q, int d)
+{
+    if (q->pk_after_ff) { q->ev.raw_ff_inside++; q->pk_after_ff = 0; } /* this 0xFF is not the segment's last byte */
+    q->pk_any = 1;
+    q->pk_acc = (q->pk_acc << 1) | (uint32_t)(d & 1);
+    if (++q->pk_have == q->pk_room) bypass_store(q);
+}
+
+/* Does the byte under construction add to the byte count?  libopenjp2 (opj_mqc_bypass_get_extra_bytes) decides by the
+ * number of bit places still free in it: fewer than 7, yes; exactly 7, only if the byte in front is not 0xFF or the
+ * termination is the predictable one; 8, or no bit in the segment at all, no. */
+static int bypass_tail_counts(const mqc_t *q, int pterm)
+{
+    if (!q->pk_any) return 0;
+    const int vacant = q->pk_room - q->pk_have;
+    if (vacant == 7) return pterm || q->bp[-1] != 0xff;
+    return vacant < 7;
+}
+
+/* The end of a raw segment as libopenjp2 writes it (opj_mqc_bypass_flush_enc).  A counted tail byte is completed with
+ * 0 1 0 1 ...  Otherwise a segment may not end in 0xFF: that byte is given up.  Nor, unless the termination is the
+ * predictable one, need it end in 0xFF 0x7F: a decoder that runs out of bytes supplies one bits, which is what the
+ * pair says, so both are given up. */
+static void bypass_close(mqc_t *q, int pterm)
+{
+    if (!q->pk_any) return;
+    const int vacant = q->pk_room - q->pk_have;
+    const int pair = vacant == 8 && q->bp[-2] == 0xff && q->bp[-1] == 0x7f;
+    if (pair) { if (pterm) q->ev.raw_ff7f_kept++; else q->ev.raw_ff7f_dropped++; }
+    if (bypass_tail_counts(q, pterm)) {
+        for (int fill = 0; q->pk_have < q->pk_room; fill ^= 1) { q->pk_acc = (q->pk_acc << 1) | (uint32_t)fill; q->pk_have++; }
+        bypass_store(q);
+    } else if (vacant == 7 && q->bp[-1] == 0xff) {
+        q->bp -= 1; q->ev.raw_ff_dropped++;
+    } else if (pair && !pterm) {
+        q->bp -= 2;
+    }
+}
+
+/* one decision of the bit modelling: traced as (context << 1) | bit, then MQ-coded or written as a raw bit */
+static void t1_code(mqc_t *q, int ctx, int d)
+{
+    if (q->sym) { if (q->nsym < q->sym_cap) q->sym[q->nsym] = (uint8_t)((ctx << 1) | d); q->nsym++; }
+    if (q->raw) bypass_bit(q, d); else mq_encode(q, ctx, d);
+}
 
 /* ------------------------------------------------------------------ A8 : bit modelling (Annex D) */
 #define F_SIG 1
@@ -451,7 +560,7 @@ static void code_sign_and_set(t1_t *t, mqc_t *q, int x, int y, int neg)
 {
     int xb;
     const int c = sc_context(t, x, y, &xb);
-    mq_encode(q, c, neg ^ xb);
+    t1_code(q, c, q->raw ? neg : neg ^ xb); /* a raw bit is the sign itself (D.6) */
     FL(t, x, y) |= (uint8_t)(F_SIG | (neg ? F_NEG : 0));
 }
 
@@ -465,7 +574,7 @@ static void pass_sig(t1_t *t, mqc_t *q, const uint8_t *neg, int bpno, int *nmsed
                 if ((f & (F_SIG | F_VISIT)) == 0 && any_sig_neighbour(t, x, y)) {
                     const uint32_t m = t->mag[y * t->w + x];
                     const int v = (m & one) ? 1 : 0;
-                    mq_encode(q, CTX_ZC + zc_context(t, x, y), v);
+                    t1_code(q, CTX_ZC + zc_context(t, x, y), v);
                     if (v) {
                         *nmsedec += nmsedec_sig(m, bpno);
                         code_sign_and_set(t, q, x, y, neg[y * t->w + x]);
@@ -486,7 +595,7 @@ static void pass_ref(t1_t *t, mqc_t *q, int bpno, int *nmsedec)
                     const uint32_t m = t->mag[y * t->w + x];
                     const int ctx = (f & F_REFINE) ? 16 : (any_sig_neighbour(t, x, y) ? 15 : 14);
                     *nmsedec += nmsedec_ref(m, bpno);
-                    mq_encode(q, ctx, (m & one) ? 1 : 0);
+                    t1_code(q, ctx, (m & one) ? 1 : 0);
                     FL(t, x, y) |= F_REFINE;
                 }
             }
@@ -507,10 +616,10 @@ static void pass_cln(t1_t *t, mqc_t *q, const uint8_t *neg, int bpno, int *nmsed
                     int runlen = 0;
                     for (; runlen < 4; runlen++)
                         if (t->mag[(k + runlen) * t->w + x] & one) break;
-                    mq_encode(q, CTX_RL, runlen != 4);
+                    t1_code(q, CTX_RL, runlen != 4);
                     if (runlen == 4) continue;
-                    mq_encode(q, CTX_UNI, runlen >> 1);
-                    mq_encode(q, CTX_UNI, runlen & 1);
+                    t1_code(q, CTX_UNI, runlen >> 1);
+                    t1_code(q, CTX_UNI, runlen & 1);
                     ystart = k + runlen;
                     partial = 1;
                 }
@@ -525,7 +634,7 @@ static void pass_cln(t1_t *t, mqc_t *q, const uint8_t *neg, int bpno, int *nmsed
                 } else if ((f & (F_SIG | F_VISIT)) == 0) {
                     const uint32_t m = t->mag[y * t->w + x];
                     const int v = (m & one) ? 1 : 0;
-                    mq_encode(q, CTX_ZC + zc_context(t, x, y), v);
+                    t1_code(q, CTX_ZC + zc_context(t, x, y), v);
                     if (v) {
                         *nmsedec += nmsedec_sig(m, bpno);
                         code_sign_and_set(t, q, x, y, neg[y * t->w + x]);
@@ -536,10 +645,28 @@ static void pass_cln(t1_t *t, mqc_t *q, const uint8_t *neg, int bpno, int *nmsed
         }
 }
 
-int j2ko_t1_encode_block(const int32_t *data, int w, int h, int orient, uint8_t *out, size_t out_cap,
-                         int *numbps_out, int *pass_rate, int *pass_nmsedec, uint8_t *sym,
-                         size_t sym_cap, size_t *nsym, int *pass_nsym)
+/* Which passes go out as raw bits and which ones end a codeword segment, as libopenjp2 decides them from the bit-plane
+ * and the kind of the pass (opj_t1_encode_cblk, opj_t1_enc_is_term_pass).  passtype 0 significance, 1 refinement, 2 cleanup. */
+static int pass_is_raw(int style, int numbps, int bpno, int passtype)
 {
+    return (style & J2KO_STYLE_BYPASS) && bpno < numbps - 4 && passtype < 2;
+}
+static int pass_is_terminated(int style, int numbps, int bpno, int passtype)
+{
+    if (passtype == 2 && bpno == 0) return 1;                  /* the last pass of the block */
+    if (style & J2KO_STYLE_TERMALL) return 1;
+    if (style & J2KO_STYLE_BYPASS) {
+        if (bpno == numbps - 4 && passtype == 2) return 1;     /* the cleanup pass in front of the first raw pass */
+        if (bpno < numbps - 4 && passtype > 0) return 1;       /* then every raw pair and every cleanup pass */
+    }
+    return 0;
+}
+
+int j2ko_t1_encode_block_styled(const int32_t *data, int w, int h, int orient, int style, uint8_t *out, size_t out_cap,
+                                int *numbps_out, int *pass_rate, int *pass_nmsedec, int *pass_term, uint8_t *sym,
+                                size_t sym_cap, size_t *nsym, int *pass_nsym, j2ko_t1_events *events)
+{
+    if (style & ~J2KO_STYLES_CODED) return -2; /* vertically causal contexts (8) and unknown bits */
     init_luts();
     const size_t n = (size_t)w * h;
     uint32_t *mag = (uint32_t *)malloc(n * sizeof(uint32_t));
@@ -555,6 +682,7 @@ int j2ko_t1_encode_block(const int32_t *data, int w, int h, int orient, uint8_t 
     if (numbps < 0) numbps = 0;
     if (numbps_out) *numbps_out = numbps;
     if (nsym) *nsym = 0;
+    if (events) memset(events, 0, sizeof *events);
     int npasses = 0;
     if (numbps > 0) {
         t1_t t;
@@ -564,21 +692,42 @@ int j2ko_t1_encode_block(const int32_t *data, int w, int h, int orient, uint8_t 
         mqc_t q;
         mq_init(&q, buf, out_cap + 8);
         q.sym = sym; q.sym_cap = sym_cap; q.nsym = 0;
-        int passtype = 2;
+        const int pterm = (style & J2KO_STYLE_PTERM) != 0;
+        int passtype = 2, prev_term = 0, prev_raw_empty = 0, raw_start = 0;
         for (int bpno = numbps - 1; bpno >= 0;) {
             int nm = 0;
+            const int raw = pass_is_raw(style, numbps, bpno, passtype);
+            if (prev_term) { /* the segment before is closed: open the next one */
+                if (raw) { bypass_open(&q); raw_start = mq_numbytes(&q); }
+                else { mq_next_segment(&q); if (prev_raw_empty) q.ev.mq_after_empty_raw++; }
+            }
+            const size_t nsym_before = q.nsym;
             switch (passtype) {
                 case 0: pass_sig(&t, &q, neg, bpno, &nm); break;
                 case 1: pass_ref(&t, &q, bpno, &nm); break;
-                default: pass_cln(&t, &q, neg, bpno, &nm); break;
+                default:
+                    pass_cln(&t, &q, neg, bpno, &nm);
+                    if (style & J2KO_STYLE_SEGSYM) { mq_segmark(&q); if (q.nsym == nsym_before) q.ev.segsym_alone++; }
+                    break;
             }
-            const int last = (passtype == 2 && bpno == 0);
-            if (last) { mq_flush(&q); pass_rate[npasses] = mq_numbytes(&q); }
-            else pass_rate[npasses] = mq_numbytes(&q) + 3;
+            const int term = pass_is_terminated(style, numbps, bpno, passtype);
+            if (term) {
+                if (raw) bypass_close(&q, pterm);
+                else if (pterm) mq_erterm(&q);
+                else mq_flush(&q);
+                prev_raw_empty = raw && mq_numbytes(&q) == raw_start; /* no bit, or all of its bytes taken back */
+                q.ev.raw_empty += prev_raw_empty;
+                pass_rate[npasses] = mq_numbytes(&q);
+            } else {
+                pass_rate[npasses] = mq_numbytes(&q) + (raw ? bypass_tail_counts(&q, pterm) : 3);
+            }
+            prev_term = term;
+            if (pass_term) pass_term[npasses] = term;
             pass_nmsedec[npasses] = nm;
             if (pass_nsym) pass_nsym[npasses] = (int)q.nsym;
             npasses++;
             if (++passtype == 3) { passtype = 0; bpno--; }
+            if (style & J2KO_STYLE_RESET) mq_reset_contexts(&q);
         }
         /* rate fix-ups: make rates non-decreasing from the end, never end a pass on 0xFF */
         int last_rate = mq_numbytes(&q);
@@ -592,12 +741,21 @@ int j2ko_t1_encode_block(const int32_t *data, int w, int h, int orient, uint8_t 
         if (q.overflow || (size_t)total > out_cap) { npasses = -1; }
         else memcpy(out, q.start, (size_t)total);
         if (nsym) *nsym = q.nsym;
+        if (events) *events = q.ev;
         free(buf);
         free(t.flags);
     }
     free(mag);
     free(neg);
     return npasses;
+}
+
+int j2ko_t1_encode_block(const int32_t *data, int w, int h, int orient, uint8_t *out, size_t out_cap,
+                         int *numbps_out, int *pass_rate, int *pass_nmsedec, uint8_t *sym,
+                         size_t sym_cap, size_t *nsym, int *pass_nsym)
+{
+    return j2ko_t1_encode_block_styled(data, w, h, orient, 0, out, out_cap, numbps_out, pass_rate, pass_nmsedec, NULL,
+                                       sym, sym_cap, nsym, pass_nsym, NULL);
 }
 
 int j2ko_included_passes(int npasses, const int *pass_rate, const int *pass_nmsedec)
@@ -738,6 +896,7 @@ typedef struct {
     int sofar, numlenbits;   /* Tier-2 state across layers */
     uint8_t *data;
     int pass_rate[100], pass_nmsedec[100];
+    int pass_term[100];      /* the pass ends a codeword segment (code-block styles) */
     double pass_disto[100];  /* cumulative weighted distortion decrease up to each pass (rate control) */
     int alloc;               /* passes already assigned to finished layers (rate control) */
     int *lay_np, *lay_len, *lay_off; /* per layer: passes, bytes, offset of the bytes in data */
@@ -758,10 +917,22 @@ typedef struct {
 
 typedef struct {
     int x0, y0, x1, y1, pw, ph, nbands;
+    int ppx, ppy;            /* log2 of the precinct size */
     band_t bands[3];
 } res_t;
 
 static int band_empty(const band_t *b) { return b->x1 - b->x0 == 0 || b->y1 - b->y0 == 0; }
+
+/* log2 precinct size of resolution r (B.6; libopenjp2's opj_j2k_setup_encoder for sizes given highest resolution first) */
+static void precinct_exps(const j2ko_params *p, int r, int *ppx, int *ppy)
+{
+    if (p->nprec <= 0) { *ppx = *ppy = 15; return; }
+    const int k = p->numres - 1 - r; /* position in the list */
+    int w, h;
+    if (k < p->nprec) { w = p->prcw[k]; h = p->prch[k]; }
+    else { w = p->prcw[p->nprec - 1] >> (k - (p->nprec - 1)); h = p->prch[p->nprec - 1] >> (k - (p->nprec - 1)); }
+    *ppx = floorlog2(imax(w, 1)); *ppy = floorlog2(imax(h, 1));
+}
 
 static void write_main_header(bytes_t *o, const j2ko_params *p, int tw, int th, const char *comment)
 {
@@ -771,10 +942,16 @@ static void write_main_header(bytes_t *o, const j2ko_params *p, int tw, int th, 
     put32(o, (uint32_t)tw); put32(o, (uint32_t)th); put32(o, 0); put32(o, 0);
     put16(o, (unsigned)p->ncomp);
     for (int c = 0; c < p->ncomp; c++) { put8(o, (unsigned)(p->prec - 1)); put8(o, 1); put8(o, 1); }
-    put16(o, 0xff52); put16(o, 12); put8(o, 0);
+    put16(o, 0xff52); put16(o, (unsigned)(12 + (p->nprec > 0 ? p->numres : 0))); put8(o, p->nprec > 0 ? 1 : 0);
     put8(o, (unsigned)p->prog); put16(o, (unsigned)p->layers); put8(o, p->mct ? 1 : 0);
     put8(o, (unsigned)(p->numres - 1)); put8(o, (unsigned)(p->cblkw_exp - 2)); put8(o, (unsigned)(p->cblkh_exp - 2));
-    put8(o, 0); put8(o, p->reversible ? 1 : 0);
+    put8(o, (unsigned)p->mode); put8(o, p->reversible ? 1 : 0);
+    if (p->nprec > 0)
+        for (int r = 0; r < p->numres; r++) {
+            int ppx, ppy;
+            precinct_exps(p, r, &ppx, &ppy);
+            put8(o, (unsigned)(ppx | (ppy << 4)));
+        }
     const int nbands = 3 * p->numres - 2;
     put16(o, 0xff5c);
     put16(o, (unsigned)(p->reversible ? 3 + nbands : 3 + 2 * nbands));
@@ -833,6 +1010,32 @@ static void t2_one_packet(bytes_t *o, const j2ko_params *p, res_t *res, int l, i
                             if (!np) continue;
                             if (!C->sofar) { C->numlenbits = 3; tgt_encode(&bio, P->imsb, k, 999); }
                             put_numpasses(&bio, np);
+                            if (p->mode & (J2KO_STYLE_BYPASS | J2KO_STYLE_TERMALL)) {
+                                /* B.10.7.2: one length per terminated codeword segment among the passes of this packet (the
+                                 * last one ends with the packet's last pass, terminated or not), each in
+                                 * Lblock + floor(log2(passes of the segment)) bits; Lblock rises once for all of them */
+                                const int first = C->sofar;
+                                int inc = 0;
+                                for (int pass = first, nump = 0, len = 0; pass < first + np; pass++) {
+                                    nump++;
+                                    len += C->pass_rate[pass] - (pass ? C->pass_rate[pass - 1] : 0);
+                                    if (C->pass_term[pass] || pass == first + np - 1) {
+                                        inc = imax(inc, floorlog2(len) + 1 - (C->numlenbits + floorlog2(nump)));
+                                        nump = 0; len = 0;
+                                    }
+                                }
+                                put_commacode(&bio, inc);
+                                C->numlenbits += inc;
+                                for (int pass = first, nump = 0, len = 0; pass < first + np; pass++) {
+                                    nump++;
+                                    len += C->pass_rate[pass] - (pass ? C->pass_rate[pass - 1] : 0);
+                                    if (C->pass_term[pass] || pass == first + np - 1) {
+                                        bio_write(&bio, (uint32_t)len, C->numlenbits + floorlog2(nump));
+                                        nump = 0; len = 0;
+                                    }
+                                }
+                                continue;
+                            }
                             const int llen = C->lay_len[l];
                             const int need = floorlog2(llen) + 1 - (C->numlenbits + floorlog2(np));
                             const int inc = imax(0, need);
@@ -860,7 +1063,32 @@ static void t2_one_packet(bytes_t *o, const j2ko_params *p, res_t *res, int l, i
 /* Packet order (T.800 B.12).  Every resolution has a single, maximal precinct here, all anchored at the
  * tile origin, so the position loops of RPCL / PCRL / CPRL visit each precinct exactly once and the five
  * progressions are plain permutations of the layer / resolution / component loops. */
-static void t2_packets(bytes_t *o, const j2ko_params *p, res_t *res, int maxlayers)
+/* RPCL with precincts of any size (B.12.1.3): the positions of the tile at which a precinct of resolution r begins, in
+ * raster order; all components are sampled alike here. */
+static void t2_packets_rpcl(bytes_t *o, const j2ko_params *p, res_t *res, int maxlayers, int tx0, int ty0, int tx1, int ty1)
+{
+    const int NL = p->numres - 1;
+    int dx = 0, dy = 0; /* the finest grid on which any precinct of any resolution begins */
+    for (int r = 0; r < p->numres; r++) {
+        const int sx = 1 << imin(res[r].ppx + NL - r, 30), sy = 1 << imin(res[r].ppy + NL - r, 30);
+        dx = dx ? imin(dx, sx) : sx; dy = dy ? imin(dy, sy) : sy;
+    }
+    for (int r = 0; r < p->numres; r++)
+        for (int y = ty0; y < ty1; y += dy - (y % dy))
+            for (int x = tx0; x < tx1; x += dx - (x % dx))
+                for (int c = 0; c < p->ncomp; c++) {
+                    const res_t *R = &res[c * p->numres + r];
+                    const int lvl = NL - r, rpx = imin(R->ppx + lvl, 30), rpy = imin(R->ppy + lvl, 30);
+                    if (!((y % (1 << rpy) == 0) || (y == ty0 && (((int64_t)R->y0 << lvl) % (1 << rpy))))) continue;
+                    if (!((x % (1 << rpx) == 0) || (x == tx0 && (((int64_t)R->x0 << lvl) % (1 << rpx))))) continue;
+                    if (R->pw == 0 || R->ph == 0 || R->x0 == R->x1 || R->y0 == R->y1) continue;
+                    const int prci = floordivpow2(ceildivpow2(x, lvl), R->ppx) - floordivpow2(R->x0, R->ppx);
+                    const int prcj = floordivpow2(ceildivpow2(y, lvl), R->ppy) - floordivpow2(R->y0, R->ppy);
+                    for (int l = 0; l < maxlayers; l++) t2_one_packet(o, p, res, l, r, c, prci + prcj * R->pw);
+                }
+}
+
+static void t2_packets(bytes_t *o, const j2ko_params *p, res_t *res, int maxlayers, int tx0, int ty0, int tx1, int ty1)
 {
 #define PREC_LOOP(l, r, c) for (int pn = 0; pn < res[(c) * p->numres + (r)].pw * res[(c) * p->numres + (r)].ph; pn++) t2_one_packet(o, p, res, l, r, c, pn)
     switch (p->prog) {
@@ -868,6 +1096,7 @@ static void t2_packets(bytes_t *o, const j2ko_params *p, res_t *res, int maxlaye
             for (int r = 0; r < p->numres; r++) for (int l = 0; l < maxlayers; l++) for (int c = 0; c < p->ncomp; c++) PREC_LOOP(l, r, c);
             break;
         case 2: /* RPCL */
+            if (p->nprec > 0) { t2_packets_rpcl(o, p, res, maxlayers, tx0, ty0, tx1, ty1); break; }
             for (int r = 0; r < p->numres; r++) for (int c = 0; c < p->ncomp; c++) for (int l = 0; l < maxlayers; l++) PREC_LOOP(l, r, c);
             break;
         case 3: /* PCRL */
@@ -1051,7 +1280,7 @@ static void rate_allocate(const j2ko_params *p, res_t *res, const float *ratios,
                 thresh = (lo + hi) / 2;
                 make_layer(p, res, layno, thresh, 0);
                 bytes_t tmp = {scratch, cap, 0, 0};
-                t2_packets(&tmp, p, res, layno + 1);
+                t2_packets(&tmp, p, res, layno + 1, tx0, ty0, tx1, ty1);
                 if ((double)tmp.len > maxlen) { lo = thresh; continue; }
                 hi = thresh;
                 stable = thresh;
@@ -1084,7 +1313,6 @@ static int encode_tile(bytes_t *o, const j2ko_params *p, const int32_t *planes, 
     }
 
     /* ---- geometry (T.800 B.5-B.7) */
-    const int PP = 15;
     res_t *res = (res_t *)calloc((size_t)p->ncomp * p->numres, sizeof(res_t));
     int32_t *blk = (int32_t *)malloc(sizeof(int32_t) << (p->cblkw_exp + p->cblkh_exp));
     for (int c = 0; c < p->ncomp; c++) {
@@ -1093,14 +1321,16 @@ static int encode_tile(bytes_t *o, const j2ko_params *p, const int32_t *planes, 
             const int lvl = NL - r;
             R->x0 = ceildivpow2(tx0, lvl); R->y0 = ceildivpow2(ty0, lvl);
             R->x1 = ceildivpow2(tx1, lvl); R->y1 = ceildivpow2(ty1, lvl);
-            const int tlprcx = floordivpow2(R->x0, PP) << PP, tlprcy = floordivpow2(R->y0, PP) << PP;
-            const int brprcx = ceildivpow2(R->x1, PP) << PP, brprcy = ceildivpow2(R->y1, PP) << PP;
-            R->pw = (R->x0 == R->x1) ? 0 : ((brprcx - tlprcx) >> PP);
-            R->ph = (R->y0 == R->y1) ? 0 : ((brprcy - tlprcy) >> PP);
+            precinct_exps(p, r, &R->ppx, &R->ppy);
+            const int PPx = R->ppx, PPy = R->ppy;
+            const int tlprcx = floordivpow2(R->x0, PPx) << PPx, tlprcy = floordivpow2(R->y0, PPy) << PPy;
+            const int brprcx = ceildivpow2(R->x1, PPx) << PPx, brprcy = ceildivpow2(R->y1, PPy) << PPy;
+            R->pw = (R->x0 == R->x1) ? 0 : ((brprcx - tlprcx) >> PPx);
+            R->ph = (R->y0 == R->y1) ? 0 : ((brprcy - tlprcy) >> PPy);
             const int nprec = R->pw * R->ph;
             int tlcbgx, tlcbgy, cbgw, cbgh;
-            if (r == 0) { tlcbgx = tlprcx; tlcbgy = tlprcy; cbgw = PP; cbgh = PP; R->nbands = 1; }
-            else { tlcbgx = ceildivpow2(tlprcx, 1); tlcbgy = ceildivpow2(tlprcy, 1); cbgw = PP - 1; cbgh = PP - 1; R->nbands = 3; }
+            if (r == 0) { tlcbgx = tlprcx; tlcbgy = tlprcy; cbgw = PPx; cbgh = PPy; R->nbands = 1; }
+            else { tlcbgx = ceildivpow2(tlprcx, 1); tlcbgy = ceildivpow2(tlprcy, 1); cbgw = PPx - 1; cbgh = PPy - 1; R->nbands = 3; }
             const int cbw = imin(p->cblkw_exp, cbgw), cbh = imin(p->cblkh_exp, cbgh);
             for (int bi = 0; bi < R->nbands; bi++) {
                 band_t *B = &R->bands[bi];
@@ -1148,10 +1378,11 @@ static int encode_tile(bytes_t *o, const j2ko_params *p, const int32_t *planes, 
                                 blk[y * w + x] = p->reversible ? j2ko_quant53(comp[c][idx])
                                                                : j2ko_quant97(((float *)comp[c])[idx], B->stepsize);
                             }
-                        const size_t cap = (size_t)w * h * 4 + 64;
+                        /* (a style adds a few bytes at every terminated pass) */
+                        const size_t cap = (size_t)w * h * 4 + 64 + (p->mode ? 8 * 100 : 0);
                         C->data = (uint8_t *)malloc(cap);
-                        C->npasses_total = j2ko_t1_encode_block(blk, w, h, B->orient, C->data, cap, &C->numbps,
-                                                                C->pass_rate, C->pass_nmsedec, NULL, 0, NULL, NULL);
+                        C->npasses_total = j2ko_t1_encode_block_styled(blk, w, h, B->orient, p->mode, C->data, cap, &C->numbps,
+                                                                       C->pass_rate, C->pass_nmsedec, C->pass_term, NULL, 0, NULL, NULL, NULL);
                         if (C->npasses_total < 0) return -1;
                         C->npasses_incl = j2ko_included_passes(C->npasses_total, C->pass_rate, C->pass_nmsedec);
                         C->len = C->npasses_incl ? C->pass_rate[C->npasses_incl - 1] : 0;
@@ -1179,7 +1410,7 @@ static int encode_tile(bytes_t *o, const j2ko_params *p, const int32_t *planes, 
     const size_t sot_pos = o->len;
     put16(o, 0xff90); put16(o, 10); put16(o, (unsigned)tileno); put32(o, 0); put8(o, 0); put8(o, 1);
     put16(o, 0xff93);
-    t2_packets(o, p, res, p->layers);
+    t2_packets(o, p, res, p->layers, tx0, ty0, tx1, ty1);
     if (!o->overflow) {
         const uint32_t psot = (uint32_t)(o->len - sot_pos);
         o->buf[sot_pos + 6] = (uint8_t)(psot >> 24); o->buf[sot_pos + 7] = (uint8_t)(psot >> 16);
@@ -1244,6 +1475,8 @@ static long encode_all(const j2ko_params *p, const int32_t *planes, uint8_t *out
     if (p->ncomp < 1 || p->ncomp > 4 || p->prec < 1 || p->prec > 16 || p->numres < 1 || p->numres > 33) return -2;
     if (p->mct && p->ncomp < 3) return -2;
     if (p->prog < 0 || p->prog > 4) return -2;
+    if ((p->mode & ~J2KO_STYLES_CODED) || (p->mode && (rates || g_psnr))) return -2; /* rate control does not price codeword segments */
+    if (p->nprec < 0 || p->nprec > 8 || (p->nprec && p->prog > 2)) return -2;
     bytes_t o = {out, cap, 0, 0};
     const int tw = p->tile_w > 0 ? p->tile_w : p->width, th = p->tile_h > 0 ? p->tile_h : p->height;
     write_main_header(&o, p, tw, th, comment);

@@ -27,7 +27,27 @@ typedef struct j2ko_params {
     int32_t layers;                     /* tcp_numlayers (reference default 12)           */
     int32_t tile_w, tile_h;             /* 0 = untiled                                    */
     int32_t prog;                       /* 0 LRCP, 1 RLCP, 2 RPCL, 3 PCRL, 4 CPRL         */
+    int32_t mode;                       /* code-block style, COD SPcod bits (J2KO_STYLE_*); not with a rate target */
+    int32_t nprec;                      /* precinct sizes given (0: maximal precincts); LRCP, RLCP and RPCL only   */
+    int32_t prcw[8], prch[8];           /* in samples, highest resolution first; the last one halves for every      */
+                                        /* resolution below it (libopenjp2: opj_compress -c)                        */
 } j2ko_params;
+
+/* Code-block styles (T.800 Table A.19).  Vertically causal contexts (8) are not coded. */
+enum { J2KO_STYLE_BYPASS = 1, J2KO_STYLE_RESET = 2, J2KO_STYLE_TERMALL = 4, J2KO_STYLE_PTERM = 16, J2KO_STYLE_SEGSYM = 32,
+       J2KO_STYLES_CODED = 1 | 2 | 4 | 16 | 32 };
+
+/* What the coder of one block met on its way (for tests that steer blocks at these cases). */
+typedef struct j2ko_t1_events {
+    int32_t raw_ff_inside;      /* 0xFF bytes of raw segments with at least one bit behind them (seven bits follow)      */
+    int32_t raw_ff_dropped;     /* raw segments that ended on a 0xFF, which was taken back                                */
+    int32_t raw_ff7f_dropped;   /* raw segments that ended on 0xFF 0x7F, both taken back (no predictable termination)     */
+    int32_t raw_ff7f_kept;      /* raw segments that ended on 0xFF 0x7F under predictable termination: both stay          */
+    int32_t raw_empty;          /* raw segments of no bytes: without a bit, or with all their bytes taken back             */
+    int32_t mq_after_empty_raw; /* MQ segments opened right behind such a segment                                          */
+    int32_t restart_ct13;       /* MQ segments opened on a last byte 0xFF (CT = 13)                                        */
+    int32_t segsym_alone;       /* cleanup passes whose only decisions were the four segmentation symbols                 */
+} j2ko_t1_events;
 
 /* A1: AE "15+1 bit" -> 16 bit (FrameSeq.cpp:311-314) and its inverse (FrameSeq.cpp:265-268). */
 uint16_t j2ko_promote(uint16_t v);
@@ -67,6 +87,14 @@ int32_t j2ko_quant97(float c, float stepsize);
 int j2ko_t1_encode_block(const int32_t *data, int w, int h, int orient, uint8_t *out, size_t out_cap,
                          int *numbps, int *pass_rate, int *pass_nmsedec, uint8_t *sym, size_t sym_cap,
                          size_t *nsym, int *pass_nsym);
+
+/* The same under a code-block style (J2KO_STYLE_* bits; 0 = none: then exactly j2ko_t1_encode_block).  pass_term[]
+ * (optional): 1 where the pass ends a codeword segment -- pass_rate[] there is the exact end of the segment, elsewhere
+ * libopenjp2's estimate.  In raw passes the traced decision of a sign is the sign itself.  The four segmentation symbols
+ * are not in the trace.  events (optional) receives the counts above.  Returns -2 for a style that is not coded. */
+int j2ko_t1_encode_block_styled(const int32_t *data, int w, int h, int orient, int style, uint8_t *out, size_t out_cap,
+                                int *numbps, int *pass_rate, int *pass_nmsedec, int *pass_term, uint8_t *sym,
+                                size_t sym_cap, size_t *nsym, int *pass_nsym, j2ko_t1_events *events);
 
 /* number of passes layer 0 receives when there is no rate target (all of them). */
 int j2ko_included_passes(int npasses, const int *pass_rate, const int *pass_nmsedec);

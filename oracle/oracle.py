@@ -23,14 +23,26 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 class Params(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "width", "height", "ncomp", "prec", "reversible", "mct", "numres",
-        "cblkw_exp", "cblkh_exp", "layers", "tile_w", "tile_h", "prog")]
+        "cblkw_exp", "cblkh_exp", "layers", "tile_w", "tile_h", "prog", "mode", "nprec")] + \
+               [("prcw", C.c_int32 * 8), ("prch", C.c_int32 * 8)]
+
+
+class T1Events(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in (
+        "raw_ff_inside", "raw_ff_dropped", "raw_ff7f_dropped", "raw_ff7f_kept", "raw_empty", "mq_after_empty_raw",
+        "restart_ct13", "segsym_alone")]
 
 
 def make_params(width, height, ncomp, prec, reversible=True, mct=False, numres=6,
-                cblk=(64, 64), layers=1, tile=0, prog=0):
+                cblk=(64, 64), layers=1, tile=0, prog=0, mode=0, precincts=None):
+    """mode: code-block style (COD SPcod bits: 1 bypass, 2 reset, 4 termall, 16 pterm, 32 segsym); precincts: [(w, h), ...],
+    highest resolution first, as OpjReplay.encode_ext takes them."""
     tw, th = (tile, tile) if isinstance(tile, int) else tile
-    return Params(width, height, ncomp, prec, int(reversible), int(mct), numres,
-                  cblk[0].bit_length() - 1, cblk[1].bit_length() - 1, layers, tw, th, prog)
+    p = Params(width, height, ncomp, prec, int(reversible), int(mct), numres,
+               cblk[0].bit_length() - 1, cblk[1].bit_length() - 1, layers, tw, th, prog, mode, len(precincts or ()))
+    for i, (pw, ph) in enumerate(precincts or ()):
+        p.prcw[i], p.prch[i] = pw, ph
+    return p
 
 
 def build(force: bool = False) -> None:
@@ -66,6 +78,12 @@ class Oracle:
                                            C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int),
                                            C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint8),
                                            C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+        L.j2ko_t1_encode_block_styled.restype = C.c_int
+        L.j2ko_t1_encode_block_styled.argtypes = [C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.c_int), C.POINTER(T1Events)]
         L.j2ko_included_passes.restype = C.c_int
         L.j2ko_included_passes.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.j2ko_copy_channel.restype = None
@@ -174,8 +192,14 @@ class Oracle:
 
     # -- whole path -----------------------------------------------------------------------------
     def encode(self, planes: np.ndarray, params: Params, comment: str | None = None,
-               want_coefs: bool = False):
-        """planes: (ncomp, h, w) int32 of unsigned sample values (post-CopyBuffer)."""
+               want_coefs: bool = False, mode: int | None = None):
+        """planes: (ncomp, h, w) int32 of unsigned sample values (post-CopyBuffer).  mode: code-block style, in place of
+        params.mode."""
+        if mode is not None:
+            q = Params()
+            C.memmove(C.byref(q), C.byref(params), C.sizeof(Params))
+            q.mode = mode
+            params = q
         planes = np.ascontiguousarray(planes, dtype=np.int32)
         assert planes.shape == (params.ncomp, params.height, params.width)
         cap = planes.size * 4 + (1 << 20)
@@ -251,11 +275,13 @@ class Oracle:
                                C.byref(nb), C.byref(ss))
         return e.value, m.value, nb.value, ss.value
 
-    def t1_block(self, data: np.ndarray, orient: int, want_symbols: bool = False):
-        """data: (h, w) int32 already scaled (6 fractional bits)."""
+    def t1_block(self, data: np.ndarray, orient: int, style: int = 0, want_symbols: bool = False):
+        """data: (h, w) int32 already scaled (6 fractional bits).  style: code-block style bits; under one the result also
+        has seg_ends (per pass: it ends a codeword segment, `rates` there is the segment's exact end) and events (dict of
+        the j2ko_t1_events counts), and the symbols of raw passes carry the plain sign."""
         data = np.ascontiguousarray(data, dtype=np.int32)
         h, w = data.shape
-        cap = w * h * 4 + 64
+        cap = w * h * 4 + 64 + (8 * 128 if style else 0)
         out = np.empty(cap, dtype=np.uint8)
         rate = (C.c_int * 128)()
         nms = (C.c_int * 128)()
@@ -264,14 +290,21 @@ class Oracle:
         ns = C.c_size_t()
         symcap = w * h * 40 if want_symbols else 0
         sym = np.empty(max(symcap, 1), dtype=np.uint8)
-        np_ = self.L.j2ko_t1_encode_block(_i32p(data), w, h, orient, _u8p(out), cap, C.byref(nb), rate, nms,
-                                          _u8p(sym) if want_symbols else None, symcap, C.byref(ns), pns)
+        term = (C.c_int * 128)()
+        ev = T1Events()
+        np_ = self.L.j2ko_t1_encode_block_styled(_i32p(data), w, h, orient, style, _u8p(out), cap, C.byref(nb), rate, nms, term,
+                                                 _u8p(sym) if want_symbols else None, symcap, C.byref(ns), pns, C.byref(ev))
+        if np_ == -2:
+            raise ValueError(f"code-block style {style} is not coded")
         if np_ < 0:
             raise RuntimeError("t1 overflow")
         incl = self.L.j2ko_included_passes(np_, rate, nms)
         total = rate[np_ - 1] if np_ else 0
         res = dict(numbps=nb.value, npasses=np_, rates=list(rate[:np_]), nmsedec=list(nms[:np_]),
                    included=incl, length=(rate[incl - 1] if incl else 0), data=out[:total].tobytes())
+        if style:
+            res["seg_ends"] = [bool(t) for t in term[:np_]]
+            res["events"] = {n: getattr(ev, n) for n, _ in T1Events._fields_}
         if want_symbols:
             assert ns.value <= symcap
             res["symbols"] = sym[:ns.value].copy()

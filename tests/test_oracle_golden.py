@@ -6,6 +6,7 @@ import hashlib
 import numpy as np
 import pytest
 
+import cblk_style_cases
 from conftest import golden_case
 from j2k_amd import synth
 from oracle.oracle import make_params, strip_com
@@ -23,6 +24,42 @@ def test_oracle_matches_golden_codestream(oracle, golden, name):
     assert len(ours) == g["length"]
     assert hashlib.sha256(ours).hexdigest() == g["sha256"]
     assert ours == cs
+
+
+@pytest.mark.parametrize("name", cblk_style_cases.NAMES)
+def test_oracle_matches_styled_golden_codestream(oracle, name):
+    """The oracle's own styled block coder (j2ko_t1_encode_block_styled, the function Oracle.t1_block exposes and the frame
+    encoder calls for every block) reproduces libopenjp2's recorded files under the code-block styles byte for byte.
+
+    What the files pin: a codestream holds each codeword segment's length and the block's bytes, so they show the byte
+    count of a block only at the passes that end a segment and at its last pass.  The count at any other pass (libopenjp2's
+    estimate) is in no file.  The block-level GPU tests (test_t1_styled_blocks.py) therefore compare `rates` with the oracle
+    only at terminated passes and at the last pass; at every other pass they check only that the counts do not decrease
+    and do not exceed the length -- all that any styled frame uses."""
+    g = cblk_style_cases.entry(name)
+    kw = dict(g["ext"])
+    mode = kw.pop("mode")
+    for k in ("cblk", "tile"):
+        if k in kw:
+            kw[k] = tuple(kw[k])
+    p = make_params(g["width"], g["height"], g["ncomp"], g["prec"], **kw)
+    assert p.mode == 0
+    ours = oracle.encode(cblk_style_cases.planes(name), p, mode=mode)  # no COM
+    want = cblk_style_cases.golden_bytes(name)
+    assert len(ours) == g["length"] == len(want)
+    assert hashlib.sha256(ours).hexdigest() == g["sha256"]
+    assert ours == want
+
+
+def test_oracle_refuses_styles_it_does_not_code(oracle):
+    pl = synth.planes(64, 64, 1, 8, 1, "A")
+    for mode in (8, 1 | 8, 64):
+        with pytest.raises(RuntimeError):
+            oracle.encode(pl, make_params(64, 64, 1, 8, numres=2, mode=mode))
+        with pytest.raises(ValueError):
+            oracle.t1_block(np.full((4, 4), 64, dtype=np.int32), 0, style=mode)
+    with pytest.raises(RuntimeError):  # a style excludes a rate target
+        oracle.encode_rates(pl, make_params(64, 64, 1, 8, numres=2, mode=1), [10.0])
 
 
 @pytest.mark.parametrize("name", ["g8_c1", "g8_c2", "g8_c3", "g8_c3_5lvl", "g8_c4", "g8_c5"])
