@@ -350,6 +350,34 @@ int j2k_hip_decode(j2k_hip_encoder *enc, const void *file, size_t len, uint32_t 
 int j2k_hip_decode_device(j2k_hip_encoder *enc, const void *file, size_t len, uint32_t subsample,
                           const j2k_hip_outplane *planes, uint32_t nplanes);
 
+/* Decode a window of the image.  `region` is in pixels of the image as j2k_hip_decode delivers it at this `subsample`:
+ * the reduced image with its top-left at (0, 0), whatever image or tile origin the file has.  Destination channel i
+ * receives, at its top-left, exactly the samples j2k_hip_decode with the same arguments would have put at
+ * [y, y + h) x [x, x + w).  Everything else is j2k_hip_decode's: planes[i].width / .height limit what is copied, only
+ * channel samples are written, sub-sampled components are replicated (at the phase of the window's origin), signed ones
+ * offset, depths converted, palettes left as indices, the first four components decoded.
+ * What is skipped: code-blocks whose coefficients the window's synthesis does not read are neither gathered nor decoded
+ * (j2k_hip_stats.num_codeblocks counts the ones that were), and the inverse DWT produces, per resolution, only the window
+ * the next resolution needs.  What is not: every packet header is parsed (they are one serial bit stream), the whole file
+ * is uploaded, and the coefficient planes keep the image's size and are cleared.
+ * region == NULL: j2k_hip_decode itself.  w == 0, h == 0 or a rectangle that leaves the reduced image:
+ * J2K_HIP_ERR_PARAM, nothing written.  J2K_HIP_ABI_VERSION is still 9: functions were added, none changed. */
+typedef struct j2k_hip_rect { uint32_t x, y, w, h; } j2k_hip_rect;
+int j2k_hip_decode_region(j2k_hip_encoder *enc, const void *file, size_t len, uint32_t subsample,
+                          const j2k_hip_rect *region, const j2k_hip_outplane *planes, uint32_t nplanes);
+/* Same with destination channels in device memory (planes[i].base are device pointers). */
+int j2k_hip_decode_region_device(j2k_hip_encoder *enc, const void *file, size_t len, uint32_t subsample,
+                                 const j2k_hip_rect *region, const j2k_hip_outplane *planes, uint32_t nplanes);
+/* Which band coefficients a window needs: for one plane of width x height at origin (x0, y0) with `levels` decompositions,
+ * rects[0] = LL, then HL, LH, HH per level from the lowest resolution up (3 * levels + 1 rects, in band coordinates of the
+ * Mallat layout the stage hooks use: x, y index the plane itself, so rects[k] is the part of the plane that is read).  A
+ * band nothing is read from has w == h == 0.  `window` is in plane coordinates.  The rectangles are what the inverse DWT
+ * kernels read, never less: outputs are produced in (even, odd) pairs of absolute positions, and a pair reads 5 (5/3) or
+ * 9 (9/7) interleaved positions around it.  Window empty or outside the plane, nrects < 3 * levels + 1: J2K_HIP_ERR_PARAM
+ * (message: j2k_hip_last_error(NULL)).  No device needed. */
+int j2k_hip_region_footprint(int reversible, uint32_t width, uint32_t height, uint32_t levels, uint32_t x0, uint32_t y0,
+                             const j2k_hip_rect *window, j2k_hip_rect *rects, uint32_t nrects);
+
 /* --- stage-level entry points (parity tests and roofline measurement call these) -----------------
  * A1+A2+A4+A5: front end only. d_out = channels planes of width*height 32-bit words (int32 for
  * reversible, float32 bit patterns otherwise), row stride = width. */
@@ -411,6 +439,14 @@ int j2k_hip_stage_idwt(j2k_hip_encoder *enc, int reversible, uint32_t width, uin
                        uint32_t nplanes, uint32_t levels, uint32_t x0, uint32_t y0,
                        const j2k_hip_idwt_region *regions, uint32_t nregions, const void *d_in,
                        void *d_out);
+/* The windowed inverse DWT of a region decode alone (idwt_win_h_kernel + idwt_win_v_kernel), on the layout of
+ * j2k_hip_stage_idwt with one region of origin (x0,y0) per plane: per resolution only the window the next one needs is
+ * synthesised, from the coefficients j2k_hip_region_footprint names and no others.  Only the window (plane coordinates)
+ * of d_out is specified; words outside it may hold anything; nothing outside the nplanes * height * width words is
+ * written.  d_in is preserved. */
+int j2k_hip_stage_idwt_window(j2k_hip_encoder *enc, int reversible, uint32_t width, uint32_t height,
+                              uint32_t nplanes, uint32_t levels, uint32_t x0, uint32_t y0,
+                              const j2k_hip_rect *window, const void *d_in, void *d_out);
 
 /* The decode's output stage alone (decode_output_kernel: inverse RCT / ICT, DC level shift, clamp, replication of
  * sub-sampled components, CopyChannel's depth conversion), its arguments filled by the function a decode fills them with.

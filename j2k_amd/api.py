@@ -84,18 +84,24 @@ WRITE_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t)
 
 EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_last_error", "j2k_hip_encode",
            "j2k_hip_encode_begin", "j2k_hip_encode_begin_borrowed", "j2k_hip_encode_end", "j2k_hip_debug_tune", "j2k_hip_debug_get_tune", "j2k_hip_debug_fused_occupancy", "j2k_hip_debug_membw", "j2k_hip_debug_dwt_time", "j2k_hip_read_info", "j2k_hip_decode",
-           "j2k_hip_decode_device", "j2k_hip_encode_tiles", "j2k_hip_device_count", "j2k_hip_encode_batch",
+           "j2k_hip_decode_device", "j2k_hip_decode_region", "j2k_hip_decode_region_device", "j2k_hip_region_footprint",
+           "j2k_hip_encode_tiles", "j2k_hip_device_count", "j2k_hip_encode_batch",
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
            "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
            "j2k_hip_stage_t1_styled",
-           "j2k_hip_stage_idwt", "j2k_hip_stage_t1_decode", "j2k_hip_stage_decode_output",
+           "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_decode_output",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink"]
 
 class IdwtRegion(C.Structure):
     """include/j2k_hip.h: j2k_hip_idwt_region."""
     _fields_ = [(n, C.c_uint32) for n in ("x", "y", "w", "h", "x0", "y0")]
+
+
+class Rect(C.Structure):
+    """include/j2k_hip.h: j2k_hip_rect."""
+    _fields_ = [(n, C.c_uint32) for n in ("x", "y", "w", "h")]
 
 
 class DecBlock(C.Structure):
@@ -154,6 +160,12 @@ def load_library():
     L.j2k_hip_read_info.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(FileInfo)]
     L.j2k_hip_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(OutPlane), C.c_uint32]
     L.j2k_hip_decode_device.argtypes = L.j2k_hip_decode.argtypes
+    L.j2k_hip_decode_region.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(Rect), C.POINTER(OutPlane), C.c_uint32]
+    L.j2k_hip_decode_region_device.argtypes = L.j2k_hip_decode_region.argtypes
+    L.j2k_hip_region_footprint.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Rect),
+                                           C.POINTER(Rect), C.c_uint32]
+    L.j2k_hip_stage_idwt_window.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.POINTER(Rect), C.c_void_p, C.c_void_p]
     L.j2k_hip_debug_dwt_time.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
     L.j2k_hip_encode_to_buffer.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Plane), C.c_void_p, C.c_size_t,
                                            C.POINTER(C.c_size_t)]
@@ -216,6 +228,18 @@ def read_info(data: bytes) -> dict:
     if rc != 0:
         raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
     return fi.as_dict()
+
+
+def region_footprint(width: int, height: int, levels: int, reversible: bool, window, x0: int = 0, y0: int = 0, nrects: int | None = None):
+    """Which coefficients of a Mallat plane a window (x, y, w, h) needs (j2k_hip_region_footprint; no device needed):
+    [(x, y, w, h)] in plane coordinates for LL, then HL, LH, HH per level from the lowest resolution up."""
+    L = load_library()
+    n = 3 * levels + 1 if nrects is None else nrects
+    rects = (Rect * max(n, 1))()
+    rc = L.j2k_hip_region_footprint(int(reversible), width, height, levels, x0, y0, C.byref(Rect(*window)), rects, n)
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+    return [(r.x, r.y, r.w, r.h) for r in rects[:n]]
 
 
 def make_params(width, height, channels, depth, reversible=True, ycc=False, layers=1, tile_size=0,
@@ -451,6 +475,37 @@ class Encoder:
         self._check(self.L.j2k_hip_decode(self.h, buf.ctypes.data, len(data), subsample, arr, nc))
         return out
 
+    def decode_region_planar(self, data: bytes, rect, subsample: int = 1, sample_bits: int | None = None, depth: int | None = None,
+                             channels: int | None = None, out: np.ndarray | None = None, device: bool = False) -> np.ndarray:
+        """Decode the window rect = (x, y, w, h) of the image decode_planar delivers at this subsample into planar buffers
+        (channels, h, w); out: a buffer to decode into, (channels, rows, cols) of any size -- it receives the window's
+        top-left part.  device=True: through a device copy of the buffer (j2k_hip_decode_region_device)."""
+        i = read_info(data)
+        nc = channels or i["channels"]
+        bits = sample_bits or (8 if i["depth"] <= 8 else 16)
+        if out is None:
+            out = np.zeros((nc, rect[3], rect[2]), dtype=np.uint8 if bits == 8 else np.uint16)
+        assert out.ndim == 3 and out.shape[0] == nc and out.itemsize * 8 == bits and out.flags.c_contiguous
+        _, h, w = out.shape
+        d = self.upload(out) if device else None
+        base = d if device else out.ctypes.data
+        arr = (OutPlane * nc)()
+        for c in range(nc):
+            arr[c].base = base + c * h * w * out.itemsize
+            arr[c].colbytes, arr[c].rowbytes = out.itemsize, w * out.itemsize
+            arr[c].sample_bits, arr[c].depth = bits, depth or min(i["depth"], bits)
+            arr[c].width, arr[c].height = w, h
+        buf = np.frombuffer(data, dtype=np.uint8)
+        try:
+            fn = self.L.j2k_hip_decode_region_device if device else self.L.j2k_hip_decode_region
+            self._check(fn(self.h, buf.ctypes.data, len(data), subsample, C.byref(Rect(*rect)), arr, nc))
+            if device:
+                out[...] = self.d2h(d, out.nbytes).view(out.dtype).reshape(out.shape)
+        finally:
+            if d:
+                self.free(d)
+        return out
+
     def decode_channels(self, data: bytes, chans: list, depth: int | None = None, subsample: int = 1):
         """Decode into one 2-D numpy view per codec channel, wherever each lies and whatever its strides (padded rows,
         samples of interleaved pixels, bottom-up rows): the general form of the C ABI's destination."""
@@ -465,9 +520,10 @@ class Encoder:
         self._check(self.L.j2k_hip_decode(self.h, buf.ctypes.data, len(data), subsample, arr, len(chans)))
 
     def decode_ae(self, data: bytes, frame: np.ndarray, layout: dict, width: int, height: int, channels: int, depth: int | None = None,
-                  subsample: int = 1, device: bool = False):
+                  subsample: int = 1, device: bool = False, region=None):
         """Decode into an After Effects ARGB frame (see synth.ae_frame): codec channels R,G,B[,A] go to their samples,
-        every other byte of `frame` must stay as it is.  device=True: through a device copy of the frame."""
+        every other byte of `frame` must stay as it is.  device=True: through a device copy of the frame.
+        region = (x, y, w, h): that window of the image goes to the frame's top-left (j2k_hip_decode_region)."""
         sb = layout["sample_bytes"]
         offs = layout["channel_offsets"]
         order = [offs[1], offs[2], offs[3], offs[0]]
@@ -484,11 +540,15 @@ class Encoder:
             arr[c].width, arr[c].height = width, height
         buf = np.frombuffer(data, dtype=np.uint8)
         try:
-            if device:
+            if region is not None:
+                fn = self.L.j2k_hip_decode_region_device if device else self.L.j2k_hip_decode_region
+                self._check(fn(self.h, buf.ctypes.data, len(data), subsample, C.byref(Rect(*region)), arr, channels))
+            elif device:
                 self._check(self.L.j2k_hip_decode_device(self.h, buf.ctypes.data, len(data), subsample, arr, channels))
-                frame[:] = self.d2h(d, frame.nbytes)
             else:
                 self._check(self.L.j2k_hip_decode(self.h, buf.ctypes.data, len(data), subsample, arr, channels))
+            if device:
+                frame[:] = self.d2h(d, frame.nbytes)
         finally:
             if d:
                 self.free(d)
@@ -604,6 +664,30 @@ class Encoder:
             self.free(d_in)
             self.free(d_out)
         return raw.view(dt).reshape(n, h, w)
+
+    def stage_idwt_window(self, planes: np.ndarray, levels: int, reversible: bool, window, x0=0, y0=0, guard=None):
+        """The windowed inverse DWT (j2k_hip_stage_idwt_window): planes (n, h, w) in Mallat layout, window = (x, y, w, h) in
+        plane coordinates.  Only the window of the result is specified.  guard = a 32-bit fill: one row of it lies before and
+        behind the planes in the same device allocation, and (result, rows before, rows behind) is returned."""
+        dt = np.int32 if reversible else np.float32
+        planes = np.ascontiguousarray(planes).view(dt) if planes.dtype in (np.uint32, np.int32, np.float32) else np.ascontiguousarray(planes, dtype=dt)
+        n, h, w = planes.shape
+        pad = w * 4 if guard is not None else 0
+        d_in = self.upload(planes)
+        d_out = self.malloc(max(planes.nbytes, 16) + 2 * pad)
+        try:
+            if pad:
+                self.h2d(d_out, np.full(n * h * w + 2 * w, guard, dtype=np.uint32))
+            self._check(self.L.j2k_hip_stage_idwt_window(self.h, int(reversible), w, h, n, levels, x0, y0, C.byref(Rect(*window)),
+                                                         d_in, d_out + pad))
+            raw = self.d2h(d_out, planes.nbytes + 2 * pad)
+        finally:
+            self.free(d_in)
+            self.free(d_out)
+        body = raw[pad:pad + planes.nbytes].view(dt).reshape(n, h, w)
+        if guard is None:
+            return body
+        return body, raw[:pad].view(np.uint32), raw[pad + planes.nbytes:].view(np.uint32)
 
     def stage_t1_decode(self, plane: np.ndarray, blocks, reversible: bool, kernel: str = "wave") -> np.ndarray:
         """plane: (H, W) int32 / float32 the blocks are decoded into (what it holds elsewhere stays).  blocks: dicts with

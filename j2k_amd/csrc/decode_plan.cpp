@@ -349,7 +349,46 @@ FileHeader parse_headers(const uint8_t *file, size_t len)
     return H;
 }
 
-DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce)
+namespace {
+
+// One line [x0, x1) of a resolution and the wanted outputs [a, b) of it (a < b, inside the line): the low-band samples
+// [lo0, lo1) and high-band samples [hi0, hi1) the synthesis of those outputs reads.  m = 1 (5/3) or 3 (9/7).
+struct Need1D { int lo0, lo1, hi0, hi1; };
+Need1D need_1d(int x0, int x1, int a, int b, int m)
+{
+    const int pa = a & ~1, pb = (b - 1) & ~1; // first and last output pair (even absolute position first)
+    const int L = std::max(pa - m, x0), H = std::min(pb + m + 2, x1 - 1);
+    return Need1D{(L + 1) >> 1, (H >> 1) + 1, L >> 1, ((H - 1) >> 1) + 1};
+}
+
+} // namespace
+
+std::vector<ResFootprint> region_footprints(const IRect *res, uint32_t nres, bool reversible, const IRect &window)
+{
+    std::vector<ResFootprint> fp(nres);
+    if (!nres) return fp;
+    const int m = reversible ? 1 : 3;
+    IRect w = window;
+    for (uint32_t r = nres - 1;; --r) {
+        fp[r].win = w;
+        if (r == 0 || w.empty()) break;
+        const Need1D nx = need_1d(res[r].x0, res[r].x1, w.x0, w.x1, m), ny = need_1d(res[r].y0, res[r].y1, w.y0, w.y1, m);
+        fp[r].band[0] = IRect{nx.hi0, ny.lo0, nx.hi1, ny.lo1}; // HL: high along x
+        fp[r].band[1] = IRect{nx.lo0, ny.hi0, nx.lo1, ny.hi1}; // LH
+        fp[r].band[2] = IRect{nx.hi0, ny.hi0, nx.hi1, ny.hi1}; // HH
+        fp[r].ly0 = ny.lo0; fp[r].ly1 = std::max(ny.lo1, ny.lo0); fp[r].hy0 = ny.hi0; fp[r].hy1 = std::max(ny.hi1, ny.hi0);
+        w = IRect{nx.lo0, ny.lo0, nx.lo1, ny.lo1};               // LL = the window of the resolution below
+    }
+    return fp;
+}
+
+void reduced_size(const Coding &cod, uint32_t reduce, int &ow, int &oh)
+{
+    ow = ceildivpow2((int)(cod.img_x0 + cod.width), (int)reduce) - ceildivpow2((int)cod.img_x0, (int)reduce);
+    oh = ceildivpow2((int)(cod.img_y0 + cod.height), (int)reduce) - ceildivpow2((int)cod.img_y0, (int)reduce);
+}
+
+DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const uint32_t *window)
 {
     DecodePlan P;
     P.hdr = parse_headers(file, len);
@@ -357,6 +396,14 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce)
     const Coding &cod = H.cod;
     if (reduce >= cod.numres) bad("cannot discard " + std::to_string(reduce) + " of " + std::to_string(cod.numres) + " resolutions");
     P.reduce = reduce;
+    if (window) {
+        int ow, oh;
+        reduced_size(cod, reduce, ow, oh);
+        if (!window[2] || !window[3] || ow <= 0 || oh <= 0 || (uint64_t)window[0] + window[2] > (uint64_t)ow || (uint64_t)window[1] + window[3] > (uint64_t)oh)
+            throw Error(J2K_HIP_ERR_PARAM, "region (" + std::to_string(window[0]) + ", " + std::to_string(window[1]) + ", " + std::to_string(window[2]) + " x " +
+                                               std::to_string(window[3]) + ") is empty or leaves the image of " + std::to_string(std::max(ow, 0)) + " x " +
+                                               std::to_string(std::max(oh, 0)) + " at this resolution");
+    }
     {
         // The header alone decides how much host and device memory the decode takes, whatever the file's length: bound it
         // before any table is built (a 90-byte file may announce 2^30 x 2^30 samples in 4 x 4 code-blocks).
@@ -608,10 +655,48 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce)
         by_block.resize(g.cblks.size());
         for (uint32_t i = 0; i < pieces.size(); ++i) by_block[pieces[i].cblk].push_back(i);
     }
+    // ---- a window decode: the footprints of every tile-component the window meets.  The output stage reads component c at
+    // (X / sub_x, Y / sub_y) of its plane for the image position (X, Y); the plane's origin is the image area's on the
+    // component's grid (decoder.cpp: pox / poy).
+    std::vector<uint32_t> tile_pos;
+    if (window) {
+        P.windowed = true;
+        P.windows.assign(g.tiles.size() * 4, {});
+        tile_pos.assign(cod.ntiles(), 0);
+        for (size_t t = 0; t < g.tiles.size(); ++t) {
+            tile_pos[g.tiles[t].index] = (uint32_t)t;
+            for (uint32_t c = 0; c < cod.ncomp_out(); ++c) {
+                const TileComp &TC = g.tiles[t].comps[c];
+                const int pox = ceildivpow2((int)((cod.img_x0 + cod.cdx[c] - 1) / cod.cdx[c]), (int)reduce);
+                const int poy = ceildivpow2((int)((cod.img_y0 + cod.cdy[c] - 1) / cod.cdy[c]), (int)reduce);
+                std::vector<IRect> rr(top_res + 1);
+                for (uint32_t r = 0; r <= top_res; ++r) rr[r] = IRect{TC.res[r].x0, TC.res[r].y0, TC.res[r].x1, TC.res[r].y1};
+                IRect w;
+                w.x0 = std::max(rr[top_res].x0, pox + (int)(window[0] / cod.cdx[c]));
+                w.y0 = std::max(rr[top_res].y0, poy + (int)(window[1] / cod.cdy[c]));
+                w.x1 = std::min(rr[top_res].x1, pox + (int)((window[0] + window[2] - 1) / cod.cdx[c]) + 1);
+                w.y1 = std::min(rr[top_res].y1, poy + (int)((window[1] + window[3] - 1) / cod.cdy[c]) + 1);
+                if (w.empty()) continue;
+                P.windows[t * 4 + c] = region_footprints(rr.data(), top_res + 1, cod.reversible != 0, w);
+            }
+        }
+    }
+    auto wanted = [&](const Cblk &cb) { // does the block's band rectangle meet its band's footprint?
+        const std::vector<ResFootprint> &fp = P.windows[(size_t)tile_pos[cb.tile] * 4 + cb.comp];
+        if (fp.empty()) return false;
+        const TileComp &TC = g.tiles[tile_pos[cb.tile]].comps[cb.comp];
+        const Band &B = TC.res[cb.res].bands[cb.band];
+        const int offx = (cb.res && (B.orient & 1)) ? TC.res[cb.res - 1].x1 - TC.res[cb.res - 1].x0 : 0;
+        const int offy = (cb.res && (B.orient & 2)) ? TC.res[cb.res - 1].y1 - TC.res[cb.res - 1].y0 : 0;
+        const int bx = (int)cb.px - TC.x0 - offx + B.x0, by = (int)cb.py - TC.y0 - offy + B.y0;
+        const IRect &need = cb.res ? fp[cb.res].band[cb.band] : fp[0].win;
+        return need.meets(bx, by, bx + cb.w, by + cb.h);
+    };
     uint64_t arena = 0;
     for (uint32_t id = 0; id < g.cblks.size(); ++id) {
         const BlockState &bs = st[id];
         if (!bs.included || !t1dec_passes(bs.numbps, bs.npasses) || g.cblks[id].res > top_res || g.cblks[id].comp >= 4) continue; // (components beyond the fourth are parsed, not decoded)
+        if (window && !wanted(g.cblks[id])) continue; // no DecBlock, no gather segments, no arena bytes
         DecBlock db;
         db.cblk = id; db.numbps = bs.numbps; db.npasses = bs.npasses;
         db.roishift = H.roishift[g.cblks[id].comp];

@@ -74,6 +74,27 @@ inline uint64_t cw_arena_next(uint64_t end) { return (end + 2 + 15) & ~(uint64_t
 inline uint64_t cw_arena_bytes(uint64_t next) { return next + 16; }
 constexpr size_t kCwArenaTail = 512;
 
+// ---- region decode: which coefficients a window of the top decoded resolution needs (no device, no file)
+// Rectangles are half open and in ABSOLUTE coordinates of their resolution or band (T.800 B.5: low-band sample n of a
+// resolution is its interleaved position 2n, high-band sample n position 2n + 1).
+struct IRect {
+    int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    bool empty() const { return x1 <= x0 || y1 <= y0; }
+    bool meets(int ax0, int ay0, int ax1, int ay1) const { return !empty() && ax0 < x1 && x0 < ax1 && ay0 < y1 && y0 < ay1; }
+};
+struct ResFootprint {
+    IRect win;      // the window of this resolution that is synthesised (resolution 0: the LL coefficients that are read)
+    IRect band[3];  // resolution >= 1: the coefficients of HL, LH, HH that its synthesis reads
+    // the band rows the vertical pass reads, so the rows the horizontal pass has to produce: low rows [ly0, ly1), high [hy0, hy1)
+    int ly0 = 0, ly1 = 0, hy0 = 0, hy1 = 0;
+};
+// res[r] = the rectangle of resolution r of one tile-component (r = 0 .. nres - 1), `window` a non-empty rectangle inside
+// res[nres - 1].  The support is idwt.hip's synth_pair: outputs come in (even, odd) pairs of absolute positions, a pair at
+// (p, p + 1) reads interleaved positions p - 1 .. p + 3 (5/3) or p - 3 .. p + 5 (9/7), reflected into the line -- within
+// those bounds every reflected position lies between the clamped ends, so clamping is exact.  Returns nres entries; below
+// a resolution whose low-band need is empty (a line of one odd sample) everything stays empty.
+std::vector<ResFootprint> region_footprints(const IRect *res, uint32_t nres, bool reversible, const IRect &window);
+
 struct DecodePlan {
     FileHeader hdr;
     Geometry geo;               // all tiles
@@ -82,9 +103,16 @@ struct DecodePlan {
     std::vector<DecSeg> segs;
     std::vector<uint32_t> cwsegs;
     uint64_t arena_bytes = 0;
+    // a window decode: per tile (in geo.tiles order) and decoded component [tile * 4 + comp], the footprints of resolutions
+    // 0 .. numres - 1 - reduce; empty where the window misses the tile-component.  Blocks outside them are not in `blocks`.
+    bool windowed = false;
+    std::vector<std::vector<ResFootprint>> windows;
 };
 
-// Tier-2 of the whole file for a decode at resolution `reduce` (0 = full size).
-DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce);
+// Tier-2 of the whole file for a decode at resolution `reduce` (0 = full size).  window (optional): x, y, w, h in pixels of
+// the image as it is delivered at this resolution (top-left at (0, 0)); outside that image: Error(J2K_HIP_ERR_PARAM).
+DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const uint32_t *window = nullptr);
+// the size of the delivered image at resolution `reduce` (opj_image_comp_header_update: both edges scaled, then subtracted)
+void reduced_size(const Coding &cod, uint32_t reduce, int &ow, int &oh);
 
 } // namespace j2k_hip

@@ -79,8 +79,9 @@ void check_outplane(const j2k_hip_outplane &p)
     if (p.sample_bits != 8 && p.sample_bits != 16) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8 or 16");
     if (p.depth < 1 || p.depth > p.sample_bits) throw Error(J2K_HIP_ERR_PARAM, "channel depth does not fit its sample type");
 }
+// (org_x, org_y: a region decode's window origin -- width and height are then the window's)
 DecOutArgs decode_output_args(bool reversible, bool mct, int width, int height, long long stride, const OutComp *comps, uint32_t ncomp,
-                              const j2k_hip_outplane *planes, uint32_t nplanes)
+                              const j2k_hip_outplane *planes, uint32_t nplanes, int org_x = 0, int org_y = 0)
 {
     if (ncomp < 1 || ncomp > 4 || !planes || nplanes < 1 || nplanes > 4) throw Error(J2K_HIP_ERR_PARAM, "1..4 components and destination channels");
     for (uint32_t c = 0; c < ncomp; ++c) {
@@ -94,7 +95,7 @@ DecOutArgs decode_output_args(bool reversible, bool mct, int width, int height, 
                 throw Error(J2K_HIP_ERR_PARAM, "component transform on components of unlike precision or sub-sampling");
     DecOutArgs oa{};
     oa.stride = stride; oa.ncomp = (int)ncomp; oa.width = width; oa.height = height; oa.prec = (int)comps[0].prec;
-    oa.reversible = reversible; oa.mct = mct;
+    oa.reversible = reversible; oa.mct = mct; oa.org_x = org_x; oa.org_y = org_y;
     for (int c = 0; c < 4; ++c) { oa.cprec[c] = (int)comps[0].prec; oa.sub_x[c] = oa.sub_y[c] = 1; }
     for (uint32_t c = 0; c < ncomp; ++c) {
         oa.comp[c] = comps[c].plane;
@@ -111,14 +112,30 @@ DecOutArgs decode_output_args(bool reversible, bool mct, int width, int height, 
     return oa;
 }
 
+// One job of a windowed inverse DWT launch: resolution rectangle `res` of a tile-component whose origin is word `off`, and
+// what region_footprints found for it (absolute coordinates -> the region's own)
+IdwtWinJob window_job(const IRect &res, const ResFootprint &f, long long off)
+{
+    IdwtWinJob j{};
+    j.off = off;
+    j.rw = res.x1 - res.x0; j.rh = res.y1 - res.y0; j.casx = res.x0 & 1; j.casy = res.y0 & 1;
+    j.wx0 = f.win.x0 - res.x0; j.wx1 = f.win.x1 - res.x0; j.wy0 = f.win.y0 - res.y0; j.wy1 = f.win.y1 - res.y0;
+    const int low0 = (res.y0 + 1) >> 1, high0 = res.y0 >> 1; // the bands' first rows
+    j.ly0 = f.ly0 - low0; j.ly1 = f.ly1 - low0; j.hy0 = f.hy0 - high0; j.hy1 = f.hy1 - high0;
+    return j;
+}
+
+// region (optional): the window of a region decode.  Null: the whole image, by the launches of every decode before regions.
 void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_outplane *planes,
-                 uint32_t nplanes, bool planes_on_device)
+                 uint32_t nplanes, bool planes_on_device, const j2k_hip_rect *region = nullptr)
 {
     const double t_begin = now_ms();
     if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
     if (!file || !len) throw Error(J2K_HIP_ERR_PARAM, "Error reading file: empty input");
     if (!planes || nplanes < 1 || nplanes > 4) throw Error(J2K_HIP_ERR_PARAM, "1..4 destination channels");
     if (subsample == 0) subsample = 1;
+    const uint32_t win[4] = {region ? region->x : 0, region ? region->y : 0, region ? region->w : 0, region ? region->h : 0};
+    const uint32_t *const window = region ? win : nullptr;
     const uint32_t reduce = (uint32_t)floorlog2(subsample); // reference: params.cp_reduce = log2(subsample), :501
     HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = e->stream;
@@ -132,7 +149,7 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     e->d_file.ensure(len + 64);
     DecodePlan P;
     if (len >= (4u << 20)) {
-        auto fut = std::async(std::launch::async, [&] { return plan_decode(fbytes, len, reduce); });
+        auto fut = std::async(std::launch::async, [&] { return plan_decode(fbytes, len, reduce, window); });
         const hipError_t up = hipMemcpyAsync(e->d_file.p, fbytes, len, hipMemcpyHostToDevice, s);
 #ifdef J2K_DEC_TRACE
         static hipEvent_t tr_ev = nullptr;
@@ -158,7 +175,7 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
         }
 #endif
     } else {
-        P = plan_decode(fbytes, len, reduce);
+        P = plan_decode(fbytes, len, reduce, window);
         HIP_CHECK(hipMemcpyAsync(e->d_file.p, fbytes, len, hipMemcpyHostToDevice, s));
     }
     const FileHeader &H = P.hdr;
@@ -167,8 +184,8 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     const double t_plan = now_ms();
     const uint32_t R = cod.numres - 1 - reduce; // highest resolution decoded
     // the image at the decoded resolution (opj_image_comp_header_update: both edges of the area are scaled, then subtracted)
-    const int ow = ceildivpow2((int)(cod.img_x0 + cod.width), (int)reduce) - ceildivpow2((int)cod.img_x0, (int)reduce);
-    const int oh = ceildivpow2((int)(cod.img_y0 + cod.height), (int)reduce) - ceildivpow2((int)cod.img_y0, (int)reduce);
+    int ow, oh;
+    reduced_size(cod, reduce, ow, oh);
     if (ow <= 0 || oh <= 0) throw Error(J2K_HIP_ERR_PARAM, "Error reading file: nothing left of the image at this resolution");
     // origin of every component's plane: the image area's origin on the component's grid at the decoded resolution
     const uint32_t nd = cod.ncomp_out(); // components decoded: the first four (reference: min(numcomps, J2K_CODEC_MAX_CHANNELS), :278, :530)
@@ -397,10 +414,46 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     HIP_CHECK(hipEventRecord(e->ev[EV_T1], s));
 
     // ---- inverse DWT: resolution 1 .. R
+    if (region) { // the windows of the tile-components the region meets, nothing else
+        std::vector<IdwtWinJob> wjobs;
+        std::vector<size_t> first(R + 2, 0);
+        std::vector<int> mh(R + 1, 0), mv(R + 1, 0);
+        for (uint32_t r = 1; r <= R; ++r) {
+            first[r] = wjobs.size();
+            for (size_t t = 0; t < g.tiles.size(); ++t)
+                for (uint32_t c = 0; c < nd; ++c) {
+                    const std::vector<ResFootprint> &fp = P.windows[t * 4 + c];
+                    if (fp.empty() || fp[r].win.empty()) continue;
+                    const TileComp &TC = g.tiles[t].comps[c];
+                    const Resolution &Rs = TC.res[r];
+                    const long long off = (long long)c * (long long)plane_elems + (long long)(ceildivpow2(TC.y0, (int)reduce) - poy[c]) * (long long)stride +
+                                          (ceildivpow2(TC.x0, (int)reduce) - pox[c]);
+                    const IdwtWinJob j = window_job(IRect{Rs.x0, Rs.y0, Rs.x1, Rs.y1}, fp[r], off);
+                    int hi, vi;
+                    idwt_window_items(j, hi, vi);
+                    wjobs.push_back(j);
+                    mh[r] = std::max(mh[r], hi); mv[r] = std::max(mv[r], vi);
+                }
+        }
+        first[R + 1] = wjobs.size();
+        if (!wjobs.empty()) {
+            e->jobs.ensure(wjobs.size() * sizeof(IdwtWinJob));
+            HIP_CHECK(hipMemcpyAsync(e->jobs.p, wjobs.data(), wjobs.size() * sizeof(IdwtWinJob), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s)); // `wjobs` is a pageable host vector
+            for (uint32_t r = 1; r <= R; ++r) {
+                IdwtWinArgs ia{};
+                ia.a = e->Z.p; ia.tmp = e->Q.p; ia.stride = (long long)stride;
+                ia.jobs = e->jobs.as<IdwtWinJob>() + first[r]; ia.njobs = (int)(first[r + 1] - first[r]);
+                ia.max_h_items = mh[r]; ia.max_v_items = mv[r]; ia.reversible = cod.reversible;
+                launch_idwt_window_level(ia, s);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+    }
     std::vector<IdwtJob> jobs;
     std::vector<size_t> job_first(R + 2, 0);
     std::vector<int> mrw(R + 1, 0), mrh(R + 1, 0);
-    for (uint32_t r = 1; r <= R; ++r) {
+    for (uint32_t r = 1; r <= R && !region; ++r) {
         job_first[r] = jobs.size();
         for (const Tile &T : g.tiles)
             for (uint32_t c = 0; c < nd; ++c) {
@@ -433,7 +486,9 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     // ---- output stage
     OutComp oc[4] = {};
     for (uint32_t c = 0; c < nd; ++c) oc[c] = OutComp{e->Z.as<int32_t>() + c * plane_elems, cod.cprec[c], cod.cdx[c], cod.cdy[c]};
-    DecOutArgs oa = decode_output_args(cod.reversible, cod.mct, ow, oh, (long long)stride, oc, nd, planes, nplanes);
+    DecOutArgs oa = region ? decode_output_args(cod.reversible, cod.mct, (int)region->w, (int)region->h, (long long)stride, oc, nd, planes, nplanes,
+                                                (int)region->x, (int)region->y)
+                           : decode_output_args(cod.reversible, cod.mct, ow, oh, (long long)stride, oc, nd, planes, nplanes);
     // The destination channels' extents in the caller's address space.  Channels whose extents overlap (the samples of
     // interleaved pixels) form one span that keeps its layout on the device; channels that lie apart (planar buffers,
     // wherever they were allocated) are spans of their own.
@@ -613,6 +668,22 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     st.ms_total = now_ms() - t_begin;
 }
 
+// The resolutions of one plane of width x height at origin (x0, y0) with `levels` decompositions, lowest first, and the
+// footprints of `window` (plane coordinates) in them -- for the footprint query and the windowed transform's stage hook.
+std::vector<ResFootprint> plane_footprints(bool reversible, uint32_t width, uint32_t height, uint32_t levels, uint32_t x0, uint32_t y0,
+                                           const j2k_hip_rect *window, std::vector<IRect> &res)
+{
+    if (!width || !height || levels > 32 || (uint64_t)x0 + width > 0x7fffffffu || (uint64_t)y0 + height > 0x7fffffffu)
+        throw Error(J2K_HIP_ERR_PARAM, "bad plane for a window: size 0, more than 32 levels or an origin beyond 2^31");
+    if (!window || !window->w || !window->h || (uint64_t)window->x + window->w > width || (uint64_t)window->y + window->h > height)
+        throw Error(J2K_HIP_ERR_PARAM, "window is empty or leaves the plane");
+    res.assign(levels + 1, IRect{});
+    for (uint32_t l = 0; l <= levels; ++l)
+        res[levels - l] = IRect{ceildivpow2((int)x0, (int)l), ceildivpow2((int)y0, (int)l), ceildivpow2((int)(x0 + width), (int)l), ceildivpow2((int)(y0 + height), (int)l)};
+    const IRect w{(int)(x0 + window->x), (int)(y0 + window->y), (int)(x0 + window->x + window->w), (int)(y0 + window->y + window->h)};
+    return region_footprints(res.data(), levels + 1, reversible, w);
+}
+
 uint32_t cs_from_enum(uint32_t enumcs)
 {
     switch (enumcs) { // reference: j2k_openjpeg_codec.cpp:318-330
@@ -678,7 +749,97 @@ int j2k_hip_decode_device(j2k_hip_encoder *e, const void *file, size_t len, uint
     return guarded(e, [&] { decode_impl(e, file, len, subsample, planes, nplanes, true); });
 }
 
+int j2k_hip_decode_region(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_rect *region,
+                          const j2k_hip_outplane *planes, uint32_t nplanes)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] { decode_impl(e, file, len, subsample, planes, nplanes, false, region); });
+}
+
+int j2k_hip_decode_region_device(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_rect *region,
+                                 const j2k_hip_outplane *planes, uint32_t nplanes)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] { decode_impl(e, file, len, subsample, planes, nplanes, true, region); });
+}
+
+int j2k_hip_region_footprint(int reversible, uint32_t width, uint32_t height, uint32_t levels, uint32_t x0, uint32_t y0,
+                             const j2k_hip_rect *window, j2k_hip_rect *rects, uint32_t nrects)
+{
+    try {
+        if (!rects || levels > 32 || nrects < 3 * levels + 1) throw Error(J2K_HIP_ERR_PARAM, "3 * levels + 1 rectangles are needed");
+        std::vector<IRect> res;
+        const std::vector<ResFootprint> fp = plane_footprints(reversible != 0, width, height, levels, x0, y0, window, res);
+        // a band's place in the Mallat layout: behind the lower resolution's columns / rows where it is the high band
+        auto put = [&](uint32_t k, const IRect &need, int bx0, int by0, int offx, int offy) {
+            j2k_hip_rect o{0, 0, 0, 0};
+            if (!need.empty()) o = j2k_hip_rect{(uint32_t)(need.x0 - bx0 + offx), (uint32_t)(need.y0 - by0 + offy), (uint32_t)(need.x1 - need.x0), (uint32_t)(need.y1 - need.y0)};
+            rects[k] = o;
+        };
+        put(0, fp[0].win, res[0].x0, res[0].y0, 0, 0);
+        for (uint32_t r = 1; r <= levels; ++r) {
+            const int lw = res[r - 1].x1 - res[r - 1].x0, lh = res[r - 1].y1 - res[r - 1].y0;
+            const int hx0 = res[r].x0 >> 1, hy0 = res[r].y0 >> 1, lx0 = (res[r].x0 + 1) >> 1, ly0 = (res[r].y0 + 1) >> 1;
+            put(3 * (r - 1) + 1, fp[r].band[0], hx0, ly0, lw, 0);
+            put(3 * (r - 1) + 2, fp[r].band[1], lx0, hy0, 0, lh);
+            put(3 * (r - 1) + 3, fp[r].band[2], hx0, hy0, lw, lh);
+        }
+        return J2K_HIP_OK;
+    } catch (const Error &x) {
+        create_error() = x.what();
+        return x.code;
+    } catch (const std::exception &x) {
+        create_error() = x.what();
+        return J2K_HIP_ERR_PARAM;
+    }
+}
+
 // ---------------------------------------------------------------------------------------- decode stages (tests)
+int j2k_hip_stage_idwt_window(j2k_hip_encoder *e, int reversible, uint32_t width, uint32_t height, uint32_t nplanes, uint32_t levels,
+                              uint32_t x0, uint32_t y0, const j2k_hip_rect *window, const void *d_in, void *d_out)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        if (!nplanes || !d_in || !d_out) throw Error(J2K_HIP_ERR_PARAM, "bad inverse DWT stage arguments");
+        std::vector<IRect> res;
+        const std::vector<ResFootprint> fp = plane_footprints(reversible != 0, width, height, levels, x0, y0, window, res);
+        const size_t plane = (size_t)width * height, bytes = plane * nplanes * 4;
+        e->Q.ensure(bytes);
+        e->geo_valid = false; e->seq_valid = false; // the encode path's job table and planes are overwritten
+        std::vector<IdwtWinJob> jobs;
+        std::vector<size_t> first(levels + 2, 0);
+        std::vector<int> mh(levels + 1, 0), mv(levels + 1, 0);
+        for (uint32_t r = 1; r <= levels; ++r) {
+            first[r] = jobs.size();
+            if (fp[r].win.empty()) continue;
+            for (uint32_t c = 0; c < nplanes; ++c) {
+                const IdwtWinJob j = window_job(res[r], fp[r], (long long)(c * plane));
+                idwt_window_items(j, mh[r], mv[r]);
+                jobs.push_back(j);
+            }
+        }
+        first[levels + 1] = jobs.size();
+        HIP_CHECK(hipMemcpyAsync(d_out, d_in, bytes, hipMemcpyDeviceToDevice, s));
+        if (!jobs.empty()) {
+            e->jobs.ensure(jobs.size() * sizeof(IdwtWinJob));
+            HIP_CHECK(hipMemcpyAsync(e->jobs.p, jobs.data(), jobs.size() * sizeof(IdwtWinJob), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s)); // `jobs` is a pageable host vector
+            for (uint32_t r = 1; r <= levels; ++r) { // lowest resolution first
+                IdwtWinArgs ia{};
+                ia.a = d_out; ia.tmp = e->Q.p; ia.stride = (long long)width;
+                ia.jobs = e->jobs.as<IdwtWinJob>() + first[r]; ia.njobs = (int)(first[r + 1] - first[r]);
+                ia.max_h_items = mh[r]; ia.max_v_items = mv[r]; ia.reversible = reversible;
+                launch_idwt_window_level(ia, s);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 int j2k_hip_stage_idwt(j2k_hip_encoder *e, int reversible, uint32_t width, uint32_t height, uint32_t nplanes, uint32_t levels,
                        uint32_t x0, uint32_t y0, const j2k_hip_idwt_region *regions, uint32_t nregions, const void *d_in, void *d_out)
 {

@@ -175,6 +175,88 @@ __global__ __launch_bounds__(256) void idwt_v_kernel(IdwtArgs g)
     }
 }
 
+// ---- a window of the resolution (region decode).  The same synth_pair / synth_pairs over the same get() and reflect_idx as
+// above, so every output is the full transform's bit for bit; only which outputs are produced differs.  A job's work items
+// are numbered row by row over its own window (one division per thread): a window a few dozen samples wide still fills its
+// wavefronts, and consecutive lanes touch consecutive words.
+__device__ __forceinline__ int win_pair0(int w0, int cas) { return (w0 + cas) >> 1; }      // the pair that holds position w0
+__device__ __forceinline__ int win_npairs(int w0, int w1, int cas) { return ((w1 - 1 + cas) >> 1) - ((w0 + cas) >> 1) + 1; }
+
+template <bool REV>
+__global__ __launch_bounds__(256) void idwt_win_h_kernel(IdwtWinArgs g)
+{
+    using T = typename std::conditional<REV, int, float>::type;
+    for (int jz = blockIdx.y; jz < g.njobs; jz += gridDim.y) {
+    const IdwtWinJob job = g.jobs[jz];
+    const int n = job.rw, cas = job.casx;
+    const int npx = win_npairs(job.wx0, job.wx1, cas);
+    const int nlow = job.ly1 - job.ly0, nrows = nlow + (job.hy1 - job.hy0);
+    const int item = blockIdx.x * 256 + threadIdx.x;
+    if (item >= npx * nrows) continue;
+    const int row = item / npx, k = win_pair0(job.wx0, cas) + (item - row * npx);
+    // the band row in the Mallat layout: low rows first, the high rows behind the resolution's low rows
+    const int y = row < nlow ? job.ly0 + row : ((job.rh + 1 - job.casy) >> 1) + job.hy0 + (row - nlow);
+    const T *src = reinterpret_cast<const T *>(g.a) + job.off + (long long)y * g.stride;
+    T *dst = reinterpret_cast<T *>(g.tmp) + job.off + (long long)y * g.stride;
+    const int sn = (n + 1 - cas) >> 1;
+    const int ie = 2 * k - cas;
+    if (n == 1) {
+        const T v = src[0];
+        if constexpr (REV) dst[0] = cas ? v / 2 : v; else dst[0] = v;
+        continue;
+    }
+    auto get = [&](int j) -> T {
+        const bool low = ((j + cas) & 1) == 0;
+        const T v = low ? src[(j - cas) >> 1] : src[sn + ((j - 1 + cas) >> 1)];
+        if constexpr (REV) return v;
+        else return low ? v * I97_K : v * I97_TWO_INVK;
+    };
+    T e, o;
+    synth_pair<REV, T>(get, n, ie, e, o);
+    if (ie >= job.wx0 && ie < job.wx1) dst[ie] = e;
+    if (ie + 1 >= job.wx0 && ie + 1 < job.wx1) dst[ie + 1] = o;
+    }
+}
+
+template <bool REV>
+__global__ __launch_bounds__(256) void idwt_win_v_kernel(IdwtWinArgs g)
+{
+    using T = typename std::conditional<REV, int, float>::type;
+    for (int jz = blockIdx.y; jz < g.njobs; jz += gridDim.y) {
+    const IdwtWinJob job = g.jobs[jz];
+    const int n = job.rh, cas = job.casy;
+    const int wcols = job.wx1 - job.wx0;
+    const int ngroups = (win_npairs(job.wy0, job.wy1, cas) + kVPairs - 1) / kVPairs;
+    const int item = blockIdx.x * 256 + threadIdx.x;
+    if (item >= wcols * ngroups) continue;
+    const int grp = item / wcols, x = job.wx0 + (item - grp * wcols);
+    const int k = win_pair0(job.wy0, cas) + grp * kVPairs;
+    const T *src = reinterpret_cast<const T *>(g.tmp) + job.off + x;
+    T *dst = reinterpret_cast<T *>(g.a) + job.off + x;
+    const int sn = (n + 1 - cas) >> 1;
+    const int ie = 2 * k - cas;
+    if (n == 1) {
+        const T v = src[0];
+        if constexpr (REV) dst[0] = cas ? v / 2 : v; else dst[0] = v;
+        continue;
+    }
+    auto get = [&](int j) -> T {
+        const bool low = ((j + cas) & 1) == 0;
+        const T v = low ? src[(long long)((j - cas) >> 1) * g.stride] : src[(long long)(sn + ((j - 1 + cas) >> 1)) * g.stride];
+        if constexpr (REV) return v;
+        else return low ? v * I97_K : v * I97_TWO_INVK;
+    };
+    T e[kVPairs], o[kVPairs];
+    synth_pairs<REV, T, kVPairs>(get, n, ie, e, o);
+#pragma unroll
+    for (int p = 0; p < kVPairs; ++p) {
+        const int i = ie + 2 * p;
+        if (i >= job.wy0 && i < job.wy1) dst[(long long)i * g.stride] = e[p];
+        if (i + 1 >= job.wy0 && i + 1 < job.wy1) dst[(long long)(i + 1) * g.stride] = o[p];
+    }
+    }
+}
+
 // CopyChannel<DESTTYPE, int> of the reference for unsigned samples: bitShift = dest.depth - src.depth
 __device__ __forceinline__ unsigned depth_out(unsigned v, int src_depth, int dst_depth, unsigned dst_mask)
 {
@@ -215,7 +297,7 @@ __global__ __launch_bounds__(256) void decode_output_kernel(DecOutArgs a)
     // its signed range and offset by 2^(depth-1) there (:250-252), an unsigned one gets the DC level shift back: one formula.
     long long o[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) o[c] = c < a.ncomp ? (long long)(y / a.sub_y[c]) * a.stride + (x / a.sub_x[c]) : 0;
+    for (int c = 0; c < 4; ++c) o[c] = c < a.ncomp ? (long long)((a.org_y + y) / a.sub_y[c]) * a.stride + ((a.org_x + x) / a.sub_x[c]) : 0;
     int v[4] = {0, 0, 0, 0};
     if constexpr (REV) {
         int s[4] = {0, 0, 0, 0};
@@ -270,6 +352,27 @@ void launch_idwt_level(const IdwtArgs &a, hipStream_t s)
     } else {
         hipLaunchKernelGGL(idwt_h_kernel<false>, gh, dim3(256), 0, s, a);
         hipLaunchKernelGGL(idwt_v_kernel<false>, gv, dim3(256), 0, s, a);
+    }
+}
+
+void idwt_window_items(const IdwtWinJob &j, int &h_items, int &v_items)
+{
+    auto npairs = [](int w0, int w1, int cas) { return ((w1 - 1 + cas) >> 1) - ((w0 + cas) >> 1) + 1; };
+    h_items = npairs(j.wx0, j.wx1, j.casx) * ((j.ly1 - j.ly0) + (j.hy1 - j.hy0));
+    v_items = (j.wx1 - j.wx0) * ((npairs(j.wy0, j.wy1, j.casy) + kVPairs - 1) / kVPairs);
+}
+
+void launch_idwt_window_level(const IdwtWinArgs &a, hipStream_t s)
+{
+    if (a.njobs <= 0 || a.max_h_items <= 0 || a.max_v_items <= 0) return;
+    const dim3 gh((unsigned)((a.max_h_items + 255) / 256), (unsigned)std::min(a.njobs, 65535), 1);
+    const dim3 gv((unsigned)((a.max_v_items + 255) / 256), (unsigned)std::min(a.njobs, 65535), 1);
+    if (a.reversible) {
+        hipLaunchKernelGGL(idwt_win_h_kernel<true>, gh, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(idwt_win_v_kernel<true>, gv, dim3(256), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(idwt_win_h_kernel<false>, gh, dim3(256), 0, s, a);
+        hipLaunchKernelGGL(idwt_win_v_kernel<false>, gv, dim3(256), 0, s, a);
     }
 }
 

@@ -279,6 +279,27 @@ struct IdwtArgs {
 };
 void launch_idwt_level(const IdwtArgs &a, hipStream_t s);
 
+// The same transform for a window of the resolution (region decode): only the window [wx0, wx1) x [wy0, wy1) of every job
+// is produced.  The horizontal pass writes the window's columns on the band rows the vertical pass reads -- low rows
+// [ly0, ly1) and high rows [hy0, hy1) of the Mallat layout (decode_plan.h: ResFootprint); the vertical pass writes the
+// window.  Everything is relative to the job's region (0 <= wx0 < wx1 <= rw ...).  Both grids are sized by the windows:
+// a work item = one output pair of a row (horizontal) or kVPairs row pairs of a column (vertical), items of a job
+// numbered row by row so that narrow windows of low resolutions still fill their wavefronts.
+struct IdwtWinJob {
+    long long off;
+    int rw, rh, casx, casy;
+    int wx0, wx1, wy0, wy1;
+    int ly0, ly1, hy0, hy1;
+};
+struct IdwtWinArgs {
+    void *a, *tmp; long long stride;
+    const IdwtWinJob *jobs; int njobs;
+    int max_h_items, max_v_items; // over the jobs: idwt_window_items()
+    int reversible;
+};
+void idwt_window_items(const IdwtWinJob &j, int &h_items, int &v_items);
+void launch_idwt_window_level(const IdwtWinArgs &a, hipStream_t s);
+
 // Inverse component transform, DC level shift, clamp, and Codec::CopyBuffer towards the destination channels
 // (reference: src/common/j2k_codec.cpp:222-427): writes only the samples of the destination channels.
 struct DecOutArgs {
@@ -288,12 +309,16 @@ struct DecOutArgs {
     int nout;                              // destination channels
     uint8_t *dst[4]; long long colbytes[4], rowbytes[4];
     int dst_bytes[4], dst_depth[4], dst_w[4], dst_h[4];
+    // region decode: image position of the destination's sample (0, 0) -- the components are read at (org_x + x, org_y + y),
+    // so a sub-sampled component keeps its replication phase; width / height are the window's.  0, 0: the whole image.
+    int org_x, org_y;
 };
 // Preconditions (not checked on the device; decoder.cpp: decode_output_args is the one place that fills the struct, for a
 // decode and for the stage hook alike):
 //   * 1 <= ncomp <= 4, nout <= ncomp; with mct, ncomp >= 3 and components 0..2 share precision and sub-sampling factors;
 //   * cprec[c] in 1..16, sub_x[c] and sub_y[c] >= 1; comp[c] holds ceil(width / sub_x[c]) x ceil(height / sub_y[c]) words at
-//     row stride `stride` (every component of ncomp is read, whether or not a channel receives it);
+//     row stride `stride` (every component of ncomp is read, whether or not a channel receives it) -- with an origin,
+//     ceil((org_x + width) / sub_x[c]) x ceil((org_y + height) / sub_y[c]) words; org_x, org_y >= 0;
 //   * dst_bytes[c] is 1 or 2 and 1 <= dst_depth[c] <= 8 * dst_bytes[c]; dst_w[c] <= width, dst_h[c] <= height;
 //   * dst[c] + y * rowbytes[c] + x * colbytes[c] is writable for x < dst_w[c], y < dst_h[c], and 2-byte aligned where
 //     dst_bytes[c] is 2 (16-bit samples go out as one store).
