@@ -378,6 +378,58 @@ int j2k_hip_decode_region_device(j2k_hip_encoder *enc, const void *file, size_t 
 int j2k_hip_region_footprint(int reversible, uint32_t width, uint32_t height, uint32_t levels, uint32_t x0, uint32_t y0,
                              const j2k_hip_rect *window, j2k_hip_rect *rects, uint32_t nrects);
 
+/* --- decode straight to R, G, B, A ----------------------------------------------------------------
+ * What RGBAinputFile::ReadFile (reference: src/common/j2k_rgba_file.cpp:450-735) does on the CPU after Codec::ReadFile --
+ * sYCC -> RGB, grey into three channels, the palette look-up, the alpha fill -- and the DemoteWorld pass of
+ * j2k_DrawSparseFrame (src/aftereffects/j2k.cpp:482-492), done by the decode's output kernel instead.
+ *
+ * j2k_hip_rgba_mode: how a file's components become R, G, B, A; header only, no device needed.  n = min(channels, 4);
+ * the rules in order:
+ *   what j2k_hip_read_info refuses is refused the same way (same status, same text);
+ *   PALETTE  a palette is present (then n == 1): R / G / B = the palette column c whose lut_column[c] is 0 / 1 / 2 (the
+ *            column HipCodec::GetFileInfo reports as LUTmap[c] = RED / GREEN / BLUE; without one, column 0 / 1 / 2); a
+ *            fourth column is ignored;
+ *   GREY     n is 1 or 2, colour space grey or unspecified (ICC included): component 0 -> R, G and B, component 1 -> A;
+ *   SYCC     colour space sYCC, n >= 3: components 0, 1, 2 are Y, Cb, Cr; a fourth component is not read, A is filled;
+ *   RGB      n >= 3, colour space sRGB or unspecified (ICC included): components 0, 1, 2 -> R, G, B, component 3 -> A;
+ *   anything else (CMYK, e-sYCC, one or two channels in a colour space that is not grey ...) is J2K_HIP_ERR_UNSUPPORTED with a
+ *   text that names the colour space -- the reference's own code asserts there; the host takes its old path.  So is an
+ *   opacity channel that the cdef box declares anywhere but last (alpha not 0 and not n) in the GREY and RGB modes. */
+enum { J2K_HIP_RGBA_RGB = 1, J2K_HIP_RGBA_GREY = 2, J2K_HIP_RGBA_PALETTE = 3, J2K_HIP_RGBA_SYCC = 4 };
+int j2k_hip_rgba_mode(const void *file, size_t len, uint32_t *mode);
+
+/* The four destination channels.  They share sample_bits (8 or 16) and depth D (1 <= D <= sample_bits).  Per pixel:
+ *   1. component samples exactly as j2k_hip_decode delivers them at depth D (replication of sub-sampled components,
+ *      inverse RCT / ICT, DC shift, clamp, CopyChannel's depth conversion);
+ *   2. RGB: R, G, B[, A] = v0, v1, v2[, v3].  GREY: R = G = B = v0[, A = v1].
+ *      PALETTE: idx = component 0 at its own precision; e = idx < lut_size ? lut[idx] : {0, 0, 0}; a channel is its column
+ *      of e for 8-bit samples and (e << 8) | e for 16-bit samples, whatever D is (ConvertToType, :57-70).
+ *      SYCC, with h = 1 << (D - 1) and sY = v0 - h, sCb = v1 - h, sCr = v2 - h, in float, every operation rounded on its
+ *      own (no fused multiply-add), the reference's irreversible branch (:185-278, :392):
+ *          fR = sY + 1.402f * sCr;  fG = (sY - kCrG * sCr) - kCbG * sCb;  fB = sY + 1.772f * sCb
+ *          channel = clamp((int)((f + h) + 0.5f), 0, 2^D - 1)                          (the cast truncates)
+ *      kCrG = (float)(2 * 0.299 * (1 - 0.299) / 0.587), kCbG = (float)(2 * 0.114 * (1 - 0.114) / 0.587);
+ *   3. a mode that delivers no A fills it with 2^D - 1 (the reference narrows that value to 8 bits first, :416, so a
+ *      16-bit world gets 255 there: deliberately not reproduced);
+ *   4. demote_ae16: every channel, the filled A included, leaves as v > 32768 ? ((v - 1) >> 1) + 1 : v >> 1 (Demote,
+ *      src/aftereffects/FrameSeq.cpp:265-268); needs sample_bits == 16 and D == 16;
+ *   5. only samples of the given channels are written; a.base == NULL: no alpha wanted.  Four channels that are the four
+ *      samples of one pixel record (A,R,G,B or R,G,B,A interleaved, record-aligned) leave as one store per pixel.
+ * Width, height, subsample and region are j2k_hip_decode's / j2k_hip_decode_region's (region == NULL: the whole image).
+ * Refused before any device work, nothing written: J2K_HIP_ERR_PARAM for a bad struct_size, a NULL r / g / b, channels of
+ * unlike sample_bits or depth, demote_ae16 without 16-bit samples of depth 16, a bad region; J2K_HIP_ERR_UNSUPPORTED for
+ * what j2k_hip_rgba_mode does not classify.  J2K_HIP_ABI_VERSION is still 9: functions were added, none changed. */
+typedef struct j2k_hip_rgba_dst {
+    uint32_t struct_size;
+    j2k_hip_outplane r, g, b, a;
+    uint32_t demote_ae16;
+} j2k_hip_rgba_dst;
+int j2k_hip_decode_rgba(j2k_hip_encoder *enc, const void *file, size_t len, uint32_t subsample,
+                        const j2k_hip_rect *region, const j2k_hip_rgba_dst *dst);
+/* Same with destination channels in device memory. */
+int j2k_hip_decode_rgba_device(j2k_hip_encoder *enc, const void *file, size_t len, uint32_t subsample,
+                               const j2k_hip_rect *region, const j2k_hip_rgba_dst *dst);
+
 /* --- stage-level entry points (parity tests and roofline measurement call these) -----------------
  * A1+A2+A4+A5: front end only. d_out = channels planes of width*height 32-bit words (int32 for
  * reversible, float32 bit patterns otherwise), row stride = width. */
@@ -466,6 +518,26 @@ int j2k_hip_stage_decode_output(j2k_hip_encoder *enc, int reversible, int mct, u
                                 const void *d_comp, size_t comp_words, uint32_t stride,
                                 const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf, size_t buf_bytes,
                                 const j2k_hip_outplane *planes, uint32_t nplanes);
+
+/* The RGBA output stage alone (decode_rgba_kernel), in the manner of j2k_hip_stage_decode_output: the components lie in
+ * d_comp as there -- ceil((org_x + width) / sub_x) x ceil((org_y + height) / sub_y) words each, the destination's pixel
+ * (0, 0) being image position (org_x, org_y) -- and the bases of dst's channels are byte OFFSETS into d_buf, so here the
+ * alpha channel is absent when dst->a.sample_bits == 0.  mode: J2K_HIP_RGBA_*; ncomp: 3 or 4 (RGB: the fourth is A), 1 or 2
+ * (GREY: the second is A), 1 (PALETTE), 3 or 4 (SYCC: three are read).  PALETTE: lut_size <= 256 entries of lut_columns <= 4
+ * bytes each in `lut`; R, G, B take columns lut_rgb[0..2].  Refused with J2K_HIP_ERR_PARAM: what j2k_hip_decode_rgba and
+ * j2k_hip_stage_decode_output refuse, a mode that cannot take ncomp components, a palette column beyond lut_columns. */
+typedef struct j2k_hip_rgba_stage {
+    uint32_t struct_size;
+    uint32_t mode;
+    uint32_t org_x, org_y;
+    uint32_t lut_size, lut_columns;
+    uint8_t lut[256][4];
+    uint8_t lut_rgb[4];
+} j2k_hip_rgba_stage;
+int j2k_hip_stage_rgba_output(j2k_hip_encoder *enc, int reversible, int mct, uint32_t width, uint32_t height,
+                              const void *d_comp, size_t comp_words, uint32_t stride,
+                              const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf, size_t buf_bytes,
+                              const j2k_hip_rgba_dst *dst, const j2k_hip_rgba_stage *stage);
 
 /* Tier-1 DECODING of `nblocks` code-blocks (default code-block style) into one coefficient plane of 32-bit
  * words (row stride `stride` words; int32 for reversible, float32 otherwise).  kernel = 0: a wavefront per

@@ -85,6 +85,7 @@ WRITE_FN = C.CFUNCTYPE(C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t)
 EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_last_error", "j2k_hip_encode",
            "j2k_hip_encode_begin", "j2k_hip_encode_begin_borrowed", "j2k_hip_encode_end", "j2k_hip_debug_tune", "j2k_hip_debug_get_tune", "j2k_hip_debug_fused_occupancy", "j2k_hip_debug_membw", "j2k_hip_debug_dwt_time", "j2k_hip_read_info", "j2k_hip_decode",
            "j2k_hip_decode_device", "j2k_hip_decode_region", "j2k_hip_decode_region_device", "j2k_hip_region_footprint",
+           "j2k_hip_rgba_mode", "j2k_hip_decode_rgba", "j2k_hip_decode_rgba_device", "j2k_hip_stage_rgba_output",
            "j2k_hip_encode_tiles", "j2k_hip_device_count", "j2k_hip_encode_batch",
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
@@ -113,6 +114,20 @@ class DecBlock(C.Structure):
 class OutComp(C.Structure):
     """include/j2k_hip.h: j2k_hip_outcomp."""
     _fields_ = [("offset", C.c_uint64), ("prec", C.c_uint32), ("sub_x", C.c_uint32), ("sub_y", C.c_uint32)]
+
+
+class RgbaDst(C.Structure):
+    """include/j2k_hip.h: j2k_hip_rgba_dst."""
+    _fields_ = [("struct_size", C.c_uint32), ("r", OutPlane), ("g", OutPlane), ("b", OutPlane), ("a", OutPlane), ("demote_ae16", C.c_uint32)]
+
+
+class RgbaStage(C.Structure):
+    """include/j2k_hip.h: j2k_hip_rgba_stage."""
+    _fields_ = [(n, C.c_uint32) for n in ("struct_size", "mode", "org_x", "org_y", "lut_size", "lut_columns")] + \
+               [("lut", (C.c_uint8 * 4) * 256), ("lut_rgb", C.c_uint8 * 4)]
+
+
+RGBA_RGB, RGBA_GREY, RGBA_PALETTE, RGBA_SYCC = 1, 2, 3, 4  # J2K_HIP_RGBA_*
 
 
 class CopySink(C.Structure):
@@ -192,6 +207,11 @@ def load_library():
                                           C.c_void_p, C.c_size_t]
     L.j2k_hip_stage_decode_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32,
                                               C.POINTER(OutComp), C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(OutPlane), C.c_uint32]
+    L.j2k_hip_rgba_mode.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.j2k_hip_decode_rgba.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(Rect), C.POINTER(RgbaDst)]
+    L.j2k_hip_decode_rgba_device.argtypes = L.j2k_hip_decode_rgba.argtypes
+    L.j2k_hip_stage_rgba_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32,
+                                            C.POINTER(OutComp), C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(RgbaDst), C.POINTER(RgbaStage)]
     L.j2k_hip_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.j2k_hip_get_dwt_level_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
     L.j2k_hip_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -228,6 +248,22 @@ def read_info(data: bytes) -> dict:
     if rc != 0:
         raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
     return fi.as_dict()
+
+
+def rgba_mode(data: bytes) -> int:
+    """How the file's components become R, G, B, A (j2k_hip_rgba_mode: RGBA_RGB / _GREY / _PALETTE / _SYCC; no device needed)."""
+    L = load_library()
+    m = C.c_uint32()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    rc = L.j2k_hip_rgba_mode(buf.ctypes.data, len(data), C.byref(m))
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+    return m.value
+
+
+def _set_outplane(p, base, colbytes, rowbytes, sample_bits, depth, width, height):
+    p.base, p.colbytes, p.rowbytes = base, colbytes, rowbytes
+    p.sample_bits, p.depth, p.width, p.height = sample_bits, depth, width, height
 
 
 def region_footprint(width: int, height: int, levels: int, reversible: bool, window, x0: int = 0, y0: int = 0, nrects: int | None = None):
@@ -554,6 +590,44 @@ class Encoder:
                 self.free(d)
         return frame
 
+    def decode_rgba(self, data: bytes, frame: np.ndarray, layout: dict, width: int, height: int, depth: int | None = None,
+                    subsample: int = 1, region=None, demote: bool = False, device: bool = False, alpha: bool = True):
+        """Decode straight into the R, G, B, A samples of an After Effects ARGB frame (see synth.ae_frame; j2k_hip_decode_rgba):
+        colour conversion, palette, alpha fill and (demote) the 16 -> 15+1 bit Demote happen in the output kernel.  alpha=False:
+        no alpha destination, the frame's A samples stay.  device=True: through a device copy of the frame.  region = (x, y, w, h)."""
+        sb = layout["sample_bytes"]
+        offs = layout["channel_offsets"]  # A,R,G,B
+        d = self.upload(frame) if device else None
+        base = d if device else frame.ctypes.data
+        dst = RgbaDst()
+        dst.struct_size, dst.demote_ae16 = C.sizeof(RgbaDst), int(demote)
+        for p, off in ((dst.r, offs[1]), (dst.g, offs[2]), (dst.b, offs[3])) + (((dst.a, offs[0]),) if alpha else ()):
+            _set_outplane(p, base + off, layout["colbytes"], layout["rowbytes"], 8 * sb, depth or 8 * sb, width, height)
+        buf = np.frombuffer(data, dtype=np.uint8)
+        try:
+            fn = self.L.j2k_hip_decode_rgba_device if device else self.L.j2k_hip_decode_rgba
+            self._check(fn(self.h, buf.ctypes.data, len(data), subsample, C.byref(Rect(*region)) if region is not None else None, C.byref(dst)))
+            if device:
+                frame[:] = self.d2h(d, frame.nbytes)
+        finally:
+            if d:
+                self.free(d)
+        return frame
+
+    def decode_rgba_channels(self, data: bytes, r, g, b, a=None, depth: int | None = None, subsample: int = 1, region=None, demote: bool = False):
+        """j2k_hip_decode_rgba into one 2-D numpy view per channel, wherever each lies and whatever its strides (planar buffers,
+        padded or bottom-up rows, samples of interleaved pixels); a=None: no alpha destination."""
+        dst = RgbaDst()
+        dst.struct_size, dst.demote_ae16 = C.sizeof(RgbaDst), int(demote)
+        for p, v in ((dst.r, r), (dst.g, g), (dst.b, b), (dst.a, a)):
+            if v is None:
+                continue
+            assert v.ndim == 2 and v.dtype in (np.uint8, np.uint16)
+            _set_outplane(p, v.ctypes.data, v.strides[1], v.strides[0], 8 * v.itemsize, depth or 8 * v.itemsize, v.shape[1], v.shape[0])
+        buf = np.frombuffer(data, dtype=np.uint8)
+        self._check(self.L.j2k_hip_decode_rgba(self.h, buf.ctypes.data, len(data), subsample,
+                                               C.byref(Rect(*region)) if region is not None else None, C.byref(dst)))
+
     def stats(self) -> dict:
         s = Stats()
         self._check(self.L.j2k_hip_get_stats(self.h, C.byref(s)))
@@ -748,6 +822,51 @@ class Encoder:
         try:
             self._check(self.L.j2k_hip_stage_decode_output(self.h, int(reversible), int(mct), width, height, d_comp, words.size, stride,
                                                            oc, len(planes), d_buf, buf.nbytes, arr, len(chans)))
+            return self.d2h(d_buf, buf.nbytes)
+        finally:
+            self.free(d_comp)
+            self.free(d_buf)
+
+    def stage_rgba_output(self, comps, precs, subs, width: int, height: int, reversible: bool, mct: bool, mode: int, chans, buf: np.ndarray,
+                          demote: bool = False, lut=None, lut_rgb=(0, 1, 2), org=(0, 0), stride: int | None = None,
+                          gap: int = 0x7fc0dead) -> np.ndarray:
+        """The RGBA output stage alone (j2k_hip_stage_rgba_output).  comps, precs, subs, stride, gap as in stage_decode_output,
+        each plane of ceil((org_y + height) / sub_y) x ceil((org_x + width) / sub_x) samples.  chans: the dicts of
+        stage_decode_output for R, G, B and A in this order; A may be None (no alpha destination).  lut: (entries, columns)
+        uint8 palette, lut_rgb the columns R, G, B take.  Returns the whole buffer as the kernel left it."""
+        dt = np.int32 if reversible else np.float32
+        planes = [np.ascontiguousarray(c).view(np.uint32) if np.asarray(c).dtype == np.uint32 else
+                  np.ascontiguousarray(c, dtype=dt).view(np.uint32) for c in comps]
+        stride = stride if stride is not None else max(p.shape[1] for p in planes)
+        words = np.full((sum(p.shape[0] for p in planes), max(stride, 1)), gap, dtype=np.uint32)
+        oc = (OutComp * len(planes))()
+        y0 = 0
+        for c, p in enumerate(planes):
+            words[y0:y0 + p.shape[0], :min(p.shape[1], stride)] = p[:, :stride]
+            oc[c].offset, oc[c].prec = y0 * stride, precs[c]
+            oc[c].sub_x, oc[c].sub_y = subs[c]
+            y0 += p.shape[0]
+        dst = RgbaDst()
+        dst.struct_size, dst.demote_ae16 = C.sizeof(RgbaDst), int(demote)
+        for p, ch in zip((dst.r, dst.g, dst.b, dst.a), chans):
+            if ch is not None:
+                _set_outplane(p, ch["base"], ch["colbytes"], ch["rowbytes"], ch["sample_bits"], ch["depth"], ch["width"], ch["height"])
+        st = RgbaStage()
+        st.struct_size, st.mode, st.org_x, st.org_y = C.sizeof(RgbaStage), mode, org[0], org[1]
+        if lut is not None:
+            lut = np.asarray(lut, dtype=np.uint8)
+            st.lut_size, st.lut_columns = lut.shape
+            for i in range(lut.shape[0]):
+                for k in range(lut.shape[1]):
+                    st.lut[i][k] = int(lut[i, k])
+            for k in range(3):
+                st.lut_rgb[k] = lut_rgb[k]
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        d_comp = self.upload(words)
+        d_buf = self.upload(buf)
+        try:
+            self._check(self.L.j2k_hip_stage_rgba_output(self.h, int(reversible), int(mct), width, height, d_comp, words.size, stride,
+                                                         oc, len(planes), d_buf, buf.nbytes, C.byref(dst), C.byref(st)))
             return self.d2h(d_buf, buf.nbytes)
         finally:
             self.free(d_comp)

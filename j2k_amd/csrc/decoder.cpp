@@ -126,8 +126,10 @@ IdwtWinJob window_job(const IRect &res, const ResFootprint &f, long long off)
 }
 
 // region (optional): the window of a region decode.  Null: the whole image, by the launches of every decode before regions.
+// rgba (optional): the output stage goes straight to R, G, B, A (rgba_out.hip); planes[0..nplanes) are then rgba's r, g, b[, a]
+// (decode_rgba_impl below), already checked.  Everything before the last launch is the same decode.
 void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_outplane *planes,
-                 uint32_t nplanes, bool planes_on_device, const j2k_hip_rect *region = nullptr)
+                 uint32_t nplanes, bool planes_on_device, const j2k_hip_rect *region = nullptr, const j2k_hip_rgba_dst *rgba = nullptr)
 {
     const double t_begin = now_ms();
     if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
@@ -144,7 +146,10 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
 
     // ---- host Tier-2, beside the upload of the file (the device needs nothing of the plan to receive the bytes).  The
     // headers are read first: a file this path cannot decode is turned away before the device is touched.
-    (void)parse_headers(fbytes, len);
+    {
+        const FileHeader early = parse_headers(fbytes, len);
+        if (rgba) (void)classify_rgba(early); // (a file the fused path does not take: J2K_HIP_ERR_UNSUPPORTED, nothing written)
+    }
     HIP_CHECK(hipEventRecord(e->ev[EV_START], s));
     e->d_file.ensure(len + 64);
     DecodePlan P;
@@ -486,9 +491,28 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     // ---- output stage
     OutComp oc[4] = {};
     for (uint32_t c = 0; c < nd; ++c) oc[c] = OutComp{e->Z.as<int32_t>() + c * plane_elems, cod.cprec[c], cod.cdx[c], cod.cdy[c]};
-    DecOutArgs oa = region ? decode_output_args(cod.reversible, cod.mct, (int)region->w, (int)region->h, (long long)stride, oc, nd, planes, nplanes,
-                                                (int)region->x, (int)region->y)
-                           : decode_output_args(cod.reversible, cod.mct, ow, oh, (long long)stride, oc, nd, planes, nplanes);
+    const int out_w = region ? (int)region->w : ow, out_h = region ? (int)region->h : oh;
+    const int org_x = region ? (int)region->x : 0, org_y = region ? (int)region->y : 0;
+    DecOutArgs oa{};
+    RgbaClass cls;
+    if (rgba) { // the channels' geometry alone, for the spans below: the RGBA kernel's arguments need the channels' device addresses
+        cls = classify_rgba(H);
+        oa.nout = (int)nplanes;
+        for (int c = 0; c < oa.nout; ++c) {
+            const j2k_hip_outplane &p = planes[c];
+            oa.colbytes[c] = p.colbytes; oa.rowbytes[c] = p.rowbytes; oa.dst_bytes[c] = (int)p.sample_bits / 8;
+            oa.dst_w[c] = (int)std::min<uint32_t>(p.width, (uint32_t)out_w); oa.dst_h[c] = (int)std::min<uint32_t>(p.height, (uint32_t)out_h);
+        }
+    } else oa = decode_output_args(cod.reversible, cod.mct, out_w, out_h, (long long)stride, oc, nd, planes, nplanes, org_x, org_y);
+    auto launch_output = [&] { // (oa.dst[] hold the channels' device addresses by now)
+        if (!rgba) { launch_decode_output(oa, s); return; }
+        j2k_hip_rgba_dst d = *rgba;
+        j2k_hip_outplane *const ch[4] = {&d.r, &d.g, &d.b, &d.a};
+        for (int c = 0; c < oa.nout; ++c) ch[c]->base = oa.dst[c];
+        RgbaComp rc[4] = {};
+        for (int c = 0; c < cls.ncomp; ++c) rc[c] = RgbaComp{oc[c].plane, oc[c].prec, oc[c].sub_x, oc[c].sub_y};
+        launch_decode_rgba(decode_rgba_args(cod.reversible, cod.mct, out_w, out_h, (long long)stride, rc, cls, d, nplanes == 4, org_x, org_y), s);
+    };
     // The destination channels' extents in the caller's address space.  Channels whose extents overlap (the samples of
     // interleaved pixels) form one span that keeps its layout on the device; channels that lie apart (planar buffers,
     // wherever they were allocated) are spans of their own.
@@ -522,7 +546,7 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     }
     if (planes_on_device) {
         for (int c = 0; c < oa.nout; ++c) oa.dst[c] = static_cast<uint8_t *>(planes[c].base);
-        launch_decode_output(oa, s);
+        launch_output();
         HIP_CHECK(hipGetLastError()); // a launch the runtime refused must not end as a frame of zeros
         HIP_CHECK(hipEventRecord(e->ev[EV_GATHER], s));
         HIP_CHECK(hipStreamSynchronize(s));
@@ -539,7 +563,7 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
                 const int c = spans[k].ch[i];
                 oa.dst[c] = e->d_outimg.as<uint8_t>() + spans[k].dev + (static_cast<const uint8_t *>(planes[c].base) - spans[k].lo);
             }
-        launch_decode_output(oa, s);
+        launch_output();
         HIP_CHECK(hipGetLastError()); // a launch the runtime refused must not end as a frame of zeros
         HIP_CHECK(hipEventRecord(e->ev[EV_GATHER], s));
         std::vector<hipEvent_t> band_ev;
@@ -684,21 +708,52 @@ std::vector<ResFootprint> plane_footprints(bool reversible, uint32_t width, uint
     return region_footprints(res.data(), levels + 1, reversible, w);
 }
 
-uint32_t cs_from_enum(uint32_t enumcs)
+// j2k_hip_decode_rgba[_device]: the destination is checked before anything else happens, then the decode above runs with
+// R, G, B[, A] as its channels and the RGBA kernel as its last launch.
+void decode_rgba_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_rect *region,
+                      const j2k_hip_rgba_dst *dst, bool on_device)
 {
-    switch (enumcs) { // reference: j2k_openjpeg_codec.cpp:318-330
-    case 16: return J2K_HIP_CS_SRGB;
-    case 17: return J2K_HIP_CS_GRAY;
-    case 18: return J2K_HIP_CS_SYCC;
-    case 24: case 19: return J2K_HIP_CS_EYCC;
-    case 12: return J2K_HIP_CS_CMYK;
-    default: return J2K_HIP_CS_UNSPECIFIED;
-    }
+    if (!dst) throw Error(J2K_HIP_ERR_PARAM, "no RGBA destination");
+    if (dst->struct_size != sizeof(j2k_hip_rgba_dst)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_rgba_dst.struct_size mismatch (ABI drift)");
+    if (!dst->r.base || !dst->g.base || !dst->b.base) throw Error(J2K_HIP_ERR_PARAM, "destination channel buffer is NULL");
+    const bool alpha = dst->a.base != nullptr;
+    check_rgba_dst(*dst, alpha);
+    const j2k_hip_outplane planes[4] = {dst->r, dst->g, dst->b, dst->a};
+    decode_impl(e, file, len, subsample, planes, alpha ? 4 : 3, on_device, region, dst);
 }
 
 } // namespace
 
 extern "C" {
+
+int j2k_hip_rgba_mode(const void *file, size_t len, uint32_t *mode)
+{
+    if (!mode) return J2K_HIP_ERR_PARAM;
+    try {
+        *mode = classify_rgba(parse_headers(static_cast<const uint8_t *>(file), len)).mode;
+        return J2K_HIP_OK;
+    } catch (const Error &x) {
+        create_error() = x.what();
+        return x.code;
+    } catch (const std::exception &x) {
+        create_error() = x.what();
+        return J2K_HIP_ERR_PARAM;
+    }
+}
+
+int j2k_hip_decode_rgba(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_rect *region,
+                        const j2k_hip_rgba_dst *dst)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] { decode_rgba_impl(e, file, len, subsample, region, dst, false); });
+}
+
+int j2k_hip_decode_rgba_device(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_rect *region,
+                               const j2k_hip_rgba_dst *dst)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] { decode_rgba_impl(e, file, len, subsample, region, dst, true); });
+}
 
 int j2k_hip_read_info(const void *file, size_t len, j2k_hip_file_info *info)
 {
@@ -936,6 +991,66 @@ int j2k_hip_stage_decode_output(j2k_hip_encoder *e, int reversible, int mct, uin
                 throw Error(J2K_HIP_ERR_PARAM, "16-bit destination channel at an odd address");
         }
         launch_decode_output(oa, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int j2k_hip_stage_rgba_output(j2k_hip_encoder *e, int reversible, int mct, uint32_t width, uint32_t height, const void *d_comp,
+                              size_t comp_words, uint32_t stride, const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf,
+                              size_t buf_bytes, const j2k_hip_rgba_dst *dst, const j2k_hip_rgba_stage *stage)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        if (!width || !height || width > (1u << 30) || height > (1u << 30) || !stride || !d_comp || !comps || !d_buf || !dst || !stage)
+            throw Error(J2K_HIP_ERR_PARAM, "bad output stage arguments");
+        if (stage->struct_size != sizeof(j2k_hip_rgba_stage)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_rgba_stage.struct_size mismatch (ABI drift)");
+        if (dst->struct_size != sizeof(j2k_hip_rgba_dst)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_rgba_dst.struct_size mismatch (ABI drift)");
+        if (stage->org_x > (1u << 30) || stage->org_y > (1u << 30)) throw Error(J2K_HIP_ERR_PARAM, "window origin beyond 2^30");
+        const bool alpha = dst->a.sample_bits != 0; // (the bases are offsets here: 0 is one)
+        check_rgba_dst(*dst, alpha);
+        RgbaClass cls = rgba_class(stage->mode, ncomp);
+        if (cls.mode == J2K_HIP_RGBA_PALETTE) {
+            if (stage->lut_size > 256 || stage->lut_columns > 4) throw Error(J2K_HIP_ERR_PARAM, "palette beyond 256 entries of 4 columns");
+            cls.lut_size = stage->lut_size;
+            for (uint32_t i = 0; i < cls.lut_size; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    if (stage->lut_rgb[j] >= stage->lut_columns) throw Error(J2K_HIP_ERR_PARAM, "palette column beyond the table");
+                    cls.lut[i] |= (uint32_t)stage->lut[i][stage->lut_rgb[j]] << (8 * j);
+                }
+        }
+        // every word the kernel reads lies in the component buffer ...
+        RgbaComp rc[4] = {};
+        for (int c = 0; c < cls.ncomp; ++c) {
+            if (comps[c].sub_x < 1 || comps[c].sub_y < 1) throw Error(J2K_HIP_ERR_PARAM, "sub-sampling factor outside 1..255");
+            const uint64_t cw = ((uint64_t)stage->org_x + width + comps[c].sub_x - 1) / comps[c].sub_x, ch = ((uint64_t)stage->org_y + height + comps[c].sub_y - 1) / comps[c].sub_y;
+            if (cw > stride || comps[c].offset > comp_words || (ch - 1) * (uint64_t)stride + cw > comp_words - comps[c].offset)
+                throw Error(J2K_HIP_ERR_PARAM, "component plane outside the buffer");
+            rc[c] = RgbaComp{static_cast<const uint32_t *>(d_comp) + comps[c].offset, comps[c].prec, comps[c].sub_x, comps[c].sub_y};
+        }
+        // ... and every sample it writes in the channel buffer, 16-bit ones at even addresses
+        j2k_hip_rgba_dst d = *dst;
+        j2k_hip_outplane *const chn[4] = {&d.r, &d.g, &d.b, &d.a};
+        for (int c = 0; c < (alpha ? 4 : 3); ++c) {
+            j2k_hip_outplane &p = *chn[c];
+            const int w = (int)std::min(p.width, width), h = (int)std::min(p.height, height), sb = (int)p.sample_bits / 8;
+            const __int128 base = (__int128)reinterpret_cast<uintptr_t>(p.base);
+            if (base > (__int128)buf_bytes) throw Error(J2K_HIP_ERR_PARAM, "destination channel outside the buffer");
+            p.base = static_cast<uint8_t *>(d_buf) + (size_t)base;
+            if (w <= 0 || h <= 0) continue;
+            const __int128 dx = (__int128)(w - 1) * p.colbytes, dy = (__int128)(h - 1) * p.rowbytes;
+            const __int128 lo = base + std::min<__int128>(dx, 0) + std::min<__int128>(dy, 0);
+            const __int128 hi = base + std::max<__int128>(dx, 0) + std::max<__int128>(dy, 0) + sb;
+            if (lo < 0 || hi > (__int128)buf_bytes) throw Error(J2K_HIP_ERR_PARAM, "destination channel outside the buffer");
+            if (sb == 2 && ((reinterpret_cast<uintptr_t>(p.base) & 1) || (w > 1 && (p.colbytes & 1)) || (h > 1 && (p.rowbytes & 1))))
+                throw Error(J2K_HIP_ERR_PARAM, "16-bit destination channel at an odd address");
+        }
+        const DecRgbaArgs ra = decode_rgba_args(reversible != 0, mct != 0, (int)width, (int)height, (long long)stride, rc, cls, d, alpha,
+                                                (int)stage->org_x, (int)stage->org_y);
+        launch_decode_rgba(ra, s);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));
     });

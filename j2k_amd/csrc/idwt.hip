@@ -13,6 +13,7 @@
 // L1/L2).  Two passes per resolution: 2 x the algorithmic bytes.  (The forward transform's register-streaming
 // single-pass structure, dwt.hip, is the next step for this kernel.)
 #include "kernels.h"
+#include "out_sample.h"
 
 #include <algorithm>
 #include <climits>
@@ -255,35 +256,6 @@ __global__ __launch_bounds__(256) void idwt_win_v_kernel(IdwtWinArgs g)
         if (i + 1 >= job.wy0 && i + 1 < job.wy1) dst[(long long)(i + 1) * g.stride] = o[p];
     }
     }
-}
-
-// CopyChannel<DESTTYPE, int> of the reference for unsigned samples: bitShift = dest.depth - src.depth
-__device__ __forceinline__ unsigned depth_out(unsigned v, int src_depth, int dst_depth, unsigned dst_mask)
-{
-    const int shift = dst_depth - src_depth;
-    if (shift == 0) return v;
-    if (shift < 0) return v >> (-shift);
-    if (src_depth >= 8) {
-        if (shift <= src_depth) return (v << shift) | (v >> (src_depth - shift));
-        const int second = shift - src_depth;
-        const unsigned t = ((v << src_depth) | v) & dst_mask; // DESTTYPE t: truncated before the second fill
-        return (t << second) | (t >> (src_depth * 2 - second));
-    }
-    unsigned pd = (unsigned)src_depth, t = v;
-    while (pd * 2 < (unsigned)dst_depth) { t = ((t << pd) | t) & dst_mask; pd *= 2; }
-    const int second = dst_depth - (int)pd;
-    return (t << second) | (t >> ((int)pd - second));
-}
-
-// lrintf with libopenjp2's explicit limits (opj_lrintf behind comparisons against +-2^31): a float below -2^31 and NaN give
-// the lowest value, one at or above 2^31 the highest, everything between rounds to nearest even.  The cast is reached by
-// in-range values only, so no bit pattern's result depends on what the compiler makes of an out-of-range conversion; the
-// clamp behind the DC offset turns the two ends into 0 and 2^prec - 1.
-__device__ __forceinline__ int sat_lrintf(float f)
-{
-    if (!(f >= -2147483648.0f)) return INT_MIN;
-    if (f >= 2147483648.0f) return INT_MAX;
-    return (int)__builtin_rintf(f);
 }
 
 template <bool REV>

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "rgba_plan.h"
+
 namespace j2k_hip {
 
 // ------------------------------------------------------------------------------------------------
@@ -323,6 +325,12 @@ struct DecOutArgs {
 //   * dst[c] + y * rowbytes[c] + x * colbytes[c] is writable for x < dst_w[c], y < dst_h[c], and 2-byte aligned where
 //     dst_bytes[c] is 2 (16-bit samples go out as one store).
 void launch_decode_output(const DecOutArgs &a, hipStream_t s);
+
+// The same stage straight to R, G, B, A (rgba_out.hip): the component samples as above, then the file's mode (RGB, grey,
+// palette, sYCC), the alpha fill and Demote, stored as one record per pixel where the four channels form one.  DecRgbaArgs
+// and its preconditions are in rgba_plan.h (no HIP types: the function that fills it, decode_rgba_args, is host code that
+// is also built and run on its own).
+void launch_decode_rgba(const DecRgbaArgs &a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Codestream assembly: copies header pieces and code-block segments to their final offsets.

@@ -1,0 +1,130 @@
+// rgba_out.hip -- the decode's output stage straight to R, G, B, A (gfx950).
+//
+// Replaces, after the inverse DWT, what the host did per pixel on the CPU once the codec channels had arrived (reference:
+// RGBAinputFile::ReadFile, src/common/j2k_rgba_file.cpp:450-735 -- sYCC -> RGB :185-278, grey into three channels, the
+// palette look-up :72-137, the alpha fill :407-448 -- and DemoteWorld, src/aftereffects/j2k.cpp:482-492).
+//
+// A thread per destination pixel, a workgroup = 256 neighbours of one row, rows strided over gridDim.y like
+// decode_output_kernel.  Reads: component words at (org + x) / sub_x -- a wavefront reads 64 (or, sub-sampled, 32)
+// consecutive words of each component.  Writes: in the packed form the pixel's record in one 4- or 8-byte store, so a
+// wavefront writes 256 or 512 contiguous bytes; in the general form one store per given channel at the channel's strides.
+// The build passes -ffp-contract=off: the sYCC arithmetic below rounds every product and every sum on its own.
+#include "kernels.h"
+#include "out_sample.h"
+
+#include <algorithm>
+
+namespace j2k_hip {
+namespace {
+
+// the reference's constants: doubles narrowed to float (j2k_rgba_file.cpp:185-278)
+constexpr float kCrR = (float)(2 * (1 - 0.299));
+constexpr float kCbB = (float)(2 * (1 - 0.114));
+constexpr float kCrG = (float)(2 * 0.299 * (1 - 0.299) / 0.587);
+constexpr float kCbG = (float)(2 * 0.114 * (1 - 0.114) / 0.587);
+
+__device__ __forceinline__ unsigned sycc_channel(float f, int h, int top)
+{
+    return (unsigned)min(max((int)((f + (float)h) + 0.5f), 0), top); // (the cast truncates; |f| < 2^19: always in range)
+}
+
+template <bool REV, int MODE, bool PACKED>
+__global__ __launch_bounds__(256) void decode_rgba_kernel(DecRgbaArgs a)
+{
+    __shared__ unsigned s_lut[MODE == J2K_HIP_RGBA_PALETTE ? 256 : 1];
+    if constexpr (MODE == J2K_HIP_RGBA_PALETTE) { // the table, once per workgroup (entries from lut_size on are 0)
+        s_lut[threadIdx.x] = a.lut[threadIdx.x];
+        __syncthreads();
+    }
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= a.width) return;
+    const int D = a.depth, top = (1 << D) - 1;
+    const unsigned mask = a.sample_bytes == 1 ? 0xffu : 0xffffu;
+    for (int y = blockIdx.y; y < a.height; y += gridDim.y) {
+        int v[4];
+        component_samples<REV>(a, x, y, v);
+        unsigned out[4]; // R, G, B, A
+        out[3] = (unsigned)top;
+        if constexpr (MODE == J2K_HIP_RGBA_RGB) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[c] = depth_out((unsigned)v[c], a.cprec[c], D, mask);
+            if (a.alpha_comp == 3) out[3] = depth_out((unsigned)v[3], a.cprec[3], D, mask);
+        } else if constexpr (MODE == J2K_HIP_RGBA_GREY) {
+            out[0] = out[1] = out[2] = depth_out((unsigned)v[0], a.cprec[0], D, mask);
+            if (a.alpha_comp == 1) out[3] = depth_out((unsigned)v[1], a.cprec[1], D, mask);
+        } else if constexpr (MODE == J2K_HIP_RGBA_PALETTE) {
+            const unsigned idx = (unsigned)v[0];
+            const unsigned e = idx < a.lut_size ? s_lut[idx] : 0u;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const unsigned b = (e >> (8 * c)) & 0xffu;
+                out[c] = a.sample_bytes == 1 ? b : ((b << 8) | b); // ConvertToType: whatever the depth
+            }
+        } else { // sYCC, the reference's irreversible branch
+            const int h = 1 << (D - 1);
+            const float sY = (float)((int)depth_out((unsigned)v[0], a.cprec[0], D, mask) - h);
+            const float sCb = (float)((int)depth_out((unsigned)v[1], a.cprec[1], D, mask) - h);
+            const float sCr = (float)((int)depth_out((unsigned)v[2], a.cprec[2], D, mask) - h);
+            out[0] = sycc_channel(sY + kCrR * sCr, h, top);
+            out[1] = sycc_channel((sY - kCrG * sCr) - kCbG * sCb, h, top);
+            out[2] = sycc_channel(sY + kCbB * sCb, h, top);
+        }
+        if (a.demote) { // Demote (FrameSeq.cpp:265-268)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) out[c] = out[c] > 32768u ? ((out[c] - 1) >> 1) + 1 : out[c] >> 1;
+        }
+        if constexpr (PACKED) {
+            if (x < a.dst_w[0] && y < a.dst_h[0]) {
+                if (a.sample_bytes == 1) {
+                    unsigned w = 0;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) w |= (out[c] & 0xffu) << (8 * a.slot[c]);
+                    *reinterpret_cast<unsigned *>(a.pix + (long long)y * a.pix_rowbytes + (long long)x * 4) = w;
+                } else {
+                    unsigned long long w = 0;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) w |= (unsigned long long)(out[c] & 0xffffu) << (16 * a.slot[c]);
+                    *reinterpret_cast<unsigned long long *>(a.pix + (long long)y * a.pix_rowbytes + (long long)x * 8) = w;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (a.dst[c] && x < a.dst_w[c] && y < a.dst_h[c]) {
+                    uint8_t *p = a.dst[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
+                    if (a.sample_bytes == 1) *p = (uint8_t)out[c];
+                    else *reinterpret_cast<unsigned short *>(p) = (unsigned short)out[c];
+                }
+        }
+    }
+}
+
+template <bool REV, int MODE>
+void launch_form(const DecRgbaArgs &a, const dim3 &grid, hipStream_t s)
+{
+    if (a.packed) hipLaunchKernelGGL((decode_rgba_kernel<REV, MODE, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((decode_rgba_kernel<REV, MODE, false>), grid, dim3(256), 0, s, a);
+}
+
+template <bool REV>
+void launch_mode(const DecRgbaArgs &a, const dim3 &grid, hipStream_t s)
+{
+    switch (a.mode) {
+    case J2K_HIP_RGBA_RGB: launch_form<REV, J2K_HIP_RGBA_RGB>(a, grid, s); break;
+    case J2K_HIP_RGBA_GREY: launch_form<REV, J2K_HIP_RGBA_GREY>(a, grid, s); break;
+    case J2K_HIP_RGBA_PALETTE: launch_form<REV, J2K_HIP_RGBA_PALETTE>(a, grid, s); break;
+    default: launch_form<REV, J2K_HIP_RGBA_SYCC>(a, grid, s); break;
+    }
+}
+
+} // namespace
+
+void launch_decode_rgba(const DecRgbaArgs &a, hipStream_t s)
+{
+    if (a.width <= 0 || a.height <= 0) return;
+    const dim3 grid((unsigned)((a.width + 255) / 256), (unsigned)std::min(a.height, 65535), 1);
+    if (a.reversible) launch_mode<true>(a, grid, s);
+    else launch_mode<false>(a, grid, s);
+}
+
+} // namespace j2k_hip

@@ -189,6 +189,48 @@ void HipCodec::ReadFile(InputFile &file, const Buffer &buffer, unsigned int subs
     t_enc.error.clear();
 }
 
+bool HipCodec::ReadRGBA(InputFile &file, const Channel &r, const Channel &g, const Channel &b, const Channel &a,
+                        unsigned int subsample, Progress *progress)
+{
+    if (!Verify(file)) throw Exception("Can't read this format");
+    const std::vector<unsigned char> data = slurp(file);
+    j2k_hip_rgba_dst dst = {};
+    dst.struct_size = sizeof(dst);
+    const Channel *src[4] = {&r, &g, &b, &a};
+    j2k_hip_outplane *out[4] = {&dst.r, &dst.g, &dst.b, &dst.a};
+    bool ok = true, all16 = true;
+    for (int i = 0; i < 4; i++) {
+        const Channel &c = *src[i];
+        if (c.buf == NULL && i == 3) { all16 = false; continue; } // no alpha wanted
+        ok = ok && c.buf != NULL && !c.sgnd && (c.sampleType == UCHAR || c.sampleType == USHORT);
+        all16 = all16 && c.sampleType == USHORT;
+        out[i]->base = c.buf; out[i]->colbytes = c.colbytes; out[i]->rowbytes = c.rowbytes;
+        out[i]->sample_bits = c.sampleType == USHORT ? 16 : 8;
+        out[i]->depth = c.depth; out[i]->width = c.width; out[i]->height = c.height;
+    }
+    if (!ok) { t_enc.error = "unsupported destination channels"; throw Exception("Error reading file"); }
+    dst.demote_ae16 = (_options & DemoteAE16) && all16 ? 1 : 0; // only 16-bit worlds are "15+1", as on the write side
+    uint32_t mode = 0; // the header tells the files of the other path apart: no device is touched for them
+    const int mode_rc = j2k_hip_rgba_mode(data.data(), data.size(), &mode);
+    if (mode_rc != J2K_HIP_OK) {
+        t_enc.error = j2k_hip_last_error(NULL);
+        if (mode_rc == J2K_HIP_ERR_UNSUPPORTED) return false;
+        throw Exception("Error reading file");
+    }
+    j2k_hip_encoder *h = thread_handle(_device);
+    if (!h) throw Exception("Error reading file");
+    const int rc = j2k_hip_decode_rgba(h, data.data(), data.size(), subsample ? subsample : 1, NULL, &dst);
+    if (rc != J2K_HIP_OK) {
+        t_enc.error = j2k_hip_last_error(h);
+        if (rc == J2K_HIP_ERR_UNSUPPORTED) return false; // (found by the host-side parser: no kernel has run, the destination is untouched)
+        throw Exception("Error reading file");
+    }
+    // the abort callback, polled once after the decode as ReadFile does
+    if (progress != NULL && progress->keepGoing && progress->abortProc != NULL) progress->keepGoing = progress->abortProc(progress->refCon);
+    t_enc.error.clear();
+    return true;
+}
+
 void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &buffer, Progress *)
 {
     assert(file.Tell() == 0);                  // reference: j2k_openjpeg_codec.cpp:592

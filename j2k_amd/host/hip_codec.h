@@ -23,7 +23,10 @@ class HipCodec : public Codec {
     //   Promote() of the AE layer (reference: src/aftereffects/FrameSeq.cpp:311-355) is applied on the GPU while the
     //   samples are loaded, so the caller drops the PromoteWorld / DemoteWorld pair around WriteFile
     //   (src/aftereffects/j2k.cpp:843-855: two host passes over the frame) and hands over the world as it is.
-    enum Options { NoOptions = 0, PromoteAE16 = 1 };
+    //   DemoteAE16: the mirror on the read side.  ReadRGBA into four 16-bit (USHORT) channels delivers 15+1-bit samples:
+    //   Demote() (FrameSeq.cpp:265-268) is applied by the decode's output kernel, so the caller drops the DemoteWorld pass
+    //   of j2k_DrawSparseFrame (src/aftereffects/j2k.cpp:482-492).
+    enum Options { NoOptions = 0, PromoteAE16 = 1, DemoteAE16 = 2 };
 
     // device: HIP device ordinal, or -1 = the host threads that call this codec take the devices in turn
     explicit HipCodec(Mode mode = ReferenceLiteral, int device = -1, unsigned options = NoOptions);
@@ -50,6 +53,18 @@ class HipCodec : public Codec {
     // goes to the top-left of the destination channels
     virtual void ReadFile(InputFile &file, const Buffer &buffer, unsigned int subsample = 1, Progress *progress = NULL);
     virtual void WriteFile(OutputFile &file, const FileInfo &info, const Buffer &buffer, Progress *progress = NULL);
+
+    // The whole of RGBAinputFile::ReadFile (src/common/j2k_rgba_file.cpp:450-735) in one decode: the file's components go
+    // straight to the R, G, B, A channels of the caller's world -- sYCC -> RGB, grey into three channels, the palette
+    // look-up, the alpha fill (full scale at the channels' depth: 2^depth - 1, where the reference stores 255 into a 16-bit
+    // world) and, with DemoteAE16 and four USHORT channels, Demote -- in the decode's output kernel (include/j2k_hip.h:
+    // j2k_hip_decode_rgba).  a.buf == NULL: no alpha wanted.
+    // true: the frame is written.  false: not a file the fused path takes (status J2K_HIP_ERR_UNSUPPORTED: CMYK, e-sYCC, an
+    // opacity channel that is not the last one, a feature the GPU decoder lacks ... -- the reference's own code asserts on the
+    // first three); nothing is written and the caller goes on as before (RGBAinputFile's own path, which reaches ReadFile and
+    // the fallback codec).  Damaged files and device failures throw "Error reading file".
+    bool ReadRGBA(InputFile &file, const Channel &r, const Channel &g, const Channel &b, const Channel &a,
+                  unsigned int subsample = 1, Progress *progress = NULL);
 
     // text of the last failure on the calling thread (the exception itself carries the reference's
     // fixed message)

@@ -155,6 +155,41 @@ long j2k_host_test_read(const unsigned char *file, unsigned long file_len, unsig
     return 0;
 }
 
+// HipCodec::ReadRGBA, driven like the three lines at the top of RGBAinputFile::ReadFile drive it: `frame` is
+// the host's interleaved A,R,G,B world as WorldToBuffer lays it out (pixel_size = bytes per sample; depth = Channel.depth) of
+// width x height pixels; demote != 0: the codec has the DemoteAE16 option; with_alpha = 0: no alpha channel is handed over.
+// Returns 1 = the frame is written, 0 = not taken (nothing written), -1 with what() in err.
+long j2k_host_test_read_rgba(const unsigned char *file, unsigned long file_len, unsigned subsample, unsigned char *frame, unsigned width,
+                             unsigned height, long rowbytes, int pixel_size, int depth, int demote, int with_alpha, char *err,
+                             unsigned long err_cap)
+{
+    using namespace j2k;
+    Channel argb[4];
+    for (int i = 0; i < 4; i++) {
+        Channel &c = argb[i];
+        c.width = width; c.height = height;
+        c.sampleType = pixel_size == 2 ? USHORT : UCHAR;
+        c.depth = (unsigned char)depth;
+        c.sgnd = false;
+        c.buf = frame + i * pixel_size;
+        c.colbytes = 4 * pixel_size;
+        c.rowbytes = rowbytes;
+    }
+    if (!with_alpha) argb[0].buf = NULL;
+    MemoryInputFile in(file, file_len);
+    HipCodec hip(HipCodec::HonourSettings, -1, demote ? HipCodec::DemoteAE16 : HipCodec::NoOptions);
+    try {
+        return hip.ReadRGBA(in, argb[1], argb[2], argb[3], argb[0], subsample, NULL) ? 1 : 0;
+    } catch (const Exception &e) {
+        if (err && err_cap) {
+            std::string m = std::string(e.what()) + " | " + HipCodec::LastError();
+            std::strncpy(err, m.c_str(), err_cap - 1);
+            err[err_cap - 1] = 0;
+        }
+        return -1;
+    }
+}
+
 // GetFileInfo through the interface: out[] = {width, height, channels, depth, format, colorSpace, alpha, profileLen,
 // reversible, channelMap[0..3]}; the ICC profile (the codec's malloc'd copy) goes to icc_out and is freed.
 long j2k_host_test_info(const unsigned char *file, unsigned long file_len, long *out, unsigned char *icc_out, unsigned long icc_cap,
