@@ -555,6 +555,19 @@ typedef struct j2k_hip_dec_block {
 int j2k_hip_stage_t1_decode(j2k_hip_encoder *enc, int kernel, int reversible, void *d_coef,
                             uint32_t stride, uint32_t nblocks, const j2k_hip_dec_block *blocks,
                             const void *cw, size_t cw_bytes);
+/* The same under a code-block style, through the lane-per-block kernel alone (the one that reads styled files).
+ * cblk_style: the COD SPcod bits, 0..63 (1 bypass, 2 reset, 4 termall, 8 vertically causal, 16 pterm, 32 segsym).  Under
+ * bypass or termall block i has the codeword segments segs[2 k], segs[2 k + 1] = (bytes, coding passes) for
+ * k = seg_first[i] .. seg_first[i] + seg_count[i] - 1, in order; a pass beyond them opens a segment without bytes, and a
+ * segment ends where the block's cw_len bytes end (what a file cut short leaves): both read as 1-bits.  Blocks, clamp,
+ * empty blocks and the overlap check as above; cblk_style = 0 without segments gives j2k_hip_stage_t1_decode at kernel = 1.
+ * Refused with J2K_HIP_ERR_PARAM: style bits above 63, a segment range outside segs[0 .. 2 nsegs_total), segments given under
+ * a style without bypass and termall, a segment of more than 2^24 - 1 bytes or 255 passes, and under bypass or termall a
+ * block that holds passes but no segment. */
+int j2k_hip_stage_t1_decode_styled(j2k_hip_encoder *enc, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                                   const j2k_hip_dec_block *blocks, const void *cw, size_t cw_bytes, uint32_t cblk_style,
+                                   const uint32_t *seg_first, const uint32_t *seg_count, const uint32_t *segs,
+                                   uint32_t nsegs_total);
 
 /* --- introspection ----------------------------------------------------------------------------- */
 int j2k_hip_get_stats(const j2k_hip_encoder *enc, j2k_hip_stats *stats);

@@ -91,7 +91,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
            "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
            "j2k_hip_stage_t1_styled",
-           "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_decode_output",
+           "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_t1_decode_styled", "j2k_hip_stage_decode_output",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink"]
 
@@ -205,6 +205,8 @@ def load_library():
                                      C.POINTER(IdwtRegion), C.c_uint32, C.c_void_p, C.c_void_p]
     L.j2k_hip_stage_t1_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DecBlock),
                                           C.c_void_p, C.c_size_t]
+    L.j2k_hip_stage_t1_decode_styled.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DecBlock), C.c_void_p,
+                                                 C.c_size_t, C.c_uint32, U32P, U32P, U32P, C.c_uint32]
     L.j2k_hip_stage_decode_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32,
                                               C.POINTER(OutComp), C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(OutPlane), C.c_uint32]
     L.j2k_hip_rgba_mode.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
@@ -784,6 +786,42 @@ class Encoder:
         try:
             self._check(self.L.j2k_hip_stage_t1_decode(self.h, {"wave": 0, "lanes": 1}[kernel], int(reversible), d, W, nb, arr,
                                                        cw.ctypes.data, pos))
+            raw = self.d2h(d, plane.nbytes)
+        finally:
+            self.free(d)
+        return raw.view(dt).reshape(H, W)
+
+    def stage_t1_decode_styled(self, plane: np.ndarray, blocks, reversible: bool, style: int, raw_table=None) -> np.ndarray:
+        """stage_t1_decode through the lane kernel under the code-block style `style`; under bypass or termall every block also
+        has segs = [(bytes, passes), ...], its codeword segments in order.  raw_table = (seg_first, seg_count, segs pairs,
+        nsegs_total) replaces the table built from the blocks (for the refusals)."""
+        dt = np.int32 if reversible else np.float32
+        plane = np.ascontiguousarray(plane, dtype=dt)
+        H, W = plane.shape
+        nb = len(blocks)
+        arr = (DecBlock * max(nb, 1))()
+        pos = 0
+        first, count, pairs = [], [], []
+        for i, b in enumerate(blocks):
+            arr[i].x, arr[i].y, arr[i].w, arr[i].h = b["rect"]
+            arr[i].orient, arr[i].numbps, arr[i].npasses = b["orient"], b["numbps"], b["npasses"]
+            arr[i].roishift, arr[i].half_step = b.get("roishift", 0), b.get("half_step", 1.0)
+            arr[i].cw_off, arr[i].cw_len = pos, len(b["data"])
+            pos += len(b["data"])
+            sg = b.get("segs") or ()
+            first.append(len(pairs))
+            count.append(len(sg))
+            pairs += [tuple(s) for s in sg]
+        total = len(pairs)
+        if raw_table is not None:
+            first, count, pairs, total = raw_table
+        mk = lambda v: (C.c_uint32 * max(len(v), 1))(*v)
+        a_first, a_count, a_segs = mk(first), mk(count), mk([v for s in pairs for v in s])
+        cw = np.frombuffer(b"".join(b["data"] for b in blocks) + b"\0", dtype=np.uint8)
+        d = self.upload(plane)
+        try:
+            self._check(self.L.j2k_hip_stage_t1_decode_styled(self.h, int(reversible), d, W, nb, arr, cw.ctypes.data, pos, style,
+                                                              a_first, a_count, a_segs, total))
             raw = self.d2h(d, plane.nbytes)
         finally:
             self.free(d)

@@ -715,8 +715,7 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const u
             db.seg_first = (uint32_t)P.cwsegs.size();
             uint64_t at = 0;
             for (const CwSeg &sg : bsegs[id]) {
-                const uint64_t have = at < bs.bytes ? std::min<uint64_t>(sg.len, bs.bytes - at) : 0;
-                P.cwsegs.push_back((uint32_t)have | (sg.np << 24));
+                P.cwsegs.push_back(cwseg_word(cwseg_have(sg.len, at, bs.bytes), sg.np));
                 at += sg.len;
             }
             db.nsegs = (uint32_t)(P.cwsegs.size() - db.seg_first);

@@ -73,6 +73,12 @@ inline uint32_t t1dec_passes(uint32_t numbps, uint32_t npasses) { return numbps 
 inline uint64_t cw_arena_next(uint64_t end) { return (end + 2 + 15) & ~(uint64_t)15; } // where the next block starts after one that ends at `end`
 inline uint64_t cw_arena_bytes(uint64_t next) { return next + 16; }
 constexpr size_t kCwArenaTail = 512;
+// A codeword segment of a block as the lane decoder reads it (DecodePlan::cwsegs, t1_dec_lane.h Block::segs), stated once for
+// the plan and the styled stage hook: the bytes of it that are there -- a segment of `len` bytes that begins `at` bytes into a
+// block of which `bytes` bytes arrived (a file cut short may have lost bytes the headers had promised) -- and the word.
+constexpr uint32_t kCwSegMaxBytes = (1u << 24) - 1u, kCwSegMaxPasses = 255;
+inline uint32_t cwseg_have(uint64_t len, uint64_t at, uint64_t bytes) { return (uint32_t)(at < bytes ? std::min<uint64_t>(len, bytes - at) : 0); }
+inline uint32_t cwseg_word(uint32_t have, uint32_t passes) { return have | (passes << 24); }
 
 // ---- region decode: which coefficients a window of the top decoded resolution needs (no device, no file)
 // Rectangles are half open and in ABSOLUTE coordinates of their resolution or band (T.800 B.5: low-band sample n of a

@@ -1056,8 +1056,14 @@ int j2k_hip_stage_rgba_output(j2k_hip_encoder *e, int reversible, int mct, uint3
     });
 }
 
-int j2k_hip_stage_t1_decode(j2k_hip_encoder *e, int kernel, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
-                            const j2k_hip_dec_block *blocks, const void *cw, size_t cw_bytes)
+} // extern "C"
+
+namespace {
+// Both Tier-1 decode hooks.  cblk_style and the segment tables are the styled hook's (seg_first == nullptr: no block has
+// segments of its own); segs = pairs (bytes, coding passes).
+int stage_t1_decode_blocks(j2k_hip_encoder *e, int kernel, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                           const j2k_hip_dec_block *blocks, const void *cw, size_t cw_bytes, uint32_t cblk_style,
+                           const uint32_t *seg_first, const uint32_t *seg_count, const uint32_t *segs, uint32_t nsegs_total)
 {
     if (!e) return J2K_HIP_ERR_PARAM;
     return guarded(e, [&] {
@@ -1075,6 +1081,14 @@ int j2k_hip_stage_t1_decode(j2k_hip_encoder *e, int kernel, int reversible, void
                 if ((uint64_t)b.x + b.w > stride) throw Error(J2K_HIP_ERR_PARAM, "code-block rectangle wider than the plane's stride");
                 if (b.numbps > 30 || b.roishift > 30) throw Error(J2K_HIP_ERR_PARAM, "more bit-planes than a 32-bit sample holds");
                 if (b.cw_len && (!bytes || b.cw_off > cw_bytes || b.cw_len > cw_bytes - b.cw_off)) throw Error(J2K_HIP_ERR_PARAM, "codeword bytes outside the buffer");
+                if (seg_first) {
+                    if (seg_first[i] > nsegs_total || seg_count[i] > nsegs_total - seg_first[i]) throw Error(J2K_HIP_ERR_PARAM, "codeword segments outside the table");
+                    if (seg_count[i] > 0xffffu) throw Error(J2K_HIP_ERR_PARAM, "more codeword segments than a block can have");
+                    for (uint32_t k = 0; k < seg_count[i]; ++k) {
+                        const uint32_t *sg = segs + 2 * (size_t)(seg_first[i] + k);
+                        if (sg[0] > kCwSegMaxBytes || sg[1] > kCwSegMaxPasses) throw Error(J2K_HIP_ERR_PARAM, "codeword segment of impossible length or pass count");
+                    }
+                }
                 order[i] = i;
             }
             std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return blocks[a].y < blocks[b].y; });
@@ -1087,6 +1101,8 @@ int j2k_hip_stage_t1_decode(j2k_hip_encoder *e, int kernel, int reversible, void
         // the kernels' table: the blocks that hold something, in the order given (t1dec_passes: the plan's rule and the clamp)
         std::vector<DecBlkDev> tab;
         std::vector<uint64_t> src;
+        std::vector<uint32_t> cwsegs;
+        const bool multiseg = (cblk_style & 5u) != 0;
         uint64_t arena = 0;
         size_t mask_words = 0;
         for (uint32_t i = 0; i < nblocks; ++i) {
@@ -1100,6 +1116,16 @@ int j2k_hip_stage_t1_decode(j2k_hip_encoder *e, int kernel, int reversible, void
             d.stepsize = b.half_step;
             d.w = (unsigned short)b.w; d.h = (unsigned short)b.h; d.npasses = (unsigned short)np;
             d.orient = (unsigned char)b.orient; d.numbps = (unsigned char)b.numbps; d.roishift = (unsigned char)b.roishift;
+            if (multiseg) { // the words of a file decode's plan: a segment ends where the block's bytes end
+                if (!seg_first || !seg_count[i]) throw Error(J2K_HIP_ERR_PARAM, "a block with passes needs a codeword segment under bypass or termall");
+                d.seg_off = (unsigned)cwsegs.size(); d.nsegs = (unsigned short)seg_count[i];
+                uint64_t at = 0;
+                for (uint32_t k = 0; k < seg_count[i]; ++k) {
+                    const uint32_t *sg = segs + 2 * (size_t)(seg_first[i] + k);
+                    cwsegs.push_back(cwseg_word(cwseg_have(sg[0], at, b.cw_len), sg[1]));
+                    at += sg[0];
+                }
+            }
             tab.push_back(d);
             src.push_back(b.cw_off);
             arena = cw_arena_next(arena + b.cw_len);
@@ -1113,13 +1139,15 @@ int j2k_hip_stage_t1_decode(j2k_hip_encoder *e, int kernel, int reversible, void
         // one pinned buffer: block table | groups | codeword arena.  A decode leaves the arena's slack and tail as they were; here
         // they are zeros, so that a kernel which took a byte from past a block's end (where the decoder is fed 1-bits) shows.
         const size_t grp_base = round_up(nb * sizeof(DecBlkDev), 16);
-        const size_t tab_bytes = grp_base + round_up(groups.size() * sizeof(DecGroupDev), 16) + 64;
+        const size_t cwseg_base = grp_base + round_up(groups.size() * sizeof(DecGroupDev), 16);
+        const size_t tab_bytes = cwseg_base + round_up(cwsegs.size() * sizeof(uint32_t), 16) + 64;
         const size_t cw_base = round_up(tab_bytes, 16);
         e->h_dtab.ensure(cw_base + arena_bytes);
         uint8_t *ht = e->h_dtab.as<uint8_t>();
         std::memset(ht, 0, cw_base + arena_bytes);
         std::memcpy(ht, tab.data(), nb * sizeof(DecBlkDev));
         if (!groups.empty()) std::memcpy(ht + grp_base, groups.data(), groups.size() * sizeof(DecGroupDev));
+        if (!cwsegs.empty()) std::memcpy(ht + cwseg_base, cwsegs.data(), cwsegs.size() * sizeof(uint32_t));
         for (size_t k = 0; k < nb; ++k)
             if (tab[k].cw_len) std::memcpy(ht + cw_base + tab[k].cw_off, bytes + src[k], tab[k].cw_len);
         e->d_dblk.ensure(tab_bytes);
@@ -1131,8 +1159,8 @@ int j2k_hip_stage_t1_decode(j2k_hip_encoder *e, int kernel, int reversible, void
         ta.cw = e->d_cw.as<uint8_t>();
         ta.coef = d_coef; ta.stride = (long long)stride;
         ta.blks = e->d_dblk.as<DecBlkDev>(); ta.nblks = (int)nb; ta.reversible = reversible;
-        ta.cwsegs = reinterpret_cast<const unsigned *>(e->d_dblk.as<uint8_t>() + grp_base); // (no block has segments of its own)
-        ta.style = 0;
+        ta.cwsegs = reinterpret_cast<const unsigned *>(e->d_dblk.as<uint8_t>() + cwseg_base); // (style 0: no block has segments of its own)
+        ta.style = cblk_style;
         if (kernel == 1) {
             const size_t state_bytes = lane_state_bytes(groups.size()), planes_bytes = lane_planes_bytes(plane_words);
             e->d_masks.ensure(state_bytes + planes_bytes);
@@ -1149,6 +1177,31 @@ int j2k_hip_stage_t1_decode(j2k_hip_encoder *e, int kernel, int reversible, void
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));
     });
+}
+} // namespace
+
+extern "C" {
+
+int j2k_hip_stage_t1_decode(j2k_hip_encoder *e, int kernel, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                            const j2k_hip_dec_block *blocks, const void *cw, size_t cw_bytes)
+{
+    return stage_t1_decode_blocks(e, kernel, reversible, d_coef, stride, nblocks, blocks, cw, cw_bytes, 0, nullptr, nullptr, nullptr, 0);
+}
+
+int j2k_hip_stage_t1_decode_styled(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                                   const j2k_hip_dec_block *blocks, const void *cw, size_t cw_bytes, uint32_t cblk_style,
+                                   const uint32_t *seg_first, const uint32_t *seg_count, const uint32_t *segs, uint32_t nsegs_total)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    const bool multiseg = (cblk_style & 5u) != 0;
+    bool bad = cblk_style > 63u || (nsegs_total && !segs) || (nblocks && multiseg && (!seg_first || !seg_count));
+    if (!bad && !multiseg) { // one segment per block: a table has no meaning
+        bad = nsegs_total != 0;
+        for (uint32_t i = 0; !bad && seg_count && blocks && i < nblocks; ++i) bad = seg_count[i] != 0;
+    }
+    if (bad) return guarded(e, [&] { throw Error(J2K_HIP_ERR_PARAM, "bad code-block style or codeword segment table"); });
+    return stage_t1_decode_blocks(e, 1, reversible, d_coef, stride, nblocks, blocks, cw, cw_bytes, cblk_style, multiseg ? seg_first : nullptr,
+                                  seg_count, segs, nsegs_total);
 }
 
 } // extern "C"

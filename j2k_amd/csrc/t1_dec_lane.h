@@ -2,7 +2,8 @@
 // per wavefront (the shape of the encoder's t1_mq2_kernel).  MQ decoder T.800 Annex C.3, bit modelling Annex D.
 // Replaces OpenJPEG's t1.c / mqc.c as reached from opj_decode (reference call site: src/common/j2k_openjpeg_codec.cpp:512;
 // SURVEY.md 8f N4).  Written once for both targets: the HIP kernel (t1_dec.hip, NL = 64 lanes per wave) and a plain
-// C++ build with NL = 1 (tests/native/t1_lane_host.cpp) that the CPU tests hold to the oracle's block decoder -- the
+// C++ build with NL = 1 (tests/native/t1_lane_host.cpp; under code-block styles tests/native/t1_lane_styled_host.cpp) that
+// the CPU tests hold to the oracle's block decoders -- the
 // per-lane state machine below IS the kernel; nothing in it depends on what the other lanes do.
 //
 // Why this shape.  Decoding a block is one serial chain (every context depends on the bits before it, the interval
@@ -301,9 +302,13 @@ T1L_FN void decode_lane(Shared<NL> &sh, int lane, const Block &b, bool live, int
                 bool fresh = false;
                 if (seg_left == 0) { // the pass opens the block's next segment
                     ++seg_i;
-                    const uint32_t sw = seg_i < b.nsegs ? b.segs[seg_i] : 0u; // (a file cut short: an empty segment, all 1-bits)
+                    const bool listed = seg_i < b.nsegs;
+                    const uint32_t sw = listed ? b.segs[seg_i] : 0u; // (a file cut short: an empty segment, all 1-bits)
                     seg_begin = seg_end; seg_end = seg_begin + (sw & 0xffffffu); seg_left = sw >> 24;
-                    if (seg_left == 0) seg_left = 0xffffu;
+                    // a segment that is not listed takes the passes B.10.7.2 gives it, so that the next one is opened (and its raw
+                    // or MQ reader initialised) where a listed one would be
+                    if (!listed) seg_left = (style & STY_TERMALL) ? 1u : (p < 10 ? 10u - (uint32_t)p : (type == 0 ? 2u : 1u));
+                    else if (seg_left == 0) seg_left = 0xffffu;
                     fresh = true;
                 }
                 if (fresh) {

@@ -142,6 +142,12 @@ size_t j2ko_jp2_header(uint32_t width, uint32_t height, uint32_t ncomp, uint32_t
  * :512), dims = {w, h, ncomp, prec}.  Returns 0, or -1 with j2ko_decode_error(). */
 int j2ko_decode(const uint8_t *file, size_t len, int reduce, int32_t *out, size_t cap_samples, int dims[4]);
 const char *j2ko_decode_error(void);
+/* The code-blocks of a file as the Tier-2 of j2ko_decode finds them (every block that holds passes): meta = 16 words per
+ * block -- tile, component, resolution, orientation, x, y (in the tile-component's Mallat plane), w, h, numbps, npasses, first
+ * segment, segments, byte offset, bytes, 0.5 x step size (float bits; 1.0 reversible), 0; segs = (bytes, passes) pairs (bypass /
+ * termall only); hdr = {code-block style, reversible, components, tiles}.  Returns the number of blocks or -1. */
+long j2ko_file_blocks(const uint8_t *file, size_t len, int32_t *meta, size_t cap_blocks, uint32_t *segs, size_t cap_segs, uint8_t *bytes,
+                      size_t cap_bytes, int hdr[4]);
 /* Header only (GetFileInfo, :222-426): info = {width, height, ncomp, prec, reversible, mct, numres, is_jp2, enumcs,
  * icc offset in the file, icc length, alpha channel mask}. */
 int j2ko_decode_info(const uint8_t *file, size_t len, int info[12]);
@@ -149,6 +155,16 @@ int j2ko_decode_info(const uint8_t *file, size_t len, int info[12]);
  * its codeword segment.  out = w*h values in the decoder's representation (sign, magnitude with one fractional
  * bit: the middle of the interval known so far).  Returns the passes decoded. */
 int j2ko_t1_decode_block(const uint8_t *data, size_t len, int w, int h, int orient, int numbps, int npasses, int32_t *out);
+/* The same under a code-block style (COD SPcod bits: 1 bypass, 2 reset, 4 termall, 8 vertically causal, 16 pterm,
+ * 32 segsym).  segs = nsegs pairs (bytes, coding passes) of the block's codeword segments, looked at under bypass or
+ * termall only; a pass beyond the listed segments, and bytes beyond a segment's end or beyond `len`, read 0xFF.
+ * Segmentation symbols are consumed, not checked.  style = 0, nsegs = 0: j2ko_t1_decode_block.
+ * _ex: *below_significant = how often a sample of a stripe's last row was coded next to a significant sample of the row
+ * below it (what vertically causal contexts hide: 0 means the style changed nothing for this block). */
+int j2ko_t1_decode_block_styled(const uint8_t *data, size_t len, int w, int h, int orient, int numbps, int npasses, int style,
+                                const uint32_t *segs, int nsegs, int32_t *out);
+int j2ko_t1_decode_block_styled_ex(const uint8_t *data, size_t len, int w, int h, int orient, int numbps, int npasses, int style,
+                                   const uint32_t *segs, int nsegs, int32_t *out, long *below_significant);
 /* Inverse DWT of a Mallat-layout plane (inverse of j2ko_dwt53 / j2ko_dwt97 up to the irreversible path's own scaling:
  * the 9/7 synthesis scales the low band by K and the high band by 2/K like libopenjp2's decoder). */
 void j2ko_idwt53(int32_t *a, int w, int h, int stride, int x0, int y0, int levels);

@@ -12,10 +12,21 @@
  * pinned sample-for-sample against those binaries through oracle/opj_replay.c (tests/test_decode_oracle.py).
  *
  * Supported: what the encode path of this repository (and the reference's WriteFile) writes, plus the
- * usual freedoms of files from elsewhere: any of the five progression orders, SOP/EPH markers, several
- * tile-parts per tile, user-defined precincts for LRCP/RLCP, 1..4 components, 1..16 bits unsigned.
- * Not supported (rejected): sub-sampled components, image/tile origin offsets, code-block styles other
- * than 0, COC/QCC/RGN/POC/PPM/PPT, signed samples.
+ * usual freedoms of files from elsewhere: any of the five progression orders (with user-defined precincts too),
+ * SOP/EPH markers, several tile-parts per tile, 1..4 components, 1..16 bits unsigned, and the six code-block
+ * styles of Table A.19 (bypass, reset, termall, vertically causal, pterm, segsym): one length per codeword
+ * segment in the packet headers (B.10.7.2) and j2ko_t1_decode_block_styled below.
+ * Not supported (rejected): sub-sampled components, image/tile origin offsets, style bits beyond the six,
+ * COC/QCC/RGN/POC/PPM/PPT, signed samples.
+ *
+ * What pins the styled half (tests/test_t1_dec_styled_refs.py): the whole decode of the eighteen styled files of
+ * libopenjp2 (tests/golden/ext s1..s5, u7; tests/golden/styles) and of the five decode-only files with vertically
+ * causal contexts (tests/golden/styles_dec) against the committed hashes of what libopenjp2 decodes from them, at full
+ * size and at every reduced size a hash is committed for, and against the live library; style invariance -- on every
+ * block of the families of tests/t1_styled_families.py under every style the oracle's encoder codes, the styled decode of
+ * the styled codeword equals j2ko_t1_decode_block of the unstyled one, at all passes and at every segment end; and
+ * style 0 without segments equals j2ko_t1_decode_block.  j2ko_file_blocks hands the blocks Tier-2 finds in a file to
+ * the block-level tests of the product's decoder.
  */
 #include "j2k_oracle.h"
 
@@ -227,6 +238,202 @@ int j2ko_t1_decode_block(const uint8_t *data, size_t len, int w, int h, int orie
     return done;
 }
 
+/* ------------------------------------------------------------------ Tier-1 decoding under code-block styles
+ * (T.800 Annex C, D.4 selective bypass D.6, reset / termination on each pass / vertically causal contexts /
+ * predictable termination / segmentation symbols D.4, D.5, D.7).  Written decision by decision from the standard; the
+ * product's lane decoder (t1_dec_lane.h) keeps column words and look-up tables, this keeps a flag byte per sample.
+ *
+ * Codeword segments: segs[2 i] = bytes, segs[2 i + 1] = coding passes of segment i (0 passes: every pass that remains).
+ * Under bypass or termall (style & 5) a pass that begins where the segment before it has run out of passes opens the
+ * next segment: MQ segments re-initialise the interval registers (the contexts go on), raw segments read plain bits.  A
+ * segment that is not listed has no bytes and the length B.10.7.2 gives it (termall: one pass; bypass: the first ten
+ * passes, then significance + refinement, cleanup, in turn).  Bytes beyond a segment's end, or beyond `len`, read 0xFF:
+ * the decoder is fed 1-bits (C.3.4; a raw segment: a byte above 0x8F behind a 0xFF is a marker and treated alike).
+ * Without bypass and termall the block is one segment of all `len` bytes and segs is not looked at.  Segmentation
+ * symbols are consumed, not checked (libopenjp2's default); predictable termination changes nothing for a decoder. */
+typedef struct { const uint8_t *d; size_t len, pos; unsigned c, ct; } rawd_t;
+static void rawd_open(rawd_t *r, const uint8_t *d, size_t len) { r->d = d; r->len = len; r->pos = 0; r->c = 0; r->ct = 0; }
+static int rawd_bit(rawd_t *r)
+{
+    if (r->ct == 0) {
+        const unsigned nx = r->pos < r->len ? r->d[r->pos] : 0xffu;
+        if (r->c == 0xff && nx > 0x8f) r->ct = 8;                   /* a marker: 1-bits from here on, nothing is consumed */
+        else { r->ct = r->c == 0xff ? 7 : 8; r->c = nx; r->pos++; } /* the bit behind a 0xFF is stuffed */
+    }
+    r->ct--;
+    return (int)((r->c >> r->ct) & 1u);
+}
+/* a new MQ segment: INITDEC on its bytes, the contexts stay as they are */
+static void mqd_restart(mqd_t *q, const uint8_t *data, size_t len)
+{
+    q->data = data; q->len = len; q->pos = 0;
+    q->c = (len == 0 ? 0xffu : data[0]) << 16;
+    mqd_bytein(q);
+    q->c <<= 7; q->ct -= 7; q->a = 0x8000;
+}
+static void mqd_reset_contexts(mqd_t *q)
+{
+    memset(q->idx, 0, sizeof q->idx);
+    memset(q->mps, 0, sizeof q->mps);
+    q->idx[DCTX_UNI] = 46; q->idx[DCTX_RL] = 3; q->idx[0] = 4;
+}
+
+typedef struct { t1d_t t; mqd_t q; rawd_t r; int raw, vc; long below; } t1s_t;
+/* the flags of neighbour (x + dx, y + dy) as sample (x, y) sees them: with vertically causal contexts (D.7) the row
+ * below the last row of a stripe counts as insignificant */
+static unsigned s_nb(t1s_t *s, int x, int y, int dx, int dy)
+{
+    const unsigned f = DFL(&s->t, x + dx, y + dy);
+    if (dy == 1 && (y & 3) == 3) {
+        if (f & DF_SIG) s->below++;
+        if (s->vc) return 0;
+    }
+    return f;
+}
+static int s_anysig(t1s_t *s, int x, int y)
+{
+    unsigned f = 0;
+    for (int dy = -1; dy <= 1; dy++)
+        for (int dx = -1; dx <= 1; dx++)
+            if (dx || dy) f |= s_nb(s, x, y, dx, dy);
+    return (int)(f & DF_SIG);
+}
+static int s_zc(t1s_t *s, int x, int y) /* Table D.1 */
+{
+    int hh = (int)(s_nb(s, x, y, -1, 0) & DF_SIG) + (int)(s_nb(s, x, y, 1, 0) & DF_SIG);
+    int vv = (int)(s_nb(s, x, y, 0, -1) & DF_SIG) + (int)(s_nb(s, x, y, 0, 1) & DF_SIG);
+    const int d = (int)(s_nb(s, x, y, -1, -1) & DF_SIG) + (int)(s_nb(s, x, y, 1, -1) & DF_SIG) + (int)(s_nb(s, x, y, -1, 1) & DF_SIG) +
+                  (int)(s_nb(s, x, y, 1, 1) & DF_SIG);
+    if (s->t.orient == 1) { const int t = hh; hh = vv; vv = t; }
+    if (s->t.orient == 3) {
+        const int hv = hh + vv;
+        if (d >= 3) return 8;
+        if (d == 2) return hv >= 1 ? 7 : 6;
+        if (d == 1) return hv >= 2 ? 5 : (hv == 1 ? 4 : 3);
+        return hv >= 2 ? 2 : hv;
+    }
+    if (hh == 2) return 8;
+    if (hh == 1) return vv >= 1 ? 7 : (d >= 1 ? 6 : 5);
+    if (vv == 2) return 4;
+    if (vv == 1) return 3;
+    return d >= 2 ? 2 : d;
+}
+static int s_contrib(unsigned f) { return (f & DF_SIG) ? ((f & DF_NEG) ? -1 : 1) : 0; }
+static int s_sc(t1s_t *s, int x, int y, int *xorbit) /* Tables D.2, D.3 */
+{
+    int hc = s_contrib(s_nb(s, x, y, -1, 0)) + s_contrib(s_nb(s, x, y, 1, 0));
+    int vc = s_contrib(s_nb(s, x, y, 0, -1)) + s_contrib(s_nb(s, x, y, 0, 1));
+    hc = hc > 1 ? 1 : (hc < -1 ? -1 : hc);
+    vc = vc > 1 ? 1 : (vc < -1 ? -1 : vc);
+    int xb = 0;
+    if (hc < 0 || (hc == 0 && vc < 0)) { xb = 1; hc = -hc; vc = -vc; }
+    *xorbit = xb;
+    if (hc == 0) return vc ? 10 : 9;
+    return 12 + vc; /* hc = 1: vc = -1, 0, 1 -> 11, 12, 13 */
+}
+static int s_bit(t1s_t *s, int ctx) { return s->raw ? rawd_bit(&s->r) : mqd_decode(&s->q, ctx); }
+static void s_newsig(t1s_t *s, int x, int y, int b)
+{
+    int xb, neg;
+    const int c = s_sc(s, x, y, &xb);
+    if (s->raw) neg = rawd_bit(&s->r);       /* a raw sign bit is the sign */
+    else neg = mqd_decode(&s->q, c) ^ xb;
+    const int32_t v = (int32_t)((1u << b) | ((1u << b) >> 1));
+    s->t.data[y * s->t.w + x] = neg ? -v : v;
+    DFL(&s->t, x, y) |= (uint8_t)(DF_SIG | (neg ? DF_NEG : 0));
+}
+
+int j2ko_t1_decode_block_styled_ex(const uint8_t *data, size_t len, int w, int h, int orient, int numbps, int npasses, int style,
+                                   const uint32_t *segs, int nsegs, int32_t *out, long *below_significant)
+{
+    t1s_t S;
+    memset(&S, 0, sizeof S);
+    t1d_t *t = &S.t;
+    t->w = w; t->h = h; t->fs = w + 2; t->orient = orient; t->data = out;
+    t->fl = (uint8_t *)calloc((size_t)(w + 2) * (size_t)(h + 2), 1);
+    memset(out, 0, sizeof(int32_t) * (size_t)w * (size_t)h);
+    S.vc = (style & 8) != 0;
+    mqd_reset_contexts(&S.q);
+    const int multiseg = (style & 5) != 0;
+    size_t seg_off = 0;
+    int seg_i = -1, seg_left = 0;
+    int b = numbps, type = 2, done = 0;
+    for (int p = 0; p < npasses && b >= 1; p++) {
+        S.raw = (style & 1) && p >= 10 && type != 2;
+        if (!multiseg) {
+            if (p == 0) mqd_restart(&S.q, data, len);
+        } else if (seg_left == 0) {
+            size_t bytes = 0;
+            seg_i++;
+            if (seg_i < nsegs) { bytes = segs[2 * seg_i]; seg_left = (int)segs[2 * seg_i + 1]; if (!seg_left) seg_left = 1 << 30; }
+            else if (style & 4) seg_left = 1;
+            else seg_left = p < 10 ? 10 - p : (type == 0 ? 2 : 1);
+            const size_t avail = seg_off < len ? (bytes < len - seg_off ? bytes : len - seg_off) : 0;
+            const uint8_t *at = data + (seg_off < len ? seg_off : len);
+            seg_off += bytes;
+            if (S.raw) rawd_open(&S.r, at, avail);
+            else mqd_restart(&S.q, at, avail);
+        }
+        if (multiseg) seg_left--;
+        if (type == 0) { /* significance propagation (D.3.1) */
+            for (int y0 = 0; y0 < h; y0 += 4)
+                for (int x = 0; x < w; x++)
+                    for (int y = y0; y < imin_(y0 + 4, h); y++) {
+                        if ((DFL(t, x, y) & (DF_SIG | DF_VISIT)) || !s_anysig(&S, x, y)) continue;
+                        if (s_bit(&S, S.raw ? 0 : s_zc(&S, x, y))) s_newsig(&S, x, y, b);
+                        DFL(t, x, y) |= DF_VISIT;
+                    }
+        } else if (type == 1) { /* magnitude refinement (D.3.3) */
+            const int32_t poshalf = (int32_t)((1u << b) >> 1);
+            for (int y0 = 0; y0 < h; y0 += 4)
+                for (int x = 0; x < w; x++)
+                    for (int y = y0; y < imin_(y0 + 4, h); y++) {
+                        if ((DFL(t, x, y) & (DF_SIG | DF_VISIT)) != DF_SIG) continue;
+                        const int c = (DFL(t, x, y) & DF_REFINE) ? 16 : (s_anysig(&S, x, y) ? 15 : 14);
+                        const int v = s_bit(&S, c);
+                        int32_t *dp = &out[y * w + x];
+                        *dp += (v ^ (*dp < 0)) ? poshalf : -poshalf;
+                        DFL(t, x, y) |= DF_REFINE;
+                    }
+        } else { /* cleanup (D.3.4) */
+            for (int y0 = 0; y0 < h; y0 += 4)
+                for (int x = 0; x < w; x++) {
+                    int y = y0;
+                    int agg = y0 + 3 < h;
+                    for (int k = 0; k < 4 && agg; k++)
+                        if ((DFL(t, x, y0 + k) & (DF_SIG | DF_VISIT)) || s_anysig(&S, x, y0 + k)) agg = 0;
+                    if (agg) {
+                        if (!mqd_decode(&S.q, DCTX_RL)) continue;
+                        int r = mqd_decode(&S.q, DCTX_UNI);
+                        r = (r << 1) | mqd_decode(&S.q, DCTX_UNI);
+                        y = y0 + r;
+                        s_newsig(&S, x, y, b);
+                        y++;
+                    }
+                    for (; y < imin_(y0 + 4, h); y++) {
+                        if (DFL(t, x, y) & (DF_SIG | DF_VISIT)) continue;
+                        if (mqd_decode(&S.q, s_zc(&S, x, y))) s_newsig(&S, x, y, b);
+                    }
+                }
+            if (style & 32) /* segmentation symbols (D.5): 1010 in the UNIFORM context, consumed */
+                for (int k = 0; k < 4; k++) (void)mqd_decode(&S.q, DCTX_UNI);
+            for (int i = 0; i < (w + 2) * (h + 2); i++) t->fl[i] &= (uint8_t)~DF_VISIT;
+        }
+        if (style & 2) mqd_reset_contexts(&S.q); /* reset of the context probabilities at every pass boundary */
+        done++;
+        if (++type == 3) { type = 0; b--; }
+    }
+    free(t->fl);
+    if (below_significant) *below_significant = S.below;
+    return done;
+}
+
+int j2ko_t1_decode_block_styled(const uint8_t *data, size_t len, int w, int h, int orient, int numbps, int npasses, int style,
+                                const uint32_t *segs, int nsegs, int32_t *out)
+{
+    return j2ko_t1_decode_block_styled_ex(data, len, w, h, orient, numbps, npasses, style, segs, nsegs, out, NULL);
+}
+
 /* ------------------------------------------------------------------ inverse DWT (Annex F.3) */
 /* one line: in = low-pass samples first, then high-pass (Mallat); out = interleaved; cas = parity of the
  * absolute coordinate of sample 0 */
@@ -383,6 +590,10 @@ typedef struct {
     int lenbits;
     size_t len, cap;
     uint8_t *data; /* concatenated contributions of all layers */
+    /* code-block styles with several codeword segments (bypass, termall; B.10.7.2): bytes, passes so far and the most
+     * passes each segment takes, in order */
+    int nseg;
+    uint32_t seg_bytes[128], seg_np[128], seg_max[128];
 } dcblk_t;
 typedef struct { int cw, ch; dcblk_t *cblks; ttree_t incl, imsb; } dprec_t;
 typedef struct { int orient, x0, y0, x1, y1, numbps; float stepsize; dprec_t *precs; } dband_t;
@@ -391,7 +602,7 @@ typedef struct { int x0, y0, x1, y1, pw, ph, nbands, ppx, ppy; dband_t bands[3];
 typedef struct {
     int width, height, ncomp, prec;
     int tw, th, ntx, nty;
-    int prog, layers, mct, numres, cbw, cbh, reversible, sop, eph;
+    int prog, layers, mct, numres, cbw, cbh, reversible, sop, eph, cblksty;
     int ppx[33], ppy[33];
     int qstyle, guard, expn[100], mant[100];
     /* file level */
@@ -476,7 +687,8 @@ static int parse_main_header(const uint8_t *d, size_t len, dhdr_t *H, size_t *po
             H->sop = (scod >> 1) & 1; H->eph = (scod >> 2) & 1;
             H->prog = s[1]; H->layers = (int)rd16(s + 2); H->mct = s[4];
             H->numres = s[5] + 1; H->cbw = s[6] + 2; H->cbh = s[7] + 2;
-            if (s[8] != 0) FAIL("code-block style 0x%02x is not supported", s[8]);
+            if (s[8] & ~63) FAIL("code-block style 0x%02x is not supported", s[8]);
+            H->cblksty = s[8];
             if (s[9] > 1) FAIL("unknown wavelet transform");
             H->reversible = s[9] == 1;
             if (H->prog > 4 || H->numres > 33 || H->cbw > 6 || H->cbh > 6 || H->cbw + H->cbh > 12) FAIL("unsupported COD parameters");
@@ -609,6 +821,7 @@ static const uint8_t *read_packet(const dhdr_t *H, dres_t *R, int pn, int layer,
     bior_t bio;
     bior_init(&bio, p, end);
     struct { dcblk_t *cb; int np; size_t len; } todo[3 * 4096];
+    const int multiseg = (H->cblksty & 5) != 0;
     int ntodo = 0;
     const int present = (int)bior_bit(&bio);
     if (present)
@@ -631,7 +844,30 @@ static const uint8_t *read_packet(const dhdr_t *H, dres_t *R, int pn, int layer,
                 }
                 const int np = get_numpasses(&bio);
                 while (bior_bit(&bio)) cb->lenbits++;
-                const size_t l = bior_read(&bio, cb->lenbits + flog2((unsigned)np));
+                size_t l = 0;
+                if (!multiseg) l = bior_read(&bio, cb->lenbits + flog2((unsigned)np));
+                else { /* one length per codeword segment the new passes fall into (B.10.7.2) */
+                    int left = np;
+                    while (left > 0) {
+                        if (cb->nseg == 0 || cb->seg_np[cb->nseg - 1] == cb->seg_max[cb->nseg - 1]) {
+                            if (cb->nseg >= 128) return NULL;
+                            /* termall: every pass its own segment; bypass: the passes of the first four bit-planes, then the raw
+                             * pair (significance, refinement) and the cleanup pass in turn */
+                            uint32_t mx = 1;
+                            if (!(H->cblksty & 4)) {
+                                if (cb->nseg == 0) mx = 10;
+                                else mx = (cb->seg_max[cb->nseg - 1] == 2) ? 1 : 2;
+                            }
+                            cb->seg_bytes[cb->nseg] = 0; cb->seg_np[cb->nseg] = 0; cb->seg_max[cb->nseg] = mx;
+                            cb->nseg++;
+                        }
+                        const int k = cb->nseg - 1;
+                        const int take = imin_((int)(cb->seg_max[k] - cb->seg_np[k]), left);
+                        const uint32_t l1 = bior_read(&bio, cb->lenbits + flog2((unsigned)take));
+                        cb->seg_bytes[k] += l1; cb->seg_np[k] += (uint32_t)take;
+                        left -= take; l += l1;
+                    }
+                }
                 if (ntodo >= 3 * 4096) return NULL;
                 todo[ntodo].cb = cb; todo[ntodo].np = np; todo[ntodo].len = l; ntodo++;
                 if (bio.overrun) return NULL;
@@ -661,9 +897,48 @@ static int read_tile_packets(const dhdr_t *H, dres_t **comps, const uint8_t *p, 
 #define PKT(l, r, c) do { dres_t *R_ = &comps[c][r]; for (int pn_ = 0; pn_ < R_->pw * R_->ph; pn_++) { \
         if (p >= end) return 0; /* truncated codestream: decode what is there */ \
         p = read_packet(H, R_, pn_, l, p, end); if (!p) return 0; /* ran out of data inside a packet: same */ } } while (0)
-    if (H->prog >= 2)
-        for (int c = 0; c < NC; c++) for (int r = 0; r < NR; r++)
-            if (comps[c][r].pw * comps[c][r].ph > 1) FAIL("RPCL/PCRL/CPRL with several precincts per resolution are not supported");
+    int several = 0;
+    for (int c = 0; c < NC; c++) for (int r = 0; r < NR; r++) if (comps[c][r].pw * comps[c][r].ph > 1) several = 1;
+    if (H->prog >= 2 && several) {
+        /* position-based progressions (B.12.1.3 to B.12.1.5; no sub-sampling here): the precinct of resolution r whose
+         * corner, on the tile's grid, is (x, y).  tx0 .. ty1 = the tile on the reference grid. */
+        const int NLv = NR - 1;
+        const int tx0 = comps[0][NLv].x0, ty0 = comps[0][NLv].y0, tx1 = comps[0][NLv].x1, ty1 = comps[0][NLv].y1;
+        int dx = 0, dy = 0;
+        for (int r = 0; r < NR; r++) {
+            const int sx = H->ppx[r] + NLv - r, sy = H->ppy[r] + NLv - r;
+            if (sx < 31 && (!dx || (1 << sx) < dx)) dx = 1 << sx;
+            if (sy < 31 && (!dy || (1 << sy) < dy)) dy = 1 << sy;
+        }
+        if (!dx) dx = 1 << 30;
+        if (!dy) dy = 1 << 30;
+        const int n1 = H->prog == 2 ? NR : (H->prog == 4 ? NC : 1);
+        for (int o = 0; o < n1; o++)
+            for (int y = ty0; y < ty1; y += dy - (y % dy))
+                for (int x = tx0; x < tx1; x += dx - (x % dx)) {
+                    const int c0 = H->prog == 4 ? o : 0, c1 = H->prog == 4 ? o + 1 : NC;
+                    for (int c = c0; c < c1; c++) {
+                        const int r0 = H->prog == 2 ? o : 0, r1 = H->prog == 2 ? o + 1 : NR;
+                        for (int r = r0; r < r1; r++) {
+                            dres_t *R_ = &comps[c][r];
+                            const int lv = NLv - r, rpx = R_->ppx + lv, rpy = R_->ppy + lv;
+                            if (R_->x0 == R_->x1 || R_->y0 == R_->y1) continue;
+                            if (rpx < 31 && !((x % (1 << rpx) == 0) || (x == tx0 && ((R_->x0 << lv) % (1 << rpx))))) continue;
+                            if (rpy < 31 && !((y % (1 << rpy) == 0) || (y == ty0 && ((R_->y0 << lv) % (1 << rpy))))) continue;
+                            if (rpx >= 31 && x != tx0) continue;
+                            if (rpy >= 31 && y != ty0) continue;
+                            const int pi = fdp2(cdp2(x, lv), R_->ppx) - fdp2(R_->x0, R_->ppx), pj = fdp2(cdp2(y, lv), R_->ppy) - fdp2(R_->y0, R_->ppy);
+                            const int pn_ = pi + pj * R_->pw;
+                            for (int l = 0; l < NLy; l++) {
+                                if (p >= end) return 0;
+                                p = read_packet(H, R_, pn_, l, p, end);
+                                if (!p) return 0;
+                            }
+                        }
+                    }
+                }
+        return 0;
+    }
     switch (H->prog) {
     case 1: for (int r = 0; r < NR; r++) for (int l = 0; l < NLy; l++) for (int c = 0; c < NC; c++) PKT(l, r, c); break;
     case 2: for (int r = 0; r < NR; r++) for (int c = 0; c < NC; c++) for (int l = 0; l < NLy; l++) PKT(l, r, c); break;
@@ -718,8 +993,18 @@ void j2ko_decode_output(int32_t *const planes[], int ncomp, const size_t n[], co
     }
 }
 
-/* decode one tile into out (ncomp planes of ow x oh, the reduced image) */
-static int decode_tile(const dhdr_t *H, int tileno, const uint8_t *data, size_t len, int reduce, int32_t *out, int ow, int oh)
+/* j2ko_file_blocks: the code-blocks as Tier-2 leaves them, 16 words each: tile, component, resolution, orientation, x, y
+ * (in the tile-component's Mallat plane), w, h, numbps, npasses, first segment, segments, byte offset, bytes, 0.5 x step size
+ * (float bits; 1.0 when reversible), 0 */
+typedef struct {
+    int32_t *meta; size_t nblk, cap_blk;
+    uint32_t *segs; size_t nseg, cap_seg;
+    uint8_t *bytes; size_t nbytes, cap_bytes;
+    int overflow;
+} blkdump_t;
+
+/* decode one tile into out (ncomp planes of ow x oh, the reduced image); dump: list its code-blocks instead */
+static int decode_tile(const dhdr_t *H, int tileno, const uint8_t *data, size_t len, int reduce, int32_t *out, int ow, int oh, blkdump_t *dump)
 {
     const int p_ = tileno % H->ntx, q_ = tileno / H->ntx;
     const int tx0 = p_ * H->tw, ty0 = q_ * H->th;
@@ -749,9 +1034,29 @@ static int decode_tile(const dhdr_t *H, int tileno, const uint8_t *data, size_t 
                         dcblk_t *cb = &P->cblks[k];
                         const int bw = cb->x1 - cb->x0, bh = cb->y1 - cb->y0;
                         if (!cb->included || cb->npasses == 0 || cb->numbps <= 0) continue;
-                        int32_t *tmp = (int32_t *)malloc(sizeof(int32_t) * (size_t)bw * (size_t)bh);
-                        j2ko_t1_decode_block(cb->data, cb->len, bw, bh, B->orient, cb->numbps, cb->npasses, tmp);
                         const float step = 0.5f * B->stepsize;
+                        uint32_t sg[256];
+                        for (int i = 0; i < cb->nseg; i++) { sg[2 * i] = cb->seg_bytes[i]; sg[2 * i + 1] = cb->seg_np[i]; }
+                        if (dump) {
+                            if (dump->nblk >= dump->cap_blk || dump->nseg + (size_t)cb->nseg > dump->cap_seg || dump->nbytes + cb->len > dump->cap_bytes) {
+                                dump->overflow = 1;
+                                continue;
+                            }
+                            int32_t *m = dump->meta + 16 * dump->nblk++;
+                            const float hs = H->reversible ? 1.0f : step;
+                            m[0] = tileno; m[1] = c; m[2] = r; m[3] = B->orient;
+                            m[4] = offx + cb->x0 - B->x0; m[5] = offy + cb->y0 - B->y0; m[6] = bw; m[7] = bh;
+                            m[8] = cb->numbps; m[9] = cb->npasses; m[10] = (int32_t)dump->nseg; m[11] = cb->nseg;
+                            m[12] = (int32_t)dump->nbytes; m[13] = (int32_t)cb->len; memcpy(&m[14], &hs, 4); m[15] = 0;
+                            memcpy(dump->segs + 2 * dump->nseg, sg, sizeof(uint32_t) * 2 * (size_t)cb->nseg);
+                            dump->nseg += (size_t)cb->nseg;
+                            if (cb->len) memcpy(dump->bytes + dump->nbytes, cb->data, cb->len);
+                            dump->nbytes += cb->len;
+                            continue;
+                        }
+                        int32_t *tmp = (int32_t *)malloc(sizeof(int32_t) * (size_t)bw * (size_t)bh);
+                        if (H->cblksty) j2ko_t1_decode_block_styled(cb->data, cb->len, bw, bh, B->orient, cb->numbps, cb->npasses, H->cblksty, sg, cb->nseg, tmp);
+                        else j2ko_t1_decode_block(cb->data, cb->len, bw, bh, B->orient, cb->numbps, cb->npasses, tmp);
                         for (int y = 0; y < bh; y++)
                             for (int x = 0; x < bw; x++) {
                                 int32_t *dst = &planes[c][(size_t)(offy + cb->y0 - B->y0 + y) * w + offx + cb->x0 - B->x0 + x];
@@ -764,11 +1069,12 @@ static int decode_tile(const dhdr_t *H, int tileno, const uint8_t *data, size_t 
                 }
             }
         }
+        if (dump) continue;
         /* origin of the tile-component at the decoded resolution */
         if (H->reversible) j2ko_idwt53(planes[c], w, h, w, top->x0, top->y0, R);
         else j2ko_idwt97((float *)planes[c], w, h, w, top->x0, top->y0, R);
     }
-    if (rc == 0) {
+    if (rc == 0 && !dump) {
         const size_t n[4] = {(size_t)w * (size_t)h, (size_t)w * (size_t)h, (size_t)w * (size_t)h, (size_t)w * (size_t)h};
         const int prec[4] = {H->prec, H->prec, H->prec, H->prec};
         j2ko_decode_output(planes, H->ncomp, n, prec, H->reversible, H->mct && H->ncomp >= 3);
@@ -784,7 +1090,7 @@ static int decode_tile(const dhdr_t *H, int tileno, const uint8_t *data, size_t 
 
 /* Whole decode.  out = ncomp planes of dims[0] x dims[1] int32 (row stride dims[0]); dims = {w, h, ncomp, prec}
  * of the image at the requested resolution (reduce = log2 of the reference's `subsample`). */
-int j2ko_decode(const uint8_t *file, size_t flen, int reduce, int32_t *out, size_t cap_samples, int dims[4])
+static int decode_impl(const uint8_t *file, size_t flen, int reduce, int32_t *out, size_t cap_samples, int dims[4], blkdump_t *dump, int hdr[4])
 {
     dhdr_t H;
     size_t off, len, pos;
@@ -795,8 +1101,9 @@ int j2ko_decode(const uint8_t *file, size_t flen, int reduce, int32_t *out, size
     if (reduce < 0 || reduce >= H.numres) FAIL("cannot discard %d resolutions of %d", reduce, H.numres);
     const int ow = cdp2(H.width, reduce), oh = cdp2(H.height, reduce);
     dims[0] = ow; dims[1] = oh; dims[2] = H.ncomp; dims[3] = H.prec;
-    if ((size_t)ow * (size_t)oh * (size_t)H.ncomp > cap_samples) FAIL("output capacity too small");
+    if (!dump && (size_t)ow * (size_t)oh * (size_t)H.ncomp > cap_samples) FAIL("output capacity too small");
     const int ntiles = H.ntx * H.nty;
+    if (hdr) { hdr[0] = H.cblksty; hdr[1] = H.reversible; hdr[2] = H.ncomp; hdr[3] = ntiles; }
     uint8_t **tdata = (uint8_t **)calloc((size_t)ntiles, sizeof(uint8_t *));
     size_t *tlen = (size_t *)calloc((size_t)ntiles, sizeof(size_t));
     int rc = 0;
@@ -826,12 +1133,31 @@ int j2ko_decode(const uint8_t *file, size_t flen, int reduce, int32_t *out, size
         tlen[isot] += n;
         pos += psot;
     }
-    memset(out, 0, sizeof(int32_t) * (size_t)ow * (size_t)oh * (size_t)H.ncomp);
+    if (!dump) memset(out, 0, sizeof(int32_t) * (size_t)ow * (size_t)oh * (size_t)H.ncomp);
     for (int t = 0; t < ntiles && rc == 0; t++)
-        if (tdata[t]) rc = decode_tile(&H, t, tdata[t], tlen[t], reduce, out, ow, oh);
+        if (tdata[t]) rc = decode_tile(&H, t, tdata[t], tlen[t], reduce, out, ow, oh, dump);
     for (int t = 0; t < ntiles; t++) free(tdata[t]);
     free(tdata); free(tlen);
     return rc;
+}
+
+int j2ko_decode(const uint8_t *file, size_t flen, int reduce, int32_t *out, size_t cap_samples, int dims[4])
+{
+    return decode_impl(file, flen, reduce, out, cap_samples, dims, NULL, NULL);
+}
+
+/* Every code-block of the file that holds passes, in the order the tile decoder meets them (tile, component, resolution,
+ * band, precinct, block).  Returns their number, or -1 (also when a capacity is too small). */
+long j2ko_file_blocks(const uint8_t *file, size_t flen, int32_t *meta, size_t cap_blocks, uint32_t *segs, size_t cap_segs, uint8_t *bytes,
+                      size_t cap_bytes, int hdr[4])
+{
+    blkdump_t d;
+    int dims[4];
+    memset(&d, 0, sizeof d);
+    d.meta = meta; d.cap_blk = cap_blocks; d.segs = segs; d.cap_seg = cap_segs; d.bytes = bytes; d.cap_bytes = cap_bytes;
+    if (decode_impl(file, flen, 0, NULL, 0, dims, &d, hdr)) return -1;
+    if (d.overflow) FAIL("j2ko_file_blocks: a capacity is too small");
+    return (long)d.nblk;
 }
 
 /* Codec::CopyBuffer towards the host's channel (reference: src/common/j2k_codec.cpp:222-427 with

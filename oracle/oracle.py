@@ -119,6 +119,12 @@ class Oracle:
         L.j2ko_decode_info.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int)]
         L.j2ko_t1_decode_block.restype = C.c_int
         L.j2ko_t1_decode_block.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        L.j2ko_t1_decode_block_styled_ex.restype = C.c_int
+        L.j2ko_t1_decode_block_styled_ex.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                     C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_long)]
+        L.j2ko_file_blocks.restype = C.c_long
+        L.j2ko_file_blocks.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
+                                       C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int32)]
         L.j2ko_idwt53.restype = None
         L.j2ko_idwt53.argtypes = L.j2ko_dwt53.argtypes
         L.j2ko_idwt97.restype = None
@@ -161,11 +167,43 @@ class Oracle:
         self.L.j2ko_idwt97(a.ctypes.data_as(C.POINTER(C.c_float)), a.shape[1], a.shape[0], a.shape[1], x0, y0, levels)
         return a
 
-    def t1_decode_block(self, data: bytes, w: int, h: int, orient: int, numbps: int, npasses: int) -> np.ndarray:
+    def t1_decode_block(self, data: bytes, w: int, h: int, orient: int, numbps: int, npasses: int, style: int = 0, segs=None,
+                        want_below: bool = False):
+        """The block's samples in the decoder's representation.  style / segs: the code-block style and the block's codeword
+        segments [(bytes, passes), ...] (j2ko_t1_decode_block_styled); want_below: also the count of decisions that saw a
+        significant sample in the row below a stripe's last row (what vertically causal contexts hide)."""
         buf = np.frombuffer(data + b"\0", dtype=np.uint8)
         out = np.empty((h, w), dtype=np.int32)
-        self.L.j2ko_t1_decode_block(_u8p(buf), len(data), w, h, orient, numbps, npasses, _i32p(out))
-        return out
+        if not style and not segs and not want_below:
+            self.L.j2ko_t1_decode_block(_u8p(buf), len(data), w, h, orient, numbps, npasses, _i32p(out))
+            return out
+        sg = np.array([v for s in (segs or ()) for v in s] + [0, 0], dtype=np.uint32)
+        below = C.c_long()
+        self.L.j2ko_t1_decode_block_styled_ex(_u8p(buf), len(data), w, h, orient, numbps, npasses, style,
+                                              sg.ctypes.data_as(C.POINTER(C.c_uint32)), len(segs or ()), _i32p(out), C.byref(below))
+        return (out, below.value) if want_below else out
+
+    def file_blocks(self, data: bytes) -> dict:
+        """Every code-block of a file that holds passes, as the oracle's Tier-2 found it (j2ko_file_blocks): dict(style,
+        reversible, blocks = [dict(tile, comp, res, orient, rect = (x, y, w, h) in the tile-component's plane, numbps,
+        npasses, half_step, segs = [(bytes, passes), ...] under bypass / termall, data)])."""
+        buf = np.frombuffer(data, dtype=np.uint8)
+        cap_b, cap_s = 1 << 16, 1 << 20
+        meta = np.zeros((cap_b, 16), dtype=np.int32)
+        segs = np.zeros((cap_s, 2), dtype=np.uint32)
+        raw = np.zeros(len(data) + 16, dtype=np.uint8)
+        hdr = (C.c_int32 * 4)()
+        n = self.L.j2ko_file_blocks(_u8p(buf), len(data), _i32p(meta), cap_b, segs.ctypes.data_as(C.POINTER(C.c_uint32)), cap_s,
+                                    _u8p(raw), raw.size, hdr)
+        if n < 0:
+            raise RuntimeError("oracle decode failed: " + self.L.j2ko_decode_error().decode())
+        blocks = []
+        for m in meta[:n]:
+            tile, comp, res, orient, x, y, w, h, nb, npass, s0, ns, off, ln, hs, _ = (int(v) for v in m)
+            blocks.append(dict(tile=tile, comp=comp, res=res, orient=orient, rect=(x, y, w, h), w=w, h=h, numbps=nb, npasses=npass,
+                               half_step=float(np.array([hs], dtype=np.int32).view(np.float32)[0]),
+                               segs=[(int(a), int(b)) for a, b in segs[s0:s0 + ns]], data=raw[off:off + ln].tobytes()))
+        return dict(style=int(hdr[0]), reversible=bool(hdr[1]), ncomp=int(hdr[2]), ntiles=int(hdr[3]), blocks=blocks)
 
     def decode_output(self, comps, precs, reversible: bool, mct: bool) -> list:
         """The tail of a tile's decode (j2ko_decode_output): comps = one 2-D plane per component, int32 (reversible) or

@@ -10,6 +10,11 @@ provably took effect in the fixture.
 
     python tests/golden/make_style_golden.py            # (re)write the files
     python tests/golden/make_style_golden.py --check    # compare with the committed files, write nothing
+    python tests/golden/make_style_golden.py --dec [--check]
+
+--dec: the decode-only fixtures tests/golden/styles_dec/<name>.j2k and styles_dec.json instead -- files with vertically
+causal contexts (style bit 8), which libopenjp2 writes and this project only reads.  They stay out of styles.json, whose
+every entry the encoder tests write; odd sizes, so that blocks are partial in both directions and a stripe is short.
 """
 import argparse
 import hashlib
@@ -43,6 +48,15 @@ STYLES = {
     "yc_65x33_rgba8_53_bypass_termall": (65, 33, 4, 8, 212, "B", dict(numres=2, mct=True, mode=1 | 4)),
 }
 
+# the decode-only fixtures (--dec): every one has the vertically causal bit
+STYLES_DEC = {
+    "z1_97x61_grey16_53_vcausal": (97, 61, 1, 16, 221, "A", dict(numres=3, mode=8)),
+    "z2_97x61_grey12_97_vcausal_bypass_termall": (97, 61, 1, 12, 222, "B", dict(numres=3, mode=8 | 1 | 4, reversible=False)),
+    "z3_17x9_grey16_53_all_six": (17, 9, 1, 16, 223, "A", dict(numres=2, mode=63)),
+    "z4_65x33_rgb8_53_vcausal_reset_segsym_cblk32": (65, 33, 3, 8, 224, "B", dict(numres=2, mct=True, mode=8 | 2 | 32, cblk=(32, 32))),
+    "z5_128_grey16_53_vcausal_bypass_3layers": (128, 128, 1, 16, 225, "B", dict(numres=2, mode=8 | 1, layers=3)),
+}
+
 
 def sha(b):
     return hashlib.sha256(b).hexdigest()
@@ -57,12 +71,13 @@ def differs_beyond_cod_style(styled: bytes, plain: bytes) -> bool:
     return any(a != b for i, (a, b) in enumerate(zip(styled, plain)) if i != style_at)
 
 
-def generate():
+def generate(table=None):
+    table = STYLES if table is None else table
     from oracle.oracle import OpjReplay, find_openjpeg_libs, strip_com
     reps = [OpjReplay(l) for l in find_openjpeg_libs()]
     meta = {"_generator": dict(libraries=[r.version for r in reps], note="COM segments stripped before hashing/storing")}
     files = {}
-    for name, (w, h, nc, prec, seed, dist, kw) in STYLES.items():
+    for name, (w, h, nc, prec, seed, dist, kw) in table.items():
         pl = synth.planes(w, h, nc, prec, seed, dist)
         comps = [np.ascontiguousarray(pl[c]) for c in range(nc)]
         outs = [strip_com(r.encode_ext(comps, prec=prec, **kw)) for r in reps]
@@ -85,20 +100,22 @@ def generate():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check", action="store_true", help="compare with the committed files instead of writing them")
+    ap.add_argument("--dec", action="store_true", help="the decode-only fixtures (tests/golden/styles_dec) instead")
     args = ap.parse_args()
-    meta, files = generate()
+    out_dir, index = (os.path.join(HERE, "styles_dec"), "styles_dec.json") if args.dec else (OUT, "styles.json")
+    meta, files = generate(STYLES_DEC if args.dec else STYLES)
     if args.check:
-        committed = json.load(open(os.path.join(OUT, "styles.json")))
-        assert committed == json.loads(json.dumps(meta)), "styles.json differs"
+        committed = json.load(open(os.path.join(out_dir, index)))
+        assert committed == json.loads(json.dumps(meta)), index + " differs"
         for name, cs in files.items():
-            assert open(os.path.join(OUT, name + ".j2k"), "rb").read() == cs, name
+            assert open(os.path.join(out_dir, name + ".j2k"), "rb").read() == cs, name
         print("all", len(files), "files match")
         return
-    os.makedirs(OUT, exist_ok=True)
+    os.makedirs(out_dir, exist_ok=True)
     for name, cs in files.items():
-        with open(os.path.join(OUT, name + ".j2k"), "wb") as f:
+        with open(os.path.join(out_dir, name + ".j2k"), "wb") as f:
             f.write(cs)
-    with open(os.path.join(OUT, "styles.json"), "w") as f:
+    with open(os.path.join(out_dir, index), "w") as f:
         json.dump(meta, f, indent=1, sort_keys=True)
 
 

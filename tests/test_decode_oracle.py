@@ -1,7 +1,10 @@
 """CPU: the decode oracle (oracle/j2k_oracle_dec.c) against what libopenjp2 2.4.0 / 2.5.4 decode
 from the same files -- the committed hashes of tests/golden/golden.json (decoded_sha256, decoded_reduced_sha256,
 made by tests/golden/make_golden.py --reduced) and, where a libopenjp2 is installed, the library itself.
-Reference path being restated: OpenJPEGCodec::ReadFile, src/common/j2k_openjpeg_codec.cpp:451-586."""
+Reference path being restated: OpenJPEGCodec::ReadFile, src/common/j2k_openjpeg_codec.cpp:451-586.
+The files here have code-block style 0; the oracle's decode under the six styles of Table A.19 (one length per codeword
+segment in the packet headers, the styled block decoder) is pinned the same way by test_t1_dec_styled_refs.py, and a style
+bit beyond them is refused."""
 import glob
 import hashlib
 import os
@@ -79,7 +82,7 @@ def test_decode_rejects_what_it_does_not_support(oracle):
     with pytest.raises(RuntimeError, match="resolutions"):
         oracle.decode(bytes(data), 2)
     cod = data.index(b"\xff\x52")
-    data[cod + 12] = 0x01  # code-block style: selective arithmetic coding bypass
+    data[cod + 12] = 0x40  # code-block style: a bit T.800 Table A.19 does not define (the six it defines are read: test_t1_dec_styled_refs.py)
     with pytest.raises(RuntimeError, match="code-block style"):
         oracle.decode(bytes(data))
     with pytest.raises(RuntimeError):
