@@ -430,6 +430,48 @@ int j2k_hip_decode_rgba(j2k_hip_encoder *enc, const void *file, size_t len, uint
 int j2k_hip_decode_rgba_device(j2k_hip_encoder *enc, const void *file, size_t len, uint32_t subsample,
                                const j2k_hip_rect *region, const j2k_hip_rgba_dst *dst);
 
+/* --- decode an image sequence in one call ---------------------------------------------------------
+ * The frames of one call share their launches: one gather, one Tier-1 launch (pair), one inverse DWT launch pair per
+ * resolution and one output launch serve the code-blocks of all of them, from one host thread on the handle's one stream,
+ * whatever GPU_MAX_HW_QUEUES is.  (A long call is cut into groups of consecutive frames whose lane waves the chip holds at
+ * once and whose arenas fit a share of the free device memory; a group is what shares launches.)
+ *
+ * Output: frame f goes to planes[f * nplanes + i] (i < nplanes) or dsts[f], and every destination receives exactly what
+ * j2k_hip_decode_region / j2k_hip_decode_rgba with the same subsample, region and destination would have written for
+ * files[f] -- region == NULL: the whole image; sub-sampled, signed and mixed-depth components, palettes, code-block styles,
+ * files cut short and the first four of sixteen components included.  Only channel samples are written.  Destinations of
+ * different frames may be pieces of one buffer but must not overlap.  Channel i has the same sample_bits and depth in every
+ * frame (RGBA: also the same demote_ae16, and an alpha destination in all frames or in none); bases, strides and extents are
+ * each frame's own.
+ * The frames must match: identical SIZ (geometry, components, their depths, signs and sub-sampling), COD (levels,
+ * code-blocks, style, wavelet, MCT, precincts, progression, layers), QCD / QCC values, RGN and POC, and for the RGBA calls
+ * the colour space, the opacity channel and the palette.  COM, TLM, the tile-part structure, PPM / PPT, SOP / EPH and JP2
+ * boxes that do not enter the decode may differ.
+ * Refused before any device work, nothing written, the text beginning with "frame k: ": J2K_HIP_ERR_PARAM for nframes == 0
+ * (k = 0), a NULL or empty file, a frame that differs from frame 0, a bad region, a bad destination;
+ * J2K_HIP_ERR_UNSUPPORTED for a file that j2k_hip_read_info (RGBA calls: j2k_hip_rgba_mode) does not take.
+ * j2k_hip_decode_sequence_check does the header part of that alone -- no device, no handle; *bad_frame (optional) receives
+ * k, the text is j2k_hip_last_error(NULL)'s -- so that a host can sort its files into calls beforehand.
+ * A frame whose headers are sound but whose packets turn out malformed fails the call with that frame's status and
+ * "frame k: "; frames before it may have been written by then (those of the groups that had completed), frame k and the
+ * frames behind it have not.
+ * nframes == 1 gives the single-frame call's output (which Tier-1 kernel runs may differ from the single-frame choice: the
+ * choice sees the blocks of all frames of a group).  j2k_hip_stats after the call holds sums over the frames;
+ * num_codeblocks counts the blocks decoded, ms_total is the call's wall time.
+ * J2K_HIP_ABI_VERSION is still 9: functions were added, none changed. */
+typedef struct j2k_hip_file { const void *data; size_t len; } j2k_hip_file;
+int j2k_hip_decode_sequence_check(const j2k_hip_file *files, uint32_t nframes, uint32_t *bad_frame);
+int j2k_hip_decode_sequence(j2k_hip_encoder *enc, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample,
+                            const j2k_hip_rect *region, const j2k_hip_outplane *planes, uint32_t nplanes);
+/* Same with destination channels in device memory (planes[].base are device pointers). */
+int j2k_hip_decode_sequence_device(j2k_hip_encoder *enc, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample,
+                                   const j2k_hip_rect *region, const j2k_hip_outplane *planes, uint32_t nplanes);
+int j2k_hip_decode_rgba_sequence(j2k_hip_encoder *enc, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample,
+                                 const j2k_hip_rect *region, const j2k_hip_rgba_dst *dsts);
+/* Same with destination channels in device memory. */
+int j2k_hip_decode_rgba_sequence_device(j2k_hip_encoder *enc, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample,
+                                        const j2k_hip_rect *region, const j2k_hip_rgba_dst *dsts);
+
 /* --- stage-level entry points (parity tests and roofline measurement call these) -----------------
  * A1+A2+A4+A5: front end only. d_out = channels planes of width*height 32-bit words (int32 for
  * reversible, float32 bit patterns otherwise), row stride = width. */
@@ -585,6 +627,9 @@ int j2k_hip_debug_get_tune(const char *key, int *value);
  * the kernel for `reversible` 5/3 or 9/7 and 1, 3 or 4 channels): the launch heuristics size their chunks by it, so a
  * compiler that changes the count changes them with it.  0 without a usable device. */
 int j2k_hip_debug_fused_occupancy(j2k_hip_encoder *enc, int reversible, int channels);
+/* Which Tier-1 decode kernel the handle's last decode call took (tools report it beside their timings): the code-blocks
+ * decoded by the lane-per-block kernel and by the wave-per-block kernel (the whole call, or the tail beside the lanes). */
+int j2k_hip_debug_decode_kernels(const j2k_hip_encoder *enc, uint64_t *lane_blocks, uint64_t *wave_blocks);
 /* Two sinks in native code for benchmarks and tools driven from a scripting language (bench.py's `host_path`): what they
  * time is then the library and a plain memcpy, not an interpreter's callback.  Both have j2k_hip_write_fn's signature.
  * j2k_hip_debug_copy_sink: `user` = a j2k_hip_copy_sink; appends the bytes at dst + pos (what OutputFile::Write into a

@@ -86,6 +86,8 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_begin", "j2k_hip_encode_begin_borrowed", "j2k_hip_encode_end", "j2k_hip_debug_tune", "j2k_hip_debug_get_tune", "j2k_hip_debug_fused_occupancy", "j2k_hip_debug_membw", "j2k_hip_debug_dwt_time", "j2k_hip_read_info", "j2k_hip_decode",
            "j2k_hip_decode_device", "j2k_hip_decode_region", "j2k_hip_decode_region_device", "j2k_hip_region_footprint",
            "j2k_hip_rgba_mode", "j2k_hip_decode_rgba", "j2k_hip_decode_rgba_device", "j2k_hip_stage_rgba_output",
+           "j2k_hip_decode_sequence_check", "j2k_hip_decode_sequence", "j2k_hip_decode_sequence_device",
+           "j2k_hip_decode_rgba_sequence", "j2k_hip_decode_rgba_sequence_device", "j2k_hip_debug_decode_kernels",
            "j2k_hip_encode_tiles", "j2k_hip_device_count", "j2k_hip_encode_batch",
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
@@ -125,6 +127,11 @@ class RgbaStage(C.Structure):
     """include/j2k_hip.h: j2k_hip_rgba_stage."""
     _fields_ = [(n, C.c_uint32) for n in ("struct_size", "mode", "org_x", "org_y", "lut_size", "lut_columns")] + \
                [("lut", (C.c_uint8 * 4) * 256), ("lut_rgb", C.c_uint8 * 4)]
+
+
+class SeqFile(C.Structure):
+    """include/j2k_hip.h: j2k_hip_file."""
+    _fields_ = [("data", C.c_void_p), ("len", C.c_size_t)]
 
 
 RGBA_RGB, RGBA_GREY, RGBA_PALETTE, RGBA_SYCC = 1, 2, 3, 4  # J2K_HIP_RGBA_*
@@ -214,6 +221,12 @@ def load_library():
     L.j2k_hip_decode_rgba_device.argtypes = L.j2k_hip_decode_rgba.argtypes
     L.j2k_hip_stage_rgba_output.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32,
                                             C.POINTER(OutComp), C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(RgbaDst), C.POINTER(RgbaStage)]
+    L.j2k_hip_decode_sequence_check.argtypes = [C.POINTER(SeqFile), C.c_uint32, C.POINTER(C.c_uint32)]
+    L.j2k_hip_decode_sequence.argtypes = [C.c_void_p, C.POINTER(SeqFile), C.c_uint32, C.c_uint32, C.POINTER(Rect), C.POINTER(OutPlane), C.c_uint32]
+    L.j2k_hip_decode_sequence_device.argtypes = L.j2k_hip_decode_sequence.argtypes
+    L.j2k_hip_decode_rgba_sequence.argtypes = [C.c_void_p, C.POINTER(SeqFile), C.c_uint32, C.c_uint32, C.POINTER(Rect), C.POINTER(RgbaDst)]
+    L.j2k_hip_decode_rgba_sequence_device.argtypes = L.j2k_hip_decode_rgba_sequence.argtypes
+    L.j2k_hip_debug_decode_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.j2k_hip_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.j2k_hip_get_dwt_level_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
     L.j2k_hip_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -261,6 +274,28 @@ def rgba_mode(data: bytes) -> int:
     if rc != 0:
         raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
     return m.value
+
+
+def _seq_files(files):
+    """The j2k_hip_file array of a list of bytes objects (and the arrays that keep the bytes alive)."""
+    bufs = [np.frombuffer(d, dtype=np.uint8) if len(d) else np.zeros(0, np.uint8) for d in files]
+    arr = (SeqFile * max(len(files), 1))()
+    for f, b in enumerate(bufs):
+        arr[f].data, arr[f].len = (b.ctypes.data if b.size else None), b.size
+    return arr, bufs
+
+
+def sequence_check(files) -> None:
+    """May these files share one sequence decode call (j2k_hip_decode_sequence_check; headers only, no device needed)?
+    Raises J2kHipError -- its text begins with "frame k: ", .frame is k -- when they may not."""
+    L = load_library()
+    arr, _keep = _seq_files(files)
+    bad = C.c_uint32(0xffffffff)
+    rc = L.j2k_hip_decode_sequence_check(arr, len(files), C.byref(bad))
+    if rc != 0:
+        err = J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+        err.frame = bad.value
+        raise err
 
 
 def _set_outplane(p, base, colbytes, rowbytes, sample_bits, depth, width, height):
@@ -629,6 +664,100 @@ class Encoder:
         buf = np.frombuffer(data, dtype=np.uint8)
         self._check(self.L.j2k_hip_decode_rgba(self.h, buf.ctypes.data, len(data), subsample,
                                                C.byref(Rect(*region)) if region is not None else None, C.byref(dst)))
+
+    # -- decode: the frames of a sequence in one call ---------------------------------------------
+    def decode_sequence_planar(self, files, subsample: int = 1, region=None, device: bool = False, sample_bits: int | None = None,
+                               depth: int | None = None, channels: int | None = None, out: np.ndarray | None = None) -> np.ndarray:
+        """Decode frames of one geometry in one call (j2k_hip_decode_sequence[_device]) into planar buffers:
+        (frames, channels, h, w) of uint8 / uint16, frame f what decode_planar / decode_region_planar gives for files[f].
+        region = (x, y, w, h); out: a buffer (frames, channels, rows, cols) to decode into (its top-left part is written);
+        device=True: through a device copy of the buffer."""
+        i = read_info(files[0])
+        nf, nc = len(files), channels or i["channels"]
+        red = max(subsample, 1).bit_length() - 1
+        w, h = (region[2], region[3]) if region is not None else (-(-i["width"] >> red), -(-i["height"] >> red))
+        bits = sample_bits or (8 if i["depth"] <= 8 else 16)
+        if out is None:
+            out = np.zeros((nf, nc, h, w), dtype=np.uint8 if bits == 8 else np.uint16)
+        assert out.ndim == 4 and out.shape[:2] == (nf, nc) and out.itemsize * 8 == bits and out.flags.c_contiguous
+        _, _, rows, cols = out.shape
+        d = self.upload(out) if device else None
+        base = d if device else out.ctypes.data
+        arr = (OutPlane * (nf * nc))()
+        for k in range(nf * nc):
+            _set_outplane(arr[k], base + k * rows * cols * out.itemsize, out.itemsize, cols * out.itemsize, bits,
+                          depth or min(i["depth"], bits), cols, rows)
+        fa, _keep = _seq_files(files)
+        try:
+            fn = self.L.j2k_hip_decode_sequence_device if device else self.L.j2k_hip_decode_sequence
+            self._check(fn(self.h, fa, nf, subsample, C.byref(Rect(*region)) if region is not None else None, arr, nc))
+            if device:
+                out[...] = self.d2h(d, out.nbytes).view(out.dtype).reshape(out.shape)
+        finally:
+            if d:
+                self.free(d)
+        return out
+
+    def decode_sequence_channels(self, files, chans: list, depth: int | None = None, subsample: int = 1, region=None):
+        """j2k_hip_decode_sequence into one 2-D numpy view per frame and codec channel (chans[f][c]), wherever each lies and
+        whatever its strides: the general form of the C ABI's destination."""
+        nf, nc = len(files), len(chans[0])
+        arr = (OutPlane * (nf * nc))()
+        for f in range(nf):
+            assert len(chans[f]) == nc
+            for c, a in enumerate(chans[f]):
+                assert a.ndim == 2 and a.dtype in (np.uint8, np.uint16)
+                _set_outplane(arr[f * nc + c], a.ctypes.data, a.strides[1], a.strides[0], 8 * a.itemsize, depth or 8 * a.itemsize, a.shape[1], a.shape[0])
+        fa, _keep = _seq_files(files)
+        self._check(self.L.j2k_hip_decode_sequence(self.h, fa, nf, subsample, C.byref(Rect(*region)) if region is not None else None, arr, nc))
+
+    def decode_rgba_sequence(self, files, frames: np.ndarray, layout: dict, width: int, height: int, depth: int | None = None,
+                             subsample: int = 1, region=None, demote: bool = False, device: bool = False, alpha: bool = True):
+        """Decode frames of one geometry straight into the R, G, B, A samples of After Effects ARGB frames (decode_rgba's
+        arguments; j2k_hip_decode_rgba_sequence[_device]): frames = one contiguous array whose slice f is frame f's buffer."""
+        nf = len(files)
+        assert frames.shape[0] == nf and frames.flags.c_contiguous
+        sb, offs = layout["sample_bytes"], layout["channel_offsets"]  # A,R,G,B
+        d = self.upload(frames) if device else None
+        base = d if device else frames.ctypes.data
+        per = frames.nbytes // nf
+        dsts = (RgbaDst * nf)()
+        for f in range(nf):
+            dst = dsts[f]
+            dst.struct_size, dst.demote_ae16 = C.sizeof(RgbaDst), int(demote)
+            for p, off in ((dst.r, offs[1]), (dst.g, offs[2]), (dst.b, offs[3])) + (((dst.a, offs[0]),) if alpha else ()):
+                _set_outplane(p, base + f * per + off, layout["colbytes"], layout["rowbytes"], 8 * sb, depth or 8 * sb, width, height)
+        fa, _keep = _seq_files(files)
+        try:
+            fn = self.L.j2k_hip_decode_rgba_sequence_device if device else self.L.j2k_hip_decode_rgba_sequence
+            self._check(fn(self.h, fa, nf, subsample, C.byref(Rect(*region)) if region is not None else None, dsts))
+            if device:
+                frames[...] = self.d2h(d, frames.nbytes).view(frames.dtype).reshape(frames.shape)
+        finally:
+            if d:
+                self.free(d)
+        return frames
+
+    def decode_rgba_sequence_channels(self, files, chans: list, depth: int | None = None, subsample: int = 1, region=None, demote: bool = False):
+        """j2k_hip_decode_rgba_sequence into 2-D numpy views: chans[f] = (r, g, b, a) of frame f, a may be None in all frames."""
+        nf = len(files)
+        dsts = (RgbaDst * nf)()
+        for f in range(nf):
+            dst = dsts[f]
+            dst.struct_size, dst.demote_ae16 = C.sizeof(RgbaDst), int(demote)
+            for p, v in zip((dst.r, dst.g, dst.b, dst.a), chans[f]):
+                if v is None:
+                    continue
+                assert v.ndim == 2 and v.dtype in (np.uint8, np.uint16)
+                _set_outplane(p, v.ctypes.data, v.strides[1], v.strides[0], 8 * v.itemsize, depth or 8 * v.itemsize, v.shape[1], v.shape[0])
+        fa, _keep = _seq_files(files)
+        self._check(self.L.j2k_hip_decode_rgba_sequence(self.h, fa, nf, subsample, C.byref(Rect(*region)) if region is not None else None, dsts))
+
+    def decode_kernels(self) -> tuple:
+        """(blocks the lane-per-block kernel took, blocks the wave-per-block kernel took) in the last decode call."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self.L.j2k_hip_debug_decode_kernels(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def stats(self) -> dict:
         s = Stats()

@@ -19,6 +19,7 @@
 #include <thread>
 
 #include "decode_plan.h"
+#include "decode_seq.h"
 #include "handle.h"
 
 using namespace j2k_hip;
@@ -125,96 +126,342 @@ IdwtWinJob window_job(const IRect &res, const ResFootprint &f, long long off)
     return j;
 }
 
-// region (optional): the window of a region decode.  Null: the whole image, by the launches of every decode before regions.
-// rgba (optional): the output stage goes straight to R, G, B, A (rgba_out.hip); planes[0..nplanes) are then rgba's r, g, b[, a]
-// (decode_rgba_impl below), already checked.  Everything before the last launch is the same decode.
-void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_outplane *planes,
-                 uint32_t nplanes, bool planes_on_device, const j2k_hip_rect *region = nullptr, const j2k_hip_rgba_dst *rgba = nullptr)
-{
-    const double t_begin = now_ms();
-    if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
-    if (!file || !len) throw Error(J2K_HIP_ERR_PARAM, "Error reading file: empty input");
-    if (!planes || nplanes < 1 || nplanes > 4) throw Error(J2K_HIP_ERR_PARAM, "1..4 destination channels");
-    if (subsample == 0) subsample = 1;
-    const uint32_t win[4] = {region ? region->x : 0, region ? region->y : 0, region ? region->w : 0, region ? region->h : 0};
-    const uint32_t *const window = region ? win : nullptr;
-    const uint32_t reduce = (uint32_t)floorlog2(subsample); // reference: params.cp_reduce = log2(subsample), :501
-    HIP_CHECK(hipSetDevice(e->device));
-    hipStream_t s = e->stream;
-    const uint8_t *fbytes = static_cast<const uint8_t *>(file);
-    const Decoding decoding(e->device); // (counted for the length of the call)
+// ---- The decode, for one frame and for the frames of a sequence call alike, in pieces that take a frame's base offsets:
+// plan a frame (decode_plan.h) -- merge the plans of a group of frames (decode_seq.h) -- build the tables of the merged
+// blocks -- launch gather, Tier-1 and the inverse DWT once for the group -- output and download frame by frame.  The
+// single-frame entry points are a call of one frame in one group.
 
-    // ---- host Tier-2, beside the upload of the file (the device needs nothing of the plan to receive the bytes).  The
-    // headers are read first: a file this path cannot decode is turned away before the device is touched.
-    {
-        const FileHeader early = parse_headers(fbytes, len);
-        if (rgba) (void)classify_rgba(early); // (a file the fused path does not take: J2K_HIP_ERR_UNSUPPORTED, nothing written)
+// a failure that belongs to one frame of a sequence call: the text begins with "frame k: "
+struct FrameError : Error {
+    uint32_t frame;
+    FrameError(int c, uint32_t f, const std::string &m) : Error(c, "frame " + std::to_string(f) + ": " + m), frame(f) {}
+};
+
+// region (optional): the window of a region decode.  Null: the whole image, by the launches of every decode before regions.
+// rgba (optional, one per frame): the output stage goes straight to R, G, B, A (rgba_out.hip); the frame's planes are then
+// rgba's r, g, b[, a], already checked.  Everything before the last launch is the same decode.
+// seq: a sequence entry point -- failures name their frame, and the output stage is the sequence kernels' one launch.
+struct DecodeCall {
+    const j2k_hip_file *files; uint32_t nframes;
+    uint32_t subsample;
+    const j2k_hip_rect *region;
+    const j2k_hip_outplane *planes; uint32_t nplanes; // frame f: planes[f * nplanes + i]
+    const j2k_hip_rgba_dst *rgba;
+    bool on_device, seq;
+};
+
+// what the frames of a call share (they have one geometry): the decoded resolution and the layout of a frame's planes
+struct Shape {
+    uint32_t reduce = 0, R = 0, nd = 0; // resolutions dropped, highest resolution decoded, components decoded
+    int ow = 0, oh = 0;                 // the image at the decoded resolution
+    int pox[4] = {0, 0, 0, 0}, poy[4] = {0, 0, 0, 0};
+    size_t stride = 0, plane_elems = 0;
+    size_t frame_words() const { return plane_elems * nd; }
+};
+Shape frame_shape(const Coding &cod, uint32_t reduce)
+{
+    Shape S;
+    S.reduce = reduce;
+    S.R = cod.numres - 1 - reduce;
+    // the image at the decoded resolution (opj_image_comp_header_update: both edges of the area are scaled, then subtracted)
+    reduced_size(cod, reduce, S.ow, S.oh);
+    if (S.ow <= 0 || S.oh <= 0) throw Error(J2K_HIP_ERR_PARAM, "Error reading file: nothing left of the image at this resolution");
+    // origin of every component's plane: the image area's origin on the component's grid at the decoded resolution
+    S.nd = cod.ncomp_out(); // components decoded: the first four (reference: min(numcomps, J2K_CODEC_MAX_CHANNELS), :278, :530)
+    for (uint32_t c = 0; c < S.nd; ++c) {
+        S.pox[c] = ceildivpow2((int)((cod.img_x0 + cod.cdx[c] - 1) / cod.cdx[c]), (int)reduce);
+        S.poy[c] = ceildivpow2((int)((cod.img_y0 + cod.cdy[c] - 1) / cod.cdy[c]), (int)reduce);
     }
-    HIP_CHECK(hipEventRecord(e->ev[EV_START], s));
-    e->d_file.ensure(len + 64);
-    DecodePlan P;
-    if (len >= (4u << 20)) {
-        auto fut = std::async(std::launch::async, [&] { return plan_decode(fbytes, len, reduce, window); });
-        const hipError_t up = hipMemcpyAsync(e->d_file.p, fbytes, len, hipMemcpyHostToDevice, s);
-#ifdef J2K_DEC_TRACE
-        static hipEvent_t tr_ev = nullptr;
-        if (!tr_ev) HIP_CHECK(hipEventCreate(&tr_ev));
-        HIP_CHECK(hipEventRecord(tr_ev, s));
-        const double t_issued = now_ms();
-#endif
+    S.stride = round_up((size_t)S.ow, 64);
+    S.plane_elems = S.stride * (size_t)S.oh;
+    return S;
+}
+
+// The destination channels' extents in the caller's address space.  Channels whose extents overlap (the samples of
+// interleaved pixels) form one span that keeps its layout on the device; channels that lie apart (planar buffers,
+// wherever they were allocated) are spans of their own.  dev: where a host destination's span lies in its frame's staged image
+// (a span keeps its address modulo 256: the samples stay aligned as on the host).
+struct Span { const uint8_t *lo, *hi; int ch[4]; int n; size_t dev; };
+struct SpanLayout { Span spans[4]; int nspans = 0; size_t dev_bytes = 0, max_span = 0, base = 0; };
+SpanLayout layout_spans(const DecOutArgs &oa, const j2k_hip_outplane *planes)
+{
+    SpanLayout L;
+    struct Ext { const uint8_t *lo, *hi; int c; } ext[4];
+    int ne = 0;
+    for (int c = 0; c < oa.nout; ++c) {
+        const j2k_hip_outplane &p = planes[c];
+        if (oa.dst_w[c] <= 0 || oa.dst_h[c] <= 0) continue;
+        const uint8_t *b = static_cast<const uint8_t *>(p.base);
+        const uint8_t *corners[4] = {b, b + (ptrdiff_t)(oa.dst_h[c] - 1) * p.rowbytes, b + (ptrdiff_t)(oa.dst_w[c] - 1) * p.colbytes,
+                                     b + (ptrdiff_t)(oa.dst_h[c] - 1) * p.rowbytes + (ptrdiff_t)(oa.dst_w[c] - 1) * p.colbytes};
+        Ext x{corners[0], corners[0] + oa.dst_bytes[c], c};
+        for (const uint8_t *q : corners) { x.lo = std::min(x.lo, q); x.hi = std::max(x.hi, q + oa.dst_bytes[c]); }
+        ext[ne++] = x;
+    }
+    if (!ne) throw Error(J2K_HIP_ERR_PARAM, "no destination channel has any sample");
+    std::sort(ext, ext + ne, [](const Ext &x, const Ext &y) { return x.lo < y.lo; });
+    for (int i = 0; i < ne; ++i) {
+        if (L.nspans && ext[i].lo < L.spans[L.nspans - 1].hi) {
+            Span &S = L.spans[L.nspans - 1];
+            S.hi = std::max(S.hi, ext[i].hi); S.ch[S.n++] = ext[i].c;
+        } else {
+            Span &S = L.spans[L.nspans++];
+            S = Span{ext[i].lo, ext[i].hi, {ext[i].c, 0, 0, 0}, 1, 0};
+        }
+    }
+    for (int k = 0; k < L.nspans; ++k) {
+        L.spans[k].dev = round_up(L.dev_bytes, 256) + (reinterpret_cast<uintptr_t>(L.spans[k].lo) & 255);
+        L.dev_bytes = L.spans[k].dev + (size_t)(L.spans[k].hi - L.spans[k].lo);
+        L.max_span = std::max(L.max_span, (size_t)(L.spans[k].hi - L.spans[k].lo));
+    }
+    return L;
+}
+
+// One frame's samples from its staged image on the device (dimg) into the host's channels: queued behind the output launch on
+// s.  staged: the pinned staging buffer has been used since the stream was last idle (it is one span's at a time).
+void download_spans(j2k_hip_encoder *e, const DecOutArgs &oa, const j2k_hip_outplane *planes, const SpanLayout &L, const uint8_t *dimg,
+                    bool &staged, hipStream_t s)
+{
+    std::vector<hipEvent_t> band_ev;
+    struct EvGuard { std::vector<hipEvent_t> &v; ~EvGuard() { for (hipEvent_t x : v) if (x) (void)hipEventDestroy(x); } } ev_guard{band_ev};
+    for (int k = 0; k < L.nspans; ++k) {
+        const Span &S = L.spans[k];
+        const uint8_t *lo = S.lo;
+        const size_t span = (size_t)(S.hi - S.lo);
+        const uint8_t *dbase = dimg + S.dev;
+        const int c0 = S.ch[0];
+        // Do the span's channels cover every byte of it (interleaved pixels with every sample decoded, or one planar
+        // channel, no row padding)?  Then it goes straight into the host's buffer.  Otherwise only the channel samples
+        // may be written (the reference's CopyBuffer touches nothing else): through a staging copy.
+        bool same = true;
+        const long long P0 = oa.colbytes[c0];
+        long long covered = 0;
+        for (int i = 0; i < S.n; ++i) {
+            const int c = S.ch[i];
+            same = same && oa.colbytes[c] == P0 && oa.rowbytes[c] == oa.rowbytes[c0] && oa.dst_w[c] == oa.dst_w[c0] && oa.dst_h[c] == oa.dst_h[c0];
+            covered += oa.dst_bytes[c];
+        }
+        const bool full = same && P0 > 0 && covered == P0 && oa.rowbytes[c0] == P0 * oa.dst_w[c0] && span == (size_t)(oa.rowbytes[c0] * oa.dst_h[c0]);
+        if (full) {
+            HIP_CHECK(hipMemcpyAsync(const_cast<uint8_t *>(lo), dbase, span, hipMemcpyDeviceToHost, s));
+            continue;
+        }
+        if (staged) HIP_CHECK(hipStreamSynchronize(s)); // (the staging buffer is one span's at a time)
+        staged = true;
+        e->h_outimg.ensure(L.max_span + 16);
+        const uint8_t *stg = e->h_outimg.as<uint8_t>();
+        // Two layouts get whole-word copies: the channels of one interleaved pixel of 4 or 8 bytes (After Effects'
+        // ARGB32 / ARGB64 with R, G, B decoded and A kept: one masked word per pixel) and planar rows.
+        bool pixels = same && (P0 == 4 || P0 == 8) && oa.rowbytes[c0] > 0;
+        // a pixel-sized window starting at the lowest channel's sample holds one sample of every channel (its remaining
+        // bytes belong to samples that are not decoded: they pass through)
+        uint64_t mask = 0;
+        for (int i = 0; i < S.n && pixels; ++i) {
+            const int c = S.ch[i];
+            const ptrdiff_t off = static_cast<const uint8_t *>(planes[c].base) - lo;
+            pixels = off >= 0 && off + oa.dst_bytes[c] <= P0;
+            if (pixels) mask |= (oa.dst_bytes[c] == 1 ? 0xffull : 0xffffull) << (8 * off);
+        }
+        // The download comes in row bands; the host merges band k while band k + 1 is on its way (a frame of pixels:
+        // the rows of the span in order; other layouts: one piece).
+        const int bands = pixels ? (int)std::max<size_t>(1, std::min<size_t>({(size_t)8, span >> 25, (size_t)oa.dst_h[c0]})) : 1;
+        auto band_row = [&](int b) { return (int)((long long)oa.dst_h[c0] * b / bands); };
+        const size_t ev0 = band_ev.size();
+        for (int b = 0; b < bands; ++b) {
+            const size_t b0 = bands > 1 ? (size_t)band_row(b) * (size_t)oa.rowbytes[c0] : 0;
+            const size_t b1 = (bands > 1 && b + 1 < bands) ? (size_t)band_row(b + 1) * (size_t)oa.rowbytes[c0] : span;
+            HIP_CHECK(hipMemcpyAsync(e->h_outimg.as<uint8_t>() + b0, dbase + b0, b1 - b0, hipMemcpyDeviceToHost, s));
+            band_ev.push_back(nullptr);
+            HIP_CHECK(hipEventCreateWithFlags(&band_ev.back(), hipEventDisableTiming));
+            HIP_CHECK(hipEventRecord(band_ev.back(), s));
+        }
+        if (pixels) {
+            const int w = oa.dst_w[c0];
+            const long long rb = oa.rowbytes[c0];
+            const bool wide = P0 == 8;
+            for (int b = 0; b < bands; ++b) {
+                const int band0 = band_row(b), hgt = band_row(b + 1) - band0;
+                HIP_CHECK(hipEventSynchronize(band_ev[ev0 + (size_t)b]));
+                parallel_rows(hgt, (size_t)w * hgt, [&](int y0, int y1) {
+                    for (int y = band0 + y0; y < band0 + y1; ++y) {
+                        const uint8_t *sp = stg + (long long)y * rb;
+                        uint8_t *dp = const_cast<uint8_t *>(lo) + (long long)y * rb;
+                        if (wide) {
+                            for (int x = 0; x + 1 < w; ++x) {
+                                uint64_t u, v;
+                                std::memcpy(&u, dp + 8 * (size_t)x, 8); std::memcpy(&v, sp + 8 * (size_t)x, 8);
+                                u = (u & ~mask) | (v & mask);
+                                std::memcpy(dp + 8 * (size_t)x, &u, 8);
+                            }
+                        } else {
+                            const uint32_t m32 = (uint32_t)mask;
+                            for (int x = 0; x + 1 < w; ++x) {
+                                uint32_t u, v;
+                                std::memcpy(&u, dp + 4 * (size_t)x, 4); std::memcpy(&v, sp + 4 * (size_t)x, 4);
+                                u = (u & ~m32) | (v & m32);
+                                std::memcpy(dp + 4 * (size_t)x, &u, 4);
+                            }
+                        }
+                        // the row's last pixel sample by sample: its window would reach past the row
+                        const size_t last = (size_t)(w - 1) * (size_t)P0;
+                        for (int i = 0; i < S.n; ++i) {
+                            const int c = S.ch[i];
+                            const ptrdiff_t off = static_cast<const uint8_t *>(planes[c].base) - lo;
+                            std::memcpy(dp + last + off, sp + last + off, (size_t)oa.dst_bytes[c]);
+                        }
+                    }
+                });
+            }
+        } else {
+            HIP_CHECK(hipEventSynchronize(band_ev[ev0]));
+            for (int i = 0; i < S.n; ++i) {
+                const int c = S.ch[i];
+                uint8_t *ub = static_cast<uint8_t *>(planes[c].base);
+                const ptrdiff_t off = ub - lo;
+                const int w = oa.dst_w[c], hgt = oa.dst_h[c], sb = oa.dst_bytes[c];
+                const long long cb = oa.colbytes[c], rb = oa.rowbytes[c];
+                parallel_rows(hgt, (size_t)w * hgt, [&](int y0, int y1) {
+                    for (int y = y0; y < y1; ++y) {
+                        const uint8_t *sp = stg + off + (long long)y * rb;
+                        uint8_t *dp = ub + (long long)y * rb;
+                        if (cb == sb) std::memcpy(dp, sp, (size_t)w * sb); // a planar channel: the row is contiguous
+                        else if (sb == 1) for (int x = 0; x < w; ++x) dp[(long long)x * cb] = sp[(long long)x * cb];
+                        else for (int x = 0; x < w; ++x) std::memcpy(dp + (long long)x * cb, sp + (long long)x * cb, 2);
+                    }
+                });
+            }
+        }
+    }
+}
+
+// Waves of the lane-per-block kernel the chip holds at once (kernels.h): a group of a sequence call has at most this many.
+int lane_waves_resident()
+{
+    static const int w = t1_decode_lanes_resident_waves();
+    return w;
+}
+// a group's arenas (files, codewords, two plane sets, state / planes / masks, staged output) stay under this share of the
+// device memory that is free, counting what the handle's arenas hold already
+constexpr double kSeqMemoryShare = 0.5;
+unsigned plan_threads() { return std::max(1u, std::min(4u, std::thread::hardware_concurrency())); } // (encoder.cpp: the Tier-2 planner's)
+
+// One group: frames [first, first + nf) of the call, plans[0 .. nf) theirs.  file_uploaded: the (single) file is on its way to
+// d_file already and EV_START is recorded.  Adds to st.
+void decode_group(j2k_hip_encoder *e, const DecodeCall &call, const Shape &S, DecodePlan *plans, uint32_t first, uint32_t nf,
+                  const Decoding &decoding, bool file_uploaded, j2k_hip_stats &st)
+{
+    hipStream_t s = e->stream;
+    const FileHeader &H = plans[0].hdr;
+    const Coding &cod = H.cod;
+    const Geometry &g = plans[0].geo; // (one geometry, and one set of windows, for every frame)
+    const uint32_t reduce = S.reduce, R = S.R, nd = S.nd, nplanes = call.nplanes;
+    const size_t stride = S.stride, plane_elems = S.plane_elems, frame_words = S.frame_words();
+    const j2k_hip_rect *const region = call.region;
+
+    // ---- the frames' plans as one, and their files back to back on the device
+    std::vector<size_t> lens(nf);
+    for (uint32_t f = 0; f < nf; ++f) lens[f] = call.files[first + f].len;
+    MergedPlan M = merge_plans(plans, nf, lens.data(), frame_words);
+    if (!file_uploaded) {
+        HIP_CHECK(hipEventRecord(e->ev[EV_START], s));
+        e->d_file.ensure(M.file_bytes + 64);
+        for (uint32_t f = 0; f < nf; ++f)
+            HIP_CHECK(hipMemcpyAsync(e->d_file.as<uint8_t>() + M.frames[f].file_off, call.files[first + f].data, lens[f], hipMemcpyHostToDevice, s));
+    }
+    const size_t plane_bytes = frame_words * sizeof(int32_t) * nf;
+    e->Z.ensure(plane_bytes);
+    e->Q.ensure(plane_bytes);
+    e->geo_valid = false; e->seq_valid = false; // the encode path's cached geometry belongs to other planes
+
+    // ---- where every frame's samples go: the channels' geometry, their spans, and for host destinations the staged images
+    const int out_w = region ? (int)region->w : S.ow, out_h = region ? (int)region->h : S.oh;
+    const int org_x = region ? (int)region->x : 0, org_y = region ? (int)region->y : 0;
+    RgbaClass cls;
+    if (call.rgba) cls = classify_rgba(H);
+    std::vector<DecOutArgs> oas(nf);
+    std::vector<SpanLayout> lay(nf);
+    std::vector<OutComp> ocs((size_t)nf * 4);
+    size_t out_bytes = 0;
+    for (uint32_t f = 0; f < nf; ++f) {
+        const j2k_hip_outplane *planes = call.planes + (size_t)(first + f) * nplanes;
+        OutComp *oc = &ocs[(size_t)f * 4];
+        for (uint32_t c = 0; c < nd; ++c) oc[c] = OutComp{e->Z.as<int32_t>() + f * frame_words + c * plane_elems, cod.cprec[c], cod.cdx[c], cod.cdy[c]};
+        DecOutArgs &oa = oas[f];
+        if (call.rgba) { // the channels' geometry alone, for the spans: the RGBA kernel's arguments need the channels' device addresses
+            oa.nout = (int)nplanes;
+            for (int c = 0; c < oa.nout; ++c) {
+                const j2k_hip_outplane &p = planes[c];
+                oa.colbytes[c] = p.colbytes; oa.rowbytes[c] = p.rowbytes; oa.dst_bytes[c] = (int)p.sample_bits / 8;
+                oa.dst_w[c] = (int)std::min<uint32_t>(p.width, (uint32_t)out_w); oa.dst_h[c] = (int)std::min<uint32_t>(p.height, (uint32_t)out_h);
+            }
+        } else oa = decode_output_args(cod.reversible, cod.mct, out_w, out_h, (long long)stride, oc, nd, planes, nplanes, org_x, org_y);
         try {
-            P = fut.get();
-        } catch (...) {
-            (void)hipStreamSynchronize(s); // the copy reads the caller's buffer: not past the end of this call
+            lay[f] = layout_spans(oa, planes);
+        } catch (const Error &x) {
+            if (call.seq) throw FrameError(x.code, first + f, x.what());
             throw;
         }
-        HIP_CHECK(up);
-#ifdef J2K_DEC_TRACE
-        {
-            const double t_got = now_ms();
-            HIP_CHECK(hipEventSynchronize(tr_ev));
-            float ms = 0;
-            HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_START], tr_ev));
-            std::fprintf(stderr, "decode trace: memcpy call returned after %.2f ms, plan joined after %.2f ms, file on the device after %.2f ms (events), host now %.2f ms\n",
-                         t_issued - t_begin, t_got - t_begin, ms, now_ms() - t_begin);
+        if (!call.on_device) {
+            lay[f].base = round_up(out_bytes, 256);
+            out_bytes = lay[f].base + lay[f].dev_bytes;
         }
-#endif
-    } else {
-        P = plan_decode(fbytes, len, reduce, window);
-        HIP_CHECK(hipMemcpyAsync(e->d_file.p, fbytes, len, hipMemcpyHostToDevice, s));
     }
-    const FileHeader &H = P.hdr;
-    const Coding &cod = H.cod;
-    const Geometry &g = P.geo;
-    const double t_plan = now_ms();
-    const uint32_t R = cod.numres - 1 - reduce; // highest resolution decoded
-    // the image at the decoded resolution (opj_image_comp_header_update: both edges of the area are scaled, then subtracted)
-    int ow, oh;
-    reduced_size(cod, reduce, ow, oh);
-    if (ow <= 0 || oh <= 0) throw Error(J2K_HIP_ERR_PARAM, "Error reading file: nothing left of the image at this resolution");
-    // origin of every component's plane: the image area's origin on the component's grid at the decoded resolution
-    const uint32_t nd = cod.ncomp_out(); // components decoded: the first four (reference: min(numcomps, J2K_CODEC_MAX_CHANNELS), :278, :530)
-    int pox[4] = {0, 0, 0, 0}, poy[4] = {0, 0, 0, 0};
-    for (uint32_t c = 0; c < nd; ++c) {
-        pox[c] = ceildivpow2((int)((cod.img_x0 + cod.cdx[c] - 1) / cod.cdx[c]), (int)reduce);
-        poy[c] = ceildivpow2((int)((cod.img_y0 + cod.cdy[c] - 1) / cod.cdy[c]), (int)reduce);
+    if (!call.on_device) e->d_outimg.ensure(out_bytes + 16);
+    for (uint32_t f = 0; f < nf; ++f) {
+        const j2k_hip_outplane *planes = call.planes + (size_t)(first + f) * nplanes;
+        if (call.on_device) {
+            for (int c = 0; c < oas[f].nout; ++c) oas[f].dst[c] = static_cast<uint8_t *>(planes[c].base);
+            continue;
+        }
+        for (int k = 0; k < lay[f].nspans; ++k)
+            for (int i = 0; i < lay[f].spans[k].n; ++i) {
+                const int c = lay[f].spans[k].ch[i];
+                oas[f].dst[c] = e->d_outimg.as<uint8_t>() + lay[f].base + lay[f].spans[k].dev + (static_cast<const uint8_t *>(planes[c].base) - lay[f].spans[k].lo);
+            }
     }
-    const size_t stride = round_up((size_t)ow, 64), plane_elems = stride * (size_t)oh;
-    for (uint32_t c = 0; c < nplanes; ++c) {
-        if (!planes[c].base) throw Error(J2K_HIP_ERR_PARAM, "destination channel buffer is NULL");
-        check_outplane(planes[c]);
+    // the output stage's arguments (a sequence call: what the frames share, and the descriptor of each)
+    std::vector<DecRgbaArgs> ras;
+    std::vector<DecSeqFrameDev> desc(call.seq ? nf : 0);
+    if (call.rgba) {
+        ras.resize(nf);
+        for (uint32_t f = 0; f < nf; ++f) {
+            j2k_hip_rgba_dst d = call.rgba[first + f];
+            j2k_hip_outplane *const ch[4] = {&d.r, &d.g, &d.b, &d.a};
+            for (int c = 0; c < oas[f].nout; ++c) ch[c]->base = oas[f].dst[c];
+            RgbaComp rc[4] = {};
+            for (int c = 0; c < cls.ncomp; ++c) rc[c] = RgbaComp{ocs[(size_t)f * 4 + c].plane, ocs[(size_t)f * 4 + c].prec, ocs[(size_t)f * 4 + c].sub_x, ocs[(size_t)f * 4 + c].sub_y};
+            ras[f] = decode_rgba_args(cod.reversible, cod.mct, out_w, out_h, (long long)stride, rc, cls, d, nplanes == 4, org_x, org_y);
+        }
+        for (uint32_t f = 1; f < nf; ++f) // one record form for the launch: the packed one only where every frame has it, slots alike
+            if (!ras[f].packed || std::memcmp(ras[f].slot, ras[0].slot, sizeof ras[0].slot) != 0) ras[0].packed = 0;
+    }
+    for (uint32_t f = 0; f < nf && call.seq; ++f) {
+        DecSeqFrameDev &D = desc[f];
+        D = DecSeqFrameDev{};
+        D.comp_off = (unsigned long long)f * frame_words;
+        for (int c = 0; c < 4; ++c) {
+            if (call.rgba) {
+                D.dst[c] = ras[f].dst[c]; D.colbytes[c] = ras[f].colbytes[c]; D.rowbytes[c] = ras[f].rowbytes[c];
+                D.dst_w[c] = ras[f].dst_w[c]; D.dst_h[c] = ras[f].dst_h[c];
+            } else {
+                D.dst[c] = oas[f].dst[c]; D.colbytes[c] = oas[f].colbytes[c]; D.rowbytes[c] = oas[f].rowbytes[c];
+                D.dst_w[c] = oas[f].dst_w[c]; D.dst_h[c] = oas[f].dst_h[c];
+            }
+        }
+        if (call.rgba) { D.pix = ras[f].pix; D.pix_rowbytes = ras[f].pix_rowbytes; }
     }
 
     // ---- tables to the device
-    const size_t nb = P.blocks.size(), nseg = P.segs.size();
+    const size_t nb = M.blocks.size(), nseg = M.segs.size();
     // Tier-1 kernel.  A lane per block (t1_dec_lane.h): all its waves are resident at once, so the launch lasts as long as
     // its longest wave -- about 1.35 ms per coding pass of 64 x 64 blocks, whatever the number of blocks up to ~1000 waves.
     // A wave per block (t1_decode_kernel) runs a block's chain 3-4 times faster but is bound by the CUs' scalar units in
     // bulk: ~0.75 ns per codeword byte of the whole file.  Big files take the lanes, small ones the waves
-    // (t1dec_lanes: 1 = by these estimates, 2 = always lanes, 0 = never).
+    // (t1dec_lanes: 1 = by these estimates, 2 = always lanes, 0 = never).  The frames of a sequence call count as one file:
+    // their blocks share the launches, so the bulk estimate sees all their bytes and the lane estimate stays one launch's.
     uint64_t cw_bytes = 0;
     uint32_t most_passes = 0, most_rows = 0;
-    for (const DecBlock &b : P.blocks) {
+    for (const DecBlock &b : M.blocks) {
         cw_bytes += b.cw_len;
         most_passes = std::max(most_passes, b.npasses);
         most_rows = std::max<uint32_t>(most_rows, g.cblks[b.cblk].h);
@@ -241,21 +488,21 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     // (stable counting sorts of block indices: keys descending, ties in the order they came in)
     std::vector<uint32_t> order(nb), scratch(nb), count;
     for (size_t i = 0; i < nb; ++i) order[i] = (uint32_t)i;
-    auto sort_desc = [&](size_t first, uint32_t key_max, auto &&key_of) { // order[first..) by key_of(index) descending, 11 bits a pass
+    auto sort_desc = [&](size_t first_k, uint32_t key_max, auto &&key_of) { // order[first_k..) by key_of(index) descending, 11 bits a pass
         for (uint32_t shift = 0; shift < 32 && (shift == 0 || (key_max >> shift) != 0); shift += 11) {
             count.assign(2049, 0);
-            for (size_t k = first; k < nb; ++k) ++count[1 + (((key_max - key_of(order[k])) >> shift) & 2047u)];
+            for (size_t k = first_k; k < nb; ++k) ++count[1 + (((key_max - key_of(order[k])) >> shift) & 2047u)];
             for (size_t d = 0; d < 2048; ++d) count[d + 1] += count[d];
-            for (size_t k = first; k < nb; ++k) scratch[first + count[((key_max - key_of(order[k])) >> shift) & 2047u]++] = order[k];
-            std::copy(scratch.begin() + (ptrdiff_t)first, scratch.end(), order.begin() + (ptrdiff_t)first);
+            for (size_t k = first_k; k < nb; ++k) scratch[first_k + count[((key_max - key_of(order[k])) >> shift) & 2047u]++] = order[k];
+            std::copy(scratch.begin() + (ptrdiff_t)first_k, scratch.end(), order.begin() + (ptrdiff_t)first_k);
         }
     };
     size_t nheavy = 0;
     if (lanes) {
         uint32_t longest = 0;
-        for (const DecBlock &b : P.blocks) longest = std::max(longest, b.cw_len);
-        sort_desc(0, longest, [&](uint32_t i) { return P.blocks[i].cw_len; }); // longest codeword first
-        auto len_at = [&](size_t k) { return (double)P.blocks[order[k]].cw_len; };
+        for (const DecBlock &b : M.blocks) longest = std::max(longest, b.cw_len);
+        sort_desc(0, longest, [&](uint32_t i) { return M.blocks[i].cw_len; }); // longest codeword first
+        auto len_at = [&](size_t k) { return (double)M.blocks[order[k]].cw_len; };
         if (H.cblk_style != 0) nheavy = 0;
         else if (tuning().t1dec_tail >= 2) nheavy = std::min(nb, std::max<size_t>(1, nb / (size_t)tuning().t1dec_tail)); // (tests: a fixed share, whatever the sizes)
         else if (tuning().t1dec_tail && nb > 128 && decoding.count == 1) { // (frames in flight: nobody waits for one frame's tail, and a second
@@ -275,21 +522,22 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
             if (cost[0] <= 1.1 * best) nheavy = 0;                      // (a flat distribution: nothing worth a second launch)
         }
         // the lanes' blocks: most passes first (they are in the order of their codeword lengths already)
-        sort_desc(nheavy, most_passes, [&](uint32_t i) { return passes_of(P.blocks[i]); });
+        sort_desc(nheavy, most_passes, [&](uint32_t i) { return passes_of(M.blocks[i]); });
     }
     // masks of the wave-per-block kernel's blocks (all of them, or the tail beside the lanes)
     const size_t nwave = lanes ? nheavy : nb;
     std::vector<size_t> mask_off(nwave + 1, 0);
-    for (size_t k = 0; k < nwave; ++k) mask_off[k + 1] = mask_off[k] + (size_t)(P.blocks[order[k]].numbps + 1) * 64;
+    for (size_t k = 0; k < nwave; ++k) mask_off[k + 1] = mask_off[k] + (size_t)(M.blocks[order[k]].numbps + 1) * 64;
     const size_t mask_words = mask_off[nwave];
     const size_t nl = nb - nheavy;
     std::vector<DecGroupDev> groups(lanes ? (nl + 63) / 64 : 0);
 
-    // one pinned table: block table | groups | seg dst | seg src | seg len
+    // one pinned table: block table | groups | seg dst | seg src | seg len | codeword segments | frame descriptors
     const size_t grp_base = round_up(nb * sizeof(DecBlkDev), 16);
     const size_t seg_base = grp_base + round_up(groups.size() * sizeof(DecGroupDev), 16);
     const size_t cwseg_base = round_up(seg_base + nseg * (8 + 8 + 4), 16);
-    const size_t tab_bytes = cwseg_base + P.cwsegs.size() * sizeof(uint32_t) + 64;
+    const size_t desc_base = round_up(cwseg_base + M.cwsegs.size() * sizeof(uint32_t), 16);
+    const size_t tab_bytes = desc_base + desc.size() * sizeof(DecSeqFrameDev) + 64;
     e->h_dtab.ensure(tab_bytes);
     e->d_dblk.ensure(tab_bytes);
     uint8_t *ht = e->h_dtab.as<uint8_t>();
@@ -303,7 +551,7 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     for (size_t k = 0; k < nb; ++k) scratch[order[k]] = (uint32_t)k; // block -> its place in the table
     auto fill = [&](size_t i0, size_t i1) { // (blocks in the plan's order: the geometry is read front to back)
         for (size_t i = i0; i < i1; ++i) {
-            const DecBlock &b = P.blocks[i];
+            const DecBlock &b = M.blocks[i];
             const size_t k = scratch[i];
             const Cblk &c = g.cblks[b.cblk];
             const Tile &T = g.tiles[tile_pos[c.tile]];
@@ -313,8 +561,9 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
             d.mask_off = k < nwave ? mask_off[k] : 0;
             const TileComp &TC = T.comps[c.comp]; // (a sub-sampled component lives in the top-left part of its plane)
             const int tx = ceildivpow2(TC.x0, (int)reduce), ty = ceildivpow2(TC.y0, (int)reduce);
-            d.coef_off = (unsigned long long)c.comp * plane_elems + (unsigned long long)(ty - poy[c.comp] + (int)(c.py - (uint32_t)TC.y0)) * stride +
-                         (unsigned long long)(tx - pox[c.comp] + (int)(c.px - (uint32_t)TC.x0));
+            d.coef_off = M.frames[M.frame_of[i]].coef_off + (unsigned long long)c.comp * plane_elems +
+                         (unsigned long long)(ty - S.poy[c.comp] + (int)(c.py - (uint32_t)TC.y0)) * stride +
+                         (unsigned long long)(tx - S.pox[c.comp] + (int)(c.px - (uint32_t)TC.x0));
             d.stepsize = steps[c.comp][bandidx];
             d.w = c.w; d.h = c.h; d.orient = c.orient;
             d.numbps = (unsigned char)b.numbps;
@@ -334,16 +583,14 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     if (!groups.empty()) std::memcpy(ht + grp_base, groups.data(), groups.size() * sizeof(DecGroupDev));
     uint64_t *h_sdst = reinterpret_cast<uint64_t *>(ht + seg_base), *h_ssrc = h_sdst + nseg;
     uint32_t *h_slen = reinterpret_cast<uint32_t *>(h_ssrc + nseg);
-    for (size_t i = 0; i < nseg; ++i) { h_sdst[i] = P.segs[i].dst; h_ssrc[i] = P.segs[i].src; h_slen[i] = P.segs[i].len; }
-    if (!P.cwsegs.empty()) std::memcpy(ht + cwseg_base, P.cwsegs.data(), P.cwsegs.size() * sizeof(uint32_t));
-#ifdef J2K_DEC_TRACE
-    std::fprintf(stderr, "decode trace: tables built %.2f ms after the plan (%.2f ms into the call)\n", now_ms() - t_plan, now_ms() - t_begin);
-#endif
+    for (size_t i = 0; i < nseg; ++i) { h_sdst[i] = M.segs[i].dst; h_ssrc[i] = M.segs[i].src; h_slen[i] = M.segs[i].len; }
+    if (!M.cwsegs.empty()) std::memcpy(ht + cwseg_base, M.cwsegs.data(), M.cwsegs.size() * sizeof(uint32_t));
+    if (!desc.empty()) std::memcpy(ht + desc_base, desc.data(), desc.size() * sizeof(DecSeqFrameDev));
     HIP_CHECK(hipMemcpyAsync(e->d_dblk.p, ht, tab_bytes, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipEventRecord(e->ev[EV_UPLOAD], s));
 
     // ---- codeword arena
-    e->d_cw.ensure(P.arena_bytes + kCwArenaTail);
+    e->d_cw.ensure(M.arena_bytes + kCwArenaTail);
     if (nseg) {
         GatherArgs ga{};
         uint8_t *dt = e->d_dblk.as<uint8_t>();
@@ -357,10 +604,6 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     }
 
     // ---- Tier-1
-    const size_t plane_bytes = plane_elems * sizeof(int32_t) * nd;
-    e->Z.ensure(plane_bytes);
-    e->Q.ensure(plane_bytes);
-    e->geo_valid = false; e->seq_valid = false; // the encode path's cached geometry belongs to other planes
     HIP_CHECK(hipMemsetAsync(e->Z.p, 0, plane_bytes, s)); // blocks without data, bands of absent packets
     T1DecArgs ta{};
     ta.cw = e->d_cw.as<uint8_t>();
@@ -418,29 +661,30 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(e->ev[EV_T1], s));
 
-    // ---- inverse DWT: resolution 1 .. R
+    // ---- inverse DWT: resolution 1 .. R, every frame's tile-components as jobs of the same launches
     if (region) { // the windows of the tile-components the region meets, nothing else
         std::vector<IdwtWinJob> wjobs;
-        std::vector<size_t> first(R + 2, 0);
+        std::vector<size_t> first_job(R + 2, 0);
         std::vector<int> mh(R + 1, 0), mv(R + 1, 0);
         for (uint32_t r = 1; r <= R; ++r) {
-            first[r] = wjobs.size();
-            for (size_t t = 0; t < g.tiles.size(); ++t)
-                for (uint32_t c = 0; c < nd; ++c) {
-                    const std::vector<ResFootprint> &fp = P.windows[t * 4 + c];
-                    if (fp.empty() || fp[r].win.empty()) continue;
-                    const TileComp &TC = g.tiles[t].comps[c];
-                    const Resolution &Rs = TC.res[r];
-                    const long long off = (long long)c * (long long)plane_elems + (long long)(ceildivpow2(TC.y0, (int)reduce) - poy[c]) * (long long)stride +
-                                          (ceildivpow2(TC.x0, (int)reduce) - pox[c]);
-                    const IdwtWinJob j = window_job(IRect{Rs.x0, Rs.y0, Rs.x1, Rs.y1}, fp[r], off);
-                    int hi, vi;
-                    idwt_window_items(j, hi, vi);
-                    wjobs.push_back(j);
-                    mh[r] = std::max(mh[r], hi); mv[r] = std::max(mv[r], vi);
-                }
+            first_job[r] = wjobs.size();
+            for (uint32_t f = 0; f < nf; ++f)
+                for (size_t t = 0; t < g.tiles.size(); ++t)
+                    for (uint32_t c = 0; c < nd; ++c) {
+                        const std::vector<ResFootprint> &fp = plans[0].windows[t * 4 + c];
+                        if (fp.empty() || fp[r].win.empty()) continue;
+                        const TileComp &TC = g.tiles[t].comps[c];
+                        const Resolution &Rs = TC.res[r];
+                        const long long off = (long long)(f * frame_words) + (long long)c * (long long)plane_elems +
+                                              (long long)(ceildivpow2(TC.y0, (int)reduce) - S.poy[c]) * (long long)stride + (ceildivpow2(TC.x0, (int)reduce) - S.pox[c]);
+                        const IdwtWinJob j = window_job(IRect{Rs.x0, Rs.y0, Rs.x1, Rs.y1}, fp[r], off);
+                        int hi, vi;
+                        idwt_window_items(j, hi, vi);
+                        wjobs.push_back(j);
+                        mh[r] = std::max(mh[r], hi); mv[r] = std::max(mv[r], vi);
+                    }
         }
-        first[R + 1] = wjobs.size();
+        first_job[R + 1] = wjobs.size();
         if (!wjobs.empty()) {
             e->jobs.ensure(wjobs.size() * sizeof(IdwtWinJob));
             HIP_CHECK(hipMemcpyAsync(e->jobs.p, wjobs.data(), wjobs.size() * sizeof(IdwtWinJob), hipMemcpyHostToDevice, s));
@@ -448,7 +692,7 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
             for (uint32_t r = 1; r <= R; ++r) {
                 IdwtWinArgs ia{};
                 ia.a = e->Z.p; ia.tmp = e->Q.p; ia.stride = (long long)stride;
-                ia.jobs = e->jobs.as<IdwtWinJob>() + first[r]; ia.njobs = (int)(first[r + 1] - first[r]);
+                ia.jobs = e->jobs.as<IdwtWinJob>() + first_job[r]; ia.njobs = (int)(first_job[r + 1] - first_job[r]);
                 ia.max_h_items = mh[r]; ia.max_v_items = mv[r]; ia.reversible = cod.reversible;
                 launch_idwt_window_level(ia, s);
                 HIP_CHECK(hipGetLastError());
@@ -460,17 +704,18 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     std::vector<int> mrw(R + 1, 0), mrh(R + 1, 0);
     for (uint32_t r = 1; r <= R && !region; ++r) {
         job_first[r] = jobs.size();
-        for (const Tile &T : g.tiles)
-            for (uint32_t c = 0; c < nd; ++c) {
-                const Resolution &Rs = T.comps[c].res[r];
-                IdwtJob j{};
-                j.rw = Rs.x1 - Rs.x0; j.rh = Rs.y1 - Rs.y0; j.casx = Rs.x0 & 1; j.casy = Rs.y0 & 1;
-                if (j.rw <= 0 || j.rh <= 0) continue;
-                j.off = (long long)c * (long long)plane_elems + (long long)(ceildivpow2(T.comps[c].y0, (int)reduce) - poy[c]) * (long long)stride +
-                        (ceildivpow2(T.comps[c].x0, (int)reduce) - pox[c]);
-                jobs.push_back(j);
-                mrw[r] = std::max(mrw[r], j.rw); mrh[r] = std::max(mrh[r], j.rh);
-            }
+        for (uint32_t f = 0; f < nf; ++f)
+            for (const Tile &T : g.tiles)
+                for (uint32_t c = 0; c < nd; ++c) {
+                    const Resolution &Rs = T.comps[c].res[r];
+                    IdwtJob j{};
+                    j.rw = Rs.x1 - Rs.x0; j.rh = Rs.y1 - Rs.y0; j.casx = Rs.x0 & 1; j.casy = Rs.y0 & 1;
+                    if (j.rw <= 0 || j.rh <= 0) continue;
+                    j.off = (long long)(f * frame_words) + (long long)c * (long long)plane_elems +
+                            (long long)(ceildivpow2(T.comps[c].y0, (int)reduce) - S.poy[c]) * (long long)stride + (ceildivpow2(T.comps[c].x0, (int)reduce) - S.pox[c]);
+                    jobs.push_back(j);
+                    mrw[r] = std::max(mrw[r], j.rw); mrh[r] = std::max(mrh[r], j.rh);
+                }
     }
     job_first[R + 1] = jobs.size();
     if (!jobs.empty()) {
@@ -488,208 +733,228 @@ void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subs
     }
     HIP_CHECK(hipEventRecord(e->ev[EV_DWT], s));
 
-    // ---- output stage
-    OutComp oc[4] = {};
-    for (uint32_t c = 0; c < nd; ++c) oc[c] = OutComp{e->Z.as<int32_t>() + c * plane_elems, cod.cprec[c], cod.cdx[c], cod.cdy[c]};
-    const int out_w = region ? (int)region->w : ow, out_h = region ? (int)region->h : oh;
-    const int org_x = region ? (int)region->x : 0, org_y = region ? (int)region->y : 0;
-    DecOutArgs oa{};
-    RgbaClass cls;
-    if (rgba) { // the channels' geometry alone, for the spans below: the RGBA kernel's arguments need the channels' device addresses
-        cls = classify_rgba(H);
-        oa.nout = (int)nplanes;
-        for (int c = 0; c < oa.nout; ++c) {
-            const j2k_hip_outplane &p = planes[c];
-            oa.colbytes[c] = p.colbytes; oa.rowbytes[c] = p.rowbytes; oa.dst_bytes[c] = (int)p.sample_bits / 8;
-            oa.dst_w[c] = (int)std::min<uint32_t>(p.width, (uint32_t)out_w); oa.dst_h[c] = (int)std::min<uint32_t>(p.height, (uint32_t)out_h);
-        }
-    } else oa = decode_output_args(cod.reversible, cod.mct, out_w, out_h, (long long)stride, oc, nd, planes, nplanes, org_x, org_y);
-    auto launch_output = [&] { // (oa.dst[] hold the channels' device addresses by now)
-        if (!rgba) { launch_decode_output(oa, s); return; }
-        j2k_hip_rgba_dst d = *rgba;
-        j2k_hip_outplane *const ch[4] = {&d.r, &d.g, &d.b, &d.a};
-        for (int c = 0; c < oa.nout; ++c) ch[c]->base = oa.dst[c];
-        RgbaComp rc[4] = {};
-        for (int c = 0; c < cls.ncomp; ++c) rc[c] = RgbaComp{oc[c].plane, oc[c].prec, oc[c].sub_x, oc[c].sub_y};
-        launch_decode_rgba(decode_rgba_args(cod.reversible, cod.mct, out_w, out_h, (long long)stride, rc, cls, d, nplanes == 4, org_x, org_y), s);
-    };
-    // The destination channels' extents in the caller's address space.  Channels whose extents overlap (the samples of
-    // interleaved pixels) form one span that keeps its layout on the device; channels that lie apart (planar buffers,
-    // wherever they were allocated) are spans of their own.
-    struct Span { const uint8_t *lo, *hi; int ch[4]; int n; size_t dev; };
-    Span spans[4];
-    int nspans = 0;
-    {
-        struct Ext { const uint8_t *lo, *hi; int c; } ext[4];
-        int ne = 0;
-        for (int c = 0; c < oa.nout; ++c) {
-            const j2k_hip_outplane &p = planes[c];
-            if (oa.dst_w[c] <= 0 || oa.dst_h[c] <= 0) continue;
-            const uint8_t *b = static_cast<const uint8_t *>(p.base);
-            const uint8_t *corners[4] = {b, b + (ptrdiff_t)(oa.dst_h[c] - 1) * p.rowbytes, b + (ptrdiff_t)(oa.dst_w[c] - 1) * p.colbytes,
-                                         b + (ptrdiff_t)(oa.dst_h[c] - 1) * p.rowbytes + (ptrdiff_t)(oa.dst_w[c] - 1) * p.colbytes};
-            Ext x{corners[0], corners[0] + oa.dst_bytes[c], c};
-            for (const uint8_t *q : corners) { x.lo = std::min(x.lo, q); x.hi = std::max(x.hi, q + oa.dst_bytes[c]); }
-            ext[ne++] = x;
-        }
-        if (!ne) throw Error(J2K_HIP_ERR_PARAM, "no destination channel has any sample");
-        std::sort(ext, ext + ne, [](const Ext &x, const Ext &y) { return x.lo < y.lo; });
-        for (int i = 0; i < ne; ++i) {
-            if (nspans && ext[i].lo < spans[nspans - 1].hi) {
-                Span &S = spans[nspans - 1];
-                S.hi = std::max(S.hi, ext[i].hi); S.ch[S.n++] = ext[i].c;
-            } else {
-                Span &S = spans[nspans++];
-                S = Span{ext[i].lo, ext[i].hi, {ext[i].c, 0, 0, 0}, 1, 0};
-            }
-        }
-    }
-    if (planes_on_device) {
-        for (int c = 0; c < oa.nout; ++c) oa.dst[c] = static_cast<uint8_t *>(planes[c].base);
-        launch_output();
-        HIP_CHECK(hipGetLastError()); // a launch the runtime refused must not end as a frame of zeros
-        HIP_CHECK(hipEventRecord(e->ev[EV_GATHER], s));
-        HIP_CHECK(hipStreamSynchronize(s));
-    } else {
-        size_t dev_bytes = 0, max_span = 0;
-        for (int k = 0; k < nspans; ++k) { // (a span keeps its address modulo 256: the samples stay aligned as on the host)
-            spans[k].dev = round_up(dev_bytes, 256) + (reinterpret_cast<uintptr_t>(spans[k].lo) & 255);
-            dev_bytes = spans[k].dev + (size_t)(spans[k].hi - spans[k].lo);
-            max_span = std::max(max_span, (size_t)(spans[k].hi - spans[k].lo));
-        }
-        e->d_outimg.ensure(dev_bytes + 16);
-        for (int k = 0; k < nspans; ++k)
-            for (int i = 0; i < spans[k].n; ++i) {
-                const int c = spans[k].ch[i];
-                oa.dst[c] = e->d_outimg.as<uint8_t>() + spans[k].dev + (static_cast<const uint8_t *>(planes[c].base) - spans[k].lo);
-            }
-        launch_output();
-        HIP_CHECK(hipGetLastError()); // a launch the runtime refused must not end as a frame of zeros
-        HIP_CHECK(hipEventRecord(e->ev[EV_GATHER], s));
-        std::vector<hipEvent_t> band_ev;
-        struct EvGuard { std::vector<hipEvent_t> &v; ~EvGuard() { for (hipEvent_t x : v) if (x) (void)hipEventDestroy(x); } } ev_guard{band_ev};
+    // ---- output stage: a frame's own launch, or the sequence kernels' one launch for the group
+    if (call.seq) {
+        const DecSeqFrameDev *dd = reinterpret_cast<const DecSeqFrameDev *>(e->d_dblk.as<uint8_t>() + desc_base);
+        if (call.rgba) launch_decode_rgba_seq(ras[0], dd, (int)nf, s);
+        else launch_decode_output_seq(oas[0], dd, (int)nf, s);
+    } else if (call.rgba) launch_decode_rgba(ras[0], s);
+    else launch_decode_output(oas[0], s);
+    HIP_CHECK(hipGetLastError()); // a launch the runtime refused must not end as a frame of zeros
+    HIP_CHECK(hipEventRecord(e->ev[EV_GATHER], s));
+    if (!call.on_device) {
         bool staged = false;
-        for (int k = 0; k < nspans; ++k) {
-            const Span &S = spans[k];
-            const uint8_t *lo = S.lo;
-            const size_t span = (size_t)(S.hi - S.lo);
-            const uint8_t *dbase = e->d_outimg.as<uint8_t>() + S.dev;
-            const int c0 = S.ch[0];
-            // Do the span's channels cover every byte of it (interleaved pixels with every sample decoded, or one planar
-            // channel, no row padding)?  Then it goes straight into the host's buffer.  Otherwise only the channel samples
-            // may be written (the reference's CopyBuffer touches nothing else): through a staging copy.
-            bool same = true;
-            const long long P0 = oa.colbytes[c0];
-            long long covered = 0;
-            for (int i = 0; i < S.n; ++i) {
-                const int c = S.ch[i];
-                same = same && oa.colbytes[c] == P0 && oa.rowbytes[c] == oa.rowbytes[c0] && oa.dst_w[c] == oa.dst_w[c0] && oa.dst_h[c] == oa.dst_h[c0];
-                covered += oa.dst_bytes[c];
+        for (uint32_t f = 0; f < nf; ++f)
+            download_spans(e, oas[f], call.planes + (size_t)(first + f) * nplanes, lay[f], e->d_outimg.as<uint8_t>() + lay[f].base, staged, s);
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_START], e->ev[EV_UPLOAD])); st.ms_upload += ms;
+    HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_UPLOAD], e->ev[EV_T1])); st.ms_t1 += ms;
+    HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_T1], e->ev[EV_DWT])); st.ms_dwt += ms;
+    HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_DWT], e->ev[EV_GATHER])); st.ms_frontend += ms;
+    for (uint32_t f = 0; f < nf; ++f) st.codestream_bytes += lens[f];
+    st.num_codeblocks += nb;
+    e->dec_lane_blocks += nl * (lanes ? 1 : 0);
+    e->dec_wave_blocks += nwave;
+}
+
+// What a group of frames [a, b) needs on the device, from their plans: the waves of a lane launch and the bytes of its arenas
+// (an estimate from above: the lane kernel's state and planes AND the wave kernel's masks, whichever is taken).
+struct GroupNeed { size_t waves = 0, bytes = 0; };
+GroupNeed frame_need(const DecodePlan &P, size_t file_len, size_t frame_words, size_t out_bytes)
+{
+    GroupNeed n;
+    uint32_t most_passes = 1;
+    size_t mask_words = 0;
+    for (const DecBlock &b : P.blocks) {
+        most_passes = std::max(most_passes, b.npasses);
+        mask_words += (size_t)(b.numbps + 1) * 64;
+    }
+    n.waves = (P.blocks.size() + 63) / 64;
+    n.bytes = round_up(file_len, 64) + P.arena_bytes + 2 * frame_words * sizeof(int32_t) + out_bytes + mask_words * 8 +
+              n.waves * ((16 * 64 + 16 * 4) * 64 * sizeof(uint32_t) + (size_t)((most_passes + 1) / 3 + 1) * 16 * 8 * 64 * sizeof(uint32_t));
+    return n;
+}
+
+void decode_frames(j2k_hip_encoder *e, const DecodeCall &call)
+{
+    const double t_begin = now_ms();
+    const uint32_t n = call.nframes, nplanes = call.nplanes;
+    auto fail = [&](uint32_t f, int code, const std::string &m) {
+        if (call.seq) throw FrameError(code, f, m);
+        throw Error(code, m);
+    };
+    if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
+    if (!call.files || !n) fail(0, J2K_HIP_ERR_PARAM, "a sequence needs at least one frame");
+    for (uint32_t f = 0; f < n; ++f)
+        if (!call.files[f].data || !call.files[f].len) fail(f, J2K_HIP_ERR_PARAM, "Error reading file: empty input");
+    if (!call.planes || nplanes < 1 || nplanes > 4) throw Error(J2K_HIP_ERR_PARAM, "1..4 destination channels");
+    const uint32_t subsample = call.subsample ? call.subsample : 1;
+    const j2k_hip_rect *const region = call.region;
+    const uint32_t win[4] = {region ? region->x : 0, region ? region->y : 0, region ? region->w : 0, region ? region->h : 0};
+    const uint32_t *const window = region ? win : nullptr;
+    const uint32_t reduce = (uint32_t)floorlog2(subsample); // reference: params.cp_reduce = log2(subsample), :501
+    HIP_CHECK(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    auto bytes_of = [&](uint32_t f) { return static_cast<const uint8_t *>(call.files[f].data); };
+    const Decoding decoding(e->device); // (counted for the length of the call: the frames of a sequence are one decode in flight)
+
+    // ---- every frame's headers are read first: a file this path cannot decode, or a frame that cannot share the launches of
+    // frame 0, is turned away before the device is touched.
+    Coding cod0;
+    {
+        FileHeader first_hdr;
+        for (uint32_t f = 0; f < n; ++f) {
+            FileHeader early;
+            try {
+                early = parse_headers(bytes_of(f), call.files[f].len);
+                if (call.rgba) (void)classify_rgba(early); // (a file the fused path does not take: J2K_HIP_ERR_UNSUPPORTED, nothing written)
+            } catch (const Error &x) {
+                if (call.seq) throw FrameError(x.code, f, x.what());
+                throw;
             }
-            const bool full = same && P0 > 0 && covered == P0 && oa.rowbytes[c0] == P0 * oa.dst_w[c0] && span == (size_t)(oa.rowbytes[c0] * oa.dst_h[c0]);
-            if (full) {
-                HIP_CHECK(hipMemcpyAsync(const_cast<uint8_t *>(lo), dbase, span, hipMemcpyDeviceToHost, s));
-                continue;
-            }
-            if (staged) HIP_CHECK(hipStreamSynchronize(s)); // (the staging buffer is one span's at a time)
-            staged = true;
-            e->h_outimg.ensure(max_span + 16);
-            const uint8_t *stg = e->h_outimg.as<uint8_t>();
-            // Two layouts get whole-word copies: the channels of one interleaved pixel of 4 or 8 bytes (After Effects'
-            // ARGB32 / ARGB64 with R, G, B decoded and A kept: one masked word per pixel) and planar rows.
-            bool pixels = same && (P0 == 4 || P0 == 8) && oa.rowbytes[c0] > 0;
-            // a pixel-sized window starting at the lowest channel's sample holds one sample of every channel (its remaining
-            // bytes belong to samples that are not decoded: they pass through)
-            uint64_t mask = 0;
-            for (int i = 0; i < S.n && pixels; ++i) {
-                const int c = S.ch[i];
-                const ptrdiff_t off = static_cast<const uint8_t *>(planes[c].base) - lo;
-                pixels = off >= 0 && off + oa.dst_bytes[c] <= P0;
-                if (pixels) mask |= (oa.dst_bytes[c] == 1 ? 0xffull : 0xffffull) << (8 * off);
-            }
-            // The download comes in row bands; the host merges band k while band k + 1 is on its way (a frame of pixels:
-            // the rows of the span in order; other layouts: one piece).
-            const int bands = pixels ? (int)std::max<size_t>(1, std::min<size_t>({(size_t)8, span >> 25, (size_t)oa.dst_h[c0]})) : 1;
-            auto band_row = [&](int b) { return (int)((long long)oa.dst_h[c0] * b / bands); };
-            const size_t ev0 = band_ev.size();
-            for (int b = 0; b < bands; ++b) {
-                const size_t b0 = bands > 1 ? (size_t)band_row(b) * (size_t)oa.rowbytes[c0] : 0;
-                const size_t b1 = (bands > 1 && b + 1 < bands) ? (size_t)band_row(b + 1) * (size_t)oa.rowbytes[c0] : span;
-                HIP_CHECK(hipMemcpyAsync(e->h_outimg.as<uint8_t>() + b0, dbase + b0, b1 - b0, hipMemcpyDeviceToHost, s));
-                band_ev.push_back(nullptr);
-                HIP_CHECK(hipEventCreateWithFlags(&band_ev.back(), hipEventDisableTiming));
-                HIP_CHECK(hipEventRecord(band_ev.back(), s));
-            }
-            if (pixels) {
-                const int w = oa.dst_w[c0];
-                const long long rb = oa.rowbytes[c0];
-                const bool wide = P0 == 8;
-                for (int b = 0; b < bands; ++b) {
-                    const int band0 = band_row(b), hgt = band_row(b + 1) - band0;
-                    HIP_CHECK(hipEventSynchronize(band_ev[ev0 + (size_t)b]));
-                    parallel_rows(hgt, (size_t)w * hgt, [&](int y0, int y1) {
-                        for (int y = band0 + y0; y < band0 + y1; ++y) {
-                            const uint8_t *sp = stg + (long long)y * rb;
-                            uint8_t *dp = const_cast<uint8_t *>(lo) + (long long)y * rb;
-                            if (wide) {
-                                for (int x = 0; x + 1 < w; ++x) {
-                                    uint64_t u, v;
-                                    std::memcpy(&u, dp + 8 * (size_t)x, 8); std::memcpy(&v, sp + 8 * (size_t)x, 8);
-                                    u = (u & ~mask) | (v & mask);
-                                    std::memcpy(dp + 8 * (size_t)x, &u, 8);
-                                }
-                            } else {
-                                const uint32_t m32 = (uint32_t)mask;
-                                for (int x = 0; x + 1 < w; ++x) {
-                                    uint32_t u, v;
-                                    std::memcpy(&u, dp + 4 * (size_t)x, 4); std::memcpy(&v, sp + 4 * (size_t)x, 4);
-                                    u = (u & ~m32) | (v & m32);
-                                    std::memcpy(dp + 4 * (size_t)x, &u, 4);
-                                }
-                            }
-                            // the row's last pixel sample by sample: its window would reach past the row
-                            const size_t last = (size_t)(w - 1) * (size_t)P0;
-                            for (int i = 0; i < S.n; ++i) {
-                                const int c = S.ch[i];
-                                const ptrdiff_t off = static_cast<const uint8_t *>(planes[c].base) - lo;
-                                std::memcpy(dp + last + off, sp + last + off, (size_t)oa.dst_bytes[c]);
-                            }
-                        }
-                    });
+            if (f == 0) { cod0 = early.cod; if (n > 1) first_hdr = std::move(early); continue; }
+            const std::string why = frames_differ(first_hdr, early, call.rgba != nullptr);
+            if (!why.empty()) throw FrameError(J2K_HIP_ERR_PARAM, f, "differs from frame 0 in its " + why + ": the frames of a sequence call share their launches");
+        }
+    }
+    // The destinations.  (One frame: after its plan, in the order of every decode before sequences.  A sequence: before any
+    // device work, with what the frames' channels must share.)
+    auto check_destinations = [&] {
+        for (uint32_t f = 0; f < n; ++f)
+            for (uint32_t c = 0; c < nplanes; ++c) {
+                const j2k_hip_outplane &p = call.planes[(size_t)f * nplanes + c];
+                try {
+                    if (!p.base) throw Error(J2K_HIP_ERR_PARAM, "destination channel buffer is NULL");
+                    check_outplane(p);
+                } catch (const Error &x) {
+                    if (call.seq) throw FrameError(x.code, f, x.what());
+                    throw;
                 }
+                if (p.sample_bits != call.planes[c].sample_bits || p.depth != call.planes[c].depth)
+                    throw FrameError(J2K_HIP_ERR_PARAM, f, "channel " + std::to_string(c) + " differs from frame 0's in sample_bits or depth");
+            }
+        for (uint32_t f = 1; f < n && call.rgba; ++f)
+            if (!call.rgba[f].demote_ae16 != !call.rgba[0].demote_ae16) throw FrameError(J2K_HIP_ERR_PARAM, f, "demote_ae16 differs from frame 0's");
+    };
+    Shape S;
+    if (call.seq) {
+        try {
+            if (reduce >= cod0.numres) throw Error(J2K_HIP_ERR_PARAM, "Error reading file: cannot discard " + std::to_string(reduce) + " of " + std::to_string(cod0.numres) + " resolutions");
+            S = frame_shape(cod0, reduce);
+            if (region && (!region->w || !region->h || (uint64_t)region->x + region->w > (uint64_t)S.ow || (uint64_t)region->y + region->h > (uint64_t)S.oh))
+                throw Error(J2K_HIP_ERR_PARAM, "region (" + std::to_string(region->x) + ", " + std::to_string(region->y) + ", " + std::to_string(region->w) + " x " +
+                                                   std::to_string(region->h) + ") is empty or leaves the image of " + std::to_string(S.ow) + " x " + std::to_string(S.oh));
+        } catch (const Error &x) {
+            throw FrameError(x.code, 0, x.what());
+        }
+        check_destinations();
+    }
+
+    // ---- host Tier-2.  One frame: beside the upload of the file (the device needs nothing of the plan to receive the bytes).
+    // Several: on a few host threads, all frames before the first group is cut -- a frame whose packets turn out malformed
+    // fails the call when its group is reached, the groups before it are complete by then.
+    j2k_hip_stats st{};
+    e->dec_lane_blocks = e->dec_wave_blocks = 0;
+    std::vector<DecodePlan> plans(n);
+    std::vector<std::exception_ptr> plan_err(n);
+    bool file_uploaded = false;
+    if (n == 1) {
+        const uint8_t *fbytes = bytes_of(0);
+        const size_t len = call.files[0].len;
+        HIP_CHECK(hipEventRecord(e->ev[EV_START], s));
+        e->d_file.ensure(len + 64);
+        file_uploaded = true;
+        try {
+            if (len >= (4u << 20)) {
+                auto fut = std::async(std::launch::async, [&] { return plan_decode(fbytes, len, reduce, window); });
+                const hipError_t up = hipMemcpyAsync(e->d_file.p, fbytes, len, hipMemcpyHostToDevice, s);
+                try {
+                    plans[0] = fut.get();
+                } catch (...) {
+                    (void)hipStreamSynchronize(s); // the copy reads the caller's buffer: not past the end of this call
+                    throw;
+                }
+                HIP_CHECK(up);
             } else {
-                HIP_CHECK(hipEventSynchronize(band_ev[ev0]));
-                for (int i = 0; i < S.n; ++i) {
-                    const int c = S.ch[i];
-                    uint8_t *ub = static_cast<uint8_t *>(planes[c].base);
-                    const ptrdiff_t off = ub - lo;
-                    const int w = oa.dst_w[c], hgt = oa.dst_h[c], sb = oa.dst_bytes[c];
-                    const long long cb = oa.colbytes[c], rb = oa.rowbytes[c];
-                    parallel_rows(hgt, (size_t)w * hgt, [&](int y0, int y1) {
-                        for (int y = y0; y < y1; ++y) {
-                            const uint8_t *sp = stg + off + (long long)y * rb;
-                            uint8_t *dp = ub + (long long)y * rb;
-                            if (cb == sb) std::memcpy(dp, sp, (size_t)w * sb); // a planar channel: the row is contiguous
-                            else if (sb == 1) for (int x = 0; x < w; ++x) dp[(long long)x * cb] = sp[(long long)x * cb];
-                            else for (int x = 0; x < w; ++x) std::memcpy(dp + (long long)x * cb, sp + (long long)x * cb, 2);
-                        }
-                    });
-                }
+                plans[0] = plan_decode(fbytes, len, reduce, window);
+                HIP_CHECK(hipMemcpyAsync(e->d_file.p, fbytes, len, hipMemcpyHostToDevice, s));
+            }
+        } catch (const Error &x) {
+            if (call.seq && !dynamic_cast<const FrameError *>(&x)) throw FrameError(x.code, 0, x.what());
+            throw;
+        }
+    } else {
+        std::atomic<uint32_t> next{0};
+        auto work = [&] {
+            for (uint32_t f; (f = next.fetch_add(1)) < n;) {
+                try { plans[f] = plan_decode(bytes_of(f), call.files[f].len, reduce, window); }
+                catch (...) { plan_err[f] = std::current_exception(); }
+            }
+        };
+        const unsigned nt = std::min<unsigned>(plan_threads(), n);
+        std::vector<std::thread> th;
+        for (unsigned t = 1; t < nt; ++t) th.emplace_back(work);
+        work();
+        for (auto &t : th) t.join();
+    }
+    const double t_plan = now_ms();
+    if (!call.seq) {
+        S = frame_shape(plans[0].hdr.cod, reduce);
+        check_destinations();
+    }
+
+    // ---- groups of consecutive frames.  A group's lane waves fit the waves the chip holds at once (so its lane launch still
+    // lasts as long as its longest wave) and its arenas a share of the free device memory; decseq_group caps the frames.
+    // One frame is always a group; a frame whose plan failed starts a group, so that every frame before it is delivered.
+    size_t budget = ~(size_t)0;
+    const size_t waves_max = (size_t)std::max(lane_waves_resident(), 1);
+    if (n > 1) {
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        const size_t held = e->d_file.cap + e->d_cw.cap + e->Z.cap + e->Q.cap + e->d_masks.cap + e->d_outimg.cap;
+        budget = (size_t)(kSeqMemoryShare * (double)(free_b + held));
+    }
+    const int cap = tuning().decseq_group;
+    for (uint32_t first = 0; first < n;) {
+        auto rethrow = [&](uint32_t f) {
+            try { std::rethrow_exception(plan_err[f]); }
+            catch (const Error &x) { throw FrameError(x.code, f, x.what()); }
+            catch (const std::bad_alloc &) { throw; }
+            catch (const std::exception &x) { throw FrameError(J2K_HIP_ERR_PARAM, f, x.what()); }
+        };
+        if (plan_err[first]) rethrow(first);
+        uint32_t nf = 1;
+        if (n > 1) {
+            auto out_bytes_of = [&](uint32_t f) {
+                size_t b = 0;
+                if (!call.on_device)
+                    for (uint32_t c = 0; c < nplanes; ++c) {
+                        const j2k_hip_outplane &p = call.planes[(size_t)f * nplanes + c];
+                        b += (size_t)std::llabs((long long)p.rowbytes) * std::min<uint32_t>(p.height, (uint32_t)S.oh) + 512;
+                    }
+                return b;
+            };
+            GroupNeed need = frame_need(plans[first], call.files[first].len, S.frame_words(), out_bytes_of(first));
+            for (; first + nf < n && !plan_err[first + nf] && (cap <= 0 || nf < (uint32_t)cap); ++nf) {
+                const GroupNeed more = frame_need(plans[first + nf], call.files[first + nf].len, S.frame_words(), out_bytes_of(first + nf));
+                if (cap <= 0 && (need.waves + more.waves > waves_max || need.bytes + more.bytes > budget)) break;
+                if (cap > 0 && need.bytes + more.bytes > budget) break;
+                need.waves += more.waves; need.bytes += more.bytes;
             }
         }
-        HIP_CHECK(hipStreamSynchronize(s));
+        try {
+            decode_group(e, call, S, plans.data() + first, first, nf, decoding, file_uploaded, st);
+        } catch (const Error &x) {
+            if (call.seq && !dynamic_cast<const FrameError *>(&x)) throw FrameError(x.code, first, x.what());
+            throw;
+        }
+        first += nf;
     }
-    j2k_hip_stats &st = e->stats;
-    st = j2k_hip_stats{};
-    float ms = 0;
-    HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_START], e->ev[EV_UPLOAD])); st.ms_upload = ms;
-    HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_UPLOAD], e->ev[EV_T1])); st.ms_t1 = ms;
-    HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_T1], e->ev[EV_DWT])); st.ms_dwt = ms;
-    HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_DWT], e->ev[EV_GATHER])); st.ms_frontend = ms;
     st.ms_t2_host = t_plan - t_begin;
-    st.codestream_bytes = len;
-    st.num_codeblocks = nb;
     st.ms_total = now_ms() - t_begin;
+    e->stats = st;
 }
 
 // The resolutions of one plane of width x height at origin (x0, y0) with `levels` decompositions, lowest first, and the
@@ -708,6 +973,14 @@ std::vector<ResFootprint> plane_footprints(bool reversible, uint32_t width, uint
     return region_footprints(res.data(), levels + 1, reversible, w);
 }
 
+// One frame through decode_frames: the single-frame entry points.
+void decode_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_outplane *planes,
+                 uint32_t nplanes, bool planes_on_device, const j2k_hip_rect *region = nullptr, const j2k_hip_rgba_dst *rgba = nullptr)
+{
+    const j2k_hip_file one{file, len};
+    decode_frames(e, DecodeCall{&one, 1, subsample, region, planes, nplanes, rgba, planes_on_device, false});
+}
+
 // j2k_hip_decode_rgba[_device]: the destination is checked before anything else happens, then the decode above runs with
 // R, G, B[, A] as its channels and the RGBA kernel as its last launch.
 void decode_rgba_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t subsample, const j2k_hip_rect *region,
@@ -720,6 +993,36 @@ void decode_rgba_impl(j2k_hip_encoder *e, const void *file, size_t len, uint32_t
     check_rgba_dst(*dst, alpha);
     const j2k_hip_outplane planes[4] = {dst->r, dst->g, dst->b, dst->a};
     decode_impl(e, file, len, subsample, planes, alpha ? 4 : 3, on_device, region, dst);
+}
+
+// j2k_hip_decode_sequence[_device] and the RGBA forms: every refusal that needs no plan happens in decode_frames before any
+// device work (the frames' destinations are checked here first, like the single-frame RGBA call does).
+void decode_sequence_impl(j2k_hip_encoder *e, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample, const j2k_hip_rect *region,
+                          const j2k_hip_outplane *planes, uint32_t nplanes, bool on_device)
+{
+    decode_frames(e, DecodeCall{files, nframes, subsample, region, planes, nplanes, nullptr, on_device, true});
+}
+void decode_rgba_sequence_impl(j2k_hip_encoder *e, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample, const j2k_hip_rect *region,
+                               const j2k_hip_rgba_dst *dsts, bool on_device)
+{
+    if (!files || !nframes) throw FrameError(J2K_HIP_ERR_PARAM, 0, "a sequence needs at least one frame");
+    if (!dsts) throw Error(J2K_HIP_ERR_PARAM, "no RGBA destination");
+    const bool alpha = dsts[0].a.base != nullptr;
+    std::vector<j2k_hip_outplane> planes((size_t)nframes * 4);
+    for (uint32_t f = 0; f < nframes; ++f) {
+        const j2k_hip_rgba_dst &d = dsts[f];
+        try {
+            if (d.struct_size != sizeof(j2k_hip_rgba_dst)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_rgba_dst.struct_size mismatch (ABI drift)");
+            if (!d.r.base || !d.g.base || !d.b.base) throw Error(J2K_HIP_ERR_PARAM, "destination channel buffer is NULL");
+            if ((d.a.base != nullptr) != alpha) throw Error(J2K_HIP_ERR_PARAM, "an alpha destination in some frames only");
+            check_rgba_dst(d, alpha);
+        } catch (const Error &x) {
+            throw FrameError(x.code, f, x.what());
+        }
+        const j2k_hip_outplane ch[4] = {d.r, d.g, d.b, d.a};
+        for (int c = 0; c < (alpha ? 4 : 3); ++c) planes[(size_t)f * (alpha ? 4 : 3) + c] = ch[c];
+    }
+    decode_frames(e, DecodeCall{files, nframes, subsample, region, planes.data(), alpha ? 4u : 3u, dsts, on_device, true});
 }
 
 } // namespace
@@ -816,6 +1119,67 @@ int j2k_hip_decode_region_device(j2k_hip_encoder *e, const void *file, size_t le
 {
     if (!e) return J2K_HIP_ERR_PARAM;
     return guarded(e, [&] { decode_impl(e, file, len, subsample, planes, nplanes, true, region); });
+}
+
+int j2k_hip_decode_sequence_check(const j2k_hip_file *files, uint32_t nframes, uint32_t *bad_frame)
+{
+    if (bad_frame) *bad_frame = 0;
+    auto failed = [&](int code, uint32_t f, const std::string &text) {
+        if (bad_frame) *bad_frame = f;
+        create_error() = "frame " + std::to_string(f) + ": " + text;
+        return code;
+    };
+    if (!files || !nframes) return failed(J2K_HIP_ERR_PARAM, 0, "a sequence needs at least one frame");
+    FileHeader first;
+    for (uint32_t f = 0; f < nframes; ++f) {
+        try {
+            if (!files[f].data || !files[f].len) throw Error(J2K_HIP_ERR_PARAM, "Error reading file: empty input");
+            FileHeader H = parse_headers(static_cast<const uint8_t *>(files[f].data), files[f].len);
+            if (f == 0) { first = std::move(H); continue; }
+            const std::string why = frames_differ(first, H, false);
+            if (!why.empty()) return failed(J2K_HIP_ERR_PARAM, f, "differs from frame 0 in its " + why + ": the frames of a sequence call share their launches");
+        } catch (const Error &x) {
+            return failed(x.code, f, x.what());
+        } catch (const std::exception &x) {
+            return failed(J2K_HIP_ERR_PARAM, f, x.what());
+        }
+    }
+    return J2K_HIP_OK;
+}
+
+int j2k_hip_decode_sequence(j2k_hip_encoder *e, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample, const j2k_hip_rect *region,
+                            const j2k_hip_outplane *planes, uint32_t nplanes)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] { decode_sequence_impl(e, files, nframes, subsample, region, planes, nplanes, false); });
+}
+
+int j2k_hip_decode_sequence_device(j2k_hip_encoder *e, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample,
+                                   const j2k_hip_rect *region, const j2k_hip_outplane *planes, uint32_t nplanes)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] { decode_sequence_impl(e, files, nframes, subsample, region, planes, nplanes, true); });
+}
+
+int j2k_hip_decode_rgba_sequence(j2k_hip_encoder *e, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample,
+                                 const j2k_hip_rect *region, const j2k_hip_rgba_dst *dsts)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] { decode_rgba_sequence_impl(e, files, nframes, subsample, region, dsts, false); });
+}
+
+int j2k_hip_decode_rgba_sequence_device(j2k_hip_encoder *e, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample,
+                                        const j2k_hip_rect *region, const j2k_hip_rgba_dst *dsts)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] { decode_rgba_sequence_impl(e, files, nframes, subsample, region, dsts, true); });
+}
+
+int j2k_hip_debug_decode_kernels(const j2k_hip_encoder *e, uint64_t *lane_blocks, uint64_t *wave_blocks)
+{
+    if (!e || !lane_blocks || !wave_blocks) return J2K_HIP_ERR_PARAM;
+    *lane_blocks = e->dec_lane_blocks; *wave_blocks = e->dec_wave_blocks;
+    return J2K_HIP_OK;
 }
 
 int j2k_hip_region_footprint(int reversible, uint32_t width, uint32_t height, uint32_t levels, uint32_t x0, uint32_t y0,

@@ -192,6 +192,7 @@ struct j2k_hip_encoder {
     // decode path (decoder.cpp): the file on the device, per-block codeword arena, bit-plane masks, block table, output staging
     j2k_hip::DevBuf d_file, d_cw, d_masks, d_dblk, d_segs, d_outimg;
     j2k_hip::PinnedBuf h_outimg, h_dtab;
+    uint64_t dec_lane_blocks = 0, dec_wave_blocks = 0; // of the last decode call: blocks the lane kernel took / the wave kernel
 };
 
 namespace j2k_hip {

@@ -310,6 +310,28 @@ __global__ __launch_bounds__(256) void decode_output_kernel(DecOutArgs a)
     }
 }
 
+// The same stage for the frames of a sequence decode: frame = blockIdx.z.  What the frames share arrives as the kernel's
+// arguments; the frame's own descriptor (kernels.h: DecSeqFrameDev) is read from the table at a wave-uniform address -- scalar
+// loads, once per workgroup -- into the argument struct's copy, and the pixels are decode_output_kernel's through out_sample.h.
+template <bool REV>
+__global__ __launch_bounds__(256) void decode_output_seq_kernel(DecOutArgs a, const DecSeqFrameDev *__restrict__ frames)
+{
+    const DecSeqFrameDev &F = frames[blockIdx.z];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        a.comp[c] = reinterpret_cast<const unsigned *>(a.comp[c]) + F.comp_off;
+        a.dst[c] = F.dst[c]; a.colbytes[c] = F.colbytes[c]; a.rowbytes[c] = F.rowbytes[c];
+        a.dst_w[c] = F.dst_w[c]; a.dst_h[c] = F.dst_h[c];
+    }
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= a.width) return;
+    for (int y = blockIdx.y; y < a.height; y += gridDim.y) {
+        int v[4];
+        component_samples<REV>(a, x, y, v);
+        store_channels(a, x, y, v);
+    }
+}
+
 } // namespace
 
 void launch_idwt_level(const IdwtArgs &a, hipStream_t s)
@@ -354,6 +376,14 @@ void launch_decode_output(const DecOutArgs &a, hipStream_t s)
     const dim3 grid((unsigned)((a.width + 255) / 256), (unsigned)std::min(a.height, 65535), 1);
     if (a.reversible) hipLaunchKernelGGL(decode_output_kernel<true>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(decode_output_kernel<false>, grid, dim3(256), 0, s, a);
+}
+
+void launch_decode_output_seq(const DecOutArgs &a, const DecSeqFrameDev *frames, int nframes, hipStream_t s)
+{
+    if (a.width <= 0 || a.height <= 0 || nframes <= 0) return;
+    const dim3 grid((unsigned)((a.width + 255) / 256), (unsigned)std::min(a.height, 65535), (unsigned)nframes);
+    if (a.reversible) hipLaunchKernelGGL(decode_output_seq_kernel<true>, grid, dim3(256), 0, s, a, frames);
+    else hipLaunchKernelGGL(decode_output_seq_kernel<false>, grid, dim3(256), 0, s, a, frames);
 }
 
 } // namespace j2k_hip

@@ -40,6 +40,7 @@ struct Tuning {
     int dwt_xcd = 1;        // XCD-aware block -> (strip, chunk) map: the strips of one chunk share an XCD (one L2)
     int t1dec_tail = 1;     // lane-per-block decode: the heaviest blocks go to the wave-per-block kernel on a second stream (0: never)
     int t1dec_lanes = 1;    // decode Tier-1: 2 = a lane per code-block (64 blocks per wave), 0 = a wave per block, 1 = by file size (decoder.cpp)
+    int decseq_group = 0;   // sequence decode: frames per group of shared launches; 0 = by resident lane waves and free memory, n = at most n (tests, A/B)
     // Band-pipelined encode of host frames (bands.h): the frame goes up in row bands, DWT level 1 and the Tier-1 of finished
     // bands run while the next band is on its way, finished stages come down while later ones are coded.  0 = by frame size
     // (off below 16 MiB of frame), -1 = never, n >= 1 = n bands whatever the size (1: the same machinery with one band)
@@ -265,6 +266,10 @@ struct T1DecArgs {
 // cw_off is 16-byte aligned and 256 readable bytes follow a block's last byte (decode_plan.h: the codeword arena).
 void launch_t1_decode(const T1DecArgs &a, hipStream_t s);
 void launch_t1_decode_lanes(const T1DecArgs &a, hipStream_t s);
+// Waves of t1_decode_lanes_kernel the current device holds at once: workgroups per CU by the kernel's registers and LDS AS
+// BUILT (read from the code object through the runtime's occupancy query) times the CU count.  A lane launch of up to this
+// many waves lasts as long as its longest wave; a sequence decode sizes its groups of frames by it.  0: the query failed.
+int t1_decode_lanes_resident_waves();
 
 // Inverse DWT, one resolution per call: horizontal synthesis a -> tmp, then vertical synthesis tmp -> a, for
 // every job (tile-component region of this resolution, Mallat layout in, samples out, in place).
@@ -331,6 +336,22 @@ void launch_decode_output(const DecOutArgs &a, hipStream_t s);
 // and its preconditions are in rgba_plan.h (no HIP types: the function that fills it, decode_rgba_args, is host code that
 // is also built and run on its own).
 void launch_decode_rgba(const DecRgbaArgs &a, hipStream_t s);
+
+// Both output stages for the frames of a sequence decode in one launch (decode_output_seq_kernel, idwt.hip;
+// decode_rgba_seq_kernel, rgba_out.hip): frame = blockIdx.z.  `a` holds what the frames share and, in comp[], frame 0's
+// component planes; what differs per frame comes from a table in device memory, read once per workgroup by wave-uniform
+// (scalar) loads: the frame's planes lie comp_off words behind frame 0's, its channels are dst / colbytes / rowbytes /
+// dst_w / dst_h (as in DecOutArgs; RGBA: R, G, B, A, dst[c] == nullptr: not written), its pixel records of the packed RGBA
+// form start at pix.  The preconditions of DecOutArgs / DecRgbaArgs hold for every frame; the packed form only when every
+// frame's channels form records with the same slots.  Frames whose destinations overlap give undefined samples.
+struct DecSeqFrameDev {
+    unsigned long long comp_off;
+    uint8_t *dst[4]; long long colbytes[4], rowbytes[4];
+    int dst_w[4], dst_h[4];
+    uint8_t *pix; long long pix_rowbytes;
+};
+void launch_decode_output_seq(const DecOutArgs &a, const DecSeqFrameDev *frames, int nframes, hipStream_t s);
+void launch_decode_rgba_seq(const DecRgbaArgs &a, const DecSeqFrameDev *frames, int nframes, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Codestream assembly: copies header pieces and code-block segments to their final offsets.

@@ -1,6 +1,7 @@
-// out_sample.h -- what the decode's two output kernels share (idwt.hip: decode_output_kernel, rgba_out.hip:
-// decode_rgba_kernel): CopyChannel's depth conversion and the saturating rounding; and the RGBA kernel's component samples,
-// decode_output_kernel's own lines as a function (that kernel keeps its text).  Device code only.
+// out_sample.h -- what the decode's output kernels share (idwt.hip: decode_output_kernel, rgba_out.hip:
+// decode_rgba_kernel, and the sequence forms of both): CopyChannel's depth conversion and the saturating rounding; the
+// component samples, decode_output_kernel's own lines as a function (that kernel keeps its text); and the store of a
+// pixel's channel samples, again that kernel's lines, for its sequence form.  Device code only.
 #pragma once
 
 #include <climits>
@@ -76,6 +77,22 @@ __device__ __forceinline__ void component_samples(const ARGS &a, int x, int y, i
             v[c] = (int)min(max(t, 0LL), (long long)((1 << a.cprec[c]) - 1));
         }
     }
+}
+
+// Destination channels c < nout of pixel (x, y) from its component samples v[]: CopyChannel's depth conversion, one store per
+// channel that has the sample (decode_output_kernel's last loop).  ARGS: DecOutArgs.
+template <typename ARGS>
+__device__ __forceinline__ void store_channels(const ARGS &a, int x, int y, const int v[4])
+{
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (c < a.nout && c < a.ncomp && x < a.dst_w[c] && y < a.dst_h[c]) {
+            const unsigned mask = a.dst_bytes[c] == 1 ? 0xffu : 0xffffu;
+            const unsigned ov = depth_out((unsigned)v[c], a.cprec[c], a.dst_depth[c], mask);
+            uint8_t *p = a.dst[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
+            if (a.dst_bytes[c] == 1) *p = (uint8_t)ov;
+            else *reinterpret_cast<unsigned short *>(p) = (unsigned short)ov;
+        }
 }
 
 } // namespace j2k_hip

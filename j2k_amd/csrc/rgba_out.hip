@@ -117,6 +117,125 @@ void launch_mode(const DecRgbaArgs &a, const dim3 &grid, hipStream_t s)
     }
 }
 
+// One pixel of decode_rgba_kernel (that kernel's own lines as a function, for its sequence form below).
+template <bool REV, int MODE, bool PACKED, typename ARGS>
+__device__ __forceinline__ void rgba_pixel(const ARGS &a, const unsigned *s_lut, int x, int y, int D, int top, unsigned mask)
+{
+    int v[4];
+    component_samples<REV>(a, x, y, v);
+    unsigned out[4]; // R, G, B, A
+    out[3] = (unsigned)top;
+    if constexpr (MODE == J2K_HIP_RGBA_RGB) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[c] = depth_out((unsigned)v[c], a.cprec[c], D, mask);
+        if (a.alpha_comp == 3) out[3] = depth_out((unsigned)v[3], a.cprec[3], D, mask);
+    } else if constexpr (MODE == J2K_HIP_RGBA_GREY) {
+        out[0] = out[1] = out[2] = depth_out((unsigned)v[0], a.cprec[0], D, mask);
+        if (a.alpha_comp == 1) out[3] = depth_out((unsigned)v[1], a.cprec[1], D, mask);
+    } else if constexpr (MODE == J2K_HIP_RGBA_PALETTE) {
+        const unsigned idx = (unsigned)v[0];
+        const unsigned e = idx < a.lut_size ? s_lut[idx] : 0u;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const unsigned b = (e >> (8 * c)) & 0xffu;
+            out[c] = a.sample_bytes == 1 ? b : ((b << 8) | b); // ConvertToType: whatever the depth
+        }
+    } else { // sYCC, the reference's irreversible branch
+        const int h = 1 << (D - 1);
+        const float sY = (float)((int)depth_out((unsigned)v[0], a.cprec[0], D, mask) - h);
+        const float sCb = (float)((int)depth_out((unsigned)v[1], a.cprec[1], D, mask) - h);
+        const float sCr = (float)((int)depth_out((unsigned)v[2], a.cprec[2], D, mask) - h);
+        out[0] = sycc_channel(sY + kCrR * sCr, h, top);
+        out[1] = sycc_channel((sY - kCrG * sCr) - kCbG * sCb, h, top);
+        out[2] = sycc_channel(sY + kCbB * sCb, h, top);
+    }
+    if (a.demote) { // Demote (FrameSeq.cpp:265-268)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) out[c] = out[c] > 32768u ? ((out[c] - 1) >> 1) + 1 : out[c] >> 1;
+    }
+    if constexpr (PACKED) {
+        if (x < a.dst_w[0] && y < a.dst_h[0]) {
+            if (a.sample_bytes == 1) {
+                unsigned w = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) w |= (out[c] & 0xffu) << (8 * a.slot[c]);
+                *reinterpret_cast<unsigned *>(a.pix + (long long)y * a.pix_rowbytes + (long long)x * 4) = w;
+            } else {
+                unsigned long long w = 0;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) w |= (unsigned long long)(out[c] & 0xffffu) << (16 * a.slot[c]);
+                *reinterpret_cast<unsigned long long *>(a.pix + (long long)y * a.pix_rowbytes + (long long)x * 8) = w;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (a.dst[c] && x < a.dst_w[c] && y < a.dst_h[c]) {
+                uint8_t *p = a.dst[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
+                if (a.sample_bytes == 1) *p = (uint8_t)out[c];
+                else *reinterpret_cast<unsigned short *>(p) = (unsigned short)out[c];
+            }
+    }
+}
+
+// The frames of a sequence decode in one launch: frame = blockIdx.z, its descriptor (kernels.h: DecSeqFrameDev) read from the
+// table at a wave-uniform address (scalar loads, once per workgroup).  The pixel code reads a frame's arguments: DecRgbaArgs
+// without the palette (which stays where the launch put it: a copy of the whole struct would live in scratch memory).
+struct RgbaFrameArgs {
+    const void *comp[4]; long long stride;
+    int ncomp, mct, cprec[4], sub_x[4], sub_y[4], org_x, org_y;
+    int alpha_comp, sample_bytes, demote, slot[4];
+    uint8_t *pix; long long pix_rowbytes;
+    uint8_t *dst[4]; long long colbytes[4], rowbytes[4];
+    int dst_w[4], dst_h[4];
+    uint32_t lut_size;
+};
+
+template <bool REV, int MODE, bool PACKED>
+__global__ __launch_bounds__(256) void decode_rgba_seq_kernel(DecRgbaArgs a, const DecSeqFrameDev *__restrict__ frames)
+{
+    __shared__ unsigned s_lut[MODE == J2K_HIP_RGBA_PALETTE ? 256 : 1];
+    if constexpr (MODE == J2K_HIP_RGBA_PALETTE) {
+        s_lut[threadIdx.x] = a.lut[threadIdx.x];
+        __syncthreads();
+    }
+    const DecSeqFrameDev &F = frames[blockIdx.z];
+    RgbaFrameArgs f;
+    f.stride = a.stride; f.ncomp = a.ncomp; f.mct = a.mct; f.org_x = a.org_x; f.org_y = a.org_y;
+    f.alpha_comp = a.alpha_comp; f.sample_bytes = a.sample_bytes; f.demote = a.demote; f.lut_size = a.lut_size;
+    f.pix = F.pix; f.pix_rowbytes = F.pix_rowbytes;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        f.comp[c] = reinterpret_cast<const unsigned *>(a.comp[c]) + F.comp_off;
+        f.cprec[c] = a.cprec[c]; f.sub_x[c] = a.sub_x[c]; f.sub_y[c] = a.sub_y[c]; f.slot[c] = a.slot[c];
+        f.dst[c] = F.dst[c]; f.colbytes[c] = F.colbytes[c]; f.rowbytes[c] = F.rowbytes[c];
+        f.dst_w[c] = F.dst_w[c]; f.dst_h[c] = F.dst_h[c];
+    }
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= a.width) return;
+    const int D = a.depth, top = (1 << D) - 1;
+    const unsigned mask = a.sample_bytes == 1 ? 0xffu : 0xffffu;
+    for (int y = blockIdx.y; y < a.height; y += gridDim.y) rgba_pixel<REV, MODE, PACKED>(f, s_lut, x, y, D, top, mask);
+}
+
+template <bool REV, int MODE>
+void launch_form_seq(const DecRgbaArgs &a, const DecSeqFrameDev *f, const dim3 &grid, hipStream_t s)
+{
+    if (a.packed) hipLaunchKernelGGL((decode_rgba_seq_kernel<REV, MODE, true>), grid, dim3(256), 0, s, a, f);
+    else hipLaunchKernelGGL((decode_rgba_seq_kernel<REV, MODE, false>), grid, dim3(256), 0, s, a, f);
+}
+
+template <bool REV>
+void launch_mode_seq(const DecRgbaArgs &a, const DecSeqFrameDev *f, const dim3 &grid, hipStream_t s)
+{
+    switch (a.mode) {
+    case J2K_HIP_RGBA_RGB: launch_form_seq<REV, J2K_HIP_RGBA_RGB>(a, f, grid, s); break;
+    case J2K_HIP_RGBA_GREY: launch_form_seq<REV, J2K_HIP_RGBA_GREY>(a, f, grid, s); break;
+    case J2K_HIP_RGBA_PALETTE: launch_form_seq<REV, J2K_HIP_RGBA_PALETTE>(a, f, grid, s); break;
+    default: launch_form_seq<REV, J2K_HIP_RGBA_SYCC>(a, f, grid, s); break;
+    }
+}
+
 } // namespace
 
 void launch_decode_rgba(const DecRgbaArgs &a, hipStream_t s)
@@ -125,6 +244,14 @@ void launch_decode_rgba(const DecRgbaArgs &a, hipStream_t s)
     const dim3 grid((unsigned)((a.width + 255) / 256), (unsigned)std::min(a.height, 65535), 1);
     if (a.reversible) launch_mode<true>(a, grid, s);
     else launch_mode<false>(a, grid, s);
+}
+
+void launch_decode_rgba_seq(const DecRgbaArgs &a, const DecSeqFrameDev *frames, int nframes, hipStream_t s)
+{
+    if (a.width <= 0 || a.height <= 0 || nframes <= 0) return;
+    const dim3 grid((unsigned)((a.width + 255) / 256), (unsigned)std::min(a.height, 65535), (unsigned)nframes);
+    if (a.reversible) launch_mode_seq<true>(a, frames, grid, s);
+    else launch_mode_seq<false>(a, frames, grid, s);
 }
 
 } // namespace j2k_hip

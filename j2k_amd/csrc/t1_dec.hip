@@ -397,6 +397,14 @@ void launch_t1_decode_lanes(const T1DecArgs &a, hipStream_t s)
     else hipLaunchKernelGGL(t1_assemble_lanes_kernel<false>, dim3((unsigned)a.nblks), dim3(64), 0, s, a);
 }
 
+int t1_decode_lanes_resident_waves()
+{
+    int per_cu = 0, dev = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(&t1_decode_lanes_kernel), 64, 0) != hipSuccess || per_cu <= 0) return 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
+    return per_cu * cus;
+}
+
 void launch_t1_decode(const T1DecArgs &a, hipStream_t s)
 {
     if (a.nblks <= 0) return;

@@ -31,6 +31,7 @@ const Knob kKnobs[] = {
     {"dwt_xcd", "J2K_DWT_XCD", &Tuning::dwt_xcd},
     {"t1dec_lanes", "J2K_T1DEC_LANES", &Tuning::t1dec_lanes},
     {"t1dec_tail", "J2K_T1DEC_TAIL", &Tuning::t1dec_tail},
+    {"decseq_group", "J2K_DECSEQ_GROUP", &Tuning::decseq_group},
     {"bands", "J2K_BANDS", &Tuning::bands},
     {"t1_sparse", "J2K_T1_SPARSE", &Tuning::t1_sparse},
 };

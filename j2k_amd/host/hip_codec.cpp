@@ -189,6 +189,54 @@ void HipCodec::ReadFile(InputFile &file, const Buffer &buffer, unsigned int subs
     t_enc.error.clear();
 }
 
+bool HipCodec::ReadFiles(InputFile *const *files, const Buffer *buffers, unsigned n, unsigned subsample)
+{
+    if (files == NULL || buffers == NULL || n == 0) { t_enc.error = "no frames"; throw Exception("Error reading file"); }
+    std::vector<std::vector<unsigned char> > data(n);
+    std::vector<j2k_hip_file> in(n);
+    const int nch = buffers[0].channels;
+    bool ok = nch >= 1 && nch <= J2K_CODEC_MAX_CHANNELS;
+    std::vector<j2k_hip_outplane> planes((size_t)n * (ok ? nch : 1));
+    for (unsigned f = 0; f < n; f++) {
+        if (files[f] == NULL || !Verify(*files[f])) throw Exception("Can't read this format");
+        data[f] = slurp(*files[f]);
+        in[f].data = data[f].data(); in[f].len = data[f].size();
+        ok = ok && buffers[f].channels == nch;
+        for (int i = 0; ok && i < nch; i++) {
+            const Channel &c = buffers[f].channel[i];
+            ok = !c.sgnd && (c.sampleType == UCHAR || c.sampleType == USHORT) && c.buf != NULL;
+            j2k_hip_outplane &p = planes[(size_t)f * nch + i];
+            p.base = c.buf; p.colbytes = c.colbytes; p.rowbytes = c.rowbytes;
+            p.sample_bits = c.sampleType == USHORT ? 16 : 8;
+            p.depth = c.depth; p.width = c.width; p.height = c.height;
+        }
+    }
+    if (!ok) { t_enc.error = "unsupported destination Buffer"; throw Exception("Error reading file"); }
+    // the headers tell whether the frames can share a call: no device is touched for those that cannot
+    uint32_t bad = 0;
+    const int check = j2k_hip_decode_sequence_check(in.data(), n, &bad);
+    if (check != J2K_HIP_OK) {
+        t_enc.error = j2k_hip_last_error(NULL);
+        if (check == J2K_HIP_ERR_UNSUPPORTED) return false;
+        if (check == J2K_HIP_ERR_PARAM && bad > 0) { // frame `bad` differs from frame 0 -- or is damaged, which its own header tells
+            j2k_hip_file_info fi = {};
+            fi.struct_size = sizeof(fi);
+            if (j2k_hip_read_info(in[bad].data, in[bad].len, &fi) == J2K_HIP_OK) return false;
+        }
+        throw Exception("Error reading file");
+    }
+    j2k_hip_encoder *h = thread_handle(_device);
+    if (!h) throw Exception("Error reading file");
+    const int rc = j2k_hip_decode_sequence(h, in.data(), n, subsample ? subsample : 1, NULL, planes.data(), (uint32_t)nch);
+    if (rc != J2K_HIP_OK) {
+        t_enc.error = j2k_hip_last_error(h);
+        if (rc == J2K_HIP_ERR_UNSUPPORTED) return false; // (found by the host-side parser: no kernel has run, the destinations are untouched)
+        throw Exception("Error reading file");
+    }
+    t_enc.error.clear();
+    return true;
+}
+
 bool HipCodec::ReadRGBA(InputFile &file, const Channel &r, const Channel &g, const Channel &b, const Channel &a,
                         unsigned int subsample, Progress *progress)
 {

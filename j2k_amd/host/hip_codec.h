@@ -66,6 +66,15 @@ class HipCodec : public Codec {
     bool ReadRGBA(InputFile &file, const Channel &r, const Channel &g, const Channel &b, const Channel &a,
                   unsigned int subsample = 1, Progress *progress = NULL);
 
+    // The frames of an image sequence in one decode (include/j2k_hip.h: j2k_hip_decode_sequence): files[i] goes to buffers[i]
+    // as ReadFile(*files[i], buffers[i], subsample) would put it, the code-blocks of all n frames sharing their kernel
+    // launches -- one host thread and one stream keep the GPU as busy as a thread and a handle per frame did.
+    // true: all n frames are written.  false: nothing is written, because the frames cannot share a call -- one of them is
+    // for the fallback reader (J2K_HIP_ERR_UNSUPPORTED) or differs from the first in geometry or coding parameters; the
+    // caller reads them frame by frame through ReadFile.  A damaged frame and device failures throw "Error reading file"
+    // (frames before the damaged one may have been written); LastError() names the frame.
+    bool ReadFiles(InputFile *const *files, const Buffer *buffers, unsigned n, unsigned subsample);
+
     // text of the last failure on the calling thread (the exception itself carries the reference's
     // fixed message)
     static const char *LastError();

@@ -115,6 +115,40 @@ long j2k_host_test_read_fallback(const unsigned char *file, unsigned long file_l
     return other.reads ? 1 : 0;
 }
 
+// HipCodec::ReadFiles: n frames of file_len[f] bytes at files[f] into planar 8-bit channels, frame f at
+// frames + f * channels * width * height.  Returns 1 = all frames written, 0 = ReadFiles returned false (the caller reads frame by
+// frame), -1 = j2k::Exception (what() in err).
+long j2k_host_test_read_files(const unsigned char *const *files, const unsigned long *file_len, unsigned n, unsigned subsample,
+                              unsigned char *frames, unsigned width, unsigned height, int channels, char *err, unsigned long err_cap)
+{
+    using namespace j2k;
+    std::vector<Buffer> bufs(n);
+    std::vector<MemoryInputFile> ins;
+    std::vector<InputFile *> ptrs;
+    ins.reserve(n);
+    for (unsigned f = 0; f < n; f++) {
+        bufs[f].channels = (unsigned char)channels;
+        for (int c = 0; c < channels; c++) {
+            Channel &ch = bufs[f].channel[c];
+            ch.width = width; ch.height = height; ch.sampleType = UCHAR; ch.depth = 8; ch.sgnd = false;
+            ch.buf = frames + ((size_t)f * channels + c) * width * height; ch.colbytes = 1; ch.rowbytes = width;
+        }
+        ins.push_back(MemoryInputFile(files[f], file_len[f]));
+    }
+    for (unsigned f = 0; f < n; f++) ptrs.push_back(&ins[f]);
+    HipCodec hip(HipCodec::HonourSettings);
+    try {
+        return hip.ReadFiles(ptrs.data(), bufs.data(), n, subsample) ? 1 : 0;
+    } catch (const Exception &e) {
+        if (err && err_cap) {
+            std::string m = std::string(e.what()) + " | " + HipCodec::LastError();
+            std::strncpy(err, m.c_str(), err_cap - 1);
+            err[err_cap - 1] = 0;
+        }
+        return -1;
+    }
+}
+
 // The read side, driven like RGBAinputFile drives a Codec (reference: src/common/j2k_rgba_file.cpp:450-735 ->
 // Codec::ReadFile, src/common/j2k_codec.h:311): `frame` is the host's interleaved A,R,G,B buffer (pixel_size = bytes
 // per sample) of width x height pixels = the image size / subsample; codec channel c goes to the RGBA channel named
