@@ -483,6 +483,23 @@ int j2k_hip_stage_frontend(j2k_hip_encoder *enc, const j2k_hip_params *params,
 int j2k_hip_stage_dwt(j2k_hip_encoder *enc, int reversible, uint32_t width, uint32_t height,
                       uint32_t nplanes, uint32_t levels, uint32_t x0, uint32_t y0, const void *d_in,
                       void *d_out, uint32_t repeat, double *ms);
+/* A1..A6 as an encode runs them: the front end and every DWT launch of j2k_hip_encode_device for these parameters and
+ * channel views (device pointers) -- the same geometry and job tables, the same choice between the fused level-1 kernel and
+ * the stand-alone front end, the same launch shapes under the tuning knobs -- and nothing behind them: no Tier-1 launch,
+ * no pending encode on the handle.  d_out (device) receives the `channels` coefficient planes, dense, width*height 32-bit
+ * words each (int32 for the reversible path, float32 bit patterns otherwise): every tile's rectangle holds that
+ * tile-component's Mallat layout; with one resolution it is the front end's output.
+ * Row-pair ranges: level l (0 = full resolution) of the first `ncut_levels` levels is launched once per interval
+ * [0, c_1), [c_1, c_2), .., [c_n, end) of its row pairs, n = ncuts[l], the intervals in ascending or (descending != 0)
+ * descending order; `cuts` holds the c_i of level 0, then those of level 1, and so on.  A level still starts after the whole
+ * level above it.  A cut point that does not exceed the one before it, or is 0, or lies at or beyond the row pairs of the
+ * level's tallest tile-component ((height + parity of its origin + 1) / 2): J2K_HIP_ERR_PARAM.  cuts == NULL with
+ * ncut_levels == 0: one launch per level, as an encode.
+ * The handle's cached geometry is dropped: the next encode builds it again.
+ * J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
+int j2k_hip_stage_transform(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes_device,
+                            const uint32_t *cuts, const uint32_t *ncuts, uint32_t ncut_levels, int descending,
+                            void *d_out);
 /* A7+A8: Tier-1 of `nblocks` code-blocks cut from one coefficient plane (row stride `stride`
  * words). Block i = rectangle (bx[i],by[i],bw[i],bh[i]), orientation orient[i], band step size
  * stepsize[i] (ignored when reversible).  Outputs (host): numbps[i], npasses[i], length[i] and the

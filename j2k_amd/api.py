@@ -92,7 +92,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
            "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
-           "j2k_hip_stage_t1_styled",
+           "j2k_hip_stage_t1_styled", "j2k_hip_stage_transform",
            "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_t1_decode_styled", "j2k_hip_stage_decode_output",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink"]
@@ -204,6 +204,7 @@ def load_library():
     L.j2k_hip_stage_dwt.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
     U32P = C.POINTER(C.c_uint32)
+    L.j2k_hip_stage_transform.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Plane), U32P, U32P, C.c_uint32, C.c_int, C.c_void_p]
     L.j2k_hip_stage_t1.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, U32P, U32P, U32P, U32P, U32P,
                                    C.POINTER(C.c_float), U32P, U32P, U32P, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t]
     L.j2k_hip_stage_t1_passes.argtypes = L.j2k_hip_stage_t1.argtypes + [U32P, C.POINTER(C.c_int32)]
@@ -789,6 +790,24 @@ class Encoder:
             self.free(d_out)
         dt = np.int32 if params.reversible else np.float32
         return raw.view(dt).reshape(params.channels, params.height, params.width)
+
+    def stage_transform(self, buf: np.ndarray, planes, params: Params, cuts=None, descending: bool = False) -> np.ndarray:
+        """j2k_hip_stage_transform: the front end and the DWT launches of an encode of the channel views `planes`
+        (a callable: device address of `buf` -> Plane array, e.g. planes_from_layout) -> (channels, H, W) coefficients.
+        cuts: per level (0 = full resolution) a list of cut points in row pairs; each level is launched once per interval."""
+        d_in = self.upload(buf)
+        n = params.channels * params.width * params.height
+        d_out = self.malloc(4 * n)
+        cuts = [list(c) for c in (cuts or [])]
+        flat = [v for c in cuts for v in c]
+        try:
+            self._check(self.L.j2k_hip_stage_transform(self.h, C.byref(params), planes(d_in), (C.c_uint32 * max(len(flat), 1))(*flat),
+                                                       (C.c_uint32 * max(len(cuts), 1))(*[len(c) for c in cuts]), len(cuts), int(descending), d_out))
+            raw = self.d2h(d_out, 4 * n)
+        finally:
+            self.free(d_in)
+            self.free(d_out)
+        return raw.view(np.int32 if params.reversible else np.float32).reshape(params.channels, params.height, params.width)
 
     def stage_dwt(self, planes: np.ndarray, levels: int, reversible: bool, x0=0, y0=0, repeat=1):
         """planes: (n, h, w) int32 / float32. Returns (result, ms per run)."""

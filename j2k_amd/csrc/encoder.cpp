@@ -282,6 +282,18 @@ FrontendArgs make_frontend_args(const Coding &cod, const j2k_hip_plane *planes, 
     return fa;
 }
 
+// Does level 1 of the DWT take its samples straight from the frame (dwt_fused_kernel) -- the one place that decides it, for
+// an encode (in one piece or in bands) and for the stage hook alike?  After Effects layout (1, 3 or 4 channels out of one
+// interleaved pixel, equal depths): the front end -- Promote and both of CopyChannel's shift branches included -- runs inside
+// the level-1 DWT kernel and the planar intermediate is never written; any other arrangement of channel views is converted
+// by a pass of its own (frontend.hip).
+bool fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tuning &tn)
+{
+    bool same_depth = true;
+    for (uint32_t c = 1; c < cod.ncomp; ++c) same_depth = same_depth && fa.src_depth[c] == fa.src_depth[0];
+    return !tn.no_fuse && cod.levels() >= 1 && fa.interleaved && same_depth && (cod.ncomp == 1 || cod.ncomp == 3 || cod.ncomp == 4);
+}
+
 struct EncodeOut {
     const void *d_cs = nullptr;
     size_t len = 0;
@@ -477,12 +489,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     // ---- working planes (one set per frame of a sequence)
     const size_t plane_bytes = e->plane_elems * sizeof(int32_t) * cod.ncomp;
     FrontendArgs fa0 = make_frontend_args(cod, dplanes, x0, y0, x1, y1);
-    // After Effects layout (1, 3 or 4 channels out of one interleaved pixel, equal depths): the front end -- Promote
-    // and both of CopyChannel's shift branches included -- runs inside the level-1 DWT kernel and the planar
-    // intermediate is never written; any other arrangement of channel views is converted by a pass of its own.
-    bool same_depth = true;
-    for (uint32_t c = 1; c < cod.ncomp; ++c) same_depth = same_depth && fa0.src_depth[c] == fa0.src_depth[0];
-    const bool fused = !tn.no_fuse && NL >= 1 && fa0.interleaved && same_depth && (cod.ncomp == 1 || cod.ncomp == 3 || cod.ncomp == 4);
+    const bool fused = fuse_frontend(cod, fa0, tn);
     // P holds the front end's output (unfused) and the LL of levels 2, 4, ..: a fused path with fewer than
     // three levels never touches it
     if (!fused || NL >= 3) e->P.ensure(plane_bytes * F);
@@ -1053,9 +1060,7 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     if (tn.bands == 0 && g_dev[e->device].inflight.load() > 1) return false;
     // the After Effects layout (front end fused into level 1), rows top to bottom and not overlapping
     const FrontendArgs fh = make_frontend_args(cod, planes, 0, 0, (int)cod.width, (int)cod.height);
-    bool same_depth = true;
-    for (uint32_t c = 1; c < cod.ncomp; ++c) same_depth = same_depth && fh.src_depth[c] == fh.src_depth[0];
-    if (!fh.interleaved || !same_depth || !(cod.ncomp == 1 || cod.ncomp == 3 || cod.ncomp == 4)) return false;
+    if (!fuse_frontend(cod, fh, tn)) return false;
     const long long rowbytes = fh.rowbytes[0];
     if (rowbytes < (long long)cod.width * fh.pixel_bytes) return false;
     const uint8_t *lo, *hi;
@@ -1885,6 +1890,78 @@ int j2k_hip_stage_dwt(j2k_hip_encoder *e, int reversible, uint32_t width, uint32
         float ms = 0;
         HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_START], e->ev[EV_DONE]));
         if (ms_out) *ms_out = ms / repeat;
+    });
+}
+
+// The front end and the DWT launches of an encode, and nothing behind them: encode_begin's own steps up to the last level
+// (device frames, one frame), with a level optionally launched in pieces over row-pair ranges.
+int j2k_hip_stage_transform(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes_device,
+                            const uint32_t *cuts, const uint32_t *ncuts, uint32_t ncut_levels, int descending, void *d_out)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        if (!planes_device || !d_out) throw Error(J2K_HIP_ERR_PARAM, "planes or d_out is NULL");
+        if (ncut_levels && (!ncuts || !cuts)) throw Error(J2K_HIP_ERR_PARAM, "cut points announced but not given");
+        HIP_CHECK(hipSetDevice(e->device));
+        const Tuning tn = tuning();
+        const Coding cod = normalise(params);
+        prepare_geometry(e, cod, 0, cod.ntiles());
+        // The handle's geometry is this call's now while last_fa still describes an earlier call's channels: nothing may
+        // replay them against it (j2k_hip_debug_dwt_time), so the next call builds its geometry afresh.
+        e->geo_valid = false; e->seq_valid = false; e->band_valid = false; e->rc_weight_valid = false;
+        const Geometry &g = e->geo;
+        hipStream_t s = e->stream;
+        const size_t S = e->stride;
+        const int NL = (int)cod.levels();
+        if (ncut_levels > (uint32_t)NL) throw Error(J2K_HIP_ERR_PARAM, "cut points for more levels than the transform has");
+        // row-pair ranges per level: [0, c_1), [c_1, c_2), .., [c_n, end)
+        std::vector<std::vector<int>> bounds((size_t)NL);
+        const uint32_t *cp = cuts;
+        for (int l = 0; l < NL; ++l) {
+            int npy = 0; // row pairs of the level's tallest job
+            for (const DwtJob &j : e->h_jobs[(size_t)l]) npy = std::max(npy, (j.rh + j.casy + 1) >> 1);
+            std::vector<int> &b = bounds[(size_t)l];
+            b.push_back(0);
+            for (uint32_t i = 0; (uint32_t)l < ncut_levels && i < ncuts[l]; ++i, ++cp) {
+                if (*cp >= (uint32_t)npy || (int)*cp <= b.back()) throw Error(J2K_HIP_ERR_PARAM, "cut points must increase and lie inside the level's row pairs");
+                b.push_back((int)*cp);
+            }
+            b.push_back(npy);
+        }
+        const int y0 = e->box_y0, x0 = e->box_x0;
+        int y1 = 0, x1 = 0;
+        for (const Tile &T : g.tiles) { y1 = std::max(y1, T.y1); x1 = std::max(x1, T.x1); }
+        FrontendArgs fa = make_frontend_args(cod, planes_device, x0, y0, x1, y1);
+        const bool fused = fuse_frontend(cod, fa, tn);
+        const size_t plane_bytes = e->plane_elems * sizeof(int32_t) * cod.ncomp;
+        // (the planes are filled first: a word that no launch writes shows as 0xA5A5A5A5 instead of an earlier call's result)
+        if (!fused || NL >= 3) { e->P.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->P.p, 0xA5, plane_bytes, s)); }
+        if (NL >= 1) { e->Z.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->Z.p, 0xA5, plane_bytes, s)); }
+        if (NL >= 2) { e->Q.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->Q.p, 0xA5, plane_bytes, s)); }
+        if (!fused) {
+            for (uint32_t c = 0; c < cod.ncomp; ++c) fa.dst[c] = e->P.as<int32_t>() + c * e->plane_elems;
+            fa.dst_stride = (long long)S; fa.dst_x0 = x0; fa.dst_y0 = y0;
+            launch_frontend(fa, s);
+        }
+        for (int l = 0; l < NL; ++l) {
+            const std::vector<int> &b = bounds[(size_t)l];
+            const int n = (int)b.size() - 1;
+            for (int i = 0; i < n; ++i) {
+                const int k = descending ? n - 1 - i : i;
+                DwtLevelArgs da = dwt_level_args(e, cod, fa, fused, 0, l);
+                if (n > 1) { da.pair0 = b[(size_t)k]; da.pair1 = b[(size_t)k + 1]; }
+                launch_dwt_level(da, s);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        // the coefficient planes without their stride padding (zero levels: the front end's output)
+        const uint8_t *from = NL >= 1 ? e->Z.as<uint8_t>() : e->P.as<uint8_t>();
+        const size_t W = (size_t)(x1 - x0), H = (size_t)(y1 - y0);
+        for (uint32_t c = 0; c < cod.ncomp; ++c)
+            HIP_CHECK(hipMemcpy2DAsync(static_cast<uint8_t *>(d_out) + (size_t)c * W * H * 4, W * 4, from + (size_t)c * e->plane_elems * 4, S * 4, W * 4, H,
+                                       hipMemcpyDeviceToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));
     });
 }
 
