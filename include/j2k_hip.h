@@ -133,6 +133,34 @@ typedef struct j2k_hip_params {
      * behind max_comp_size) the field takes that padding and sizeof does not move: a caller of the older header that
      * zero-initialises the whole struct, as the header has always asked for, passes style 0. */
     uint32_t cblk_style;
+    /* ---- sub-sampled components (T.800 A.5.1, SIZ XRsiz / YRsiz; 4:2:2 and 4:2:0 Y Cb Cr).  comp_sub_x[c] / comp_sub_y[c]:
+     * component c has one sample per comp_sub_x[c] x comp_sub_y[c] points of the reference grid; 0 = 1; 1, 2 or 4.  All ones
+     * (or all zero) = the file the library has always written.  `width` and `height` stay the image area on the reference grid
+     * (origin 0); component c is ceil(width / sub_x) x ceil(height / sub_y) samples.
+     *   rgb_to_sycc == 0: planes[c] views component c on its OWN grid -- that many samples.  Host planes may be
+     *     allocations of their own: channels that do not share a buffer are uploaded one by one, nothing between them is read.
+     *   rgb_to_sycc == 1: `channels` is 3 or 4, planes are R, G, B[, A] of the full image (width x height each) and the library
+     *     makes Y, Cb, Cr[, A] from them on the GPU while it loads them: components 1 and 2 share one factor pair out of
+     *     (1,1), (2,1), (2,2); a fourth component (alpha) is (1,1) and passes through.  Exact integer arithmetic on the samples
+     *     at `depth` bits (after Promote and the depth conversion), h = 2^(depth-1), top = 2^depth - 1, >> a floor shift:
+     *         Y   = (19595 R + 38470 G + 7471 B + 32768) >> 16
+     *         cb' = -11059 R - 21709 G + 32768 B,   cr' = 32768 R - 27439 G - 5329 B        (per pixel, not rounded)
+     *         Cb  = clamp(h + ((sum cb' + (1 << (15 + k))) >> (16 + k)), 0, top),  Cr alike,   k = log2(sub_x * sub_y)
+     *     the sum over the chroma sample's sub_x x sub_y pixels; a pixel beyond the right or bottom edge repeats the last column
+     *     or row.  This is the analysis to the replicating sYCC read of j2k_hip_decode_rgba.  Set color_space = J2K_HIP_CS_SYCC
+     *     for a JP2 file that says so.
+     * Component 0 is never sub-sampled (libopenjp2's byte budget is computed from component 0's factors; nothing else is pinned).
+     * J2K_HIP_ERR_PARAM, the text naming the field: a factor outside {1, 2, 4}; comp_sub on component 0; `ycc` with a sub-sampled
+     * component or with rgb_to_sycc; dci_profile or layer_psnr with either; rgb_to_sycc with fewer than 3 channels or with other
+     * factor pairs than the above.  layer_rates and cblk_style combine with sub-sampling as they do without.
+     * Entry points: j2k_hip_encode, _encode_to_buffer, _encode_device, _encode_begin / _end and _encode_begin_borrowed / _end
+     * write identical bytes, byte for byte what libopenjp2 writes for the same components (the synchronous host call is then not
+     * band-pipelined: j2k_hip_stats.bands = 0); so do j2k_hip_encode_sequence_device and j2k_hip_encode_batch, frame by frame.
+     * The tile-sharded entry points -- j2k_hip_encode_tiles, _encode_tiles_device, _encode_tiles_distributed -- refuse a
+     * sub-sampled frame or rgb_to_sycc with J2K_HIP_ERR_PARAM ("comp_sub / rgb_to_sycc: ...") before any device work.
+     * J2K_HIP_ABI_VERSION is still 9: fields were appended, no function changed; struct_size is the guard. */
+    uint32_t comp_sub_x[4], comp_sub_y[4];
+    uint32_t rgb_to_sycc;
 } j2k_hip_params;
 
 enum { J2K_HIP_CBLK_BYPASS = 1, J2K_HIP_CBLK_RESET = 2, J2K_HIP_CBLK_TERMALL = 4, J2K_HIP_CBLK_VCAUSAL = 8 /* decode only */,
@@ -474,7 +502,8 @@ int j2k_hip_decode_rgba_sequence_device(j2k_hip_encoder *enc, const j2k_hip_file
 
 /* --- stage-level entry points (parity tests and roofline measurement call these) -----------------
  * A1+A2+A4+A5: front end only. d_out = channels planes of width*height 32-bit words (int32 for
- * reversible, float32 bit patterns otherwise), row stride = width. */
+ * reversible, float32 bit patterns otherwise), row stride = width.  With sub-sampled components (comp_sub_x / _y,
+ * rgb_to_sycc) the components follow one another, each dense at its own size ceil(width / sub_x) x ceil(height / sub_y). */
 int j2k_hip_stage_frontend(j2k_hip_encoder *enc, const j2k_hip_params *params,
                            const j2k_hip_plane *planes_device, void *d_out);
 /* A6: forward DWT of `nplanes` planes of width*height 32-bit words (row stride = width), in the
@@ -488,7 +517,8 @@ int j2k_hip_stage_dwt(j2k_hip_encoder *enc, int reversible, uint32_t width, uint
  * the stand-alone front end, the same launch shapes under the tuning knobs -- and nothing behind them: no Tier-1 launch,
  * no pending encode on the handle.  d_out (device) receives the `channels` coefficient planes, dense, width*height 32-bit
  * words each (int32 for the reversible path, float32 bit patterns otherwise): every tile's rectangle holds that
- * tile-component's Mallat layout; with one resolution it is the front end's output.
+ * tile-component's Mallat layout; with one resolution it is the front end's output.  With sub-sampled components
+ * (comp_sub_x / _y, rgb_to_sycc) the planes follow one another, each dense at its own size, as j2k_hip_stage_frontend's.
  * Row-pair ranges: level l (0 = full resolution) of the first `ncut_levels` levels is launched once per interval
  * [0, c_1), [c_1, c_2), .., [c_n, end) of its row pairs, n = ncuts[l], the intervals in ascending or (descending != 0)
  * descending order; `cuts` holds the c_i of level 0, then those of level 1, and so on.  A level still starts after the whole

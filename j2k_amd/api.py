@@ -41,7 +41,8 @@ class Params(C.Structure):
                 ("pixel_aspect_num", C.c_uint32), ("pixel_aspect_den", C.c_uint32), ("dpi", C.c_float),
                 ("num_precincts", C.c_uint32), ("precinct_w", C.c_uint32 * 33), ("precinct_h", C.c_uint32 * 33),
                 ("dci_profile", C.c_uint32), ("max_cs_size", C.c_uint32), ("max_comp_size", C.c_uint32),
-                ("cblk_style", C.c_uint32)]
+                ("cblk_style", C.c_uint32),
+                ("comp_sub_x", C.c_uint32 * 4), ("comp_sub_y", C.c_uint32 * 4), ("rgb_to_sycc", C.c_uint32)]
 
 
 class Plane(C.Structure):
@@ -319,9 +320,12 @@ def region_footprint(width: int, height: int, levels: int, reversible: bool, win
 def make_params(width, height, channels, depth, reversible=True, ycc=False, layers=1, tile_size=0,
                 num_resolutions=6, cblk=(64, 64), promote=False, comment="", jp2=False, color_space=0,
                 alpha_channel=-1, alpha_premultiplied=False, icc=None, rates=None, psnr=None, progression=0,
-                pixel_aspect=None, dpi=0.0, precincts=None, dci_profile=0, max_cs_size=0, max_comp_size=0, cblk_style=0):
+                pixel_aspect=None, dpi=0.0, precincts=None, dci_profile=0, max_cs_size=0, max_comp_size=0, cblk_style=0,
+                sub=None, rgb_to_sycc=False):
     """comment: None -> library default COM, "" -> no COM segment.  jp2/color_space/alpha_channel/icc describe
-    the JP2 file wrapper (color_space in OPJ_COLOR_SPACE numbering: 1 sRGB, 2 grey, 3 sYCC)."""
+    the JP2 file wrapper (color_space in OPJ_COLOR_SPACE numbering: 1 sRGB, 2 grey, 3 sYCC).
+    sub = [(dx, dy), ...]: the sub-sampling factors of the components (SIZ XRsiz / YRsiz), one pair per channel; rgb_to_sycc:
+    the planes are R, G, B[, A] of the full image and the library makes Y, Cb, Cr[, A] at those factors."""
     p = Params()
     p.struct_size = C.sizeof(Params)
     p.width, p.height, p.channels, p.depth = width, height, channels, depth
@@ -335,6 +339,10 @@ def make_params(width, height, channels, depth, reversible=True, ycc=False, laye
         p.pixel_aspect_num, p.pixel_aspect_den = pixel_aspect
     p.dpi = dpi
     p.dci_profile, p.max_cs_size, p.max_comp_size = dci_profile, max_cs_size, max_comp_size  # 3 / 4: OpenJPEG's cinema 2K / 4K profile
+    if sub is not None:
+        for c, (dx, dy) in enumerate(sub):
+            p.comp_sub_x[c], p.comp_sub_y[c] = dx, dy
+    p.rgb_to_sycc = int(rgb_to_sycc)
     p.cblk_style = cblk_style  # COD SPcod code-block style: 1 bypass, 2 reset, 4 termall, 16 pterm, 32 segsym, in any combination
     if precincts:  # [(w, h), ...] highest resolution first (OpenJPEG's -c / res_spec semantics)
         p.num_precincts = len(precincts)
@@ -389,6 +397,39 @@ def planes_from_layout(base_addr: int, layout: dict, channels: int, depth_bits: 
         arr[c].sample_bits = 8 * sb
         arr[c].depth = depth_bits if depth_bits is not None else 8 * sb
     return arr
+
+
+def comp_shapes(params: Params):
+    """(rows, columns) of every component of `params` on its own grid: ceil(height / sub_y) x ceil(width / sub_x)."""
+    return [(-(-params.height // max(params.comp_sub_y[c], 1)), -(-params.width // max(params.comp_sub_x[c], 1)))
+            for c in range(params.channels)]
+
+
+def planes_from_arrays(arrays, depth_bits: int, base_of=None):
+    """Channel views over a list of 2-D uint8 / uint16 arrays of any sizes and strides (the components of a sub-sampled image,
+    one array each; padded rows, samples of interleaved pixels).  depth_bits: the significant bits of the samples.
+    base_of: array index -> address of its first sample (default: the array's own host address; a device copy otherwise)."""
+    arr = (Plane * len(arrays))()
+    for c, a in enumerate(arrays):
+        assert a.ndim == 2 and a.dtype in (np.uint8, np.uint16)
+        arr[c].base = base_of(c) if base_of else a.ctypes.data
+        arr[c].colbytes, arr[c].rowbytes = a.strides[1], a.strides[0]
+        arr[c].sample_bits, arr[c].depth = 8 * a.itemsize, depth_bits
+    return arr
+
+
+def _split_comps(raw: np.ndarray, params: Params):
+    """The dense 32-bit words of a stage hook -> (channels, H, W) for components of one size, a list of 2-D arrays otherwise."""
+    dt = np.int32 if params.reversible else np.float32
+    shapes = comp_shapes(params)
+    words = raw.view(dt)
+    if all(s == shapes[0] for s in shapes):
+        return words.reshape(params.channels, params.height, params.width)
+    out, pos = [], 0
+    for (h, w) in shapes:
+        out.append(words[pos:pos + h * w].reshape(h, w))
+        pos += h * w
+    return out
 
 
 class Encoder:
@@ -459,6 +500,13 @@ class Encoder:
             arr[c].colbytes, arr[c].rowbytes = buf.itemsize, w * buf.itemsize
             arr[c].sample_bits, arr[c].depth = 8 * buf.itemsize, params.depth  # samples already hold `depth` bits
         return self._encode_planes_host(arr, buf.nbytes, params, via_sink)
+
+    def encode_components_host(self, comps, params: Params, via_sink: bool = False) -> bytes:
+        """comps: one 2-D array of unsigned samples per component, each of its own size (sub-sampled components) -> planar host
+        buffers of 8- or 16-bit samples, encoded through j2k_hip_encode_to_buffer (via_sink: j2k_hip_encode)."""
+        dt = np.uint16 if params.depth > 8 else np.uint8
+        bufs = [np.ascontiguousarray(np.asarray(c).astype(dt)) for c in comps]
+        return self._encode_planes_host(planes_from_arrays(bufs, params.depth), sum(b.nbytes for b in bufs), params, via_sink)
 
     def _encode_planes_host(self, planes, in_bytes: int, params: Params, via_sink: bool) -> bytes:
         if via_sink:
@@ -788,12 +836,26 @@ class Encoder:
         finally:
             self.free(d_in)
             self.free(d_out)
-        dt = np.int32 if params.reversible else np.float32
-        return raw.view(dt).reshape(params.channels, params.height, params.width)
+        return _split_comps(raw[:4 * sum(h * w for h, w in comp_shapes(params))], params)
+
+    def stage_frontend_planes(self, buf: np.ndarray, planes, params: Params):
+        """j2k_hip_stage_frontend of any channel views: `planes` is a callable, device address of `buf` -> Plane array.
+        Components of one size: (channels, H, W); sub-sampled ones: a list of 2-D arrays."""
+        d_in = self.upload(buf)
+        n = sum(h * w for h, w in comp_shapes(params))
+        d_out = self.malloc(4 * n)
+        try:
+            self._check(self.L.j2k_hip_stage_frontend(self.h, C.byref(params), planes(d_in), d_out))
+            raw = self.d2h(d_out, 4 * n)
+        finally:
+            self.free(d_in)
+            self.free(d_out)
+        return _split_comps(raw, params)
 
     def stage_transform(self, buf: np.ndarray, planes, params: Params, cuts=None, descending: bool = False) -> np.ndarray:
         """j2k_hip_stage_transform: the front end and the DWT launches of an encode of the channel views `planes`
-        (a callable: device address of `buf` -> Plane array, e.g. planes_from_layout) -> (channels, H, W) coefficients.
+        (a callable: device address of `buf` -> Plane array, e.g. planes_from_layout) -> (channels, H, W) coefficients
+        (sub-sampled components: a list of 2-D arrays, each at its own size).
         cuts: per level (0 = full resolution) a list of cut points in row pairs; each level is launched once per interval."""
         d_in = self.upload(buf)
         n = params.channels * params.width * params.height
@@ -807,7 +869,7 @@ class Encoder:
         finally:
             self.free(d_in)
             self.free(d_out)
-        return raw.view(np.int32 if params.reversible else np.float32).reshape(params.channels, params.height, params.width)
+        return _split_comps(raw[:4 * sum(h * w for h, w in comp_shapes(params))], params)
 
     def stage_dwt(self, planes: np.ndarray, levels: int, reversible: bool, x0=0, y0=0, repeat=1):
         """planes: (n, h, w) int32 / float32. Returns (result, ms per run)."""

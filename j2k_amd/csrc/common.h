@@ -36,9 +36,11 @@ struct Coding {
     uint32_t dci = 0, max_comp_size = 0;
     // code-block style (COD SPcod; cblk_style.h): encode 0 or bypass / reset / termall / pterm / segsym in any combination
     uint32_t cblk_style = 0;
+    // encode: the planes are R, G, B[, A] of the full image and the front end makes Y, Cb, Cr[, A] at the components' own sizes
+    bool rgb_to_sycc = false;
     uint32_t dci_tileparts() const { return dci == 4 ? 6u : (dci == 3 ? 3u : 1u); }
-    // per component (decode only; the encode path of the reference never sub-samples: SIZ XRsiz = YRsiz = 1, one depth, unsigned):
-    // sub-sampling factors on the reference grid, precision, signedness
+    // per component: sub-sampling factors on the reference grid (decode: whatever SIZ holds; encode: comp_sub_x / _y, 1, 2 or 4, the
+    // reference's own encode call never sub-samples), and -- decode only, the encode path writes one unsigned depth -- precision, signedness
     // (kMaxComps entries: a codestream read may hold more than the four components the plug-in's Buffer has channels for -- the
     //  reference then takes the first four, j2k_openjpeg_codec.cpp:278, :530 -- and Tier-2 has to walk the packets of all of them)
     static constexpr uint32_t kMaxComps = 16;
@@ -78,6 +80,9 @@ struct Coding {
 // Validates exactly what the reference path would reject (OpenJPEG setup/validation errors) plus
 // the limits of this implementation; throws Error(J2K_HIP_ERR_PARAM, ...).
 Coding normalise(const j2k_hip_params *p);
+// The tile-sharded entry points do not write sub-sampled components (a tile range whose origin is no multiple of the factors):
+// throws Error(J2K_HIP_ERR_PARAM, ...) for such parameters.  Host code: called before any device work.
+void refuse_subsampled_tiles(const Coding &cod);
 
 // A handful of worker threads that run the same function on slices 0..n-1 (host-side loops over all
 // code-blocks of a large tile; starting threads per loop would cost more than the loops).

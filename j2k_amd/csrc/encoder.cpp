@@ -114,7 +114,8 @@ bool same_coding(const Coding &a, const Coding &b)
            a.reversible == b.reversible && a.mct == b.mct && a.layers == b.layers && a.numres == b.numres &&
            a.cbw == b.cbw && a.cbh == b.cbh && a.tile_w == b.tile_w && a.tile_h == b.tile_h &&
            std::memcmp(a.ppx, b.ppx, sizeof a.ppx) == 0 && std::memcmp(a.ppy, b.ppy, sizeof a.ppy) == 0 && a.prog == b.prog &&
-           a.cblk_style == b.cblk_style; // (a style changes the codeword capacities)
+           a.cblk_style == b.cblk_style && // (a style changes the codeword capacities)
+           std::memcmp(a.cdx, b.cdx, sizeof a.cdx) == 0 && std::memcmp(a.cdy, b.cdy, sizeof a.cdy) == 0;
 }
 
 // Decision-stream and codeword capacities of a code-block of `area` samples with up to Mb bit-planes under code-block style
@@ -132,6 +133,26 @@ CblkCaps cblk_capacities(size_t area, uint32_t Mb, uint32_t style)
     // a raw pass itself takes a bit per decision, less than the quarter byte counted for it.
     const size_t style_room = style ? 8 * (size_t)(3 * Mb) : 0;
     return {symcap, round_up(symcap / 4 + 64 + style_room, 16)};
+}
+
+// The working planes of one frame over the box [bx0, bx1) x [by0, by1) of the reference grid: one row stride for every
+// component (the box width rounded to 64 words: T1Args and DwtLevelArgs carry one stride), component c with the rows of its
+// own grid -- the box on that grid is ceil(box / sub-sampling factor), origin (cbx0, cby0) -- starting comp_off[c] words in;
+// frame_elems words hold them all.  Without sub-sampling: ncomp planes of stride x box rows.  The one place that lays planes
+// out, for an encode and for the front-end stage hook alike.
+struct PlaneLayout { size_t stride, comp_off[4], frame_elems; int cbx0[4], cby0[4], cw[4], ch[4]; };
+PlaneLayout plane_layout(const Coding &cod, int bx0, int by0, int bx1, int by1)
+{
+    PlaneLayout l{};
+    l.stride = round_up((size_t)(bx1 - bx0), 64);
+    for (uint32_t c = 0; c < cod.ncomp && c < 4; ++c) {
+        const int sx = cod.cdx[c], sy = cod.cdy[c];
+        l.cbx0[c] = (bx0 + sx - 1) / sx; l.cby0[c] = (by0 + sy - 1) / sy;
+        l.cw[c] = (bx1 + sx - 1) / sx - l.cbx0[c]; l.ch[c] = (by1 + sy - 1) / sy - l.cby0[c];
+        l.comp_off[c] = l.frame_elems;
+        l.frame_elems += l.stride * (size_t)l.ch[c];
+    }
+    return l;
 }
 
 // Build (or reuse) geometry, code-block table and DWT job lists; upload the device images.
@@ -156,6 +177,10 @@ void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first
     e->box_x0 = bx0; e->box_y0 = by0;
     e->stride = stride;
     e->plane_elems = stride * (size_t)(by1 - by0);
+    const PlaneLayout lay = plane_layout(cod, bx0, by0, bx1, by1);
+    const int *const cbx0 = lay.cbx0, *const cby0 = lay.cby0;
+    for (uint32_t c = 0; c < 4; ++c) e->comp_off[c] = lay.comp_off[c];
+    e->frame_elems = lay.frame_elems;
     const Geometry &g = e->geo;
     if (g.max_Mb * 3 - 2 > (uint32_t)kDevMaxPasses)
         throw Error(J2K_HIP_ERR_PARAM, "precision/levels combination needs more coding passes than supported");
@@ -166,7 +191,7 @@ void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first
     for (size_t i = 0; i < g.cblks.size(); ++i) {
         const Cblk &c = g.cblks[i];
         CblkDev d{};
-        d.coef_off = (unsigned long long)c.comp * e->plane_elems + (unsigned long long)(c.py - (uint32_t)by0) * stride + (c.px - (uint32_t)bx0);
+        d.coef_off = (unsigned long long)e->comp_off[c.comp] + (unsigned long long)(c.py - (uint32_t)cby0[c.comp]) * stride + (c.px - (uint32_t)cbx0[c.comp]);
         const size_t area = (size_t)c.w * c.h;
         const CblkCaps caps = cblk_capacities(area, c.Mb, cod.cblk_style);
         const size_t symcap = caps.sym, outcap = caps.out;
@@ -193,10 +218,11 @@ void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first
             if (T.index / cod.ntx != cur_row) { cur_row = T.index / cod.ntx; e->job_row_first[(size_t)l].push_back((uint32_t)e->h_jobs[(size_t)l].size()); }
             for (uint32_t c = 0; c < cod.ncomp; ++c) {
                 DwtJob j{};
-                const int x0 = ceildivpow2(T.x0, l), x1 = ceildivpow2(T.x1, l);
-                const int y0 = ceildivpow2(T.y0, l), y1 = ceildivpow2(T.y1, l);
+                const TileComp &TC = T.comps[c]; // (the tile on the component's own grid; the tile itself without sub-sampling)
+                const int x0 = ceildivpow2(TC.x0, l), x1 = ceildivpow2(TC.x1, l);
+                const int y0 = ceildivpow2(TC.y0, l), y1 = ceildivpow2(TC.y1, l);
                 j.rw = x1 - x0; j.rh = y1 - y0; j.casx = x0 & 1; j.casy = y0 & 1;
-                const long long off = (long long)c * (long long)e->plane_elems + (long long)(T.y0 - by0) * (long long)stride + (T.x0 - bx0);
+                const long long off = (long long)e->comp_off[c] + (long long)(TC.y0 - cby0[c]) * (long long)stride + (TC.x0 - cbx0[c]);
                 j.src_off = off; j.ll_off = off; j.z_off = off;
                 if (j.rw <= 0 || j.rh <= 0) continue;
                 e->h_jobs[(size_t)l].push_back(j);
@@ -291,7 +317,31 @@ bool fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tuning &tn)
 {
     bool same_depth = true;
     for (uint32_t c = 1; c < cod.ncomp; ++c) same_depth = same_depth && fa.src_depth[c] == fa.src_depth[0];
+    if (cod.subsampled() || cod.rgb_to_sycc) return false; // (the fused kernel keeps its contract: components of one size, straight from the samples)
     return !tn.no_fuse && cod.levels() >= 1 && fa.interleaved && same_depth && (cod.ncomp == 1 || cod.ncomp == 3 || cod.ncomp == 4);
+}
+
+// The stand-alone front end of one frame into planes of row stride S words, component c at dst + comp_off[c]; fa: the frame's
+// channel views (make_frontend_args), its dst_x0 / dst_y0 the planes' origin.  Components of one size: one launch of
+// frontend_kernel.  rgb_to_sycc: the channels are R, G, B[, A] of the whole image, one launch of the Y Cb Cr kernel writes every
+// component at its own size.  Sub-sampled planes given as they are: every component is a frame of its own -- one launch each.
+void run_frontend(const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t comp_off[4], size_t S, hipStream_t s)
+{
+    fa.dst_stride = (long long)S;
+    for (uint32_t c = 0; c < cod.ncomp; ++c) fa.dst[c] = dst + comp_off[c];
+    if (cod.rgb_to_sycc) { launch_frontend_sycc(fa, cod.cdx[1], cod.cdy[1], s); return; }
+    if (!cod.subsampled()) { launch_frontend(fa, s); return; }
+    for (uint32_t c = 0; c < cod.ncomp; ++c) {
+        FrontendArgs f1 = fa;
+        f1.ncomp = 1; f1.interleaved = 0; f1.mct = 0;
+        f1.src[0] = fa.src[c]; f1.colbytes[0] = fa.colbytes[c]; f1.rowbytes[0] = fa.rowbytes[c];
+        f1.sample_bytes[0] = fa.sample_bytes[c]; f1.src_depth[0] = fa.src_depth[c];
+        f1.dst[0] = fa.dst[c];
+        const int sx = cod.cdx[c], sy = cod.cdy[c];
+        f1.x0 = (fa.x0 + sx - 1) / sx; f1.width = (fa.width + sx - 1) / sx; f1.y0 = (fa.y0 + sy - 1) / sy; f1.y1 = (fa.y1 + sy - 1) / sy;
+        f1.dst_x0 = (fa.dst_x0 + sx - 1) / sx; f1.dst_y0 = (fa.dst_y0 + sy - 1) / sy;
+        launch_frontend(f1, s);
+    }
 }
 
 struct EncodeOut {
@@ -348,7 +398,7 @@ DwtLevelArgs dwt_level_args(j2k_hip_encoder *e, const Coding &cod, const Fronten
 {
     const int NL = (int)cod.levels();
     const size_t S = e->stride;
-    const size_t plane_bytes = e->plane_elems * sizeof(int32_t) * cod.ncomp;
+    const size_t plane_bytes = e->frame_elems * sizeof(int32_t);
     uint8_t *const Pf = e->P.p ? e->P.as<uint8_t>() + f * plane_bytes : nullptr;
     uint8_t *const Qf = NL >= 2 ? e->Q.as<uint8_t>() + f * plane_bytes : nullptr;
     uint8_t *const Zf = e->Z.as<uint8_t>() + f * plane_bytes;
@@ -413,10 +463,11 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     const size_t F = nframes;
     if (F < 1 || F > 1024) throw Error(J2K_HIP_ERR_PARAM, "number of frames must be 1..1024");
     if (F > 1 && (!planes_on_device || !framed)) throw Error(J2K_HIP_ERR_PARAM, "frame sequences take whole frames resident on the device");
+    const Coding cod = normalise(params); // (before the device is touched: what is refused for its parameters costs no device work)
+    if (!framed) refuse_subsampled_tiles(cod);
     HIP_CHECK(hipSetDevice(e->device));
     const Tuning tn = tuning(); // one consistent snapshot per call
     DeviceShared &dev = g_dev[e->device];
-    const Coding cod = normalise(params);
     if (cod.dci && !framed) throw Error(J2K_HIP_ERR_PARAM, "a cinema-profile frame is one tile with its TLM in the main header: encode it whole");
     if (framed) { tile_first = 0; tile_count = cod.ntiles(); }
     prepare_geometry(e, cod, tile_first, tile_count);
@@ -439,29 +490,55 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     for (uint32_t c = 0; c < cod.ncomp; ++c) dplanes[c] = planes[c];
     if (!planes_on_device) {
         Range r("j2k_hip upload");
-        // upload the byte span that holds rows [y0,y1) of every channel (one copy for interleaved frames)
-        const uint8_t *lo = nullptr, *hi = nullptr;
+        // upload the bytes that hold rows [y0,y1) of every channel: one copy for channels that share a buffer (the samples of
+        // interleaved pixels, planes that lie back to back), a copy of its own for every channel -- or group of channels --
+        // that is an allocation of its own (the planes of sub-sampled components usually are).  Nothing between two groups
+        // is read: it may be unmapped.
+        struct Span { const uint8_t *lo, *hi; };
+        Span span_of[4];
         for (uint32_t c = 0; c < cod.ncomp; ++c) {
+            const uint8_t *lo = nullptr, *hi = nullptr;
             const j2k_hip_plane &p = planes[c];
             if (!p.base) throw Error(J2K_HIP_ERR_PARAM, "channel buffer is NULL");
             if (p.sample_bits != 8 && p.sample_bits != 16) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8 or 16");
             const uint8_t *b = static_cast<const uint8_t *>(p.base);
-            const uint8_t *corners[4] = {b + (ptrdiff_t)y0 * p.rowbytes, b + (ptrdiff_t)(y1 - 1) * p.rowbytes,
-                                         b + (ptrdiff_t)y0 * p.rowbytes + (ptrdiff_t)(cod.width - 1) * p.colbytes,
-                                         b + (ptrdiff_t)(y1 - 1) * p.rowbytes + (ptrdiff_t)(cod.width - 1) * p.colbytes};
+            // (a sub-sampled component given as it is holds its own grid's samples; R, G, B, A for the Y Cb Cr front end are full size)
+            const int sx = cod.rgb_to_sycc ? 1 : cod.cdx[c], sy = cod.rgb_to_sycc ? 1 : cod.cdy[c];
+            const ptrdiff_t cy0 = (y0 + sy - 1) / sy, cy1 = (y1 + sy - 1) / sy, cw = ((ptrdiff_t)cod.width + sx - 1) / sx;
+            const uint8_t *corners[4] = {b + cy0 * p.rowbytes, b + (cy1 - 1) * p.rowbytes,
+                                         b + cy0 * p.rowbytes + (cw - 1) * p.colbytes,
+                                         b + (cy1 - 1) * p.rowbytes + (cw - 1) * p.colbytes};
             for (const uint8_t *q : corners) {
                 if (!lo || q < lo) lo = q;
                 if (!hi || q + p.sample_bits / 8 > hi) hi = q + p.sample_bits / 8;
             }
+            span_of[c] = Span{lo, hi};
         }
-        const size_t pad = reinterpret_cast<uintptr_t>(lo) & 15; // keep the host alignment phase on the device
-        const size_t span = (size_t)(hi - lo);
-        e->in.ensure(span + pad + 16);
-        uint8_t *dbase = e->in.as<uint8_t>() + pad;
+        // groups: channels whose spans overlap, touch or lie less than a page apart (bytes that close to two mapped spans are
+        // mapped themselves: padding between the planes of one buffer stays inside one copy)
+        uint32_t order[4] = {0, 1, 2, 3};
+        std::sort(order, order + cod.ncomp, [&](uint32_t a, uint32_t b) { return std::less<const uint8_t *>()(span_of[a].lo, span_of[b].lo); });
+        Span group[4];
+        uint32_t group_of[4] = {0, 0, 0, 0}, ngroups = 0;
+        for (uint32_t k = 0; k < cod.ncomp; ++k) {
+            const Span &sp = span_of[order[k]];
+            if (ngroups && reinterpret_cast<uintptr_t>(sp.lo) < reinterpret_cast<uintptr_t>(group[ngroups - 1].hi) + 4096) {
+                if (std::less<const uint8_t *>()(group[ngroups - 1].hi, sp.hi)) group[ngroups - 1].hi = sp.hi;
+            } else group[ngroups++] = sp;
+            group_of[order[k]] = ngroups - 1;
+        }
+        // (every group keeps its host alignment phase on the device)
+        size_t goff[4], total = 0;
+        for (uint32_t k = 0; k < ngroups; ++k) {
+            goff[k] = total + (reinterpret_cast<uintptr_t>(group[k].lo) & 15);
+            total = round_up(goff[k] + (size_t)(group[k].hi - group[k].lo) + 16, 256);
+        }
+        e->in.ensure(total);
         // (from the caller's pageable buffer: the runtime pins the pages in place and DMAs straight from them)
-        HIP_CHECK(hipMemcpyAsync(dbase, lo, span, hipMemcpyHostToDevice, s));
+        for (uint32_t k = 0; k < ngroups; ++k)
+            HIP_CHECK(hipMemcpyAsync(e->in.as<uint8_t>() + goff[k], group[k].lo, (size_t)(group[k].hi - group[k].lo), hipMemcpyHostToDevice, s));
         for (uint32_t c = 0; c < cod.ncomp; ++c)
-            dplanes[c].base = dbase + (static_cast<const uint8_t *>(planes[c].base) - lo);
+            dplanes[c].base = e->in.as<uint8_t>() + goff[group_of[c]] + (static_cast<const uint8_t *>(planes[c].base) - group[group_of[c]].lo);
     }
     // the upload of one frame runs beside the kernels of the others; the dense phase starts here
     Range dense_range("j2k_hip dwt+t1 enqueue");
@@ -487,7 +564,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     HIP_CHECK(hipEventRecord(e->ev[EV_UPLOAD], s));
 
     // ---- working planes (one set per frame of a sequence)
-    const size_t plane_bytes = e->plane_elems * sizeof(int32_t) * cod.ncomp;
+    const size_t plane_bytes = e->frame_elems * sizeof(int32_t);
     FrontendArgs fa0 = make_frontend_args(cod, dplanes, x0, y0, x1, y1);
     const bool fused = fuse_frontend(cod, fa0, tn);
     // P holds the front end's output (unfused) and the LL of levels 2, 4, ..: a fused path with fewer than
@@ -507,9 +584,8 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     if (f > 0) for (uint32_t c = 0; c < cod.ncomp; ++c) dplanes[c] = planes[f * cod.ncomp + c];
     FrontendArgs fa = f == 0 ? fa0 : make_frontend_args(cod, dplanes, x0, y0, x1, y1);
     if (!fused) {
-        for (uint32_t c = 0; c < cod.ncomp; ++c) fa.dst[c] = reinterpret_cast<int32_t *>(e->P.as<uint8_t>() + f * plane_bytes) + c * e->plane_elems;
-        fa.dst_stride = (long long)S; fa.dst_x0 = x0; fa.dst_y0 = y0;
-        launch_frontend(fa, s);
+        fa.dst_x0 = x0; fa.dst_y0 = y0;
+        run_frontend(cod, fa, reinterpret_cast<int32_t *>(e->P.as<uint8_t>() + f * plane_bytes), e->comp_off, S, s);
     }
     if (f == 0) e->last_fa = fa;
     if (f == 0) HIP_CHECK(hipEventRecord(e->ev[EV_FRONT], s));
@@ -552,7 +628,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
         for (size_t f = 0; f < F; ++f)
             for (size_t i = 0; i < nb1; ++i) {
                 CblkDev d = e->h_blks[i];
-                d.coef_off += (unsigned long long)f * cod.ncomp * e->plane_elems;
+                d.coef_off += (unsigned long long)f * e->frame_elems;
                 d.sym_off += (unsigned long long)f * e->sym_bytes;
                 d.out_off += (unsigned long long)f * e->out_bytes;
                 e->h_blks_seq[f * nb1 + i] = d;
@@ -1053,6 +1129,7 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     const int NL = (int)cod.levels();
     // (a code-block style: its coder is not the gated two-wave kernel this path is built around)
     if (tn.bands < 0 || NL < 1 || tn.no_fuse || cod.rate_control() || cod.dci || cod.cblk_style || g.cblks.empty()) return false;
+    if (cod.subsampled() || cod.rgb_to_sycc) return false; // (components of their own sizes run the unfused path, in one piece)
     // Other encode calls in progress on the device (a host that renders on several threads, or pipelines handles with _begin /
     // _end): their frames overlap as wholes -- one frame's upload beside another's coder chains -- and ten more coder launches
     // per frame only get in each other's way (three handles from one thread: 31 -> 50 ms per frame).  The bands are for the call
@@ -1477,8 +1554,6 @@ std::string &j2k_hip::create_error()
 
 namespace {
 
-
-
 } // namespace
 
 extern "C" {
@@ -1830,6 +1905,21 @@ int j2k_hip_stage_frontend(j2k_hip_encoder *e, const j2k_hip_params *params, con
         HIP_CHECK(hipSetDevice(e->device));
         const Coding cod = normalise(params);
         FrontendArgs fa = make_frontend_args(cod, planes_device, 0, 0, (int)cod.width, (int)cod.height);
+        if (cod.subsampled() || cod.rgb_to_sycc) {
+            // components of their own sizes: into planes of a common, aligned row stride as an encode has them, then dense to d_out
+            const PlaneLayout lay = plane_layout(cod, 0, 0, (int)cod.width, (int)cod.height);
+            e->P.ensure(lay.frame_elems * sizeof(int32_t));
+            run_frontend(cod, fa, e->P.as<int32_t>(), lay.comp_off, lay.stride, e->stream);
+            HIP_CHECK(hipGetLastError());
+            uint8_t *out = static_cast<uint8_t *>(d_out);
+            for (uint32_t c = 0; c < cod.ncomp; ++c) {
+                const size_t cw = (size_t)lay.cw[c], chh = (size_t)lay.ch[c];
+                HIP_CHECK(hipMemcpy2DAsync(out, cw * 4, e->P.as<int32_t>() + lay.comp_off[c], lay.stride * 4, cw * 4, chh, hipMemcpyDeviceToDevice, e->stream));
+                out += cw * chh * 4;
+            }
+            HIP_CHECK(hipStreamSynchronize(e->stream));
+            return;
+        }
         for (uint32_t c = 0; c < cod.ncomp; ++c) fa.dst[c] = static_cast<int32_t *>(d_out) + (size_t)c * cod.width * cod.height;
         fa.dst_stride = cod.width;
         launch_frontend(fa, e->stream);
@@ -1934,15 +2024,14 @@ int j2k_hip_stage_transform(j2k_hip_encoder *e, const j2k_hip_params *params, co
         for (const Tile &T : g.tiles) { y1 = std::max(y1, T.y1); x1 = std::max(x1, T.x1); }
         FrontendArgs fa = make_frontend_args(cod, planes_device, x0, y0, x1, y1);
         const bool fused = fuse_frontend(cod, fa, tn);
-        const size_t plane_bytes = e->plane_elems * sizeof(int32_t) * cod.ncomp;
+        const size_t plane_bytes = e->frame_elems * sizeof(int32_t);
         // (the planes are filled first: a word that no launch writes shows as 0xA5A5A5A5 instead of an earlier call's result)
         if (!fused || NL >= 3) { e->P.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->P.p, 0xA5, plane_bytes, s)); }
         if (NL >= 1) { e->Z.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->Z.p, 0xA5, plane_bytes, s)); }
         if (NL >= 2) { e->Q.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->Q.p, 0xA5, plane_bytes, s)); }
         if (!fused) {
-            for (uint32_t c = 0; c < cod.ncomp; ++c) fa.dst[c] = e->P.as<int32_t>() + c * e->plane_elems;
-            fa.dst_stride = (long long)S; fa.dst_x0 = x0; fa.dst_y0 = y0;
-            launch_frontend(fa, s);
+            fa.dst_x0 = x0; fa.dst_y0 = y0;
+            run_frontend(cod, fa, e->P.as<int32_t>(), e->comp_off, S, s);
         }
         for (int l = 0; l < NL; ++l) {
             const std::vector<int> &b = bounds[(size_t)l];
@@ -1957,10 +2046,13 @@ int j2k_hip_stage_transform(j2k_hip_encoder *e, const j2k_hip_params *params, co
         }
         // the coefficient planes without their stride padding (zero levels: the front end's output)
         const uint8_t *from = NL >= 1 ? e->Z.as<uint8_t>() : e->P.as<uint8_t>();
-        const size_t W = (size_t)(x1 - x0), H = (size_t)(y1 - y0);
-        for (uint32_t c = 0; c < cod.ncomp; ++c)
-            HIP_CHECK(hipMemcpy2DAsync(static_cast<uint8_t *>(d_out) + (size_t)c * W * H * 4, W * 4, from + (size_t)c * e->plane_elems * 4, S * 4, W * 4, H,
-                                       hipMemcpyDeviceToDevice, s));
+        uint8_t *out = static_cast<uint8_t *>(d_out);
+        for (uint32_t c = 0; c < cod.ncomp; ++c) { // (every component at its own size: the box on the component's grid)
+            const int sx = cod.cdx[c], sy = cod.cdy[c];
+            const size_t W = (size_t)((x1 + sx - 1) / sx - (x0 + sx - 1) / sx), H = (size_t)((y1 + sy - 1) / sy - (y0 + sy - 1) / sy);
+            HIP_CHECK(hipMemcpy2DAsync(out, W * 4, from + e->comp_off[c] * 4, S * 4, W * 4, H, hipMemcpyDeviceToDevice, s));
+            out += W * H * 4;
+        }
         HIP_CHECK(hipStreamSynchronize(s));
     });
 }

@@ -8,6 +8,7 @@
 // Algorithmic bytes per pixel: 4*S read (S = bytes per sample, interleaved ARGB) + 4*Ncomp written.
 // When the frame has the After Effects layout and 1 or 3 components, this stage is fused into the
 // level-1 DWT kernel instead (dwt.hip) and this kernel is not launched at all.
+// A second kernel (frontend_sycc_kernel, below) makes Y, Cb, Cr from R, G, B and decimates the chroma as it loads it.
 #include "frontend_ops.h"
 
 #include <type_traits>
@@ -44,7 +45,114 @@ __global__ __launch_bounds__(256) void frontend_kernel(FrontendArgs a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// RGB -> Y Cb Cr with chroma decimation (j2k_hip_params.rgb_to_sycc): the analysis to the replicating sYCC read of the decode's
+// RGBA output kernel.  One lane = one chroma sample = SX x SY pixels: it loads each of them once (the interleaved pixel as one
+// 4- or 8-byte word, or the strided samples), applies Promote and the depth conversion, writes their Y (and A) -- SX adjacent
+// words of a row, one 8-byte store for SX = 2 -- and one Cb and one Cr.  Lanes run along the row, so a wave's loads and stores
+// cover contiguous bytes; nothing of full size but Y (and A) is ever written.  A pixel beyond the right or bottom edge repeats
+// the last column or row -- out of the registers that hold it, not out of memory.
+// Exact integer arithmetic (include/j2k_hip.h): Y's sum stays below 2^32, a pixel's chroma term within +-2^31, the sum over up
+// to four pixels in 64 bits; the shift is arithmetic (floor).  The float planes of the 9/7 path receive the same integers.
+// Algorithmic bytes per pixel: 4*S read + 4*(1 [+ 1 alpha] + 2 / (SX*SY)) written.
+__device__ __forceinline__ int fe_sample(const FrontendArgs &a, int c, unsigned raw)
+{
+    if (a.promote && a.sample_bytes[c] == 2) raw = promote16(raw);
+    return (int)depth_convert(raw, a.src_depth[c], a.prec);
+}
+
+template <bool REV, int SX, int SY>
+__global__ __launch_bounds__(256) void frontend_sycc_kernel(FrontendArgs a)
+{
+    using T = typename std::conditional<REV, int, float>::type;
+    constexpr int K = (SX == 2 ? 1 : 0) + (SY == 2 ? 1 : 0);
+    const int cw = (a.width + SX - 1) / SX, ch = (a.y1 + SY - 1) / SY;
+    const int cx = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (cx >= cw) return;
+    const int dc = 1 << (a.prec - 1), top = (1 << a.prec) - 1;
+    const bool alpha = a.ncomp == 4;
+    T *const dy = reinterpret_cast<T *>(a.dst[0]), *const dcb = reinterpret_cast<T *>(a.dst[1]), *const dcr = reinterpret_cast<T *>(a.dst[2]);
+    T *const da = reinterpret_cast<T *>(a.dst[3]);
+    for (int cy = (int)blockIdx.y; cy < ch; cy += (int)gridDim.y) {
+        long long scb = 0, scr = 0, rcb = 0, rcr = 0;
+#pragma unroll
+        for (int j = 0; j < SY; ++j) {
+            const int y = cy * SY + j;
+            if (y < a.y1) { // (a row below the image repeats the sums of the row above it)
+                rcb = 0; rcr = 0;
+                T yv[SX], av[SX];
+                long long pcb = 0, pcr = 0;
+#pragma unroll
+                for (int i = 0; i < SX; ++i) {
+                    const int x = cx * SX + i;
+                    if (x < a.width) { // (a column right of the image repeats the pixel left of it)
+                        unsigned raw[4] = {0, 0, 0, 0};
+                        if (a.interleaved) {
+                            const uint8_t *p = a.pixel_base + (long long)y * a.rowbytes[0] + (long long)x * a.pixel_bytes;
+                            if (a.pixel_bytes == 8) fe_unpack64(a, *reinterpret_cast<const uint2 *>(p), raw);
+                            else fe_unpack32(a, *reinterpret_cast<const unsigned *>(p), raw);
+                        } else {
+#pragma unroll
+                            for (int c = 0; c < 4; ++c)
+                                if (c < a.ncomp) {
+                                    const uint8_t *p = a.src[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
+                                    raw[c] = a.sample_bytes[c] == 2 ? *reinterpret_cast<const unsigned short *>(p) : *p;
+                                }
+                        }
+                        const int r = fe_sample(a, 0, raw[0]), g = fe_sample(a, 1, raw[1]), b = fe_sample(a, 2, raw[2]);
+                        const unsigned yy = (19595u * (unsigned)r + 38470u * (unsigned)g + 7471u * (unsigned)b + 32768u) >> 16;
+                        yv[i] = (T)((int)yy - dc);
+                        av[i] = alpha ? (T)(fe_sample(a, 3, raw[3]) - dc) : (T)0;
+                        pcb = -11059LL * r - 21709LL * g + 32768LL * b;
+                        pcr = 32768LL * r - 27439LL * g - 5329LL * b;
+                    }
+                    rcb += pcb; rcr += pcr;
+                }
+                const long long o = (long long)y * a.dst_stride + (long long)cx * SX;
+                if constexpr (SX == 2) {
+                    if (cx * 2 + 1 < a.width) { // (dst_stride is even and the planes are 8-byte aligned)
+                        using T2 = typename std::conditional<REV, int2, float2>::type;
+                        *reinterpret_cast<T2 *>(dy + o) = T2{yv[0], yv[1]};
+                        if (alpha) *reinterpret_cast<T2 *>(da + o) = T2{av[0], av[1]};
+                    } else {
+                        dy[o] = yv[0];
+                        if (alpha) da[o] = av[0];
+                    }
+                } else {
+                    dy[o] = yv[0];
+                    if (alpha) da[o] = av[0];
+                }
+            }
+            scb += rcb; scr += rcr;
+        }
+        const long long half = 1LL << (15 + K);
+        long long cb = dc + ((scb + half) >> (16 + K)), cr = dc + ((scr + half) >> (16 + K));
+        cb = cb < 0 ? 0 : (cb > top ? top : cb);
+        cr = cr < 0 ? 0 : (cr > top ? top : cr);
+        const long long oc = (long long)cy * a.dst_stride + cx;
+        dcb[oc] = (T)((int)cb - dc);
+        dcr[oc] = (T)((int)cr - dc);
+    }
+}
+
+template <bool REV>
+void launch_sycc(const FrontendArgs &a, int sub_x, int sub_y, dim3 grid, hipStream_t s)
+{
+    if (sub_x == 1 && sub_y == 1) hipLaunchKernelGGL((frontend_sycc_kernel<REV, 1, 1>), grid, dim3(256), 0, s, a);
+    else if (sub_x == 2 && sub_y == 1) hipLaunchKernelGGL((frontend_sycc_kernel<REV, 2, 1>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((frontend_sycc_kernel<REV, 2, 2>), grid, dim3(256), 0, s, a);
+}
+
 } // namespace
+
+void launch_frontend_sycc(const FrontendArgs &a, int sub_x, int sub_y, hipStream_t s)
+{
+    if (a.y1 <= 0 || a.width <= 0) return;
+    const int cw = (a.width + sub_x - 1) / sub_x, ch = (a.y1 + sub_y - 1) / sub_y;
+    dim3 grid((unsigned)((cw + 255) / 256), (unsigned)(ch < 65535 ? ch : 65535), 1);
+    if (a.reversible) launch_sycc<true>(a, sub_x, sub_y, grid, s);
+    else launch_sycc<false>(a, sub_x, sub_y, grid, s);
+}
 
 void launch_frontend(const FrontendArgs &a, hipStream_t s)
 {

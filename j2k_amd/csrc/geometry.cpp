@@ -121,6 +121,32 @@ Coding normalise(const j2k_hip_params *p)
         if (p->layer_psnr) throw Error(J2K_HIP_ERR_PARAM, "cblk_style cannot be combined with layer_psnr: rate control does not price codeword segments");
         c.cblk_style = p->cblk_style;
     }
+    // sub-sampled components (SIZ XRsiz / YRsiz) and the RGB -> Y Cb Cr front end
+    for (uint32_t i = 0; i < 4; ++i) {
+        const uint32_t sx = p->comp_sub_x[i] ? p->comp_sub_x[i] : 1, sy = p->comp_sub_y[i] ? p->comp_sub_y[i] : 1;
+        if ((sx != 1 && sx != 2 && sx != 4) || (sy != 1 && sy != 2 && sy != 4))
+            throw Error(J2K_HIP_ERR_PARAM, "comp_sub_x / comp_sub_y: a sub-sampling factor must be 1, 2 or 4");
+        if (i >= c.ncomp) { if (sx != 1 || sy != 1) throw Error(J2K_HIP_ERR_PARAM, "comp_sub_x / comp_sub_y: a factor for a channel that does not exist"); continue; }
+        c.cdx[i] = (uint8_t)sx; c.cdy[i] = (uint8_t)sy;
+    }
+    if (p->rgb_to_sycc > 1) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_sycc must be 0 or 1");
+    c.rgb_to_sycc = p->rgb_to_sycc != 0;
+    if (c.subsampled() || c.rgb_to_sycc) {
+        const char *what = c.subsampled() ? "comp_sub_x / comp_sub_y" : "rgb_to_sycc";
+        if (c.cdx[0] != 1 || c.cdy[0] != 1) throw Error(J2K_HIP_ERR_PARAM, "comp_sub_x / comp_sub_y: component 0 cannot be sub-sampled");
+        if (c.rgb_to_sycc && p->ycc) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_sycc cannot be combined with ycc: the components are Y Cb Cr already");
+        if (p->ycc) throw Error(J2K_HIP_ERR_PARAM, "comp_sub_x / comp_sub_y cannot be combined with ycc: the colour transform needs components of one size");
+        if (p->dci_profile) throw Error(J2K_HIP_ERR_PARAM, std::string(what) + " cannot be combined with dci_profile: a digital cinema profile has three full-size components");
+        if (p->layer_psnr) throw Error(J2K_HIP_ERR_PARAM, std::string(what) + " cannot be combined with layer_psnr (use layer_rates)");
+        if (c.rgb_to_sycc) {
+            if (c.ncomp < 3) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_sycc needs 3 or 4 channels (R, G, B[, A])");
+            const uint32_t sx = c.cdx[1], sy = c.cdy[1];
+            if (c.cdx[2] != sx || c.cdy[2] != sy || !((sx == 1 && sy == 1) || (sx == 2 && sy == 1) || (sx == 2 && sy == 2)))
+                throw Error(J2K_HIP_ERR_PARAM, "rgb_to_sycc: comp_sub_x / comp_sub_y of components 1 and 2 must both be (1,1), (2,1) or (2,2)");
+            if (c.ncomp == 4 && (c.cdx[3] != 1 || c.cdy[3] != 1))
+                throw Error(J2K_HIP_ERR_PARAM, "rgb_to_sycc: comp_sub_x / comp_sub_y of the fourth component (alpha) must be (1,1)");
+        }
+    }
     // file wrapper
     if (p->file_format != J2K_HIP_FMT_J2K && p->file_format != J2K_HIP_FMT_JP2)
         throw Error(J2K_HIP_ERR_PARAM, "file_format must be J2K_HIP_FMT_J2K or J2K_HIP_FMT_JP2");
@@ -142,6 +168,12 @@ Coding normalise(const j2k_hip_params *p)
     if (!(p->dpi >= 0.0f) || p->dpi > 1e6f) throw Error(J2K_HIP_ERR_PARAM, "dpi must be finite and >= 0");
     c.dpi = p->dpi;
     return c;
+}
+
+void refuse_subsampled_tiles(const Coding &cod)
+{
+    if (cod.subsampled() || cod.rgb_to_sycc)
+        throw Error(J2K_HIP_ERR_PARAM, "comp_sub / rgb_to_sycc: sub-sampled components are not written by the tile-sharded entry points");
 }
 
 // L2 norms of the synthesis basis vectors, as tabulated for the 5/3 and 9/7 kernels (used by

@@ -170,6 +170,9 @@ struct j2k_hip_encoder {
     // share of the image, not for the whole image): box origin in image coordinates, row stride and plane size in words
     int box_x0 = 0, box_y0 = 0;
     size_t stride = 0, plane_elems = 0;
+    // component c's working plane starts comp_off[c] words into a frame's planes and has the rows of its own grid (sub-sampled
+    // components: fewer); frame_elems words hold all of them.  Without sub-sampling: c * plane_elems, ncomp * plane_elems.
+    size_t comp_off[4] = {0, 0, 0, 0}, frame_elems = 0;
     // band-pipelined encode (bands.h).  Streams: the row bands' H2D, the stages' D2H; events: band k has arrived, stage k's
     // coder + packing + results are through, stage k's codewords are in host memory
     static constexpr int kMaxBands = 8, kMaxStages = kMaxBands + 2; // (a coder stream per stage: mqs[]; the last band's blocks are up to three stages)

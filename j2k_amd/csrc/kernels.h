@@ -78,6 +78,11 @@ struct FrontendArgs {
     long long dst_stride; // words per row
 };
 void launch_frontend(const FrontendArgs &a, hipStream_t s);
+// RGB -> Y Cb Cr with chroma decimation (j2k_hip_params.rgb_to_sycc): the channels are R, G, B[, A] of the whole image
+// [0, width) x [0, y1) (x0 = y0 = dst_x0 = dst_y0 = 0); dst[0] (Y) and dst[3] (A) receive width x y1 samples, dst[1] / dst[2]
+// (Cb, Cr) ceil(width / sub_x) x ceil(y1 / sub_y), all at dst_stride (even) words per row, DC-shifted; (sub_x, sub_y) one of
+// (1,1), (2,1), (2,2).  mct is ignored.
+void launch_frontend_sycc(const FrontendArgs &a, int sub_x, int sub_y, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Forward DWT, one decomposition level per launch, vertical + horizontal lifting fused in

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/j2k_hip.h"
+#include "common.h"
 
 namespace {
 
@@ -85,6 +86,8 @@ int j2k_hip_encode_tiles_distributed(const int *devices, uint32_t num_devices, c
     int rc = j2k_hip_main_header(params, header.data(), header.size(), &hlen, &ntiles);
     if (rc != J2K_HIP_OK) { g_multi_err = j2k_hip_last_error(nullptr); return rc; }
     header.resize(hlen);
+    try { j2k_hip::refuse_subsampled_tiles(j2k_hip::normalise(params)); } // (before a handle is created)
+    catch (const j2k_hip::Error &x) { g_multi_err = x.what(); return x.code; }
     const uint32_t nd = std::min(num_devices, ntiles);
     // contiguous blocks of tiles in raster order, sizes differing by at most one (SURVEY.md 8e "Partitioning")
     std::vector<uint32_t> first(nd + 1, 0);

@@ -114,7 +114,7 @@ std::vector<uint8_t> main_header(const Coding &c)
     o.u32(c.width); o.u32(c.height); o.u32(0); o.u32(0);
     o.u32(c.tile_w); o.u32(c.tile_h); o.u32(0); o.u32(0);
     o.u16(c.ncomp);
-    for (uint32_t i = 0; i < c.ncomp; ++i) { o.u8(c.prec - 1); o.u8(1); o.u8(1); }
+    for (uint32_t i = 0; i < c.ncomp; ++i) { o.u8(c.prec - 1); o.u8(c.cdx[i]); o.u8(c.cdy[i]); }
     o.u16(0xff52); o.u16(c.user_precincts ? 12 + c.numres : 12); o.u8(c.user_precincts ? 1 : 0); // COD; Scod bit 0 = precinct sizes follow
     o.u8(c.prog); o.u16(c.layers); o.u8(c.mct ? 1 : 0);
     o.u8(c.numres - 1); o.u8(c.cbw - 2); o.u8(c.cbh - 2); o.u8(c.cblk_style); o.u8(c.reversible ? 1 : 0);

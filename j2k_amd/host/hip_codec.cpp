@@ -388,6 +388,15 @@ void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &b
         p.promote_ae16 = all16 ? 1 : 0;
     }
 
+    if (_mode == HonourSettings && (_options & (Chroma422 | Chroma420)) && buffer.channels >= 3 && !p.dci_profile) {
+        // Y Cb Cr with sub-sampled chroma out of the world's R, G, B: the front end converts and decimates (j2k_hip.h)
+        p.rgb_to_sycc = 1; p.ycc = 0;
+        p.comp_sub_x[1] = p.comp_sub_x[2] = 2;
+        p.comp_sub_y[1] = p.comp_sub_y[2] = (_options & Chroma420) ? 2 : 1;
+        p.color_space = J2K_HIP_CS_SYCC; // (reaches the file with the JP2 wrapper only)
+        p.icc_profile = NULL; p.icc_profile_len = 0; // (a profile of the RGB world does not describe Y Cb Cr)
+    }
+
     if (!thread_handle(_device)) throw Exception("Error writing file"); // reference: :756-757 (no CPU fallback)
     int rc = j2k_hip_encode(t_enc.h, &p, planes, sink_write, &file);
     if (rc == J2K_HIP_ERR_DEVICE && file.Tell() == 0) {

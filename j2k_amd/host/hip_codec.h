@@ -26,7 +26,12 @@ class HipCodec : public Codec {
     //   DemoteAE16: the mirror on the read side.  ReadRGBA into four 16-bit (USHORT) channels delivers 15+1-bit samples:
     //   Demote() (FrameSeq.cpp:265-268) is applied by the decode's output kernel, so the caller drops the DemoteWorld pass
     //   of j2k_DrawSparseFrame (src/aftereffects/j2k.cpp:482-492).
-    enum Options { NoOptions = 0, PromoteAE16 = 1, DemoteAE16 = 2 };
+    //   Chroma422 / Chroma420 (HonourSettings, buffers of 3 or 4 channels; ignored in ReferenceLiteral mode, for 1- and
+    //   2-channel buffers and under a cinema profile): WriteFile writes Y Cb Cr with the chroma sub-sampled 2 x 1 / 2 x 2 --
+    //   what broadcast and proxy JPEG 2000 use -- made from the world's R, G, B on the GPU while the samples are loaded
+    //   (j2k_hip_params.rgb_to_sycc; settings.ycc is not used, an alpha channel stays full size).  The colour space written
+    //   is sYCC: with FileInfo.format JP2 the colr box says so and ReadRGBA returns R, G, B again.  Both bits: 4:2:0.
+    enum Options { NoOptions = 0, PromoteAE16 = 1, DemoteAE16 = 2, Chroma422 = 4, Chroma420 = 8 };
 
     // device: HIP device ordinal, or -1 = the host threads that call this codec take the devices in turn
     explicit HipCodec(Mode mode = ReferenceLiteral, int device = -1, unsigned options = NoOptions);

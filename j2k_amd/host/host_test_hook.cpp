@@ -346,7 +346,10 @@ long j2k_host_test_write_ex(const unsigned char *frame, unsigned width, unsigned
     MemoryOutputFile file;
     if (max_write >= 0) file.max_write = (size_t)max_write;
     const bool promote = std::getenv("J2K_HOST_TEST_PROMOTE") != NULL; // test knob: the world holds 15+1-bit samples
-    HipCodec hip(honour ? HipCodec::HonourSettings : HipCodec::ReferenceLiteral, -1, promote ? HipCodec::PromoteAE16 : HipCodec::NoOptions);
+    unsigned options = promote ? HipCodec::PromoteAE16 : HipCodec::NoOptions;
+    if (const char *ch = std::getenv("J2K_HOST_TEST_CHROMA")) // test knob: 422 | 420 -> HipCodec::Chroma422 / Chroma420
+        options |= std::atoi(ch) == 420 ? HipCodec::Chroma420 : (std::atoi(ch) == 422 ? HipCodec::Chroma422 : 0u);
+    HipCodec hip(honour ? HipCodec::HonourSettings : HipCodec::ReferenceLiteral, -1, options);
     Codec *codec = &hip; // through the interface, as RGBAoutputFile does (j2k_rgba_file.cpp:812)
     try {
         codec->WriteFile(file, info, buf, NULL);
