@@ -174,13 +174,31 @@ enum { J2K_HIP_CS_UNSPECIFIED = 0, J2K_HIP_CS_SRGB = 1, J2K_HIP_CS_GRAY = 2, J2K
  * One image channel = a faithful image of j2k::Channel (reference: src/common/j2k_codec.h:221-247):
  * a borrowed, strided view, valid only for the duration of the call, never written.
  * For the *_device entry points `base` is a device pointer.
+ *
+ * Float samples (an After Effects 32-bpc world, PF_PixelFormat_ARGB128): sample_bits == 32 means IEEE binary32 samples of
+ * nominal range 0..1.  depth keeps its meaning: it is the integer depth d (1..16) that the float stands for; d < 1 or
+ * d > 16 is J2K_HIP_ERR_PARAM.  base, colbytes and rowbytes must be multiples of 4 (J2K_HIP_ERR_PARAM before any device
+ * work).  A float sample x becomes the d-bit integer sample v that everything downstream sees as it sees a d-bit integer
+ * sample -- the depth conversion to params.depth, the DC shift, the colour transform, rgb_to_sycc:
+ *     t = x > 1 ? 1 : (x > 0 ? x : 0)                 NaN, -0.0, negatives and -inf give 0, +inf gives 1
+ *     v = (unsigned)(t * (float)(2^d - 1) + 0.5f)     product and sum each rounded to binary32; the cast truncates
+ *     v = Promote((unsigned)(t * 32768.0f + 0.5f))    with promote_ae16, which needs d == 16 on a float channel
+ * (d = 8: the reference's Convert<PF_FpShort, A_u_char>; d = 16: FLOAT_TO_SIXTEEN, src/aftereffects/FrameSeq.h:47; the
+ * promote form: its ARGB128 -> ARGB64 copy followed by PromoteWorld, FrameSeq.cpp:95-110, :189-198, taken as the 16-bit
+ * value it evidently means).  The float of a grid point, (float)p / (float)(2^d - 1), returns p for every d and p, and
+ * v / 32768 returns Promote(v): a float world made from integers encodes to the integer world's bytes.
+ * Every entry point that takes planes takes float ones, and float and integer channels may mix in one call.  Float frames
+ * run the front end as a pass of its own (like sub-sampled ones: never fused into DWT level 1, never band-pipelined --
+ * j2k_hip_stats.bands = 0).  sample_bits other than 8, 16 or 32: J2K_HIP_ERR_PARAM.  J2K_HIP_ABI_VERSION is still 9: no
+ * struct and no function changed -- a sample type was added that every earlier version refused.
  */
 typedef struct j2k_hip_plane {
     const void *base;    /* Channel.buf                                                          */
     ptrdiff_t colbytes;  /* Channel.colbytes                                                     */
     ptrdiff_t rowbytes;  /* Channel.rowbytes                                                     */
-    uint32_t sample_bits; /* 8 (sampleType UCHAR) or 16 (USHORT)                                 */
-    uint32_t depth;       /* Channel.depth (significant bits in the sample, = sample_bits in AE) */
+    uint32_t sample_bits; /* 8 (sampleType UCHAR), 16 (USHORT) or 32 (IEEE float, see above)     */
+    uint32_t depth;       /* Channel.depth (significant bits in the sample, = sample_bits in AE);
+                             float samples: the integer depth 1..16 they stand for              */
 } j2k_hip_plane;
 
 /* Sink = OutputFile::Write (reference: src/common/j2k_io.h:58-79). Must return n on success.
@@ -361,11 +379,21 @@ int j2k_hip_read_info(const void *file, size_t len, j2k_hip_file_info *info);
 /* One destination channel = a faithful image of the j2k::Channel the host passes in its Buffer (reference:
  * src/common/j2k_codec.h:221-247): a borrowed, strided view that is written.  Only the channel's samples are
  * written, like Codec::CopyBuffer (src/common/j2k_codec.cpp:402-427) does; width/height = Channel.width/.height
- * decide how much is copied (:496-499). */
+ * decide how much is copied (:496-499).
+ * Float destinations: sample_bits == 32 means IEEE binary32 samples of nominal range 0..1, depth the integer depth d (1..16)
+ * they stand for, base / colbytes / rowbytes multiples of 4 (anything else: J2K_HIP_ERR_PARAM before any device work).  The
+ * integer ov of depth d is computed exactly as for an integer destination -- component samples, colour conversion,
+ * palette, CopyChannel's depth conversion, the alpha fill -- and stored as (float)ov / (float)(2^d - 1), a correctly
+ * rounded division; the highest value gives exactly 1.0f.  (A palette entry widens to 16 bits, b * 257, for d > 8, as it
+ * does for 16-bit samples.)  This holds for every decode entry point, the four planes of j2k_hip_rgba_dst included; there
+ * demote_ae16 (d == 16) stores (float)Demote(ov) / 32768.0f -- what the reference's DemoteWorld and its ARGB64 -> ARGB128
+ * copy leave (src/aftereffects/FrameSeq.cpp:82-86, :211-216) -- and the opaque alpha fill is exactly 1.0f.  Outside
+ * j2k_hip_rgba_dst, float and integer channels may mix in one call.  The 9/7 path still rounds to integers first: the floats
+ * are those of libopenjp2's samples. */
 typedef struct j2k_hip_outplane {
     void *base;
     ptrdiff_t colbytes, rowbytes;
-    uint32_t sample_bits;        /* 8 (UCHAR) or 16 (USHORT)                                             */
+    uint32_t sample_bits;        /* 8 (UCHAR), 16 (USHORT) or 32 (IEEE float, see above)                 */
     uint32_t depth;              /* Channel.depth: the decoded precision is converted to it like CopyChannel */
     uint32_t width, height;
 } j2k_hip_outplane;
@@ -426,7 +454,8 @@ int j2k_hip_region_footprint(int reversible, uint32_t width, uint32_t height, ui
 enum { J2K_HIP_RGBA_RGB = 1, J2K_HIP_RGBA_GREY = 2, J2K_HIP_RGBA_PALETTE = 3, J2K_HIP_RGBA_SYCC = 4 };
 int j2k_hip_rgba_mode(const void *file, size_t len, uint32_t *mode);
 
-/* The four destination channels.  They share sample_bits (8 or 16) and depth D (1 <= D <= sample_bits).  Per pixel:
+/* The four destination channels.  They share sample_bits (8, 16 or 32 = float: j2k_hip_outplane) and depth D (1 <= D <=
+ * sample_bits; float: 1 <= D <= 16).  Per pixel:
  *   1. component samples exactly as j2k_hip_decode delivers them at depth D (replication of sub-sampled components,
  *      inverse RCT / ICT, DC shift, clamp, CopyChannel's depth conversion);
  *   2. RGB: R, G, B[, A] = v0, v1, v2[, v3].  GREY: R = G = B = v0[, A = v1].
@@ -440,12 +469,13 @@ int j2k_hip_rgba_mode(const void *file, size_t len, uint32_t *mode);
  *   3. a mode that delivers no A fills it with 2^D - 1 (the reference narrows that value to 8 bits first, :416, so a
  *      16-bit world gets 255 there: deliberately not reproduced);
  *   4. demote_ae16: every channel, the filled A included, leaves as v > 32768 ? ((v - 1) >> 1) + 1 : v >> 1 (Demote,
- *      src/aftereffects/FrameSeq.cpp:265-268); needs sample_bits == 16 and D == 16;
+ *      src/aftereffects/FrameSeq.cpp:265-268); needs sample_bits == 16 or 32 and D == 16;
  *   5. only samples of the given channels are written; a.base == NULL: no alpha wanted.  Four channels that are the four
- *      samples of one pixel record (A,R,G,B or R,G,B,A interleaved, record-aligned) leave as one store per pixel.
+ *      samples of one pixel record (A,R,G,B or R,G,B,A interleaved, record-aligned) leave as one store per pixel (an
+ *      ARGB128 pixel: one 16-byte store).
  * Width, height, subsample and region are j2k_hip_decode's / j2k_hip_decode_region's (region == NULL: the whole image).
  * Refused before any device work, nothing written: J2K_HIP_ERR_PARAM for a bad struct_size, a NULL r / g / b, channels of
- * unlike sample_bits or depth, demote_ae16 without 16-bit samples of depth 16, a bad region; J2K_HIP_ERR_UNSUPPORTED for
+ * unlike sample_bits or depth, demote_ae16 without 16-bit or float samples of depth 16, a bad region; J2K_HIP_ERR_UNSUPPORTED for
  * what j2k_hip_rgba_mode does not classify.  J2K_HIP_ABI_VERSION is still 9: functions were added, none changed. */
 typedef struct j2k_hip_rgba_dst {
     uint32_t struct_size;
@@ -595,7 +625,8 @@ int j2k_hip_stage_idwt_window(j2k_hip_encoder *enc, int reversible, uint32_t wid
  * for reversible, float32 otherwise) at row stride `stride` words, starting `offset` words into the device buffer d_comp of
  * comp_words words.  planes[i] receives component i as in j2k_hip_decode, except that planes[i].base is a byte OFFSET into
  * the device buffer d_buf of buf_bytes bytes; only the channels' samples are written.  Refused with J2K_HIP_ERR_PARAM:
- * what j2k_hip_decode refuses (sample_bits other than 8 / 16, depth outside 1..sample_bits, precisions outside 1..16,
+ * what j2k_hip_decode refuses (sample_bits other than 8 / 16 / 32, depth outside 1..sample_bits -- float: 1..16 --, a float
+ * channel off the 4-byte grid, precisions outside 1..16,
  * unlike precision or sub-sampling on components 0..2 with mct), a component plane or a channel that leaves its buffer,
  * and a 16-bit channel with a sample at an odd address. */
 typedef struct j2k_hip_outcomp {

@@ -384,8 +384,28 @@ def file_header(params: Params, codestream_len: int) -> bytes:
     return buf.raw[:n.value]
 
 
+_SAMPLE_DTYPES = (np.uint8, np.uint16, np.float32)
+
+
+def _sample_dtype(bits: int):
+    """numpy type of a sample_bits value: 8 / 16-bit unsigned integers, 32 = IEEE binary32 of nominal range 0..1."""
+    return {8: np.uint8, 16: np.uint16, 32: np.float32}[bits]
+
+
+def _layout_depth(layout: dict) -> int:
+    """Channel.depth of an AE frame's samples: the sample type's bits; a float frame (sample_bytes 4, synth.ae_frame_float)
+    stands for integers of layout["depth"] bits (default 16)."""
+    sb = layout["sample_bytes"]
+    return layout.get("depth", 16) if sb == 4 else 8 * sb
+
+
+def _array_depth(a: np.ndarray) -> int:
+    return 16 if a.dtype == np.float32 else 8 * a.itemsize
+
+
 def planes_from_layout(base_addr: int, layout: dict, channels: int, depth_bits: int | None = None):
-    """Channel views (R,G,B[,A] = codec channels 0..) over an AE ARGB frame (see synth.ae_frame)."""
+    """Channel views (R,G,B[,A] = codec channels 0..) over an AE ARGB frame (see synth.ae_frame; sample_bytes 4: an ARGB128
+    frame of floats, synth.ae_frame_float)."""
     sb = layout["sample_bytes"]
     offs = layout["channel_offsets"]  # A,R,G,B
     order = [offs[1], offs[2], offs[3], offs[0]]
@@ -395,7 +415,7 @@ def planes_from_layout(base_addr: int, layout: dict, channels: int, depth_bits: 
         arr[c].colbytes = layout["colbytes"]
         arr[c].rowbytes = layout["rowbytes"]
         arr[c].sample_bits = 8 * sb
-        arr[c].depth = depth_bits if depth_bits is not None else 8 * sb
+        arr[c].depth = depth_bits if depth_bits is not None else _layout_depth(layout)
     return arr
 
 
@@ -406,12 +426,12 @@ def comp_shapes(params: Params):
 
 
 def planes_from_arrays(arrays, depth_bits: int, base_of=None):
-    """Channel views over a list of 2-D uint8 / uint16 arrays of any sizes and strides (the components of a sub-sampled image,
+    """Channel views over a list of 2-D uint8 / uint16 / float32 arrays of any sizes and strides (the components of a sub-sampled image,
     one array each; padded rows, samples of interleaved pixels).  depth_bits: the significant bits of the samples.
     base_of: array index -> address of its first sample (default: the array's own host address; a device copy otherwise)."""
     arr = (Plane * len(arrays))()
     for c, a in enumerate(arrays):
-        assert a.ndim == 2 and a.dtype in (np.uint8, np.uint16)
+        assert a.ndim == 2 and a.dtype in _SAMPLE_DTYPES
         arr[c].base = base_of(c) if base_of else a.ctypes.data
         arr[c].colbytes, arr[c].rowbytes = a.strides[1], a.strides[0]
         arr[c].sample_bits, arr[c].depth = 8 * a.itemsize, depth_bits
@@ -585,13 +605,13 @@ class Encoder:
         w, h = -(-i["width"] >> red), -(-i["height"] >> red)
         bits = sample_bits or (8 if i["depth"] <= 8 else 16)
         if out is None:
-            out = np.zeros((nc, h, w), dtype=np.uint8 if bits == 8 else np.uint16)
+            out = np.zeros((nc, h, w), dtype=_sample_dtype(bits))
         assert out.shape == (nc, h, w) and out.itemsize * 8 == bits and out.flags.c_contiguous
         arr = (OutPlane * nc)()
         for c in range(nc):
             arr[c].base = out.ctypes.data + c * h * w * out.itemsize
             arr[c].colbytes, arr[c].rowbytes = out.itemsize, w * out.itemsize
-            arr[c].sample_bits, arr[c].depth = bits, depth or min(i["depth"], bits)
+            arr[c].sample_bits, arr[c].depth = bits, depth or min(i["depth"], 16, bits)
             arr[c].width, arr[c].height = w, h
         buf = np.frombuffer(data, dtype=np.uint8)
         self._check(self.L.j2k_hip_decode(self.h, buf.ctypes.data, len(data), subsample, arr, nc))
@@ -606,7 +626,7 @@ class Encoder:
         nc = channels or i["channels"]
         bits = sample_bits or (8 if i["depth"] <= 8 else 16)
         if out is None:
-            out = np.zeros((nc, rect[3], rect[2]), dtype=np.uint8 if bits == 8 else np.uint16)
+            out = np.zeros((nc, rect[3], rect[2]), dtype=_sample_dtype(bits))
         assert out.ndim == 3 and out.shape[0] == nc and out.itemsize * 8 == bits and out.flags.c_contiguous
         _, h, w = out.shape
         d = self.upload(out) if device else None
@@ -615,7 +635,7 @@ class Encoder:
         for c in range(nc):
             arr[c].base = base + c * h * w * out.itemsize
             arr[c].colbytes, arr[c].rowbytes = out.itemsize, w * out.itemsize
-            arr[c].sample_bits, arr[c].depth = bits, depth or min(i["depth"], bits)
+            arr[c].sample_bits, arr[c].depth = bits, depth or min(i["depth"], 16, bits)
             arr[c].width, arr[c].height = w, h
         buf = np.frombuffer(data, dtype=np.uint8)
         try:
@@ -633,10 +653,10 @@ class Encoder:
         samples of interleaved pixels, bottom-up rows): the general form of the C ABI's destination."""
         arr = (OutPlane * len(chans))()
         for c, a in enumerate(chans):
-            assert a.ndim == 2 and a.dtype in (np.uint8, np.uint16)
+            assert a.ndim == 2 and a.dtype in _SAMPLE_DTYPES
             arr[c].base = a.ctypes.data
             arr[c].colbytes, arr[c].rowbytes = a.strides[1], a.strides[0]
-            arr[c].sample_bits, arr[c].depth = 8 * a.itemsize, depth or 8 * a.itemsize
+            arr[c].sample_bits, arr[c].depth = 8 * a.itemsize, depth or _array_depth(a)
             arr[c].width, arr[c].height = a.shape[1], a.shape[0]
         buf = np.frombuffer(data, dtype=np.uint8)
         self._check(self.L.j2k_hip_decode(self.h, buf.ctypes.data, len(data), subsample, arr, len(chans)))
@@ -658,7 +678,7 @@ class Encoder:
         for c in range(channels):
             arr[c].base = base + order[c]
             arr[c].colbytes, arr[c].rowbytes = layout["colbytes"], layout["rowbytes"]
-            arr[c].sample_bits, arr[c].depth = 8 * sb, depth or 8 * sb
+            arr[c].sample_bits, arr[c].depth = 8 * sb, depth or _layout_depth(layout)
             arr[c].width, arr[c].height = width, height
         buf = np.frombuffer(data, dtype=np.uint8)
         try:
@@ -688,7 +708,7 @@ class Encoder:
         dst = RgbaDst()
         dst.struct_size, dst.demote_ae16 = C.sizeof(RgbaDst), int(demote)
         for p, off in ((dst.r, offs[1]), (dst.g, offs[2]), (dst.b, offs[3])) + (((dst.a, offs[0]),) if alpha else ()):
-            _set_outplane(p, base + off, layout["colbytes"], layout["rowbytes"], 8 * sb, depth or 8 * sb, width, height)
+            _set_outplane(p, base + off, layout["colbytes"], layout["rowbytes"], 8 * sb, depth or _layout_depth(layout), width, height)
         buf = np.frombuffer(data, dtype=np.uint8)
         try:
             fn = self.L.j2k_hip_decode_rgba_device if device else self.L.j2k_hip_decode_rgba
@@ -708,8 +728,8 @@ class Encoder:
         for p, v in ((dst.r, r), (dst.g, g), (dst.b, b), (dst.a, a)):
             if v is None:
                 continue
-            assert v.ndim == 2 and v.dtype in (np.uint8, np.uint16)
-            _set_outplane(p, v.ctypes.data, v.strides[1], v.strides[0], 8 * v.itemsize, depth or 8 * v.itemsize, v.shape[1], v.shape[0])
+            assert v.ndim == 2 and v.dtype in _SAMPLE_DTYPES
+            _set_outplane(p, v.ctypes.data, v.strides[1], v.strides[0], 8 * v.itemsize, depth or _array_depth(v), v.shape[1], v.shape[0])
         buf = np.frombuffer(data, dtype=np.uint8)
         self._check(self.L.j2k_hip_decode_rgba(self.h, buf.ctypes.data, len(data), subsample,
                                                C.byref(Rect(*region)) if region is not None else None, C.byref(dst)))
@@ -727,7 +747,7 @@ class Encoder:
         w, h = (region[2], region[3]) if region is not None else (-(-i["width"] >> red), -(-i["height"] >> red))
         bits = sample_bits or (8 if i["depth"] <= 8 else 16)
         if out is None:
-            out = np.zeros((nf, nc, h, w), dtype=np.uint8 if bits == 8 else np.uint16)
+            out = np.zeros((nf, nc, h, w), dtype=_sample_dtype(bits))
         assert out.ndim == 4 and out.shape[:2] == (nf, nc) and out.itemsize * 8 == bits and out.flags.c_contiguous
         _, _, rows, cols = out.shape
         d = self.upload(out) if device else None
@@ -735,7 +755,7 @@ class Encoder:
         arr = (OutPlane * (nf * nc))()
         for k in range(nf * nc):
             _set_outplane(arr[k], base + k * rows * cols * out.itemsize, out.itemsize, cols * out.itemsize, bits,
-                          depth or min(i["depth"], bits), cols, rows)
+                          depth or min(i["depth"], 16, bits), cols, rows)
         fa, _keep = _seq_files(files)
         try:
             fn = self.L.j2k_hip_decode_sequence_device if device else self.L.j2k_hip_decode_sequence
@@ -755,8 +775,8 @@ class Encoder:
         for f in range(nf):
             assert len(chans[f]) == nc
             for c, a in enumerate(chans[f]):
-                assert a.ndim == 2 and a.dtype in (np.uint8, np.uint16)
-                _set_outplane(arr[f * nc + c], a.ctypes.data, a.strides[1], a.strides[0], 8 * a.itemsize, depth or 8 * a.itemsize, a.shape[1], a.shape[0])
+                assert a.ndim == 2 and a.dtype in _SAMPLE_DTYPES
+                _set_outplane(arr[f * nc + c], a.ctypes.data, a.strides[1], a.strides[0], 8 * a.itemsize, depth or _array_depth(a), a.shape[1], a.shape[0])
         fa, _keep = _seq_files(files)
         self._check(self.L.j2k_hip_decode_sequence(self.h, fa, nf, subsample, C.byref(Rect(*region)) if region is not None else None, arr, nc))
 
@@ -775,7 +795,7 @@ class Encoder:
             dst = dsts[f]
             dst.struct_size, dst.demote_ae16 = C.sizeof(RgbaDst), int(demote)
             for p, off in ((dst.r, offs[1]), (dst.g, offs[2]), (dst.b, offs[3])) + (((dst.a, offs[0]),) if alpha else ()):
-                _set_outplane(p, base + f * per + off, layout["colbytes"], layout["rowbytes"], 8 * sb, depth or 8 * sb, width, height)
+                _set_outplane(p, base + f * per + off, layout["colbytes"], layout["rowbytes"], 8 * sb, depth or _layout_depth(layout), width, height)
         fa, _keep = _seq_files(files)
         try:
             fn = self.L.j2k_hip_decode_rgba_sequence_device if device else self.L.j2k_hip_decode_rgba_sequence
@@ -797,8 +817,8 @@ class Encoder:
             for p, v in zip((dst.r, dst.g, dst.b, dst.a), chans[f]):
                 if v is None:
                     continue
-                assert v.ndim == 2 and v.dtype in (np.uint8, np.uint16)
-                _set_outplane(p, v.ctypes.data, v.strides[1], v.strides[0], 8 * v.itemsize, depth or 8 * v.itemsize, v.shape[1], v.shape[0])
+                assert v.ndim == 2 and v.dtype in _SAMPLE_DTYPES
+                _set_outplane(p, v.ctypes.data, v.strides[1], v.strides[0], 8 * v.itemsize, depth or _array_depth(v), v.shape[1], v.shape[0])
         fa, _keep = _seq_files(files)
         self._check(self.L.j2k_hip_decode_rgba_sequence(self.h, fa, nf, subsample, C.byref(Rect(*region)) if region is not None else None, dsts))
 

@@ -84,6 +84,19 @@ Coding normalise(const j2k_hip_params *p);
 // throws Error(J2K_HIP_ERR_PARAM, ...) for such parameters.  Host code: called before any device work.
 void refuse_subsampled_tiles(const Coding &cod);
 
+// The sample type of a channel view (j2k_hip_plane, j2k_hip_outplane; include/j2k_hip.h): 8- and 16-bit unsigned integers
+// holding `depth` significant bits, or 32-bit floats of nominal range 0..1 that stand for integers of `depth` (1..16) bits and
+// lie at multiples of 4 bytes.  Throws Error(J2K_HIP_ERR_PARAM, ...).  Host code: called before any device work.
+inline void check_sample_type(uint32_t sample_bits, uint32_t depth, const void *base, ptrdiff_t colbytes, ptrdiff_t rowbytes)
+{
+    if (sample_bits != 8 && sample_bits != 16 && sample_bits != 32) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8, 16 or 32");
+    if (sample_bits == 32) {
+        if (depth < 1 || depth > 16) throw Error(J2K_HIP_ERR_PARAM, "a float channel stands for an integer depth of 1..16");
+        if (reinterpret_cast<uintptr_t>(base) % 4 || colbytes % 4 || rowbytes % 4)
+            throw Error(J2K_HIP_ERR_PARAM, "a float channel's base, colbytes and rowbytes must be multiples of 4");
+    } else if (depth < 1 || depth > sample_bits) throw Error(J2K_HIP_ERR_PARAM, "channel depth does not fit its sample type");
+}
+
 // A handful of worker threads that run the same function on slices 0..n-1 (host-side loops over all
 // code-blocks of a large tile; starting threads per loop would cost more than the loops).
 class Workers {

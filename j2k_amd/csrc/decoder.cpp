@@ -77,8 +77,7 @@ size_t lane_planes_bytes(size_t plane_words) { return round_up(std::max<size_t>(
 struct OutComp { const void *plane; uint32_t prec, sub_x, sub_y; };
 void check_outplane(const j2k_hip_outplane &p)
 {
-    if (p.sample_bits != 8 && p.sample_bits != 16) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8 or 16");
-    if (p.depth < 1 || p.depth > p.sample_bits) throw Error(J2K_HIP_ERR_PARAM, "channel depth does not fit its sample type");
+    check_sample_type(p.sample_bits, p.depth, p.base, p.colbytes, p.rowbytes);
 }
 // (org_x, org_y: a region decode's window origin -- width and height are then the window's)
 DecOutArgs decode_output_args(bool reversible, bool mct, int width, int height, long long stride, const OutComp *comps, uint32_t ncomp,
@@ -260,7 +259,7 @@ void download_spans(j2k_hip_encoder *e, const DecOutArgs &oa, const j2k_hip_outp
             const int c = S.ch[i];
             const ptrdiff_t off = static_cast<const uint8_t *>(planes[c].base) - lo;
             pixels = off >= 0 && off + oa.dst_bytes[c] <= P0;
-            if (pixels) mask |= (oa.dst_bytes[c] == 1 ? 0xffull : 0xffffull) << (8 * off);
+            if (pixels) mask |= (oa.dst_bytes[c] == 1 ? 0xffull : (oa.dst_bytes[c] == 2 ? 0xffffull : 0xffffffffull)) << (8 * off);
         }
         // The download comes in row bands; the host merges band k while band k + 1 is on its way (a frame of pixels:
         // the rows of the span in order; other layouts: one piece).
@@ -326,7 +325,8 @@ void download_spans(j2k_hip_encoder *e, const DecOutArgs &oa, const j2k_hip_outp
                         uint8_t *dp = ub + (long long)y * rb;
                         if (cb == sb) std::memcpy(dp, sp, (size_t)w * sb); // a planar channel: the row is contiguous
                         else if (sb == 1) for (int x = 0; x < w; ++x) dp[(long long)x * cb] = sp[(long long)x * cb];
-                        else for (int x = 0; x < w; ++x) std::memcpy(dp + (long long)x * cb, sp + (long long)x * cb, 2);
+                        else if (sb == 2) for (int x = 0; x < w; ++x) std::memcpy(dp + (long long)x * cb, sp + (long long)x * cb, 2);
+                        else for (int x = 0; x < w; ++x) std::memcpy(dp + (long long)x * cb, sp + (long long)x * cb, 4);
                     }
                 });
             }

@@ -271,6 +271,14 @@ void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first
     e->geo_valid = true;
 }
 
+// What an encode refuses about a channel view's sample type (J2K_HIP_ERR_PARAM, host code: before any device work).  A float
+// channel under promote_ae16 is the After Effects 15+1-bit world as floats: it stands for depth 16.
+void check_plane(const Coding &cod, const j2k_hip_plane &p)
+{
+    check_sample_type(p.sample_bits, p.depth, p.base, p.colbytes, p.rowbytes);
+    if (p.sample_bits == 32 && cod.promote && p.depth != 16) throw Error(J2K_HIP_ERR_PARAM, "promote_ae16 on a float channel needs depth 16");
+}
+
 // Fill FrontendArgs from channel views whose `base` pointers are device pointers.
 FrontendArgs make_frontend_args(const Coding &cod, const j2k_hip_plane *planes, int x0, int y0, int x1, int y1)
 {
@@ -280,8 +288,7 @@ FrontendArgs make_frontend_args(const Coding &cod, const j2k_hip_plane *planes, 
     for (uint32_t c = 0; c < cod.ncomp; ++c) {
         const j2k_hip_plane &p = planes[c];
         if (!p.base) throw Error(J2K_HIP_ERR_PARAM, "channel buffer is NULL");
-        if (p.sample_bits != 8 && p.sample_bits != 16) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8 or 16");
-        if (p.depth < 1 || p.depth > p.sample_bits) throw Error(J2K_HIP_ERR_PARAM, "channel depth does not fit its sample type");
+        check_plane(cod, p);
         fa.src[c] = static_cast<const uint8_t *>(p.base);
         fa.colbytes[c] = p.colbytes; fa.rowbytes[c] = p.rowbytes;
         fa.sample_bytes[c] = (int)p.sample_bits / 8; fa.src_depth[c] = (int)p.depth;
@@ -318,6 +325,8 @@ bool fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tuning &tn)
     bool same_depth = true;
     for (uint32_t c = 1; c < cod.ncomp; ++c) same_depth = same_depth && fa.src_depth[c] == fa.src_depth[0];
     if (cod.subsampled() || cod.rgb_to_sycc) return false; // (the fused kernel keeps its contract: components of one size, straight from the samples)
+    for (uint32_t c = 0; c < cod.ncomp; ++c)
+        if (fa.sample_bytes[c] == 4) return false; // (... and integer samples: a float world is quantised by the front end's own pass)
     return !tn.no_fuse && cod.levels() >= 1 && fa.interleaved && same_depth && (cod.ncomp == 1 || cod.ncomp == 3 || cod.ncomp == 4);
 }
 
@@ -465,6 +474,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     if (F > 1 && (!planes_on_device || !framed)) throw Error(J2K_HIP_ERR_PARAM, "frame sequences take whole frames resident on the device");
     const Coding cod = normalise(params); // (before the device is touched: what is refused for its parameters costs no device work)
     if (!framed) refuse_subsampled_tiles(cod);
+    for (size_t i = 0; i < F * cod.ncomp; ++i) check_plane(cod, planes[i]);
     HIP_CHECK(hipSetDevice(e->device));
     const Tuning tn = tuning(); // one consistent snapshot per call
     DeviceShared &dev = g_dev[e->device];
@@ -500,7 +510,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
             const uint8_t *lo = nullptr, *hi = nullptr;
             const j2k_hip_plane &p = planes[c];
             if (!p.base) throw Error(J2K_HIP_ERR_PARAM, "channel buffer is NULL");
-            if (p.sample_bits != 8 && p.sample_bits != 16) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8 or 16");
+            check_plane(cod, p);
             const uint8_t *b = static_cast<const uint8_t *>(p.base);
             // (a sub-sampled component given as it is holds its own grid's samples; R, G, B, A for the Y Cb Cr front end are full size)
             const int sx = cod.rgb_to_sycc ? 1 : cod.cdx[c], sy = cod.rgb_to_sycc ? 1 : cod.cdy[c];
@@ -1100,7 +1110,7 @@ void frame_span(const Coding &cod, const j2k_hip_plane *planes, int y0, int y1, 
     for (uint32_t c = 0; c < cod.ncomp; ++c) {
         const j2k_hip_plane &p = planes[c];
         if (!p.base) throw Error(J2K_HIP_ERR_PARAM, "channel buffer is NULL");
-        if (p.sample_bits != 8 && p.sample_bits != 16) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8 or 16");
+        check_plane(cod, p);
         const uint8_t *b = static_cast<const uint8_t *>(p.base);
         const uint8_t *corners[4] = {b + (ptrdiff_t)y0 * p.rowbytes, b + (ptrdiff_t)(y1 - 1) * p.rowbytes,
                                      b + (ptrdiff_t)y0 * p.rowbytes + (ptrdiff_t)(cod.width - 1) * p.colbytes,

@@ -5,7 +5,7 @@
 //   A2  Codec::CopyBuffer/CopyChannel  reference: src/common/j2k_codec.cpp:222-427
 //   A4  DC level shift                 T.800 G.1  (OpenJPEG tcd.c, reached from opj_encode,
 //   A5  RCT / ICT                      T.800 G.2 / G.3          j2k_openjpeg_codec.cpp:730)
-// Algorithmic bytes per pixel: 4*S read (S = bytes per sample, interleaved ARGB) + 4*Ncomp written.
+// Algorithmic bytes per pixel: 4*S read (S = bytes per sample, interleaved ARGB; 4 for a float world) + 4*Ncomp written.
 // When the frame has the After Effects layout and 1 or 3 components, this stage is fused into the
 // level-1 DWT kernel instead (dwt.hip) and this kernel is not launched at all.
 // A second kernel (frontend_sycc_kernel, below) makes Y, Cb, Cr from R, G, B and decimates the chroma as it loads it.
@@ -16,7 +16,8 @@
 namespace j2k_hip {
 namespace {
 
-template <bool REV>
+// FLT: the frame has 32-bit float channels (fe_load: quantised as they are loaded); everything behind the load is one text.
+template <bool REV, bool FLT>
 __global__ __launch_bounds__(256) void frontend_kernel(FrontendArgs a)
 {
     using T = typename std::conditional<REV, int, float>::type;
@@ -24,18 +25,7 @@ __global__ __launch_bounds__(256) void frontend_kernel(FrontendArgs a)
     if (x >= a.width) return;
     for (int y = a.y0 + (int)blockIdx.y; y < a.y1; y += (int)gridDim.y) {
         unsigned raw[4] = {0, 0, 0, 0};
-        if (a.interleaved) {
-            const uint8_t *p = a.pixel_base + (long long)y * a.rowbytes[0] + (long long)x * a.pixel_bytes;
-            if (a.pixel_bytes == 8) fe_unpack64(a, *reinterpret_cast<const uint2 *>(p), raw); // one ARGB64 pixel
-            else fe_unpack32(a, *reinterpret_cast<const unsigned *>(p), raw);                  // one ARGB32 pixel
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c)
-                if (c < a.ncomp) {
-                    const uint8_t *p = a.src[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
-                    raw[c] = a.sample_bytes[c] == 2 ? *reinterpret_cast<const unsigned short *>(p) : *p;
-                }
-        }
+        fe_load<FLT>(a, x, y, raw);
         T v[4];
         fe_convert<REV, T>(a, raw, v);
         const long long o = (long long)(y - a.dst_y0) * a.dst_stride + (x - a.dst_x0);
@@ -61,7 +51,7 @@ __device__ __forceinline__ int fe_sample(const FrontendArgs &a, int c, unsigned 
     return (int)depth_convert(raw, a.src_depth[c], a.prec);
 }
 
-template <bool REV, int SX, int SY>
+template <bool REV, int SX, int SY, bool FLT>
 __global__ __launch_bounds__(256) void frontend_sycc_kernel(FrontendArgs a)
 {
     using T = typename std::conditional<REV, int, float>::type;
@@ -87,18 +77,7 @@ __global__ __launch_bounds__(256) void frontend_sycc_kernel(FrontendArgs a)
                     const int x = cx * SX + i;
                     if (x < a.width) { // (a column right of the image repeats the pixel left of it)
                         unsigned raw[4] = {0, 0, 0, 0};
-                        if (a.interleaved) {
-                            const uint8_t *p = a.pixel_base + (long long)y * a.rowbytes[0] + (long long)x * a.pixel_bytes;
-                            if (a.pixel_bytes == 8) fe_unpack64(a, *reinterpret_cast<const uint2 *>(p), raw);
-                            else fe_unpack32(a, *reinterpret_cast<const unsigned *>(p), raw);
-                        } else {
-#pragma unroll
-                            for (int c = 0; c < 4; ++c)
-                                if (c < a.ncomp) {
-                                    const uint8_t *p = a.src[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
-                                    raw[c] = a.sample_bytes[c] == 2 ? *reinterpret_cast<const unsigned short *>(p) : *p;
-                                }
-                        }
+                        fe_load<FLT>(a, x, y, raw);
                         const int r = fe_sample(a, 0, raw[0]), g = fe_sample(a, 1, raw[1]), b = fe_sample(a, 2, raw[2]);
                         const unsigned yy = (19595u * (unsigned)r + 38470u * (unsigned)g + 7471u * (unsigned)b + 32768u) >> 16;
                         yv[i] = (T)((int)yy - dc);
@@ -135,12 +114,19 @@ __global__ __launch_bounds__(256) void frontend_sycc_kernel(FrontendArgs a)
     }
 }
 
-template <bool REV>
+template <bool REV, bool FLT>
 void launch_sycc(const FrontendArgs &a, int sub_x, int sub_y, dim3 grid, hipStream_t s)
 {
-    if (sub_x == 1 && sub_y == 1) hipLaunchKernelGGL((frontend_sycc_kernel<REV, 1, 1>), grid, dim3(256), 0, s, a);
-    else if (sub_x == 2 && sub_y == 1) hipLaunchKernelGGL((frontend_sycc_kernel<REV, 2, 1>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((frontend_sycc_kernel<REV, 2, 2>), grid, dim3(256), 0, s, a);
+    if (sub_x == 1 && sub_y == 1) hipLaunchKernelGGL((frontend_sycc_kernel<REV, 1, 1, FLT>), grid, dim3(256), 0, s, a);
+    else if (sub_x == 2 && sub_y == 1) hipLaunchKernelGGL((frontend_sycc_kernel<REV, 2, 1, FLT>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((frontend_sycc_kernel<REV, 2, 2, FLT>), grid, dim3(256), 0, s, a);
+}
+
+bool has_float(const FrontendArgs &a)
+{
+    for (int c = 0; c < a.ncomp; ++c)
+        if (a.sample_bytes[c] == 4) return true;
+    return false;
 }
 
 } // namespace
@@ -150,8 +136,11 @@ void launch_frontend_sycc(const FrontendArgs &a, int sub_x, int sub_y, hipStream
     if (a.y1 <= 0 || a.width <= 0) return;
     const int cw = (a.width + sub_x - 1) / sub_x, ch = (a.y1 + sub_y - 1) / sub_y;
     dim3 grid((unsigned)((cw + 255) / 256), (unsigned)(ch < 65535 ? ch : 65535), 1);
-    if (a.reversible) launch_sycc<true>(a, sub_x, sub_y, grid, s);
-    else launch_sycc<false>(a, sub_x, sub_y, grid, s);
+    if (has_float(a)) {
+        if (a.reversible) launch_sycc<true, true>(a, sub_x, sub_y, grid, s);
+        else launch_sycc<false, true>(a, sub_x, sub_y, grid, s);
+    } else if (a.reversible) launch_sycc<true, false>(a, sub_x, sub_y, grid, s);
+    else launch_sycc<false, false>(a, sub_x, sub_y, grid, s);
 }
 
 void launch_frontend(const FrontendArgs &a, hipStream_t s)
@@ -159,8 +148,11 @@ void launch_frontend(const FrontendArgs &a, hipStream_t s)
     if (a.y1 <= a.y0 || a.width <= a.x0) return;
     const int rows = a.y1 - a.y0;
     dim3 grid((unsigned)((a.width - a.x0 + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535), 1);
-    if (a.reversible) hipLaunchKernelGGL(frontend_kernel<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(frontend_kernel<false>, grid, dim3(256), 0, s, a);
+    if (has_float(a)) {
+        if (a.reversible) hipLaunchKernelGGL((frontend_kernel<true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((frontend_kernel<false, true>), grid, dim3(256), 0, s, a);
+    } else if (a.reversible) hipLaunchKernelGGL((frontend_kernel<true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((frontend_kernel<false, false>), grid, dim3(256), 0, s, a);
 }
 
 } // namespace j2k_hip

@@ -3,6 +3,7 @@
 //   A1 Promote              reference: src/aftereffects/FrameSeq.cpp:311-314
 //   A2 CopyChannel shifts   reference: src/common/j2k_codec.cpp:254-371
 //   A4 DC level shift, A5 RCT / ICT   T.800 G.1-G.3
+//   A0 float worlds         reference: src/aftereffects/FrameSeq.cpp:95-110 (CopyWorldIterate<PF_FpShort, ...>), FrameSeq.h:47
 #pragma once
 
 #include "kernels.h"
@@ -30,7 +31,18 @@ __device__ __forceinline__ unsigned depth_convert(unsigned v, int src_depth, int
     return (t << second) | (t >> ((int)pd - second));
 }
 
-// raw[c] = sample of codec channel c as stored; out[c] = component value after promote, depth
+// A 32-bit float sample of nominal range 0..1 as the unsigned integer of depth d that it stands for (include/j2k_hip.h): the
+// one definition of that rounding.  NaN, -0.0, negatives and -inf fail both comparisons and give 0, +inf gives 2^d - 1.  The
+// product and the sum are each rounded to binary32 (-ffp-contract=off), the cast truncates a value in 0 .. 65535.5.
+// promote (d = 16): the After Effects 15+1-bit value the float world converts to (x 32768), then Promote.
+__device__ __forceinline__ unsigned fe_quantise_float(float x, int d, bool promote)
+{
+    const float t = x > 1.0f ? 1.0f : (x > 0.0f ? x : 0.0f);
+    if (promote) return promote16((unsigned)(t * 32768.0f + 0.5f));
+    return (unsigned)(t * (float)((1 << d) - 1) + 0.5f);
+}
+
+// raw[c] = sample of codec channel c as stored (a float sample: as quantised, Promote included); out[c] = component value after promote, depth
 // conversion, DC shift and colour transform (int for the reversible path, float otherwise).
 template <bool REV, typename T>
 __device__ __forceinline__ void fe_convert(const FrontendArgs &a, const unsigned raw[4], T out[4])
@@ -84,6 +96,45 @@ __device__ __forceinline__ void fe_unpack32(const FrontendArgs &a, unsigned q, u
 {
 #pragma unroll
     for (int c = 0; c < 4; ++c) raw[c] = (q >> (8 * a.chan_off[c])) & 0xffu;
+}
+// one ARGB128 pixel (four floats, one 16-byte load per lane: a wave reads 1 KiB of contiguous bytes), quantised
+__device__ __forceinline__ void fe_unpack128(const FrontendArgs &a, uint4 q, unsigned raw[4])
+{
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int k = a.chan_off[c] >> 2;
+        const unsigned bits = k == 0 ? q.x : (k == 1 ? q.y : (k == 2 ? q.z : q.w));
+        raw[c] = c < a.ncomp ? fe_quantise_float(__uint_as_float(bits), a.src_depth[c], a.promote != 0) : 0u;
+    }
+}
+
+// The stored samples of pixel (x, y) of codec channels 0 .. ncomp - 1.  FLT: the frame has float channels -- an interleaved
+// pixel is ARGB128, a strided sample is loaded by its own width (1, 2 or 4 bytes).  Without FLT the text is what the kernels
+// held before float samples existed, so their code does not change.
+template <bool FLT>
+__device__ __forceinline__ void fe_load(const FrontendArgs &a, int x, int y, unsigned raw[4])
+{
+    if (a.interleaved) {
+        const uint8_t *p = a.pixel_base + (long long)y * a.rowbytes[0] + (long long)x * a.pixel_bytes;
+        if constexpr (FLT) {
+            fe_unpack128(a, *reinterpret_cast<const uint4 *>(p), raw);
+        } else {
+            if (a.pixel_bytes == 8) fe_unpack64(a, *reinterpret_cast<const uint2 *>(p), raw); // one ARGB64 pixel
+            else fe_unpack32(a, *reinterpret_cast<const unsigned *>(p), raw);                  // one ARGB32 pixel
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c < a.ncomp) {
+                const uint8_t *p = a.src[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
+                if constexpr (FLT) {
+                    if (a.sample_bytes[c] == 4) raw[c] = fe_quantise_float(*reinterpret_cast<const float *>(p), a.src_depth[c], a.promote != 0);
+                    else raw[c] = a.sample_bytes[c] == 2 ? *reinterpret_cast<const unsigned short *>(p) : *p;
+                } else {
+                    raw[c] = a.sample_bytes[c] == 2 ? *reinterpret_cast<const unsigned short *>(p) : *p;
+                }
+            }
+    }
 }
 
 } // namespace j2k_hip

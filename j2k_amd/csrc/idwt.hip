@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void idwt_win_v_kernel(IdwtWinArgs g)
     }
 }
 
-template <bool REV>
+template <bool REV, bool FLT> // FLT: some destination channel holds 32-bit floats (out_sample.h: store_float)
 __global__ __launch_bounds__(256) void decode_output_kernel(DecOutArgs a)
 {
     const int x = blockIdx.x * 256 + threadIdx.x;
@@ -304,6 +304,9 @@ __global__ __launch_bounds__(256) void decode_output_kernel(DecOutArgs a)
             const unsigned mask = a.dst_bytes[c] == 1 ? 0xffu : 0xffffu;
             const unsigned ov = depth_out((unsigned)v[c], a.cprec[c], a.dst_depth[c], mask);
             uint8_t *p = a.dst[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
+            if constexpr (FLT) {
+                if (a.dst_bytes[c] == 4) { store_float(p, ov, a.dst_depth[c], false); continue; }
+            }
             if (a.dst_bytes[c] == 1) *p = (uint8_t)ov;
             else *reinterpret_cast<unsigned short *>(p) = (unsigned short)ov;
         }
@@ -313,7 +316,7 @@ __global__ __launch_bounds__(256) void decode_output_kernel(DecOutArgs a)
 // The same stage for the frames of a sequence decode: frame = blockIdx.z.  What the frames share arrives as the kernel's
 // arguments; the frame's own descriptor (kernels.h: DecSeqFrameDev) is read from the table at a wave-uniform address -- scalar
 // loads, once per workgroup -- into the argument struct's copy, and the pixels are decode_output_kernel's through out_sample.h.
-template <bool REV>
+template <bool REV, bool FLT>
 __global__ __launch_bounds__(256) void decode_output_seq_kernel(DecOutArgs a, const DecSeqFrameDev *__restrict__ frames)
 {
     const DecSeqFrameDev &F = frames[blockIdx.z];
@@ -328,8 +331,15 @@ __global__ __launch_bounds__(256) void decode_output_seq_kernel(DecOutArgs a, co
     for (int y = blockIdx.y; y < a.height; y += gridDim.y) {
         int v[4];
         component_samples<REV>(a, x, y, v);
-        store_channels(a, x, y, v);
+        store_channels<FLT>(a, x, y, v);
     }
+}
+
+bool float_channels(const DecOutArgs &a)
+{
+    for (int c = 0; c < a.nout && c < a.ncomp; ++c)
+        if (a.dst_bytes[c] == 4) return true;
+    return false;
 }
 
 } // namespace
@@ -374,16 +384,22 @@ void launch_decode_output(const DecOutArgs &a, hipStream_t s)
 {
     if (a.width <= 0 || a.height <= 0) return;
     const dim3 grid((unsigned)((a.width + 255) / 256), (unsigned)std::min(a.height, 65535), 1);
-    if (a.reversible) hipLaunchKernelGGL(decode_output_kernel<true>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(decode_output_kernel<false>, grid, dim3(256), 0, s, a);
+    if (float_channels(a)) {
+        if (a.reversible) hipLaunchKernelGGL((decode_output_kernel<true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((decode_output_kernel<false, true>), grid, dim3(256), 0, s, a);
+    } else if (a.reversible) hipLaunchKernelGGL((decode_output_kernel<true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((decode_output_kernel<false, false>), grid, dim3(256), 0, s, a);
 }
 
 void launch_decode_output_seq(const DecOutArgs &a, const DecSeqFrameDev *frames, int nframes, hipStream_t s)
 {
     if (a.width <= 0 || a.height <= 0 || nframes <= 0) return;
     const dim3 grid((unsigned)((a.width + 255) / 256), (unsigned)std::min(a.height, 65535), (unsigned)nframes);
-    if (a.reversible) hipLaunchKernelGGL(decode_output_seq_kernel<true>, grid, dim3(256), 0, s, a, frames);
-    else hipLaunchKernelGGL(decode_output_seq_kernel<false>, grid, dim3(256), 0, s, a, frames);
+    if (float_channels(a)) {
+        if (a.reversible) hipLaunchKernelGGL((decode_output_seq_kernel<true, true>), grid, dim3(256), 0, s, a, frames);
+        else hipLaunchKernelGGL((decode_output_seq_kernel<false, true>), grid, dim3(256), 0, s, a, frames);
+    } else if (a.reversible) hipLaunchKernelGGL((decode_output_seq_kernel<true, false>), grid, dim3(256), 0, s, a, frames);
+    else hipLaunchKernelGGL((decode_output_seq_kernel<false, false>), grid, dim3(256), 0, s, a, frames);
 }
 
 } // namespace j2k_hip

@@ -59,8 +59,8 @@ int get_tune(const char *key, int *value);
 struct FrontendArgs {
     const uint8_t *src[4];
     long long colbytes[4], rowbytes[4];
-    int sample_bytes[4]; // 1 or 2
-    int src_depth[4];    // Channel.depth
+    int sample_bytes[4]; // 1 or 2; 4: 32-bit floats of nominal range 0..1 (frontend_ops.h: fe_quantise_float), 4-byte aligned
+    int src_depth[4];    // Channel.depth (a float channel: the integer depth it stands for, 1..16)
     int ncomp;
     int width;           // columns [x0,width) are converted
     int x0;
@@ -70,6 +70,7 @@ struct FrontendArgs {
     int reversible, mct, promote;
     // Fast path for the After Effects layout (one interleaved pixel = 4 samples of equal size,
     // all channels inside it): pixel_base/pixel_bytes set, chan_off[c] = byte offset in the pixel.
+    // pixel_bytes 4 (ARGB32), 8 (ARGB64) or 16 (ARGB128, floats); pixel_base and rowbytes[0] are multiples of it.
     int interleaved;
     const uint8_t *pixel_base;
     int pixel_bytes;
@@ -331,9 +332,10 @@ struct DecOutArgs {
 //   * cprec[c] in 1..16, sub_x[c] and sub_y[c] >= 1; comp[c] holds ceil(width / sub_x[c]) x ceil(height / sub_y[c]) words at
 //     row stride `stride` (every component of ncomp is read, whether or not a channel receives it) -- with an origin,
 //     ceil((org_x + width) / sub_x[c]) x ceil((org_y + height) / sub_y[c]) words; org_x, org_y >= 0;
-//   * dst_bytes[c] is 1 or 2 and 1 <= dst_depth[c] <= 8 * dst_bytes[c]; dst_w[c] <= width, dst_h[c] <= height;
+//   * dst_bytes[c] is 1 or 2 and 1 <= dst_depth[c] <= 8 * dst_bytes[c], or 4 (32-bit floats, out_sample.h: store_float) and
+//     1 <= dst_depth[c] <= 16; dst_w[c] <= width, dst_h[c] <= height;
 //   * dst[c] + y * rowbytes[c] + x * colbytes[c] is writable for x < dst_w[c], y < dst_h[c], and 2-byte aligned where
-//     dst_bytes[c] is 2 (16-bit samples go out as one store).
+//     dst_bytes[c] is 2 (16-bit samples go out as one store), 4-byte aligned where it is 4.
 void launch_decode_output(const DecOutArgs &a, hipStream_t s);
 
 // The same stage straight to R, G, B, A (rgba_out.hip): the component samples as above, then the file's mode (RGB, grey,

@@ -79,9 +79,23 @@ __device__ __forceinline__ void component_samples(const ARGS &a, int x, int y, i
     }
 }
 
+// A destination sample of 32-bit float type (include/j2k_hip.h): the integer ov of depth d, computed as for an integer
+// destination, as the float of nominal range 0..1 that it stands for -- ov / (2^d - 1), an IEEE division (correctly rounded:
+// what `/` is on this target without fast-math; a multiplication by the reciprocal would miss it for most depths).
+// demoted: ov is an After Effects 15+1-bit value (0 .. 32768) and the divisor 32768 (exact).  The highest value gives 1.0f.
+__device__ __forceinline__ float out_float(unsigned ov, int d, bool demoted)
+{
+    return (float)ov / (demoted ? 32768.0f : (float)((1 << d) - 1));
+}
+__device__ __forceinline__ void store_float(uint8_t *p, unsigned ov, int d, bool demoted)
+{
+    *reinterpret_cast<float *>(p) = out_float(ov, d, demoted); // (4-byte aligned: base, colbytes and rowbytes are multiples of 4)
+}
+
 // Destination channels c < nout of pixel (x, y) from its component samples v[]: CopyChannel's depth conversion, one store per
-// channel that has the sample (decode_output_kernel's last loop).  ARGS: DecOutArgs.
-template <typename ARGS>
+// channel that has the sample (decode_output_kernel's last loop).  ARGS: DecOutArgs.  FLT: some channel is of float type
+// (dst_bytes 4); without it the text is the one the kernels held before float destinations existed.
+template <bool FLT, typename ARGS>
 __device__ __forceinline__ void store_channels(const ARGS &a, int x, int y, const int v[4])
 {
 #pragma unroll
@@ -90,6 +104,9 @@ __device__ __forceinline__ void store_channels(const ARGS &a, int x, int y, cons
             const unsigned mask = a.dst_bytes[c] == 1 ? 0xffu : 0xffffu;
             const unsigned ov = depth_out((unsigned)v[c], a.cprec[c], a.dst_depth[c], mask);
             uint8_t *p = a.dst[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
+            if constexpr (FLT) {
+                if (a.dst_bytes[c] == 4) { store_float(p, ov, a.dst_depth[c], false); continue; }
+            }
             if (a.dst_bytes[c] == 1) *p = (uint8_t)ov;
             else *reinterpret_cast<unsigned short *>(p) = (unsigned short)ov;
         }

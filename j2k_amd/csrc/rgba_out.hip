@@ -7,7 +7,8 @@
 // A thread per destination pixel, a workgroup = 256 neighbours of one row, rows strided over gridDim.y like
 // decode_output_kernel.  Reads: component words at (org + x) / sub_x -- a wavefront reads 64 (or, sub-sampled, 32)
 // consecutive words of each component.  Writes: in the packed form the pixel's record in one 4- or 8-byte store, so a
-// wavefront writes 256 or 512 contiguous bytes; in the general form one store per given channel at the channel's strides.
+// wavefront writes 256 or 512 contiguous bytes (float destinations: one 16-byte store, 1 KiB); in the general form one store per
+// given channel at the channel's strides.
 // The build passes -ffp-contract=off: the sYCC arithmetic below rounds every product and every sum on its own.
 #include "kernels.h"
 #include "out_sample.h"
@@ -28,7 +29,22 @@ __device__ __forceinline__ unsigned sycc_channel(float f, int h, int top)
     return (unsigned)min(max((int)((f + (float)h) + 0.5f), 0), top); // (the cast truncates; |f| < 2^19: always in range)
 }
 
-template <bool REV, int MODE, bool PACKED>
+// Float destinations (FLT; out_sample.h: out_float): the pixel's record is four floats -- After Effects' ARGB128 -- stored as one
+// 16-byte word, so a wavefront writes 1 KiB of contiguous bytes.  The samples go to their slots by comparisons (no indexed
+// register array: nothing lands in scratch memory).
+template <typename ARGS>
+__device__ __forceinline__ void store_record128(const ARGS &a, int x, int y, const unsigned out[4], int D)
+{
+    float f[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) f[c] = out_float(out[c], D, a.demote != 0);
+    float w[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = a.slot[0] == k ? f[0] : (a.slot[1] == k ? f[1] : (a.slot[2] == k ? f[2] : f[3]));
+    *reinterpret_cast<float4 *>(a.pix + (long long)y * a.pix_rowbytes + (long long)x * 16) = float4{w[0], w[1], w[2], w[3]};
+}
+
+template <bool REV, int MODE, bool PACKED, bool FLT>
 __global__ __launch_bounds__(256) void decode_rgba_kernel(DecRgbaArgs a)
 {
     __shared__ unsigned s_lut[MODE == J2K_HIP_RGBA_PALETTE ? 256 : 1];
@@ -58,7 +74,8 @@ __global__ __launch_bounds__(256) void decode_rgba_kernel(DecRgbaArgs a)
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const unsigned b = (e >> (8 * c)) & 0xffu;
-                out[c] = a.sample_bytes == 1 ? b : ((b << 8) | b); // ConvertToType: whatever the depth
+                if constexpr (FLT) out[c] = D <= 8 ? b : ((b << 8) | b); // (a float stands for the integer type that holds its depth)
+                else out[c] = a.sample_bytes == 1 ? b : ((b << 8) | b); // ConvertToType: whatever the depth
             }
         } else { // sYCC, the reference's irreversible branch
             const int h = 1 << (D - 1);
@@ -75,7 +92,9 @@ __global__ __launch_bounds__(256) void decode_rgba_kernel(DecRgbaArgs a)
         }
         if constexpr (PACKED) {
             if (x < a.dst_w[0] && y < a.dst_h[0]) {
-                if (a.sample_bytes == 1) {
+                if constexpr (FLT) {
+                    store_record128(a, x, y, out, D);
+                } else if (a.sample_bytes == 1) {
                     unsigned w = 0;
 #pragma unroll
                     for (int c = 0; c < 4; ++c) w |= (out[c] & 0xffu) << (8 * a.slot[c]);
@@ -92,7 +111,8 @@ __global__ __launch_bounds__(256) void decode_rgba_kernel(DecRgbaArgs a)
             for (int c = 0; c < 4; ++c)
                 if (a.dst[c] && x < a.dst_w[c] && y < a.dst_h[c]) {
                     uint8_t *p = a.dst[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
-                    if (a.sample_bytes == 1) *p = (uint8_t)out[c];
+                    if constexpr (FLT) store_float(p, out[c], D, a.demote != 0);
+                    else if (a.sample_bytes == 1) *p = (uint8_t)out[c];
                     else *reinterpret_cast<unsigned short *>(p) = (unsigned short)out[c];
                 }
         }
@@ -102,8 +122,11 @@ __global__ __launch_bounds__(256) void decode_rgba_kernel(DecRgbaArgs a)
 template <bool REV, int MODE>
 void launch_form(const DecRgbaArgs &a, const dim3 &grid, hipStream_t s)
 {
-    if (a.packed) hipLaunchKernelGGL((decode_rgba_kernel<REV, MODE, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((decode_rgba_kernel<REV, MODE, false>), grid, dim3(256), 0, s, a);
+    if (a.sample_bytes == 4) {
+        if (a.packed) hipLaunchKernelGGL((decode_rgba_kernel<REV, MODE, true, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((decode_rgba_kernel<REV, MODE, false, true>), grid, dim3(256), 0, s, a);
+    } else if (a.packed) hipLaunchKernelGGL((decode_rgba_kernel<REV, MODE, true, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((decode_rgba_kernel<REV, MODE, false, false>), grid, dim3(256), 0, s, a);
 }
 
 template <bool REV>
@@ -118,7 +141,7 @@ void launch_mode(const DecRgbaArgs &a, const dim3 &grid, hipStream_t s)
 }
 
 // One pixel of decode_rgba_kernel (that kernel's own lines as a function, for its sequence form below).
-template <bool REV, int MODE, bool PACKED, typename ARGS>
+template <bool REV, int MODE, bool PACKED, bool FLT, typename ARGS>
 __device__ __forceinline__ void rgba_pixel(const ARGS &a, const unsigned *s_lut, int x, int y, int D, int top, unsigned mask)
 {
     int v[4];
@@ -138,7 +161,8 @@ __device__ __forceinline__ void rgba_pixel(const ARGS &a, const unsigned *s_lut,
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const unsigned b = (e >> (8 * c)) & 0xffu;
-            out[c] = a.sample_bytes == 1 ? b : ((b << 8) | b); // ConvertToType: whatever the depth
+            if constexpr (FLT) out[c] = D <= 8 ? b : ((b << 8) | b); // (a float stands for the integer type that holds its depth)
+            else out[c] = a.sample_bytes == 1 ? b : ((b << 8) | b); // ConvertToType: whatever the depth
         }
     } else { // sYCC, the reference's irreversible branch
         const int h = 1 << (D - 1);
@@ -155,7 +179,9 @@ __device__ __forceinline__ void rgba_pixel(const ARGS &a, const unsigned *s_lut,
     }
     if constexpr (PACKED) {
         if (x < a.dst_w[0] && y < a.dst_h[0]) {
-            if (a.sample_bytes == 1) {
+            if constexpr (FLT) {
+                store_record128(a, x, y, out, D);
+            } else if (a.sample_bytes == 1) {
                 unsigned w = 0;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) w |= (out[c] & 0xffu) << (8 * a.slot[c]);
@@ -172,7 +198,8 @@ __device__ __forceinline__ void rgba_pixel(const ARGS &a, const unsigned *s_lut,
         for (int c = 0; c < 4; ++c)
             if (a.dst[c] && x < a.dst_w[c] && y < a.dst_h[c]) {
                 uint8_t *p = a.dst[c] + (long long)y * a.rowbytes[c] + (long long)x * a.colbytes[c];
-                if (a.sample_bytes == 1) *p = (uint8_t)out[c];
+                if constexpr (FLT) store_float(p, out[c], D, a.demote != 0);
+                else if (a.sample_bytes == 1) *p = (uint8_t)out[c];
                 else *reinterpret_cast<unsigned short *>(p) = (unsigned short)out[c];
             }
     }
@@ -191,7 +218,7 @@ struct RgbaFrameArgs {
     uint32_t lut_size;
 };
 
-template <bool REV, int MODE, bool PACKED>
+template <bool REV, int MODE, bool PACKED, bool FLT>
 __global__ __launch_bounds__(256) void decode_rgba_seq_kernel(DecRgbaArgs a, const DecSeqFrameDev *__restrict__ frames)
 {
     __shared__ unsigned s_lut[MODE == J2K_HIP_RGBA_PALETTE ? 256 : 1];
@@ -215,14 +242,17 @@ __global__ __launch_bounds__(256) void decode_rgba_seq_kernel(DecRgbaArgs a, con
     if (x >= a.width) return;
     const int D = a.depth, top = (1 << D) - 1;
     const unsigned mask = a.sample_bytes == 1 ? 0xffu : 0xffffu;
-    for (int y = blockIdx.y; y < a.height; y += gridDim.y) rgba_pixel<REV, MODE, PACKED>(f, s_lut, x, y, D, top, mask);
+    for (int y = blockIdx.y; y < a.height; y += gridDim.y) rgba_pixel<REV, MODE, PACKED, FLT>(f, s_lut, x, y, D, top, mask);
 }
 
 template <bool REV, int MODE>
 void launch_form_seq(const DecRgbaArgs &a, const DecSeqFrameDev *f, const dim3 &grid, hipStream_t s)
 {
-    if (a.packed) hipLaunchKernelGGL((decode_rgba_seq_kernel<REV, MODE, true>), grid, dim3(256), 0, s, a, f);
-    else hipLaunchKernelGGL((decode_rgba_seq_kernel<REV, MODE, false>), grid, dim3(256), 0, s, a, f);
+    if (a.sample_bytes == 4) {
+        if (a.packed) hipLaunchKernelGGL((decode_rgba_seq_kernel<REV, MODE, true, true>), grid, dim3(256), 0, s, a, f);
+        else hipLaunchKernelGGL((decode_rgba_seq_kernel<REV, MODE, false, true>), grid, dim3(256), 0, s, a, f);
+    } else if (a.packed) hipLaunchKernelGGL((decode_rgba_seq_kernel<REV, MODE, true, false>), grid, dim3(256), 0, s, a, f);
+    else hipLaunchKernelGGL((decode_rgba_seq_kernel<REV, MODE, false, false>), grid, dim3(256), 0, s, a, f);
 }
 
 template <bool REV>

@@ -87,11 +87,11 @@ void check_rgba_dst(const j2k_hip_rgba_dst &dst, bool alpha)
     const j2k_hip_outplane *ch[4] = {&dst.r, &dst.g, &dst.b, &dst.a};
     for (int c = 0; c < (alpha ? 4 : 3); ++c) {
         const j2k_hip_outplane &p = *ch[c];
-        if (p.sample_bits != 8 && p.sample_bits != 16) throw Error(J2K_HIP_ERR_PARAM, "sample_bits must be 8 or 16");
-        if (p.depth < 1 || p.depth > p.sample_bits) throw Error(J2K_HIP_ERR_PARAM, "channel depth does not fit its sample type");
+        check_sample_type(p.sample_bits, p.depth, p.base, p.colbytes, p.rowbytes);
         if (p.sample_bits != dst.r.sample_bits || p.depth != dst.r.depth) throw Error(J2K_HIP_ERR_PARAM, "the RGBA channels must share sample_bits and depth");
     }
-    if (dst.demote_ae16 && (dst.r.sample_bits != 16 || dst.r.depth != 16)) throw Error(J2K_HIP_ERR_PARAM, "demote_ae16 needs 16-bit samples of depth 16");
+    if (dst.demote_ae16 && ((dst.r.sample_bits != 16 && dst.r.sample_bits != 32) || dst.r.depth != 16))
+        throw Error(J2K_HIP_ERR_PARAM, "demote_ae16 needs 16-bit or float samples of depth 16");
 }
 
 DecRgbaArgs decode_rgba_args(bool reversible, bool mct, int width, int height, long long stride, const RgbaComp *comps,

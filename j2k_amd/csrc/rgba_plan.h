@@ -52,16 +52,17 @@ struct DecRgbaArgs {
 //     precision and sub-sampling factors;
 //   * cprec[c] in 1..16, sub_x[c] and sub_y[c] >= 1, org_x, org_y >= 0; comp[c] holds ceil((org_x + width) / sub_x[c]) x
 //     ceil((org_y + height) / sub_y[c]) words at row stride `stride` for every c < ncomp (each is read);
-//   * sample_bytes is 1 or 2, 1 <= depth <= 8 * sample_bytes; demote only with sample_bytes == 2 and depth == 16;
+//   * sample_bytes is 1 or 2, 1 <= depth <= 8 * sample_bytes, or 4 (32-bit floats) with 1 <= depth <= 16; demote only with
+//     sample_bytes 2 or 4 and depth == 16;
 //   * dst_w[c] <= width, dst_h[c] <= height; dst[c] + y * rowbytes[c] + x * colbytes[c] is writable for x < dst_w[c],
-//     y < dst_h[c] and 2-byte aligned where sample_bytes is 2 (general form: dst[0..2] given, dst[3] may be nullptr);
+//     y < dst_h[c] and aligned to sample_bytes (general form: dst[0..2] given, dst[3] may be nullptr);
 //   * packed: slot[] is a permutation of 0..3, pix and pix_rowbytes are multiples of 4 * sample_bytes, and every record of
 //     dst_w[0] x dst_h[0] is writable.
 
 struct RgbaComp { const void *plane; uint32_t prec, sub_x, sub_y; };
 // What j2k_hip_decode_rgba refuses about its destination before anything else happens (J2K_HIP_ERR_PARAM): a struct of
-// another size, sample_bits other than 8 / 16, a depth outside 1..sample_bits, channels of unlike
-// sample_bits or depth, demote_ae16 on anything but 16-bit samples of depth 16.  `alpha`: whether dst.a is a destination
+// another size, sample_bits other than 8 / 16 / 32, a depth outside 1..sample_bits (float: 1..16), a float channel off the
+// 4-byte grid, channels of unlike sample_bits or depth, demote_ae16 on anything but 16-bit or float samples of depth 16.  `alpha`: whether dst.a is a destination
 // (the C ABI: a.base != NULL; the stage hook, whose bases are offsets: a.sample_bits != 0).
 void check_rgba_dst(const j2k_hip_rgba_dst &dst, bool alpha);
 // Fills the arguments.  comps: the cls.ncomp components the mode reads.  ch[0..3] = R, G, B, A with their FINAL (device)

@@ -62,6 +62,16 @@ std::atomic<unsigned> g_next_device{0};
 // A handle on `device`, or -- with device < 0 -- on the next device in turn.  A thread keeps its handle (and device) across
 // frames; `renew` drops it first (the caller saw J2K_HIP_ERR_DEVICE: the thread moves on to the next device, and with a
 // fixed device gets a fresh handle on the same one).
+// Channel.sampleType / .depth -> sample_bits / depth of the C ABI.  A FLOAT channel (depth 32: a 32-bpc world) stands for 16-bit
+// integers: what SmartCopyWorld's ARGB128 -> ARGB64 copy made of it, without the copy (include/j2k_hip.h: float samples).
+bool sample_type_ok(const j2k::Channel &c)
+{
+    return c.sampleType == j2k::UCHAR || c.sampleType == j2k::USHORT || (c.sampleType == j2k::FLOAT && c.depth == 32);
+}
+uint32_t sample_bits_of(const j2k::Channel &c) { return c.sampleType == j2k::FLOAT ? 32 : (c.sampleType == j2k::USHORT ? 16 : 8); }
+uint32_t depth_of(const j2k::Channel &c) { return c.sampleType == j2k::FLOAT ? 16 : c.depth; }
+bool deep(const j2k::Channel &c) { return c.sampleType == j2k::USHORT || c.sampleType == j2k::FLOAT; } // a "15+1-bit" world under Promote / Demote
+
 j2k_hip_encoder *thread_handle(int device, bool renew = false)
 {
     if (renew && t_enc.h) { j2k_hip_destroy(t_enc.h); t_enc.h = nullptr; }
@@ -157,10 +167,10 @@ void HipCodec::ReadFile(InputFile &file, const Buffer &buffer, unsigned int subs
     bool ok = buffer.channels >= 1 && buffer.channels <= J2K_CODEC_MAX_CHANNELS;
     for (int i = 0; ok && i < buffer.channels; i++) {
         const Channel &c = buffer.channel[i];
-        ok = !c.sgnd && (c.sampleType == UCHAR || c.sampleType == USHORT) && c.buf != NULL;
+        ok = !c.sgnd && sample_type_ok(c) && c.buf != NULL;
         planes[i].base = c.buf; planes[i].colbytes = c.colbytes; planes[i].rowbytes = c.rowbytes;
-        planes[i].sample_bits = c.sampleType == USHORT ? 16 : 8;
-        planes[i].depth = c.depth; planes[i].width = c.width; planes[i].height = c.height;
+        planes[i].sample_bits = sample_bits_of(c);
+        planes[i].depth = depth_of(c); planes[i].width = c.width; planes[i].height = c.height;
     }
     if (!ok) { t_enc.error = "unsupported destination Buffer"; throw Exception("Error reading file"); }
     if (_fallback != NULL) { // the header already tells most unsupported files apart: no device is touched for them
@@ -204,11 +214,11 @@ bool HipCodec::ReadFiles(InputFile *const *files, const Buffer *buffers, unsigne
         ok = ok && buffers[f].channels == nch;
         for (int i = 0; ok && i < nch; i++) {
             const Channel &c = buffers[f].channel[i];
-            ok = !c.sgnd && (c.sampleType == UCHAR || c.sampleType == USHORT) && c.buf != NULL;
+            ok = !c.sgnd && sample_type_ok(c) && c.buf != NULL;
             j2k_hip_outplane &p = planes[(size_t)f * nch + i];
             p.base = c.buf; p.colbytes = c.colbytes; p.rowbytes = c.rowbytes;
-            p.sample_bits = c.sampleType == USHORT ? 16 : 8;
-            p.depth = c.depth; p.width = c.width; p.height = c.height;
+            p.sample_bits = sample_bits_of(c);
+            p.depth = depth_of(c); p.width = c.width; p.height = c.height;
         }
     }
     if (!ok) { t_enc.error = "unsupported destination Buffer"; throw Exception("Error reading file"); }
@@ -250,14 +260,14 @@ bool HipCodec::ReadRGBA(InputFile &file, const Channel &r, const Channel &g, con
     for (int i = 0; i < 4; i++) {
         const Channel &c = *src[i];
         if (c.buf == NULL && i == 3) { all16 = false; continue; } // no alpha wanted
-        ok = ok && c.buf != NULL && !c.sgnd && (c.sampleType == UCHAR || c.sampleType == USHORT);
-        all16 = all16 && c.sampleType == USHORT;
+        ok = ok && c.buf != NULL && !c.sgnd && sample_type_ok(c);
+        all16 = all16 && deep(c);
         out[i]->base = c.buf; out[i]->colbytes = c.colbytes; out[i]->rowbytes = c.rowbytes;
-        out[i]->sample_bits = c.sampleType == USHORT ? 16 : 8;
-        out[i]->depth = c.depth; out[i]->width = c.width; out[i]->height = c.height;
+        out[i]->sample_bits = sample_bits_of(c);
+        out[i]->depth = depth_of(c); out[i]->width = c.width; out[i]->height = c.height;
     }
     if (!ok) { t_enc.error = "unsupported destination channels"; throw Exception("Error reading file"); }
-    dst.demote_ae16 = (_options & DemoteAE16) && all16 ? 1 : 0; // only 16-bit worlds are "15+1", as on the write side
+    dst.demote_ae16 = (_options & DemoteAE16) && all16 ? 1 : 0; // only 16-bit and float worlds are "15+1", as on the write side
     uint32_t mode = 0; // the header tells the files of the other path apart: no device is touched for them
     const int mode_rc = j2k_hip_rgba_mode(data.data(), data.size(), &mode);
     if (mode_rc != J2K_HIP_OK) {
@@ -376,15 +386,15 @@ void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &b
     for (int i = 0; ok && i < buffer.channels; i++) {
         const Channel &c = buffer.channel[i];
         assert(c.width == info.width && c.height == info.height); // reference: :637
-        ok = c.width == info.width && c.height == info.height && !c.sgnd && (c.sampleType == UCHAR || c.sampleType == USHORT);
+        ok = c.width == info.width && c.height == info.height && !c.sgnd && sample_type_ok(c);
         planes[i].base = c.buf; planes[i].colbytes = c.colbytes; planes[i].rowbytes = c.rowbytes;
-        planes[i].sample_bits = c.sampleType == USHORT ? 16 : 8;  // reference: param.bpp, :646
-        planes[i].depth = c.depth;
+        planes[i].sample_bits = sample_bits_of(c);  // reference: param.bpp, :646
+        planes[i].depth = depth_of(c);
     }
     if (!ok) { t_enc.error = "inconsistent FileInfo/Buffer"; throw Exception("Error writing file"); }
-    if (_options & PromoteAE16) { // only 16-bit worlds are "15+1" (the AE layer promotes ARGB64 alone, aftereffects/j2k.cpp:843)
-        bool all16 = true;
-        for (int i = 0; i < buffer.channels; i++) all16 = all16 && buffer.channel[i].sampleType == USHORT;
+    if (_options & PromoteAE16) { // only 16-bit worlds are "15+1" (the AE layer promotes ARGB64 alone, aftereffects/j2k.cpp:843) -- and the float
+        bool all16 = true;        // worlds that SmartCopyWorld brings there first (FrameSeq.cpp:189-198): x 32768, then Promote
+        for (int i = 0; i < buffer.channels; i++) all16 = all16 && deep(buffer.channel[i]);
         p.promote_ae16 = all16 ? 1 : 0;
     }
 

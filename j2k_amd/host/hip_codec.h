@@ -58,11 +58,14 @@ class HipCodec : public Codec {
     // goes to the top-left of the destination channels
     virtual void ReadFile(InputFile &file, const Buffer &buffer, unsigned int subsample = 1, Progress *progress = NULL);
     virtual void WriteFile(OutputFile &file, const FileInfo &info, const Buffer &buffer, Progress *progress = NULL);
+    // Channels of sampleType FLOAT, depth 32 (a 32-bpc world, ARGB128) are taken by WriteFile, ReadFile, ReadRGBA and ReadFiles
+    // as they are: they stand for 16-bit samples (planes of sample_bits 32, depth 16; include/j2k_hip.h), quantised by the
+    // front-end kernel and written as floats by the output kernels.  PromoteAE16 / DemoteAE16 select the 15+1-bit forms.
 
     // The whole of RGBAinputFile::ReadFile (src/common/j2k_rgba_file.cpp:450-735) in one decode: the file's components go
     // straight to the R, G, B, A channels of the caller's world -- sYCC -> RGB, grey into three channels, the palette
     // look-up, the alpha fill (full scale at the channels' depth: 2^depth - 1, where the reference stores 255 into a 16-bit
-    // world) and, with DemoteAE16 and four USHORT channels, Demote -- in the decode's output kernel (include/j2k_hip.h:
+    // world) and, with DemoteAE16 and four USHORT or FLOAT channels, Demote -- in the decode's output kernel (include/j2k_hip.h:
     // j2k_hip_decode_rgba).  a.buf == NULL: no alpha wanted.
     // true: the frame is written.  false: not a file the fused path takes (status J2K_HIP_ERR_UNSUPPORTED: CMYK, e-sYCC, an
     // opacity channel that is not the last one, a feature the GPU decoder lacks ... -- the reference's own code asserts on the

@@ -161,7 +161,7 @@ long j2k_host_test_read(const unsigned char *file, unsigned long file_len, unsig
     for (int i = 0; i < 4; i++) {
         Channel &c = argb[i];
         c.width = width; c.height = height;
-        c.sampleType = pixel_size == 2 ? USHORT : UCHAR;
+        c.sampleType = pixel_size == 4 ? FLOAT : (pixel_size == 2 ? USHORT : UCHAR); // (4: an ARGB128 world of floats, depth 32)
         c.depth = (unsigned char)depth;
         c.sgnd = false;
         c.buf = frame + i * pixel_size;
@@ -202,7 +202,7 @@ long j2k_host_test_read_rgba(const unsigned char *file, unsigned long file_len, 
     for (int i = 0; i < 4; i++) {
         Channel &c = argb[i];
         c.width = width; c.height = height;
-        c.sampleType = pixel_size == 2 ? USHORT : UCHAR;
+        c.sampleType = pixel_size == 4 ? FLOAT : (pixel_size == 2 ? USHORT : UCHAR); // (4: an ARGB128 world of floats, depth 32)
         c.depth = (unsigned char)depth;
         c.sgnd = false;
         c.buf = frame + i * pixel_size;
@@ -275,7 +275,7 @@ long j2k_host_test_lut(const unsigned char *file, unsigned long file_len, unsign
     return (long)info.LUTsize;
 }
 
-// frame: interleaved A,R,G,B samples (pixel_size = bytes per sample: 1 or 2), rowbytes as in
+// frame: interleaved A,R,G,B samples (pixel_size = bytes per sample: 1, 2 or 4 = floats), rowbytes as in
 // PF_EffectWorld.  channels = 1, 3 or 4 (FileInfo.channels); honour != 0 -> HipCodec::HonourSettings.
 // Returns the codestream length (copied to out if it fits), or -1 after a j2k::Exception whose
 // what() is copied to err.
@@ -306,7 +306,7 @@ long j2k_host_test_write_ex(const unsigned char *frame, unsigned width, unsigned
     for (int i = 0; i < 4; i++) {
         Channel &c = argb[i];
         c.width = width; c.height = height;
-        c.sampleType = pixel_size == 2 ? USHORT : UCHAR;
+        c.sampleType = pixel_size == 4 ? FLOAT : (pixel_size == 2 ? USHORT : UCHAR); // (4: an ARGB128 world of floats, depth 32)
         c.depth = (unsigned char)(pixel_size * 8);
         c.sgnd = false;
         c.buf = const_cast<unsigned char *>(frame) + i * pixel_size;

@@ -130,7 +130,9 @@ typedef struct FileInfo {
     }
 } FileInfo;
 
-enum SampleType { UCHAR, USHORT, UINT, INT };
+// FLOAT (the reference has it commented out, src/aftereffects/j2k.cpp:341): IEEE binary32 samples of nominal range 0..1, the
+// channels of a 32-bpc world (PF_PixelFormat_ARGB128); Channel.depth is then 32.  HipCodec takes them (hip_codec.h).
+enum SampleType { UCHAR, USHORT, UINT, INT, FLOAT };
 
 // A borrowed strided view of one channel of the host's frame.
 typedef struct Channel {

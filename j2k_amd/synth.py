@@ -82,3 +82,33 @@ def ae_frame(pl: np.ndarray, prec: int, row_pad_bytes: int = 0) -> tuple[np.ndar
         view[:, :, 1 + i] = (src.astype(np.int64) << shift).astype(dt)
     return buf, dict(sample_bytes=sb, colbytes=4 * sb, rowbytes=rowbytes,
                      channel_offsets=(0, sb, 2 * sb, 3 * sb))
+
+
+def ae_frame_float(pl: np.ndarray, depth: int, row_pad_bytes: int = 0, promote: bool = False, prec: int | None = None) -> tuple[np.ndarray, dict]:
+    """The same planes as an After Effects 32-bpc world (PF_PixelFormat_ARGB128: four IEEE floats A,R,G,B per pixel).
+
+    The floats stand for integer samples of `depth` bits (1..16): sample / (2^depth - 1) in float32 arithmetic -- the value the
+    library's quantisation returns to `sample` exactly.  pl holds samples of `prec` bits (default: depth), left-justified to
+    `depth` as ae_frame stores them.  promote (depth 16): the world is the 15+1-bit one as floats, Demote(sample) / 32768,
+    to be encoded with promote_ae16.  The layout carries sample_bytes = 4 and the depth.
+    """
+    ncomp, h, w = pl.shape
+    shift = depth - (depth if prec is None else prec)
+    assert 1 <= depth <= 16 and shift >= 0 and (not promote or depth == 16)
+    full = (1 << depth) - 1
+    rowbytes = 16 * w + row_pad_bytes
+    assert rowbytes % 4 == 0
+    buf = np.zeros(h * rowbytes, dtype=np.uint8)
+    view = np.lib.stride_tricks.as_strided(buf.view(np.float32), shape=(h, w, 4), strides=(rowbytes, 16, 4), writeable=True)
+
+    def as_float(samples):
+        v = np.asarray(samples, dtype=np.int64)
+        if promote:  # Demote (reference: src/aftereffects/FrameSeq.cpp:265-268)
+            v = np.where(v > 32768, ((v - 1) >> 1) + 1, v >> 1)
+            return v.astype(np.float32) / np.float32(32768)
+        return v.astype(np.float32) / np.float32(full)
+    view[:, :, 0] = as_float(full if ncomp < 4 else (pl[3].astype(np.int64) << shift))
+    for i in range(3):
+        src = pl[i] if ncomp >= 3 else pl[0]
+        view[:, :, 1 + i] = as_float(src.astype(np.int64) << shift)
+    return buf, dict(sample_bytes=4, colbytes=16, rowbytes=rowbytes, channel_offsets=(0, 4, 8, 12), depth=depth)
