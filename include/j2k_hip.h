@@ -530,6 +530,26 @@ int j2k_hip_decode_rgba_sequence(j2k_hip_encoder *enc, const j2k_hip_file *files
 int j2k_hip_decode_rgba_sequence_device(j2k_hip_encoder *enc, const j2k_hip_file *files, uint32_t nframes, uint32_t subsample,
                                         const j2k_hip_rect *region, const j2k_hip_rgba_dst *dsts);
 
+/* --- decode only the first quality layers of a file -------------------------------------------------
+ * A property of the handle, as decoder parameters are of libopenjp2's codec (opj_dparameters_t::cp_layer): max_layers = 0
+ * (the initial value) decodes every layer; L >= 1 makes every decode call on the handle -- j2k_hip_decode[_device],
+ * _decode_region[_device], _decode_rgba[_device], _decode_sequence[_device] and _decode_rgba_sequence[_device], all frames
+ * of a sequence call alike -- deliver, sample for sample, what it would deliver for the file that holds only the first L
+ * layers: the codestream with every packet of layer index >= L removed, COD's layer count set to L and the tile-part
+ * lengths fixed up.  The setting is sticky until it is set again.
+ * What happens: every packet header is still parsed (the headers are one serial bit stream whose inclusion, length and
+ * segment state advance with every layer), the contributions of layers >= L are dropped, a code-block keeps the coding
+ * passes and bytes of the layers below L, and one first included in a later layer stays all zero.  Under the bypass and
+ * termall styles the segments handed to Tier-1 list the kept passes and bytes only (the last may hold fewer passes than it
+ * has room for; bytes past the kept ones read 0xFF, as for a file cut short).  Files with POC are filtered the same way.
+ * L equal to the file's layer count, or larger, is the decode of 0: the same launches, tables and bytes.  A malformed file is
+ * malformed whatever L is.  Tier-1 time follows the coding passes that remain (j2k_hip_debug_decode_work).
+ * enc == NULL: J2K_HIP_ERR_PARAM; between j2k_hip_encode_begin_borrowed and its _end both calls are refused like every
+ * other.  j2k_hip_read_info, j2k_hip_rgba_mode and j2k_hip_decode_sequence_check take no handle and are unaffected.
+ * J2K_HIP_ABI_VERSION is still 9: functions were added, none changed. */
+int j2k_hip_decode_set_max_layers(j2k_hip_encoder *enc, uint32_t max_layers);
+int j2k_hip_decode_get_max_layers(const j2k_hip_encoder *enc, uint32_t *max_layers);
+
 /* --- stage-level entry points (parity tests and roofline measurement call these) -----------------
  * A1+A2+A4+A5: front end only. d_out = channels planes of width*height 32-bit words (int32 for
  * reversible, float32 bit patterns otherwise), row stride = width.  With sub-sampled components (comp_sub_x / _y,
@@ -708,6 +728,9 @@ int j2k_hip_debug_fused_occupancy(j2k_hip_encoder *enc, int reversible, int chan
 /* Which Tier-1 decode kernel the handle's last decode call took (tools report it beside their timings): the code-blocks
  * decoded by the lane-per-block kernel and by the wave-per-block kernel (the whole call, or the tail beside the lanes). */
 int j2k_hip_debug_decode_kernels(const j2k_hip_encoder *enc, uint64_t *lane_blocks, uint64_t *wave_blocks);
+/* The work the handle's last decode call handed to Tier-1, summed over the frames of a sequence call: the coding passes of
+ * the code-blocks decoded and their codeword bytes (what a layer limit, a region or a subsample leaves of the file). */
+int j2k_hip_debug_decode_work(const j2k_hip_encoder *enc, uint64_t *passes, uint64_t *codeword_bytes);
 /* Two sinks in native code for benchmarks and tools driven from a scripting language (bench.py's `host_path`): what they
  * time is then the library and a plain memcpy, not an interpreter's callback.  Both have j2k_hip_write_fn's signature.
  * j2k_hip_debug_copy_sink: `user` = a j2k_hip_copy_sink; appends the bytes at dst + pos (what OutputFile::Write into a

@@ -89,6 +89,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_rgba_mode", "j2k_hip_decode_rgba", "j2k_hip_decode_rgba_device", "j2k_hip_stage_rgba_output",
            "j2k_hip_decode_sequence_check", "j2k_hip_decode_sequence", "j2k_hip_decode_sequence_device",
            "j2k_hip_decode_rgba_sequence", "j2k_hip_decode_rgba_sequence_device", "j2k_hip_debug_decode_kernels",
+           "j2k_hip_decode_set_max_layers", "j2k_hip_decode_get_max_layers", "j2k_hip_debug_decode_work",
            "j2k_hip_encode_tiles", "j2k_hip_device_count", "j2k_hip_encode_batch",
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
@@ -229,6 +230,9 @@ def load_library():
     L.j2k_hip_decode_rgba_sequence.argtypes = [C.c_void_p, C.POINTER(SeqFile), C.c_uint32, C.c_uint32, C.POINTER(Rect), C.POINTER(RgbaDst)]
     L.j2k_hip_decode_rgba_sequence_device.argtypes = L.j2k_hip_decode_rgba_sequence.argtypes
     L.j2k_hip_debug_decode_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.j2k_hip_debug_decode_work.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.j2k_hip_decode_set_max_layers.argtypes = [C.c_void_p, C.c_uint32]
+    L.j2k_hip_decode_get_max_layers.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.j2k_hip_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.j2k_hip_get_dwt_level_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
     L.j2k_hip_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -821,6 +825,22 @@ class Encoder:
                 _set_outplane(p, v.ctypes.data, v.strides[1], v.strides[0], 8 * v.itemsize, depth or _array_depth(v), v.shape[1], v.shape[0])
         fa, _keep = _seq_files(files)
         self._check(self.L.j2k_hip_decode_rgba_sequence(self.h, fa, nf, subsample, C.byref(Rect(*region)) if region is not None else None, dsts))
+
+    def set_max_layers(self, layers: int):
+        """j2k_hip_decode_set_max_layers: every decode call on this handle keeps the first `layers` quality layers of its file
+        (0 = all); sticky until set again."""
+        self._check(self.L.j2k_hip_decode_set_max_layers(self.h, layers))
+
+    def max_layers(self) -> int:
+        v = C.c_uint32()
+        self._check(self.L.j2k_hip_decode_get_max_layers(self.h, C.byref(v)))
+        return v.value
+
+    def decode_work(self) -> tuple:
+        """(coding passes, codeword bytes) handed to Tier-1 by the last decode call, summed over the frames of a sequence call."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self.L.j2k_hip_debug_decode_work(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def decode_kernels(self) -> tuple:
         """(blocks the lane-per-block kernel took, blocks the wave-per-block kernel took) in the last decode call."""

@@ -388,7 +388,7 @@ void reduced_size(const Coding &cod, uint32_t reduce, int &ow, int &oh)
     oh = ceildivpow2((int)(cod.img_y0 + cod.height), (int)reduce) - ceildivpow2((int)cod.img_y0, (int)reduce);
 }
 
-DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const uint32_t *window)
+DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const uint32_t *window, uint32_t max_layers)
 {
     DecodePlan P;
     P.hdr = parse_headers(file, len);
@@ -486,8 +486,18 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const u
     }
 
     // ---- packets
-    struct BlockState { uint32_t numbps = 0, npasses = 0, lenbits = 3; bool included = false; uint32_t first_seg = 0, nseg = 0; uint64_t bytes = 0; };
+    // A layer limit (max_layers) keeps the contributions of layers < max_layers.  Every packet header is still parsed -- the
+    // headers are one bit stream, and inclusion, Lblock and the segment state advance with every layer -- so what is PARSED
+    // (included, lenbits, seen_passes, bsegs) is kept apart from what is KEPT (npasses, bytes, the pieces, and of the
+    // segments the first kept_segs, the last of them with kept_last_np passes in kept_last_len bytes): layers reach a block
+    // in order, so what is kept is the state at its first dropped contribution.
+    struct BlockState {
+        uint32_t numbps = 0, npasses = 0, lenbits = 3; bool included = false; uint32_t first_seg = 0, nseg = 0; uint64_t bytes = 0;
+        uint32_t seen_passes = 0;
+        bool cut = false; uint32_t kept_segs = 0, kept_last_np = 0, kept_last_len = 0;
+    };
     std::vector<BlockState> st(g.cblks.size());
+    const uint32_t keep_layers = (max_layers == 0 || max_layers >= cod.layers) ? 0xffffffffu : max_layers; // (0, or all of them: today's plan)
     // Code-block styles that terminate the codeword inside a block (B.10.7.2): the passes of a block come in segments --
     // termall: one pass each; bypass: the first ten passes, then (significance + refinement, raw) and (cleanup, MQ) in
     // turn -- and a packet header carries one length per segment it contributes to.
@@ -578,6 +588,13 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const u
                                 if (nb > 30) { if (H.roishift[c]) unsupported("region-of-interest shift beyond 30 bit-planes"); bad("code-block with an impossible number of bit-planes"); } // (libopenjp2: bpno_plus_one >= 31 is an error)
                                 bs.numbps = (uint32_t)nb; bs.lenbits = 3; bs.included = true;
                             }
+                            if (l >= keep_layers && !bs.cut) { // the block's first dropped contribution: freeze what is kept
+                                bs.cut = true;
+                                if (multiseg && !bsegs[id].empty()) {
+                                    bs.kept_segs = (uint32_t)bsegs[id].size();
+                                    bs.kept_last_np = bsegs[id].back().np; bs.kept_last_len = bsegs[id].back().len;
+                                }
+                            }
                             const int np = read_numpasses(br);
                             while (br.bit()) { if (++bs.lenbits > 32 || br.overrun) break; }
                             uint64_t ln = 0;
@@ -623,8 +640,10 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const u
                     BlockState &bs = st[t.id];
                     // A block of numbps bit-planes (a region-of-interest shift included) has 3 numbps - 2 coding passes at most: more is a
                     // malformed file, rejected here -- the device tables are sized by this bound and nothing downstream clamps silently.
-                    if (bs.npasses + t.np > (uint32_t)kMaxPasses + 13 || (bs.numbps && bs.npasses + t.np > 3 * bs.numbps - 2))
+                    if (bs.seen_passes + t.np > (uint32_t)kMaxPasses + 13 || (bs.numbps && bs.seen_passes + t.np > 3 * bs.numbps - 2))
                         bad("code-block with more coding passes than its bit-planes allow");
+                    bs.seen_passes += t.np;
+                    if (l >= keep_layers) { p += t.len; continue; } // a dropped layer: parsed, its bytes skipped
                     // a contribution may straddle two tile-parts of the tile: cut it at the boundary of the file span
                     uint32_t left = t.len;
                     const uint8_t *q = p;
@@ -714,7 +733,10 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const u
             // (a file cut short may have lost bytes the headers had promised: a segment ends where the block's bytes end)
             db.seg_first = (uint32_t)P.cwsegs.size();
             uint64_t at = 0;
-            for (const CwSeg &sg : bsegs[id]) {
+            const size_t nsg = bs.cut ? bs.kept_segs : bsegs[id].size();
+            for (size_t k = 0; k < nsg; ++k) {
+                CwSeg sg = bsegs[id][k];
+                if (bs.cut && k + 1 == nsg) { sg.np = bs.kept_last_np; sg.len = bs.kept_last_len; } // (it went on growing in dropped layers)
                 P.cwsegs.push_back(cwseg_word(cwseg_have(sg.len, at, bs.bytes), sg.np));
                 at += sg.len;
             }

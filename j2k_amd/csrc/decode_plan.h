@@ -117,7 +117,12 @@ struct DecodePlan {
 
 // Tier-2 of the whole file for a decode at resolution `reduce` (0 = full size).  window (optional): x, y, w, h in pixels of
 // the image as it is delivered at this resolution (top-left at (0, 0)); outside that image: Error(J2K_HIP_ERR_PARAM).
-DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const uint32_t *window = nullptr);
+// max_layers (0 = all): keep the first max_layers quality layers only.  The plan is, block for block, the plan of the file
+// with every packet of a later layer removed and COD's layer count set to max_layers (what libopenjp2 decodes for
+// opj_dparameters_t::cp_layer): all packet headers are parsed, a block keeps the passes and bytes of the kept layers, a block
+// first included later holds nothing, and under bypass / termall the segment table lists the kept passes and bytes only
+// (its last segment may hold fewer passes than it has room for).  max_layers >= the file's layers: the plan of 0.
+DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const uint32_t *window = nullptr, uint32_t max_layers = 0);
 // the size of the delivered image at resolution `reduce` (opj_image_comp_header_update: both edges scaled, then subtracted)
 void reduced_size(const Coding &cod, uint32_t reduce, int &ow, int &oh);
 

@@ -757,6 +757,8 @@ void decode_group(j2k_hip_encoder *e, const DecodeCall &call, const Shape &S, De
     st.num_codeblocks += nb;
     e->dec_lane_blocks += nl * (lanes ? 1 : 0);
     e->dec_wave_blocks += nwave;
+    for (const DecBlock &b : M.blocks) e->dec_passes += passes_of(b);
+    e->dec_cw_bytes += cw_bytes;
 }
 
 // What a group of frames [a, b) needs on the device, from their plans: the waves of a lane launch and the bytes of its arenas
@@ -857,6 +859,8 @@ void decode_frames(j2k_hip_encoder *e, const DecodeCall &call)
     // fails the call when its group is reached, the groups before it are complete by then.
     j2k_hip_stats st{};
     e->dec_lane_blocks = e->dec_wave_blocks = 0;
+    e->dec_passes = e->dec_cw_bytes = 0;
+    const uint32_t max_layers = e->dec_max_layers; // (read once: the planning threads share it)
     std::vector<DecodePlan> plans(n);
     std::vector<std::exception_ptr> plan_err(n);
     bool file_uploaded = false;
@@ -868,7 +872,7 @@ void decode_frames(j2k_hip_encoder *e, const DecodeCall &call)
         file_uploaded = true;
         try {
             if (len >= (4u << 20)) {
-                auto fut = std::async(std::launch::async, [&] { return plan_decode(fbytes, len, reduce, window); });
+                auto fut = std::async(std::launch::async, [&] { return plan_decode(fbytes, len, reduce, window, max_layers); });
                 const hipError_t up = hipMemcpyAsync(e->d_file.p, fbytes, len, hipMemcpyHostToDevice, s);
                 try {
                     plans[0] = fut.get();
@@ -878,7 +882,7 @@ void decode_frames(j2k_hip_encoder *e, const DecodeCall &call)
                 }
                 HIP_CHECK(up);
             } else {
-                plans[0] = plan_decode(fbytes, len, reduce, window);
+                plans[0] = plan_decode(fbytes, len, reduce, window, max_layers);
                 HIP_CHECK(hipMemcpyAsync(e->d_file.p, fbytes, len, hipMemcpyHostToDevice, s));
             }
         } catch (const Error &x) {
@@ -889,7 +893,7 @@ void decode_frames(j2k_hip_encoder *e, const DecodeCall &call)
         std::atomic<uint32_t> next{0};
         auto work = [&] {
             for (uint32_t f; (f = next.fetch_add(1)) < n;) {
-                try { plans[f] = plan_decode(bytes_of(f), call.files[f].len, reduce, window); }
+                try { plans[f] = plan_decode(bytes_of(f), call.files[f].len, reduce, window, max_layers); }
                 catch (...) { plan_err[f] = std::current_exception(); }
             }
         };
@@ -1180,6 +1184,28 @@ int j2k_hip_debug_decode_kernels(const j2k_hip_encoder *e, uint64_t *lane_blocks
     if (!e || !lane_blocks || !wave_blocks) return J2K_HIP_ERR_PARAM;
     *lane_blocks = e->dec_lane_blocks; *wave_blocks = e->dec_wave_blocks;
     return J2K_HIP_OK;
+}
+
+int j2k_hip_debug_decode_work(const j2k_hip_encoder *e, uint64_t *passes, uint64_t *codeword_bytes)
+{
+    if (!e || !passes || !codeword_bytes) return J2K_HIP_ERR_PARAM;
+    *passes = e->dec_passes; *codeword_bytes = e->dec_cw_bytes;
+    return J2K_HIP_OK;
+}
+
+int j2k_hip_decode_set_max_layers(j2k_hip_encoder *e, uint32_t max_layers)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] { e->dec_max_layers = max_layers; });
+}
+
+int j2k_hip_decode_get_max_layers(const j2k_hip_encoder *e, uint32_t *max_layers)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(const_cast<j2k_hip_encoder *>(e), [&] {
+        if (!max_layers) throw Error(J2K_HIP_ERR_PARAM, "no place for the layer limit");
+        *max_layers = e->dec_max_layers;
+    });
 }
 
 int j2k_hip_region_footprint(int reversible, uint32_t width, uint32_t height, uint32_t levels, uint32_t x0, uint32_t y0,

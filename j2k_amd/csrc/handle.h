@@ -196,6 +196,8 @@ struct j2k_hip_encoder {
     j2k_hip::DevBuf d_file, d_cw, d_masks, d_dblk, d_segs, d_outimg;
     j2k_hip::PinnedBuf h_outimg, h_dtab;
     uint64_t dec_lane_blocks = 0, dec_wave_blocks = 0; // of the last decode call: blocks the lane kernel took / the wave kernel
+    uint64_t dec_passes = 0, dec_cw_bytes = 0;         // ... and the coding passes and codeword bytes handed to Tier-1
+    uint32_t dec_max_layers = 0; // j2k_hip_decode_set_max_layers: every decode call keeps the first so many quality layers (0: all)
 };
 
 namespace j2k_hip {

@@ -11,6 +11,11 @@
 
 #include "j2k_hip.h"
 
+// The layer limit joined the C ABI without a version step (functions were added, none changed): a weak reference lets this
+// binding link and load against a libj2k_hip that predates it.  Asking such a library for a limit is an error, never a
+// quiet read of all layers (apply_read_layers).
+extern "C" int j2k_hip_decode_set_max_layers(j2k_hip_encoder *enc, uint32_t max_layers) __attribute__((weak));
+
 namespace j2k {
 namespace {
 
@@ -31,7 +36,7 @@ size_t sink_write(void *user, const void *buf, size_t n)
 
 } // namespace
 
-HipCodec::HipCodec(Mode mode, int device, unsigned options) : _mode(mode), _device(device), _options(options), _fallback(NULL) {}
+HipCodec::HipCodec(Mode mode, int device, unsigned options) : _mode(mode), _device(device), _options(options), _fallback(NULL), _read_layers(0) {}
 HipCodec::~HipCodec() {}
 
 const char *HipCodec::LastError() { return t_enc.error.c_str(); }
@@ -97,6 +102,17 @@ j2k_hip_encoder *thread_handle(int device, bool renew = false)
         t_enc.device = device;
     }
     return t_enc.h;
+}
+
+// SetReadLayers: the thread's handle serves every codec object, so the object's setting goes to it before every read.
+void apply_read_layers(j2k_hip_encoder *h, unsigned layers)
+{
+    if (j2k_hip_decode_set_max_layers == NULL) { // (a library without the entry point: no handle of it can hold a limit)
+        if (layers == 0) return;
+        t_enc.error = "this libj2k_hip has no j2k_hip_decode_set_max_layers: SetReadLayers needs a newer library";
+        throw Exception("Error reading file");
+    }
+    if (j2k_hip_decode_set_max_layers(h, layers) != J2K_HIP_OK) { t_enc.error = j2k_hip_last_error(h); throw Exception("Error reading file"); }
 }
 
 } // namespace
@@ -184,6 +200,7 @@ void HipCodec::ReadFile(InputFile &file, const Buffer &buffer, unsigned int subs
     }
     j2k_hip_encoder *h = thread_handle(_device);
     if (!h) throw Exception("Error reading file");
+    apply_read_layers(h, _read_layers);
     const int rc = j2k_hip_decode(h, data.data(), data.size(), subsample ? subsample : 1, planes, buffer.channels);
     if (rc != J2K_HIP_OK) {
         t_enc.error = j2k_hip_last_error(h);
@@ -237,6 +254,7 @@ bool HipCodec::ReadFiles(InputFile *const *files, const Buffer *buffers, unsigne
     }
     j2k_hip_encoder *h = thread_handle(_device);
     if (!h) throw Exception("Error reading file");
+    apply_read_layers(h, _read_layers);
     const int rc = j2k_hip_decode_sequence(h, in.data(), n, subsample ? subsample : 1, NULL, planes.data(), (uint32_t)nch);
     if (rc != J2K_HIP_OK) {
         t_enc.error = j2k_hip_last_error(h);
@@ -277,6 +295,7 @@ bool HipCodec::ReadRGBA(InputFile &file, const Channel &r, const Channel &g, con
     }
     j2k_hip_encoder *h = thread_handle(_device);
     if (!h) throw Exception("Error reading file");
+    apply_read_layers(h, _read_layers);
     const int rc = j2k_hip_decode_rgba(h, data.data(), data.size(), subsample ? subsample : 1, NULL, &dst);
     if (rc != J2K_HIP_OK) {
         t_enc.error = j2k_hip_last_error(h);

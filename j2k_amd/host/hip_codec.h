@@ -83,6 +83,14 @@ class HipCodec : public Codec {
     // (frames before the damaged one may have been written); LastError() names the frame.
     bool ReadFiles(InputFile *const *files, const Buffer *buffers, unsigned n, unsigned subsample);
 
+    // Draft reads: ReadFile, ReadRGBA and ReadFiles decode only the first `layers` quality layers of their files (0, the
+    // initial value: all of them; a file with fewer layers is read in full) -- sample for sample what they deliver for the
+    // file cut down to those layers, what libopenjp2 does for opj_dparameters_t::cp_layer (include/j2k_hip.h:
+    // j2k_hip_decode_set_max_layers).  Tier-1, the longest stage of a read, shrinks with the coding passes that remain.  A file
+    // handed to the fallback codec is read in full: the Codec interface has no such parameter.
+    void SetReadLayers(unsigned layers) { _read_layers = layers; }
+    unsigned ReadLayers() const { return _read_layers; }
+
     // text of the last failure on the calling thread (the exception itself carries the reference's
     // fixed message)
     static const char *LastError();
@@ -92,6 +100,7 @@ class HipCodec : public Codec {
     int _device;
     unsigned _options;
     Codec *_fallback;
+    unsigned _read_layers;
 };
 
 } // namespace j2k

@@ -76,6 +76,12 @@ class RecordingCodec : public j2k::Codec {
     virtual void WriteFile(j2k::OutputFile &, const j2k::FileInfo &, const j2k::Buffer &, j2k::Progress *) { throw j2k::Exception("read only"); }
 };
 
+// test knob of the read hooks: HipCodec::SetReadLayers
+void read_knobs(j2k::HipCodec &hip)
+{
+    if (const char *l = std::getenv("J2K_HOST_TEST_READ_LAYERS")) hip.SetReadLayers((unsigned)std::atoi(l));
+}
+
 } // namespace
 
 extern "C" {
@@ -95,6 +101,7 @@ long j2k_host_test_read_fallback(const unsigned char *file, unsigned long file_l
     }
     MemoryInputFile in(file, file_len);
     HipCodec hip(HipCodec::HonourSettings);
+    read_knobs(hip);
     RecordingCodec other;
     if (with_fallback) hip.SetFallback(&other);
     Codec *codec = &hip;
@@ -137,6 +144,7 @@ long j2k_host_test_read_files(const unsigned char *const *files, const unsigned 
     }
     for (unsigned f = 0; f < n; f++) ptrs.push_back(&ins[f]);
     HipCodec hip(HipCodec::HonourSettings);
+    read_knobs(hip);
     try {
         return hip.ReadFiles(ptrs.data(), bufs.data(), n, subsample) ? 1 : 0;
     } catch (const Exception &e) {
@@ -174,6 +182,7 @@ long j2k_host_test_read(const unsigned char *file, unsigned long file_len, unsig
     for (int c = 0; c < channels; c++) buf.channel[c] = *by_name[c];
     MemoryInputFile in(file, file_len);
     HipCodec hip(HipCodec::HonourSettings);
+    read_knobs(hip);
     Codec *codec = &hip;
     try {
         if (!codec->Verify(in)) throw Exception("Can't read this format");
@@ -212,6 +221,7 @@ long j2k_host_test_read_rgba(const unsigned char *file, unsigned long file_len, 
     if (!with_alpha) argb[0].buf = NULL;
     MemoryInputFile in(file, file_len);
     HipCodec hip(HipCodec::HonourSettings, -1, demote ? HipCodec::DemoteAE16 : HipCodec::NoOptions);
+    read_knobs(hip);
     try {
         return hip.ReadRGBA(in, argb[1], argb[2], argb[3], argb[0], subsample, NULL) ? 1 : 0;
     } catch (const Exception &e) {
