@@ -550,6 +550,47 @@ int j2k_hip_decode_rgba_sequence_device(j2k_hip_encoder *enc, const j2k_hip_file
 int j2k_hip_decode_set_max_layers(j2k_hip_encoder *enc, uint32_t max_layers);
 int j2k_hip_decode_get_max_layers(const j2k_hip_encoder *enc, uint32_t *max_layers);
 
+/* --- compare a file with its source frame ------------------------------------------------------------
+ * What did a file lose?  The source frame is given exactly as j2k_hip_encode takes it (params + planes), the file is decoded
+ * as j2k_hip_decode decodes it (subsample 1, the handle's max_layers), and both stay on the device: only the file goes up and
+ * only the results come down.  For every component c < params->channels, on the component's own grid of
+ * ceil(width / sub_x) x ceil(height / sub_y) samples:
+ *   S_c(x, y)  the unsigned integer of params->depth bits that the encode's front end makes of the planes, before the DC shift
+ *              and before any RCT / ICT: promote_ae16, the float quantisation of j2k_hip_plane, CopyChannel's depth conversion,
+ *              and with rgb_to_sycc the integer Y / Cb / Cr formula of j2k_hip_params with its decimation;
+ *   D_c(x, y)  what j2k_hip_decode delivers for component c at the file's own depth; for a sub-sampled component the delivered
+ *              sample at (x * sub_x, y * sub_y) (the decode replicates: that is the component's own sample);
+ *   e = D - S, per sample.
+ * j2k_hip_diff, one per component (struct_size set by the caller in every element): samples = the grid's size; differing = the
+ * samples with e != 0; sum_abs, sum_sq, max_abs over |e|, e^2; (first_x, first_y) = the first differing sample in raster order
+ * on the component's grid, both 0 when differing == 0.  These are exact integers, whatever order the device sums in.  The two
+ * doubles are made on the host from them: mse = (double)sum_sq / (double)samples, psnr = 10 * log10((top * top) / mse) with
+ * top = (double)(2^depth - 1), and +infinity when sum_sq == 0.  min(ndiffs, channels) elements are written.
+ * The file must describe the image of `params`: the same width, height, number of components (of more than four the first
+ * four count, as for the decode) and sub-sampling factors, unsigned components, every compared component of params->depth
+ * bits; anything else is J2K_HIP_ERR_PARAM, the text naming the field, before any device work and with nothing written.  So is
+ * a component of 2^32 samples or more (sum_sq could not hold it).  A file the decoder does not read stays
+ * J2K_HIP_ERR_UNSUPPORTED and a malformed one J2K_HIP_ERR_PARAM, both with j2k_hip_read_info's texts; a file cut short
+ * compares what decodes; a handle with an encode pending refuses as j2k_hip_decode does.  Only the fields of `params` that
+ * define the source samples and the geometry count -- width, height, channels, depth, promote_ae16, comp_sub_x / _y,
+ * rgb_to_sycc; the coding fields (wavelet, ycc, layers, tiles, precincts, style, rates, profile, wrapper) are not read.
+ * j2k_hip_compare: planes in host memory.  j2k_hip_compare_device: planes[i].base are device pointers and the image never
+ * crosses the bus.  j2k_hip_compare_check: the agreement test above alone -- no handle, no device, the text through
+ * j2k_hip_last_error(NULL); both calls run it first.
+ * J2K_HIP_ABI_VERSION is still 9: functions and a struct were added, none changed. */
+typedef struct j2k_hip_diff {
+    uint32_t struct_size;    /* = sizeof(j2k_hip_diff) */
+    uint32_t max_abs;
+    uint64_t samples, differing, sum_abs, sum_sq;
+    uint32_t first_x, first_y;
+    double mse, psnr;
+} j2k_hip_diff;
+int j2k_hip_compare_check(const j2k_hip_params *params, const void *file, size_t len);
+int j2k_hip_compare(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes, const void *file, size_t len,
+                    j2k_hip_diff *diffs, uint32_t ndiffs);
+int j2k_hip_compare_device(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes, const void *file,
+                           size_t len, j2k_hip_diff *diffs, uint32_t ndiffs);
+
 /* --- stage-level entry points (parity tests and roofline measurement call these) -----------------
  * A1+A2+A4+A5: front end only. d_out = channels planes of width*height 32-bit words (int32 for
  * reversible, float32 bit patterns otherwise), row stride = width.  With sub-sampled components (comp_sub_x / _y,
@@ -678,6 +719,13 @@ int j2k_hip_stage_rgba_output(j2k_hip_encoder *enc, int reversible, int mct, uin
                               const void *d_comp, size_t comp_words, uint32_t stride,
                               const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf, size_t buf_bytes,
                               const j2k_hip_rgba_dst *dst, const j2k_hip_rgba_stage *stage);
+
+/* The compare's reduction alone (compare_kernel), with no file involved: the source planes (device pointers, as for
+ * j2k_hip_compare_device) against decoded component planes that the caller supplies.  d_decoded (device) holds `channels` planes
+ * of unsigned 16-bit samples, each dense at the component's own size ceil(width / sub_x) x ceil(height / sub_y), one after
+ * another.  Parameters, refusals and results as for j2k_hip_compare. */
+int j2k_hip_stage_compare(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes_device,
+                          const void *d_decoded, j2k_hip_diff *diffs, uint32_t ndiffs);
 
 /* Tier-1 DECODING of `nblocks` code-blocks (default code-block style) into one coefficient plane of 32-bit
  * words (row stride `stride` words; int32 for reversible, float32 otherwise).  kernel = 0: a wavefront per

@@ -90,6 +90,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_decode_sequence_check", "j2k_hip_decode_sequence", "j2k_hip_decode_sequence_device",
            "j2k_hip_decode_rgba_sequence", "j2k_hip_decode_rgba_sequence_device", "j2k_hip_debug_decode_kernels",
            "j2k_hip_decode_set_max_layers", "j2k_hip_decode_get_max_layers", "j2k_hip_debug_decode_work",
+           "j2k_hip_compare_check", "j2k_hip_compare", "j2k_hip_compare_device", "j2k_hip_stage_compare",
            "j2k_hip_encode_tiles", "j2k_hip_device_count", "j2k_hip_encode_batch",
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
@@ -129,6 +130,16 @@ class RgbaStage(C.Structure):
     """include/j2k_hip.h: j2k_hip_rgba_stage."""
     _fields_ = [(n, C.c_uint32) for n in ("struct_size", "mode", "org_x", "org_y", "lut_size", "lut_columns")] + \
                [("lut", (C.c_uint8 * 4) * 256), ("lut_rgb", C.c_uint8 * 4)]
+
+
+class Diff(C.Structure):
+    """include/j2k_hip.h: j2k_hip_diff -- one component of a compare."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_abs", C.c_uint32)] + \
+               [(n, C.c_uint64) for n in ("samples", "differing", "sum_abs", "sum_sq")] + \
+               [("first_x", C.c_uint32), ("first_y", C.c_uint32), ("mse", C.c_double), ("psnr", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "struct_size"}
 
 
 class SeqFile(C.Structure):
@@ -233,6 +244,10 @@ def load_library():
     L.j2k_hip_debug_decode_work.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.j2k_hip_decode_set_max_layers.argtypes = [C.c_void_p, C.c_uint32]
     L.j2k_hip_decode_get_max_layers.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    L.j2k_hip_compare_check.argtypes = [C.POINTER(Params), C.c_void_p, C.c_size_t]
+    L.j2k_hip_compare.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Plane), C.c_void_p, C.c_size_t, C.POINTER(Diff), C.c_uint32]
+    L.j2k_hip_compare_device.argtypes = L.j2k_hip_compare.argtypes
+    L.j2k_hip_stage_compare.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Plane), C.c_void_p, C.POINTER(Diff), C.c_uint32]
     L.j2k_hip_get_stats.argtypes = [C.c_void_p, C.POINTER(Stats)]
     L.j2k_hip_get_dwt_level_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int]
     L.j2k_hip_malloc.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]
@@ -454,6 +469,36 @@ def _split_comps(raw: np.ndarray, params: Params):
         out.append(words[pos:pos + h * w].reshape(h, w))
         pos += h * w
     return out
+
+
+def compare_check(params: Params, data: bytes) -> None:
+    """Does the file describe the image of `params` (j2k_hip_compare_check: width, height, channels, depth, sub-sampling,
+    unsigned components; headers only, no device needed)?  Raises J2kHipError when it does not."""
+    L = load_library()
+    buf = np.frombuffer(data, dtype=np.uint8) if len(data) else np.zeros(0, np.uint8)
+    rc = L.j2k_hip_compare_check(C.byref(params), buf.ctypes.data if buf.size else None, buf.size)
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+
+
+def _source_views(params: Params, frame=None, layout=None, planar=None, comps=None, views=None):
+    """A source frame, given the way the encode_* methods take it, as (buffer, address of the buffer -> Plane array):
+    frame + layout (an AE frame, encode_host), planar = (channels, h, w) samples (encode_planar_host), comps = one 2-D array
+    per component (encode_components_host), or views = (buffer, callable) for any other channel views."""
+    if views is not None:
+        return views
+    if frame is not None:
+        return frame, lambda a: planes_from_layout(a, layout, params.channels)
+    dt = np.uint16 if params.depth > 8 else np.uint8
+    arrs = [np.ascontiguousarray(np.asarray(c).astype(dt)) for c in (planar if planar is not None else comps)]
+    offs, pos = [], 0
+    for a in arrs:  # (every plane at a multiple of 16 bytes of one buffer)
+        offs.append(pos)
+        pos += -(-a.nbytes // 16) * 16
+    buf = np.zeros(max(pos, 16), np.uint8)
+    for a, o in zip(arrs, offs):
+        buf[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+    return buf, lambda addr: planes_from_arrays(arrs, params.depth, base_of=lambda c: addr + offs[c])
 
 
 class Encoder:
@@ -863,6 +908,50 @@ class Encoder:
         buf = (C.c_double * 40)()
         n = self.L.j2k_hip_get_dwt_level_ms(self.h, buf, 40)
         return list(buf[:n])
+
+    # -- compare ----------------------------------------------------------------------------------
+    def _diffs(self, n: int):
+        arr = (Diff * n)()
+        for d in arr:
+            d.struct_size = C.sizeof(Diff)
+        return arr
+
+    def compare(self, data: bytes, params: Params, frame=None, layout=None, planar=None, comps=None, views=None) -> list:
+        """j2k_hip_compare: the file `data` against the source frame it was written from (host memory; given as frame + layout,
+        planar, comps or views: _source_views) -> one dict per component (samples, differing, sum_abs, sum_sq, max_abs,
+        first_x, first_y, mse, psnr)."""
+        buf, planes = _source_views(params, frame, layout, planar, comps, views)
+        diffs = self._diffs(params.channels)
+        file = np.frombuffer(data, dtype=np.uint8)
+        self._check(self.L.j2k_hip_compare(self.h, C.byref(params), planes(buf.ctypes.data), file.ctypes.data, file.size, diffs, len(diffs)))
+        return [d.as_dict() for d in diffs]
+
+    def compare_device(self, data: bytes, params: Params, frame=None, layout=None, planar=None, comps=None, views=None, d_buf=None) -> list:
+        """j2k_hip_compare_device: the same with the source frame in device memory (d_buf: it is there already)."""
+        buf, planes = _source_views(params, frame, layout, planar, comps, views)
+        diffs = self._diffs(params.channels)
+        file = np.frombuffer(data, dtype=np.uint8)
+        d_in = d_buf if d_buf is not None else self.upload(buf)
+        try:
+            self._check(self.L.j2k_hip_compare_device(self.h, C.byref(params), planes(d_in), file.ctypes.data, file.size, diffs, len(diffs)))
+        finally:
+            if d_buf is None:
+                self.free(d_in)
+        return [d.as_dict() for d in diffs]
+
+    def stage_compare(self, decoded, params: Params, frame=None, layout=None, planar=None, comps=None, views=None) -> list:
+        """j2k_hip_stage_compare: the source frame against decoded component planes supplied by the caller -- `decoded`: one 2-D
+        array of unsigned samples per component, each at the component's own size."""
+        buf, planes = _source_views(params, frame, layout, planar, comps, views)
+        dec = np.concatenate([np.ascontiguousarray(np.asarray(d).astype(np.uint16)).reshape(-1) for d in decoded])
+        diffs = self._diffs(params.channels)
+        d_in, d_dec = self.upload(buf), self.upload(dec)
+        try:
+            self._check(self.L.j2k_hip_stage_compare(self.h, C.byref(params), planes(d_in), d_dec, diffs, len(diffs)))
+        finally:
+            self.free(d_in)
+            self.free(d_dec)
+        return [d.as_dict() for d in diffs]
 
     # -- stages -----------------------------------------------------------------------------------
     def stage_frontend(self, frame: np.ndarray, layout: dict, params: Params) -> np.ndarray:

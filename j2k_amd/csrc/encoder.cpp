@@ -135,13 +135,14 @@ CblkCaps cblk_capacities(size_t area, uint32_t Mb, uint32_t style)
     return {symcap, round_up(symcap / 4 + 64 + style_room, 16)};
 }
 
+} // namespace
+
 // The working planes of one frame over the box [bx0, bx1) x [by0, by1) of the reference grid: one row stride for every
 // component (the box width rounded to 64 words: T1Args and DwtLevelArgs carry one stride), component c with the rows of its
 // own grid -- the box on that grid is ceil(box / sub-sampling factor), origin (cbx0, cby0) -- starting comp_off[c] words in;
 // frame_elems words hold them all.  Without sub-sampling: ncomp planes of stride x box rows.  The one place that lays planes
 // out, for an encode and for the front-end stage hook alike.
-struct PlaneLayout { size_t stride, comp_off[4], frame_elems; int cbx0[4], cby0[4], cw[4], ch[4]; };
-PlaneLayout plane_layout(const Coding &cod, int bx0, int by0, int bx1, int by1)
+PlaneLayout j2k_hip::plane_layout(const Coding &cod, int bx0, int by0, int bx1, int by1)
 {
     PlaneLayout l{};
     l.stride = round_up((size_t)(bx1 - bx0), 64);
@@ -154,6 +155,7 @@ PlaneLayout plane_layout(const Coding &cod, int bx0, int by0, int bx1, int by1)
     }
     return l;
 }
+namespace {
 
 // Build (or reuse) geometry, code-block table and DWT job lists; upload the device images.
 void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first, uint32_t tile_count)
@@ -279,8 +281,10 @@ void check_plane(const Coding &cod, const j2k_hip_plane &p)
     if (p.sample_bits == 32 && cod.promote && p.depth != 16) throw Error(J2K_HIP_ERR_PARAM, "promote_ae16 on a float channel needs depth 16");
 }
 
+} // namespace
+
 // Fill FrontendArgs from channel views whose `base` pointers are device pointers.
-FrontendArgs make_frontend_args(const Coding &cod, const j2k_hip_plane *planes, int x0, int y0, int x1, int y1)
+FrontendArgs j2k_hip::make_frontend_args(const Coding &cod, const j2k_hip_plane *planes, int x0, int y0, int x1, int y1)
 {
     FrontendArgs fa{};
     fa.ncomp = (int)cod.ncomp; fa.x0 = x0; fa.width = x1; fa.y0 = y0; fa.y1 = y1;
@@ -314,6 +318,7 @@ FrontendArgs make_frontend_args(const Coding &cod, const j2k_hip_plane *planes, 
     }
     return fa;
 }
+namespace {
 
 // Does level 1 of the DWT take its samples straight from the frame (dwt_fused_kernel) -- the one place that decides it, for
 // an encode (in one piece or in bands) and for the stage hook alike?  After Effects layout (1, 3 or 4 channels out of one
@@ -330,11 +335,13 @@ bool fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tuning &tn)
     return !tn.no_fuse && cod.levels() >= 1 && fa.interleaved && same_depth && (cod.ncomp == 1 || cod.ncomp == 3 || cod.ncomp == 4);
 }
 
+} // namespace
+
 // The stand-alone front end of one frame into planes of row stride S words, component c at dst + comp_off[c]; fa: the frame's
 // channel views (make_frontend_args), its dst_x0 / dst_y0 the planes' origin.  Components of one size: one launch of
 // frontend_kernel.  rgb_to_sycc: the channels are R, G, B[, A] of the whole image, one launch of the Y Cb Cr kernel writes every
 // component at its own size.  Sub-sampled planes given as they are: every component is a frame of its own -- one launch each.
-void run_frontend(const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t comp_off[4], size_t S, hipStream_t s)
+void j2k_hip::run_frontend(const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t comp_off[4], size_t S, hipStream_t s)
 {
     fa.dst_stride = (long long)S;
     for (uint32_t c = 0; c < cod.ncomp; ++c) fa.dst[c] = dst + comp_off[c];
@@ -352,6 +359,7 @@ void run_frontend(const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t
         launch_frontend(f1, s);
     }
 }
+namespace {
 
 struct EncodeOut {
     const void *d_cs = nullptr;
@@ -451,6 +459,65 @@ void launch_dwt_levels(j2k_hip_encoder *e, const Coding &cod, const FrontendArgs
 
 bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_plane *planes, const Tuning &tn);
 
+} // namespace
+
+// A frame's channels from host memory into the handle's input arena, queued on s: rows [y0, y1) of the reference grid.
+// dplanes[c] = planes[c] with `base` pointing at the device copy.
+void j2k_hip::upload_planes(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_plane *planes, int y0, int y1, j2k_hip_plane dplanes[4], hipStream_t s)
+{
+    Range r("j2k_hip upload");
+    // upload the bytes that hold rows [y0,y1) of every channel: one copy for channels that share a buffer (the samples of
+    // interleaved pixels, planes that lie back to back), a copy of its own for every channel -- or group of channels --
+    // that is an allocation of its own (the planes of sub-sampled components usually are).  Nothing between two groups
+    // is read: it may be unmapped.
+    struct Span { const uint8_t *lo, *hi; };
+    Span span_of[4];
+    for (uint32_t c = 0; c < cod.ncomp; ++c) {
+        const uint8_t *lo = nullptr, *hi = nullptr;
+        const j2k_hip_plane &p = planes[c];
+        if (!p.base) throw Error(J2K_HIP_ERR_PARAM, "channel buffer is NULL");
+        check_plane(cod, p);
+        const uint8_t *b = static_cast<const uint8_t *>(p.base);
+        // (a sub-sampled component given as it is holds its own grid's samples; R, G, B, A for the Y Cb Cr front end are full size)
+        const int sx = cod.rgb_to_sycc ? 1 : cod.cdx[c], sy = cod.rgb_to_sycc ? 1 : cod.cdy[c];
+        const ptrdiff_t cy0 = (y0 + sy - 1) / sy, cy1 = (y1 + sy - 1) / sy, cw = ((ptrdiff_t)cod.width + sx - 1) / sx;
+        const uint8_t *corners[4] = {b + cy0 * p.rowbytes, b + (cy1 - 1) * p.rowbytes,
+                                     b + cy0 * p.rowbytes + (cw - 1) * p.colbytes,
+                                     b + (cy1 - 1) * p.rowbytes + (cw - 1) * p.colbytes};
+        for (const uint8_t *q : corners) {
+            if (!lo || q < lo) lo = q;
+            if (!hi || q + p.sample_bits / 8 > hi) hi = q + p.sample_bits / 8;
+        }
+        span_of[c] = Span{lo, hi};
+    }
+    // groups: channels whose spans overlap, touch or lie less than a page apart (bytes that close to two mapped spans are
+    // mapped themselves: padding between the planes of one buffer stays inside one copy)
+    uint32_t order[4] = {0, 1, 2, 3};
+    std::sort(order, order + cod.ncomp, [&](uint32_t a, uint32_t b) { return std::less<const uint8_t *>()(span_of[a].lo, span_of[b].lo); });
+    Span group[4];
+    uint32_t group_of[4] = {0, 0, 0, 0}, ngroups = 0;
+    for (uint32_t k = 0; k < cod.ncomp; ++k) {
+        const Span &sp = span_of[order[k]];
+        if (ngroups && reinterpret_cast<uintptr_t>(sp.lo) < reinterpret_cast<uintptr_t>(group[ngroups - 1].hi) + 4096) {
+            if (std::less<const uint8_t *>()(group[ngroups - 1].hi, sp.hi)) group[ngroups - 1].hi = sp.hi;
+        } else group[ngroups++] = sp;
+        group_of[order[k]] = ngroups - 1;
+    }
+    // (every group keeps its host alignment phase on the device)
+    size_t goff[4], total = 0;
+    for (uint32_t k = 0; k < ngroups; ++k) {
+        goff[k] = total + (reinterpret_cast<uintptr_t>(group[k].lo) & 15);
+        total = round_up(goff[k] + (size_t)(group[k].hi - group[k].lo) + 16, 256);
+    }
+    e->in.ensure(total);
+    // (from the caller's pageable buffer: the runtime pins the pages in place and DMAs straight from them)
+    for (uint32_t k = 0; k < ngroups; ++k)
+        HIP_CHECK(hipMemcpyAsync(e->in.as<uint8_t>() + goff[k], group[k].lo, (size_t)(group[k].hi - group[k].lo), hipMemcpyHostToDevice, s));
+    for (uint32_t c = 0; c < cod.ncomp; ++c)
+        dplanes[c].base = e->in.as<uint8_t>() + goff[group_of[c]] + (static_cast<const uint8_t *>(planes[c].base) - group[group_of[c]].lo);
+}
+namespace {
+
 // First half of the path: input, front end, DWT, Tier-1 launches, per-block results on their way to the
 // host.  Returns as soon as everything is queued (host frames: once the frame has left the caller's buffer,
 // which may be reused at once); encode_end() waits, plans the codestream and assembles it.
@@ -498,58 +565,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     // ---- input
     j2k_hip_plane dplanes[4];
     for (uint32_t c = 0; c < cod.ncomp; ++c) dplanes[c] = planes[c];
-    if (!planes_on_device) {
-        Range r("j2k_hip upload");
-        // upload the bytes that hold rows [y0,y1) of every channel: one copy for channels that share a buffer (the samples of
-        // interleaved pixels, planes that lie back to back), a copy of its own for every channel -- or group of channels --
-        // that is an allocation of its own (the planes of sub-sampled components usually are).  Nothing between two groups
-        // is read: it may be unmapped.
-        struct Span { const uint8_t *lo, *hi; };
-        Span span_of[4];
-        for (uint32_t c = 0; c < cod.ncomp; ++c) {
-            const uint8_t *lo = nullptr, *hi = nullptr;
-            const j2k_hip_plane &p = planes[c];
-            if (!p.base) throw Error(J2K_HIP_ERR_PARAM, "channel buffer is NULL");
-            check_plane(cod, p);
-            const uint8_t *b = static_cast<const uint8_t *>(p.base);
-            // (a sub-sampled component given as it is holds its own grid's samples; R, G, B, A for the Y Cb Cr front end are full size)
-            const int sx = cod.rgb_to_sycc ? 1 : cod.cdx[c], sy = cod.rgb_to_sycc ? 1 : cod.cdy[c];
-            const ptrdiff_t cy0 = (y0 + sy - 1) / sy, cy1 = (y1 + sy - 1) / sy, cw = ((ptrdiff_t)cod.width + sx - 1) / sx;
-            const uint8_t *corners[4] = {b + cy0 * p.rowbytes, b + (cy1 - 1) * p.rowbytes,
-                                         b + cy0 * p.rowbytes + (cw - 1) * p.colbytes,
-                                         b + (cy1 - 1) * p.rowbytes + (cw - 1) * p.colbytes};
-            for (const uint8_t *q : corners) {
-                if (!lo || q < lo) lo = q;
-                if (!hi || q + p.sample_bits / 8 > hi) hi = q + p.sample_bits / 8;
-            }
-            span_of[c] = Span{lo, hi};
-        }
-        // groups: channels whose spans overlap, touch or lie less than a page apart (bytes that close to two mapped spans are
-        // mapped themselves: padding between the planes of one buffer stays inside one copy)
-        uint32_t order[4] = {0, 1, 2, 3};
-        std::sort(order, order + cod.ncomp, [&](uint32_t a, uint32_t b) { return std::less<const uint8_t *>()(span_of[a].lo, span_of[b].lo); });
-        Span group[4];
-        uint32_t group_of[4] = {0, 0, 0, 0}, ngroups = 0;
-        for (uint32_t k = 0; k < cod.ncomp; ++k) {
-            const Span &sp = span_of[order[k]];
-            if (ngroups && reinterpret_cast<uintptr_t>(sp.lo) < reinterpret_cast<uintptr_t>(group[ngroups - 1].hi) + 4096) {
-                if (std::less<const uint8_t *>()(group[ngroups - 1].hi, sp.hi)) group[ngroups - 1].hi = sp.hi;
-            } else group[ngroups++] = sp;
-            group_of[order[k]] = ngroups - 1;
-        }
-        // (every group keeps its host alignment phase on the device)
-        size_t goff[4], total = 0;
-        for (uint32_t k = 0; k < ngroups; ++k) {
-            goff[k] = total + (reinterpret_cast<uintptr_t>(group[k].lo) & 15);
-            total = round_up(goff[k] + (size_t)(group[k].hi - group[k].lo) + 16, 256);
-        }
-        e->in.ensure(total);
-        // (from the caller's pageable buffer: the runtime pins the pages in place and DMAs straight from them)
-        for (uint32_t k = 0; k < ngroups; ++k)
-            HIP_CHECK(hipMemcpyAsync(e->in.as<uint8_t>() + goff[k], group[k].lo, (size_t)(group[k].hi - group[k].lo), hipMemcpyHostToDevice, s));
-        for (uint32_t c = 0; c < cod.ncomp; ++c)
-            dplanes[c].base = e->in.as<uint8_t>() + goff[group_of[c]] + (static_cast<const uint8_t *>(planes[c].base) - group[group_of[c]].lo);
-    }
+    if (!planes_on_device) upload_planes(e, cod, planes, y0, y1, dplanes, s);
     // the upload of one frame runs beside the kernels of the others; the dense phase starts here
     Range dense_range("j2k_hip dwt+t1 enqueue");
     std::unique_lock<std::mutex> dense(dev.dense);
@@ -1621,8 +1637,8 @@ void j2k_hip_destroy(j2k_hip_encoder *e)
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     for (auto &v : e->mqs) if (v) (void)hipStreamSynchronize(v);
     for (DevBuf *b : {&e->in, &e->P, &e->Q, &e->Z, &e->blks, &e->blks_seq, &e->jobs, &e->sym, &e->out, &e->meta, &e->passes, &e->cs, &e->plan, &e->blks_band, &e->pack_dst, &e->gate_groups, &e->gate_group_of, &e->gate_state,
-                      &e->d_file, &e->d_cw, &e->d_masks, &e->d_dblk, &e->d_segs, &e->d_outimg}) b->release();
-    for (PinnedBuf *b : {&e->h_meta, &e->h_cs, &e->h_plan, &e->h_passes, &e->h_outimg, &e->h_dtab}) b->release();
+                      &e->d_file, &e->d_cw, &e->d_masks, &e->d_dblk, &e->d_segs, &e->d_outimg, &e->cmp_dec, &e->cmp_acc}) b->release();
+    for (PinnedBuf *b : {&e->h_meta, &e->h_cs, &e->h_plan, &e->h_passes, &e->h_outimg, &e->h_dtab, &e->h_cmp}) b->release();
     for (auto &v : e->ev) if (v) (void)hipEventDestroy(v);
     for (auto &v : e->lev) if (v) (void)hipEventDestroy(v);
     for (auto &v : e->gev) if (v) (void)hipEventDestroy(v);

@@ -45,11 +45,6 @@ __global__ __launch_bounds__(256) void frontend_kernel(FrontendArgs a)
 // Exact integer arithmetic (include/j2k_hip.h): Y's sum stays below 2^32, a pixel's chroma term within +-2^31, the sum over up
 // to four pixels in 64 bits; the shift is arithmetic (floor).  The float planes of the 9/7 path receive the same integers.
 // Algorithmic bytes per pixel: 4*S read + 4*(1 [+ 1 alpha] + 2 / (SX*SY)) written.
-__device__ __forceinline__ int fe_sample(const FrontendArgs &a, int c, unsigned raw)
-{
-    if (a.promote && a.sample_bytes[c] == 2) raw = promote16(raw);
-    return (int)depth_convert(raw, a.src_depth[c], a.prec);
-}
 
 template <bool REV, int SX, int SY, bool FLT>
 __global__ __launch_bounds__(256) void frontend_sycc_kernel(FrontendArgs a)

@@ -42,6 +42,14 @@ __device__ __forceinline__ unsigned fe_quantise_float(float x, int d, bool promo
     return (unsigned)(t * (float)((1 << d) - 1) + 0.5f);
 }
 
+// raw = sample of codec channel c as stored (fe_load); the unsigned sample of a.prec bits it stands for: Promote and the depth
+// conversion, before the DC shift and any colour transform (the Y Cb Cr front end and the compare kernel work on these).
+__device__ __forceinline__ int fe_sample(const FrontendArgs &a, int c, unsigned raw)
+{
+    if (a.promote && a.sample_bytes[c] == 2) raw = promote16(raw);
+    return (int)depth_convert(raw, a.src_depth[c], a.prec);
+}
+
 // raw[c] = sample of codec channel c as stored (a float sample: as quantised, Promote included); out[c] = component value after promote, depth
 // conversion, DC shift and colour transform (int for the reversible path, float otherwise).
 template <bool REV, typename T>

@@ -198,9 +198,23 @@ struct j2k_hip_encoder {
     uint64_t dec_lane_blocks = 0, dec_wave_blocks = 0; // of the last decode call: blocks the lane kernel took / the wave kernel
     uint64_t dec_passes = 0, dec_cw_bytes = 0;         // ... and the coding passes and codeword bytes handed to Tier-1
     uint32_t dec_max_layers = 0; // j2k_hip_decode_set_max_layers: every decode call keeps the first so many quality layers (0: all)
+    // compare (compare.cpp): the decoded components as dense 16-bit planes, the accumulators, and their host image
+    j2k_hip::DevBuf cmp_dec, cmp_acc;
+    j2k_hip::PinnedBuf h_cmp;
 };
 
 namespace j2k_hip {
+
+// The front end's host side (encoder.cpp), shared with the compare calls (compare.cpp), which make the encode's source samples:
+// the working planes of one frame over a box of the reference grid ...
+struct PlaneLayout { size_t stride, comp_off[4], frame_elems; int cbx0[4], cby0[4], cw[4], ch[4]; };
+PlaneLayout plane_layout(const Coding &cod, int bx0, int by0, int bx1, int by1);
+// ... FrontendArgs from channel views whose `base` pointers are device pointers (checks the views) ...
+FrontendArgs make_frontend_args(const Coding &cod, const j2k_hip_plane *planes, int x0, int y0, int x1, int y1);
+// ... the stand-alone front end of one frame into planes of row stride S words, component c at dst + comp_off[c] ...
+void run_frontend(const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t comp_off[4], size_t S, hipStream_t s);
+// ... and a host frame's rows [y0, y1) into the handle's input arena, queued on s: dplanes[c].base = the device copy of planes[c]'s
+void upload_planes(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_plane *planes, int y0, int y1, j2k_hip_plane dplanes[4], hipStream_t s);
 
 // After a failure nothing of a handle may stay in flight (the next call reuses every arena): waits for its streams.
 void drain(j2k_hip_encoder *e);

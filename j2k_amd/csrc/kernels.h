@@ -86,6 +86,32 @@ void launch_frontend(const FrontendArgs &a, hipStream_t s);
 void launch_frontend_sycc(const FrontendArgs &a, int sub_x, int sub_y, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// Compare (compare.hip; include/j2k_hip.h: j2k_hip_compare): error sums of decoded samples against the source samples the
+// front end makes, a streaming reduction.  One launch covers `ncomp` components that share one grid of width x height samples.
+//   source:  planes == nullptr: the channel views of src (x0 = y0 = 0; ncomp channels, fe_load + fe_sample: Promote, the float
+//            quantisation and the depth conversion to src.prec) -- `wide`: every channel is a dense plane of 8- or 16-bit samples
+//            whose base and rowbytes are multiples of four samples (four samples per load);
+//            otherwise planes[c] = int32 words at row stride plane_stride holding the sample minus plane_dc (what the front-end
+//            kernels write on the reversible path without a colour transform).
+//   decoded: sample (x, y) of component c = dec[c][y * dec_sy[c] * dec_stride[c] + x * dec_sx[c]], unsigned 16-bit.
+//   result:  acc + kCompareWords * (4 * set + slot[c]), 64-bit words, zero before the first launch of a call: sum of squares, sum of
+//            absolute values, samples that differ, largest absolute difference, and ~(y * width + x) of the first one that differs in
+//            raster order (kept by a maximum, so that zero means "none").  A workgroup adds to one of kCompareSets sets; the host
+//            folds them (sums, maxima).  Integer sums: the order of the reduction does not matter.
+constexpr int kCompareWords = 8; // five used; a component's words fill one 64-byte line
+constexpr int kCompareSets = 16;
+struct CompareArgs {
+    FrontendArgs src;
+    int wide;
+    const int *planes[4]; long long plane_stride; int plane_dc;
+    const uint16_t *dec[4]; long long dec_stride[4]; int dec_sx[4], dec_sy[4];
+    int ncomp, width, height;
+    int slot[4];
+    unsigned long long *acc;
+};
+void launch_compare(const CompareArgs &a, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // Forward DWT, one decomposition level per launch, vertical + horizontal lifting fused in
 // registers (no LDS, no inter-wave exchange).  One job = one tile-component.
 struct DwtJob {

@@ -15,6 +15,10 @@
 // binding link and load against a libj2k_hip that predates it.  Asking such a library for a limit is an error, never a
 // quiet read of all layers (apply_read_layers).
 extern "C" int j2k_hip_decode_set_max_layers(j2k_hip_encoder *enc, uint32_t max_layers) __attribute__((weak));
+// The compare calls joined the same way: a library that predates them makes Compare fail loudly, and everything else links.
+extern "C" int j2k_hip_compare_check(const j2k_hip_params *params, const void *file, size_t len) __attribute__((weak));
+extern "C" int j2k_hip_compare(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes, const void *file, size_t len,
+                               j2k_hip_diff *diffs, uint32_t ndiffs) __attribute__((weak));
 
 namespace j2k {
 namespace {
@@ -308,26 +312,31 @@ bool HipCodec::ReadRGBA(InputFile &file, const Channel &r, const Channel &g, con
     return true;
 }
 
-void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &buffer, Progress *)
-{
-    assert(file.Tell() == 0);                  // reference: j2k_openjpeg_codec.cpp:592
-    assert(info.channels == buffer.channels);  // reference: :629
-    bool ok = info.channels == buffer.channels && buffer.channels >= 1 && buffer.channels <= J2K_CODEC_MAX_CHANNELS;
+namespace {
 
-    j2k_hip_params p = {};
+// FileInfo / Buffer -> j2k_hip_params / j2k_hip_plane: the one mapping, for WriteFile and for Compare (which reads the fields
+// that define the source samples and the geometry, and none of the coding fields).  rates: room for the layer targets that
+// p.layer_rates may point to.  false: FileInfo and Buffer do not agree.
+bool map_frame(HipCodec::Mode mode, unsigned options, const FileInfo &info, const Buffer &buffer, j2k_hip_params &p,
+               j2k_hip_plane planes[J2K_CODEC_MAX_CHANNELS], float rates[J2K_CODEC_MAX_LAYERS])
+{
+    bool ok = info.channels == buffer.channels && buffer.channels >= 1 && buffer.channels <= J2K_CODEC_MAX_CHANNELS;
+    if (!ok) return false;
+
+    p = j2k_hip_params();
     p.struct_size = sizeof(p);
     p.width = info.width; p.height = info.height;
     p.channels = buffer.channels; p.depth = info.depth;
     p.layers = info.settings.layers;           // reference: :708
     p.tile_size = info.settings.tileSize;      // reference: :712-719
-    if (_mode == HonourSettings) {
+    if (mode == HipCodec::HonourSettings) {
         p.reversible = info.settings.reversible; p.ycc = info.settings.ycc && buffer.channels >= 3;
         p.progression = (uint32_t)info.settings.order; // j2k::Order and the COD progression byte share their numbering
     }
     else { p.reversible = 1; p.ycc = 0; }      // what opj_set_default_encoder_parameters leaves (:705)
     p.num_resolutions = 0; p.cblk_w = 0; p.cblk_h = 0;
     p.comment = NULL;
-    if (_mode == HonourSettings && info.format != J2C && info.format != UNKNOWN_FORMAT) {
+    if (mode == HipCodec::HonourSettings && info.format != J2C && info.format != UNKNOWN_FORMAT) {
         // The reference's own JP2 branch (j2k_openjpeg_codec.cpp:613, disabled there because OpenJPEG's JP2
         // writer seeks): JP2 boxes around the same codestream, written sequentially.  JPX asks for nothing
         // this writer adds beyond JP2, so it gets a JP2-compatible file.
@@ -353,9 +362,8 @@ void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &b
         if (info.dpi > 0) p.dpi = info.dpi;
     }
 
-    float rates[J2K_CODEC_MAX_LAYERS];
     CompressionMethod method = info.settings.method;
-    if (_mode == HonourSettings && method == CINEMA) {
+    if (mode == HipCodec::HonourSettings && method == CINEMA) {
         // settings.method == CINEMA (aftereffects/j2k.cpp:639-646, :817-830): fileSize is then the budget of one frame
         // in KiB (the DCI data rate divided by the frame rate).  Frames beyond 4096 x 2160 fall back to lossless like
         // the AE layer does (:639-646).  Three 12-bit channels inside the profile's container get the real thing
@@ -385,7 +393,7 @@ void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &b
     // settings.method == QUALITY: `quality` (1..100) has no defined meaning in the reference (its WriteFile never
     // reads it, and OpenJPEG's own quality mode takes PSNR values in dB): left unmapped on purpose; a host that has a
     // PSNR in mind uses j2k_hip_params.layer_psnr directly.
-    if (_mode == HonourSettings && method == SIZE && info.settings.fileSize > 0) {
+    if (mode == HipCodec::HonourSettings && method == SIZE && info.settings.fileSize > 0) {
         // settings.fileSize (KiB) as a rate target -- the reference stores it (aftereffects/j2k.cpp:793-830) but
         // its WriteFile never hands it to OpenJPEG (:707).  Expressed the way OpenJPEG takes targets: one
         // compression ratio per layer (tcp_rates, cp_disto_alloc); the last layer meets the file size, every
@@ -401,7 +409,7 @@ void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &b
         } // a target at or above the raw size asks for nothing: lossless / full quality
     }
 
-    j2k_hip_plane planes[J2K_CODEC_MAX_CHANNELS] = {};
+    for (int i = 0; i < J2K_CODEC_MAX_CHANNELS; i++) planes[i] = j2k_hip_plane();
     for (int i = 0; ok && i < buffer.channels; i++) {
         const Channel &c = buffer.channel[i];
         assert(c.width == info.width && c.height == info.height); // reference: :637
@@ -410,21 +418,34 @@ void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &b
         planes[i].sample_bits = sample_bits_of(c);  // reference: param.bpp, :646
         planes[i].depth = depth_of(c);
     }
-    if (!ok) { t_enc.error = "inconsistent FileInfo/Buffer"; throw Exception("Error writing file"); }
-    if (_options & PromoteAE16) { // only 16-bit worlds are "15+1" (the AE layer promotes ARGB64 alone, aftereffects/j2k.cpp:843) -- and the float
+    if (!ok) return false;
+    if (options & HipCodec::PromoteAE16) { // only 16-bit worlds are "15+1" (the AE layer promotes ARGB64 alone, aftereffects/j2k.cpp:843) -- and the float
         bool all16 = true;        // worlds that SmartCopyWorld brings there first (FrameSeq.cpp:189-198): x 32768, then Promote
         for (int i = 0; i < buffer.channels; i++) all16 = all16 && deep(buffer.channel[i]);
         p.promote_ae16 = all16 ? 1 : 0;
     }
 
-    if (_mode == HonourSettings && (_options & (Chroma422 | Chroma420)) && buffer.channels >= 3 && !p.dci_profile) {
+    if (mode == HipCodec::HonourSettings && (options & (HipCodec::Chroma422 | HipCodec::Chroma420)) && buffer.channels >= 3 && !p.dci_profile) {
         // Y Cb Cr with sub-sampled chroma out of the world's R, G, B: the front end converts and decimates (j2k_hip.h)
         p.rgb_to_sycc = 1; p.ycc = 0;
         p.comp_sub_x[1] = p.comp_sub_x[2] = 2;
-        p.comp_sub_y[1] = p.comp_sub_y[2] = (_options & Chroma420) ? 2 : 1;
+        p.comp_sub_y[1] = p.comp_sub_y[2] = (options & HipCodec::Chroma420) ? 2 : 1;
         p.color_space = J2K_HIP_CS_SYCC; // (reaches the file with the JP2 wrapper only)
         p.icc_profile = NULL; p.icc_profile_len = 0; // (a profile of the RGB world does not describe Y Cb Cr)
     }
+    return true;
+}
+
+} // namespace
+
+void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &buffer, Progress *)
+{
+    assert(file.Tell() == 0);                  // reference: j2k_openjpeg_codec.cpp:592
+    assert(info.channels == buffer.channels);  // reference: :629
+    j2k_hip_params p;
+    j2k_hip_plane planes[J2K_CODEC_MAX_CHANNELS];
+    float rates[J2K_CODEC_MAX_LAYERS];
+    if (!map_frame(_mode, _options, info, buffer, p, planes, rates)) { t_enc.error = "inconsistent FileInfo/Buffer"; throw Exception("Error writing file"); }
 
     if (!thread_handle(_device)) throw Exception("Error writing file"); // reference: :756-757 (no CPU fallback)
     int rc = j2k_hip_encode(t_enc.h, &p, planes, sink_write, &file);
@@ -448,6 +469,46 @@ void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &b
         throw Exception("Error writing file");
     }
     t_enc.error.clear();
+}
+
+bool HipCodec::Compare(InputFile &file, const FileInfo &info, const Buffer &buffer, Difference out[J2K_CODEC_MAX_CHANNELS])
+{
+    if (j2k_hip_compare_check == NULL || j2k_hip_compare == NULL) {
+        t_enc.error = "this libj2k_hip has no j2k_hip_compare: Compare needs a newer library";
+        throw Exception("Error reading file");
+    }
+    if (!Verify(file)) throw Exception("Can't read this format");
+    const std::vector<unsigned char> data = slurp(file);
+    j2k_hip_params p;
+    j2k_hip_plane planes[J2K_CODEC_MAX_CHANNELS];
+    float rates[J2K_CODEC_MAX_LAYERS];
+    if (out == NULL || !map_frame(_mode, _options, info, buffer, p, planes, rates)) { t_enc.error = "inconsistent FileInfo/Buffer"; throw Exception("Error reading file"); }
+    // the header tells a file for the other reader -- and one that is not this frame's -- apart before a device is touched
+    const int check = j2k_hip_compare_check(&p, data.data(), data.size());
+    if (check != J2K_HIP_OK) {
+        t_enc.error = j2k_hip_last_error(NULL);
+        if (check == J2K_HIP_ERR_UNSUPPORTED) return false;
+        throw Exception("Error reading file");
+    }
+    j2k_hip_encoder *h = thread_handle(_device);
+    if (!h) throw Exception("Error reading file");
+    apply_read_layers(h, _read_layers);
+    j2k_hip_diff diffs[J2K_CODEC_MAX_CHANNELS] = {};
+    for (int i = 0; i < J2K_CODEC_MAX_CHANNELS; i++) diffs[i].struct_size = sizeof(j2k_hip_diff);
+    const int rc = j2k_hip_compare(h, &p, planes, data.data(), data.size(), diffs, (uint32_t)buffer.channels);
+    if (rc != J2K_HIP_OK) {
+        t_enc.error = j2k_hip_last_error(h);
+        if (rc == J2K_HIP_ERR_UNSUPPORTED) return false; // (found by the host-side parser: no kernel has run)
+        throw Exception("Error reading file");
+    }
+    for (int i = 0; i < buffer.channels; i++) {
+        const j2k_hip_diff &d = diffs[i];
+        Difference &o = out[i];
+        o.samples = d.samples; o.differing = d.differing; o.sumAbs = d.sum_abs; o.sumSq = d.sum_sq;
+        o.maxAbs = d.max_abs; o.firstX = d.first_x; o.firstY = d.first_y; o.mse = d.mse; o.psnr = d.psnr;
+    }
+    t_enc.error.clear();
+    return true;
 }
 
 } // namespace j2k

@@ -83,6 +83,22 @@ class HipCodec : public Codec {
     // (frames before the damaged one may have been written); LastError() names the frame.
     bool ReadFiles(InputFile *const *files, const Buffer *buffers, unsigned n, unsigned subsample);
 
+    // What did a file lose against the frame it was written from?  `info` and `buffer` are what WriteFile was given (the same
+    // FileInfo / Buffer -> parameters / planes mapping: PromoteAE16, FLOAT channels and Chroma422 / Chroma420 included); the
+    // file is decoded and compared on the GPU (include/j2k_hip.h: j2k_hip_compare), nothing but a few sums comes back.
+    // out[c], c < buffer.channels: component c on its own grid -- error = decoded - source sample, at FileInfo.depth bits,
+    // before any colour transform; firstX / firstY: the first differing sample in raster order (0, 0 when none differs);
+    // psnr is +infinity when nothing differs.  SetReadLayers applies: a draft read's loss is the draft's.
+    // true: out is filled.  false: a file for the fallback reader (status J2K_HIP_ERR_UNSUPPORTED); nothing is written -- the
+    // fallback codec has no such call.  A file that is not this frame's (size, channels, depth, sub-sampling), a damaged
+    // file and device failures throw "Error reading file"; LastError() names the field.
+    struct Difference {
+        unsigned long long samples, differing, sumAbs, sumSq;
+        unsigned maxAbs, firstX, firstY;
+        double mse, psnr;
+    };
+    bool Compare(InputFile &file, const FileInfo &info, const Buffer &buffer, Difference out[J2K_CODEC_MAX_CHANNELS]);
+
     // Draft reads: ReadFile, ReadRGBA and ReadFiles decode only the first `layers` quality layers of their files (0, the
     // initial value: all of them; a file with fewer layers is read in full) -- sample for sample what they deliver for the
     // file cut down to those layers, what libopenjp2 does for opj_dparameters_t::cp_layer (include/j2k_hip.h:

@@ -375,6 +375,65 @@ long j2k_host_test_write_ex(const unsigned char *frame, unsigned width, unsigned
     return (long)file.data.size();
 }
 
+// HipCodec::Compare of `file` against the A,R,G,B world `frame` (as in j2k_host_test_write: HonourSettings, the PROMOTE and
+// CHROMA knobs, FileInfo of width x height x channels at `depth` bits; the coding settings do not matter).  ints_out = 7 values
+// per channel (samples, differing, sumAbs, sumSq, maxAbs, firstX, firstY), dbl_out = 2 (mse, psnr).  Returns 1 = compared,
+// 0 = Compare returned false (nothing written), -1 = j2k::Exception (what() in err).
+long j2k_host_test_compare(const unsigned char *file, unsigned long file_len, int with_fallback, const unsigned char *frame, unsigned width,
+                           unsigned height, long rowbytes, int pixel_size, int channels, int depth, unsigned long long *ints_out,
+                           double *dbl_out, char *err, unsigned long err_cap)
+{
+    using namespace j2k;
+    Channel argb[4];
+    for (int i = 0; i < 4; i++) {
+        Channel &c = argb[i];
+        c.width = width; c.height = height;
+        c.sampleType = pixel_size == 4 ? FLOAT : (pixel_size == 2 ? USHORT : UCHAR);
+        c.depth = (unsigned char)(pixel_size * 8);
+        c.sgnd = false;
+        c.buf = const_cast<unsigned char *>(frame) + i * pixel_size;
+        c.colbytes = 4 * pixel_size;
+        c.rowbytes = rowbytes;
+    }
+    FileInfo info;
+    info.width = width; info.height = height;
+    info.channels = (unsigned char)channels; info.depth = (unsigned char)depth;
+    info.alpha = channels == 4 ? STRAIGHT : NO_ALPHA;
+    const Channel *by_name[4] = {&argb[1], &argb[2], &argb[3], &argb[0]}; // RED, GREEN, BLUE, ALPHA
+    Buffer buf;
+    buf.channels = info.channels;
+    for (int c = 0; c < channels; c++) buf.channel[c] = *by_name[info.channelMap[c]];
+    unsigned options = std::getenv("J2K_HOST_TEST_PROMOTE") != NULL ? HipCodec::PromoteAE16 : HipCodec::NoOptions;
+    if (const char *ch = std::getenv("J2K_HOST_TEST_CHROMA"))
+        options |= std::atoi(ch) == 420 ? HipCodec::Chroma420 : (std::atoi(ch) == 422 ? HipCodec::Chroma422 : 0u);
+    HipCodec hip(HipCodec::HonourSettings, -1, options);
+    read_knobs(hip);
+    RecordingCodec other;
+    if (with_fallback) hip.SetFallback(&other);
+    MemoryInputFile in(file, file_len);
+    HipCodec::Difference d[J2K_CODEC_MAX_CHANNELS];
+    std::memset(d, 0xA5, sizeof(d));
+    try {
+        if (!hip.Compare(in, info, buf, d)) {
+            for (size_t i = 0; i < sizeof(d); i++) if (reinterpret_cast<const unsigned char *>(d)[i] != 0xA5) return -2; // (false: nothing written)
+            return other.infos || other.reads ? -3 : 0; // (... and the fallback codec has no such call)
+        }
+    } catch (const Exception &e) {
+        if (err && err_cap) {
+            std::string m = std::string(e.what()) + " | " + HipCodec::LastError();
+            std::strncpy(err, m.c_str(), err_cap - 1);
+            err[err_cap - 1] = 0;
+        }
+        return -1;
+    }
+    for (int c = 0; c < channels; c++) {
+        unsigned long long *o = ints_out + 7 * c;
+        o[0] = d[c].samples; o[1] = d[c].differing; o[2] = d[c].sumAbs; o[3] = d[c].sumSq; o[4] = d[c].maxAbs; o[5] = d[c].firstX; o[6] = d[c].firstY;
+        dbl_out[2 * c] = d[c].mse; dbl_out[2 * c + 1] = d[c].psnr;
+    }
+    return 1;
+}
+
 const char *j2k_host_codec_name(void)
 {
     static j2k::HipCodec c;
