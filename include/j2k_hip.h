@@ -656,6 +656,52 @@ int j2k_hip_stage_t1_styled(j2k_hip_encoder *enc, int reversible, void *d_coef, 
                             uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
                             void *data, size_t data_cap, uint32_t *pass_rate, uint32_t cblk_style);
 
+/* The rate control's kernels alone (rate_prepare_kernel, rate_ahead_kernel, rate_scan_kernel), on Tier-1 tables the caller
+ * supplies, driven through the objects an encode drives them with.  All arrays are host memory.
+ * In, per block i < nblocks (>= 1): weight[i] (the block's weight without the bit-plane), comp[i] (0..3), numbps[i] (<= 31),
+ * npasses[i] (<= 3 numbps - 2 and <= J2K_HIP_MAX_PASSES; 0: an empty block), and the rows pass_rate[i][..], pass_dist[i][..]
+ * of J2K_HIP_MAX_PASSES entries each, as j2k_hip_stage_t1_passes returns them.
+ * Out, after the prepare kernel: disto[nblocks][J2K_HIP_MAX_PASSES] (cumulative weighted distortion), reach[nblocks][..]
+ * and bounds[3][nblocks] (smallest / largest single-pass slope, steepest piece).  Entries of a row at and beyond npasses
+ * are not written by the kernel: every byte of them comes back as 0xA5.
+ * Then, for the blocks [first, first + count) as one tile's layer, done[count] = their passes in earlier layers (NULL: none):
+ *   - K > 0: ahead[K], descending thresholds, give body[4][K], the per-component bound on the candidates' body bytes;
+ *   - nscans scans, in order.  scans[i].mode = J2K_HIP_RATE_SCAN: the scan whose per-block results come back with it;
+ *     J2K_HIP_RATE_SUMS_FETCH: the scan that brings back only its sums, into slot scans[i].slot (0..2), and a fetch of that
+ *     slot straight behind it; J2K_HIP_RATE_SUMS_FETCH_LAST: the same with the fetch put off until every scan of the list
+ *     has run (no later scan of the list may then use the slot; J2K_HIP_RATE_SCAN uses slot 0).  Scan i leaves
+ *     taken[i][count], bytes[i][count] and sums[i][8] (per component c: [2c] body bytes in the layer, [2c + 1] header bits).
+ * Refused with J2K_HIP_ERR_PARAM: what is outside the limits above, K > 128, thresholds ahead that ascend, a block range
+ * outside the blocks or empty with a query, done[i] > npasses, an encode pending on the handle.  The handle's cached
+ * geometry is dropped.  J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
+typedef struct j2k_hip_rate_taken { uint64_t lo; uint32_t hi; uint32_t n; } j2k_hip_rate_taken; /* bit p: the scan moved on at pass p; n: passes in layers 0..this one */
+typedef struct j2k_hip_rate_scan { double thresh; uint32_t mode; uint32_t slot; } j2k_hip_rate_scan;
+#define J2K_HIP_RATE_SCAN 0
+#define J2K_HIP_RATE_SUMS_FETCH 1
+#define J2K_HIP_RATE_SUMS_FETCH_LAST 2
+int j2k_hip_stage_rate(j2k_hip_encoder *enc, uint32_t nblocks, const double *weight, const uint8_t *comp,
+                       const uint32_t *numbps, const uint32_t *npasses, const uint32_t *pass_rate, const int32_t *pass_dist,
+                       double *disto, float *reach, double *bounds, uint32_t first, uint32_t count, const uint8_t *done,
+                       const double *ahead, uint32_t K, uint64_t *body, const j2k_hip_rate_scan *scans, uint32_t nscans,
+                       j2k_hip_rate_taken *taken, uint32_t *bytes, uint64_t *sums);
+
+/* The codestream assembly alone: ONE launch of gather_kernel over three lists of pieces, its arguments filled as an encode
+ * and a decode fill them.  dst (host, dst_bytes) goes up as it is, receives the pieces and comes back; `src` (host) is the
+ * codeword arena, `blob` (host) the packet-header blob.  A piece copies len bytes from offset src of its source to offset dst:
+ * blocks[] read `src` at 4-byte aligned offsets through a code-block table (a block of length 0 is skipped), headers[] read
+ * `blob` at offsets below 2^32, segments[] read `src` at any 64-bit offset.
+ * Refused with J2K_HIP_ERR_PARAM: a piece that reaches outside its source or the destination, a block source off the 4-byte
+ * grid, destinations that overlap, an encode pending on the handle.  The handle's cached geometry is dropped.
+ * J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
+typedef struct j2k_hip_gather_piece { uint64_t dst, src; uint32_t len, reserved; } j2k_hip_gather_piece;
+int j2k_hip_stage_gather(j2k_hip_encoder *enc, const void *src, size_t src_bytes, const void *blob, size_t blob_bytes,
+                         void *dst, size_t dst_bytes, const j2k_hip_gather_piece *blocks, uint32_t nblocks,
+                         const j2k_hip_gather_piece *headers, uint32_t nheaders,
+                         const j2k_hip_gather_piece *segments, uint32_t nsegments);
+/* One launch of pack_offsets_kernel: dst[i] = base + len[0] + .. + len[i - 1] for i < n (host arrays).  n = 0: no launch,
+ * dst is left alone.  J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
+int j2k_hip_stage_pack_offsets(j2k_hip_encoder *enc, const uint32_t *len, uint32_t n, uint64_t base, uint64_t *dst);
+
 /* Inverse DWT (the mirror of j2k_hip_stage_dwt): `nplanes` planes of width*height 32-bit words (row stride =
  * width) in the Mallat layout of the oracle are synthesised from the lowest of `levels` resolutions upwards,
  * one kernel launch pair per level, the jobs built like a decode builds them.  With nregions == 0 a plane is

@@ -96,6 +96,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
            "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
            "j2k_hip_stage_t1_styled", "j2k_hip_stage_transform",
+           "j2k_hip_stage_rate", "j2k_hip_stage_gather", "j2k_hip_stage_pack_offsets",
            "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_t1_decode_styled", "j2k_hip_stage_decode_output",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink"]
@@ -130,6 +131,17 @@ class RgbaStage(C.Structure):
     """include/j2k_hip.h: j2k_hip_rgba_stage."""
     _fields_ = [(n, C.c_uint32) for n in ("struct_size", "mode", "org_x", "org_y", "lut_size", "lut_columns")] + \
                [("lut", (C.c_uint8 * 4) * 256), ("lut_rgb", C.c_uint8 * 4)]
+
+
+class RateScan(C.Structure):
+    """include/j2k_hip.h: j2k_hip_rate_scan."""
+    _fields_ = [("thresh", C.c_double), ("mode", C.c_uint32), ("slot", C.c_uint32)]
+
+
+RATE_SCAN, RATE_SUMS_FETCH, RATE_SUMS_FETCH_LAST = 0, 1, 2  # J2K_HIP_RATE_*
+# j2k_hip_rate_taken / j2k_hip_gather_piece as numpy records (the hooks take and fill arrays of them)
+RATE_TAKEN = np.dtype([("lo", "<u8"), ("hi", "<u4"), ("n", "<u4")])
+GATHER_PIECE = np.dtype([("dst", "<u8"), ("src", "<u8"), ("len", "<u4"), ("reserved", "<u4")])
 
 
 class Diff(C.Structure):
@@ -222,6 +234,11 @@ def load_library():
                                    C.POINTER(C.c_float), U32P, U32P, U32P, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t]
     L.j2k_hip_stage_t1_passes.argtypes = L.j2k_hip_stage_t1.argtypes + [U32P, C.POINTER(C.c_int32)]
     L.j2k_hip_stage_t1_styled.argtypes = L.j2k_hip_stage_t1.argtypes + [U32P, C.c_uint32]
+    L.j2k_hip_stage_rate.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 9 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                     C.c_void_p, C.POINTER(RateScan), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.j2k_hip_stage_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                       C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+    L.j2k_hip_stage_pack_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p]
     L.j2k_hip_stage_idwt.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                      C.POINTER(IdwtRegion), C.c_uint32, C.c_void_p, C.c_void_p]
     L.j2k_hip_stage_t1_decode.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DecBlock),
@@ -1057,6 +1074,67 @@ class Encoder:
             for i, o in enumerate(out):
                 o["rates"] = list(rates[i * MP:i * MP + o["npasses"]])
                 o["nmsedec"] = list(dist[i * MP:i * MP + o["npasses"]])
+        return out
+
+    def stage_rate(self, weight, comp, numbps, npasses, pass_rate, pass_dist, first=0, count=0, done=None, ahead=None, scans=()):
+        """j2k_hip_stage_rate.  Tables per block (pass_rate / pass_dist: (n, 96)); scans: (thresh, mode, slot) with mode one
+        of RATE_SCAN / RATE_SUMS_FETCH / RATE_SUMS_FETCH_LAST.  Returns a dict: disto (n, 96) float64, reach (n, 96) float32,
+        bounds (3, n); with queries also body (4, K) uint64, taken (nscans, count) RATE_TAKEN records, bytes (nscans, count)
+        uint32 and sums (nscans, 8) uint64."""
+        MP = 96
+        n = len(npasses)
+        weight = np.ascontiguousarray(weight, dtype=np.float64)
+        comp = np.ascontiguousarray(comp, dtype=np.uint8)
+        numbps = np.ascontiguousarray(numbps, dtype=np.uint32)
+        npasses = np.ascontiguousarray(npasses, dtype=np.uint32)
+        pass_rate = np.ascontiguousarray(pass_rate, dtype=np.uint32).reshape(n, MP)
+        pass_dist = np.ascontiguousarray(pass_dist, dtype=np.int32).reshape(n, MP)
+        assert weight.size == comp.size == numbps.size == n
+        disto, reach, bounds = np.zeros((n, MP), np.float64), np.zeros((n, MP), np.float32), np.zeros((3, max(n, 1)), np.float64)
+        K = 0 if ahead is None else len(ahead)
+        ah = np.ascontiguousarray(ahead if K else [0.0], dtype=np.float64)
+        body = np.zeros((4, max(K, 1)), np.uint64)
+        dn = None if done is None else np.ascontiguousarray(done, dtype=np.uint8)
+        assert dn is None or dn.size == count
+        ns = len(scans)
+        sc = (RateScan * max(ns, 1))()
+        for i, (t, mode, slot) in enumerate(scans):
+            sc[i].thresh, sc[i].mode, sc[i].slot = t, mode, slot
+        taken = np.zeros((max(ns, 1), max(count, 1)), RATE_TAKEN)
+        nbytes = np.zeros((max(ns, 1), max(count, 1)), np.uint32)
+        sums = np.zeros((max(ns, 1), 8), np.uint64)
+        ptr = lambda a: a.ctypes.data
+        self._check(self.L.j2k_hip_stage_rate(self.h, n, ptr(weight), ptr(comp), ptr(numbps), ptr(npasses), ptr(pass_rate), ptr(pass_dist),
+                                              ptr(disto), ptr(reach), ptr(bounds), first, count, None if dn is None else ptr(dn),
+                                              ptr(ah) if K else None, K, ptr(body) if K else None, sc if ns else None, ns,
+                                              ptr(taken) if ns else None, ptr(nbytes) if ns else None, ptr(sums) if ns else None))
+        out = dict(disto=disto, reach=reach, bounds=bounds[:, :n])
+        if K:
+            out["body"] = body
+        if ns:
+            out.update(taken=taken[:ns, :count], bytes=nbytes[:ns, :count], sums=sums)
+        return out
+
+    def stage_gather(self, src, dst, blocks=(), headers=(), segments=(), blob=None) -> np.ndarray:
+        """j2k_hip_stage_gather: src / dst (/ blob, default: src) uint8 arrays, the piece lists [(dst, src, len)].  Returns
+        the destination after the launch; `dst` itself is not changed."""
+        src = np.ascontiguousarray(src, dtype=np.uint8)
+        blob = src if blob is None else np.ascontiguousarray(blob, dtype=np.uint8)
+        out = np.array(dst, dtype=np.uint8, copy=True)
+        tables = [np.array([(d, s, ln, 0) for d, s, ln in pieces], dtype=GATHER_PIECE) for pieces in (blocks, headers, segments)]
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self._check(self.L.j2k_hip_stage_gather(self.h, ptr(src), src.size, ptr(blob), blob.size, ptr(out), out.size,
+                                                ptr(tables[0]), tables[0].size, ptr(tables[1]), tables[1].size,
+                                                ptr(tables[2]), tables[2].size))
+        return out
+
+    def stage_pack_offsets(self, lens, base: int = 0, dst=None) -> np.ndarray:
+        """j2k_hip_stage_pack_offsets: dst[i] = base + lens[0] + .. + lens[i - 1] (uint64); dst: what the array holds before."""
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        out = np.zeros(lens.size, np.uint64) if dst is None else np.array(dst, dtype=np.uint64, copy=True)
+        assert out.size == lens.size
+        self._check(self.L.j2k_hip_stage_pack_offsets(self.h, lens.ctypes.data if lens.size else None, lens.size, C.c_uint64(base),
+                                                      out.ctypes.data if out.size else None))
         return out
 
     def stage_idwt(self, planes: np.ndarray, levels: int, reversible: bool, x0=0, y0=0, regions=None):

@@ -2221,6 +2221,214 @@ static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uin
     });
 }
 
+// The rate control's kernels alone (rate.hip), on tables the caller supplies, through the objects an encode drives them with:
+// rate_args lays out the device memory, launch_rate_prepare runs where encode_begin queues it, and a HipRateDevice over the
+// uploaded tables answers begin_layer / ahead / scan / scan_sums / fetch -- slot layout, copy sizes, memsets and the running
+// sums over `delta` included.
+int j2k_hip_stage_rate(j2k_hip_encoder *e, uint32_t nblocks, const double *weight, const uint8_t *comp, const uint32_t *numbps,
+                       const uint32_t *npasses, const uint32_t *pass_rate, const int32_t *pass_dist, double *disto, float *reach,
+                       double *bounds, uint32_t first, uint32_t count, const uint8_t *done, const double *ahead, uint32_t K,
+                       uint64_t *body, const j2k_hip_rate_scan *scans, uint32_t nscans, j2k_hip_rate_taken *taken, uint32_t *bytes,
+                       uint64_t *sums)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        static_assert(sizeof(j2k_hip_rate_taken) == sizeof(Taken), "the scan's records go out as they are");
+        static_assert(J2K_HIP_MAX_PASSES == kDevMaxPasses, "the header's row length is the tables'");
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        const size_t nb = nblocks;
+        if (!nb || !weight || !comp || !numbps || !npasses || !pass_rate || !pass_dist || !disto || !reach || !bounds)
+            throw Error(J2K_HIP_ERR_PARAM, "rate stage: no blocks, or a table is NULL");
+        for (size_t i = 0; i < nb; ++i) {
+            if (comp[i] > 3) throw Error(J2K_HIP_ERR_PARAM, "rate stage: component above 3");
+            if (numbps[i] > 31) throw Error(J2K_HIP_ERR_PARAM, "rate stage: more than 31 bit-planes");
+            if (npasses[i] > (uint32_t)kDevMaxPasses || (npasses[i] && npasses[i] + 2 > 3 * numbps[i]))
+                throw Error(J2K_HIP_ERR_PARAM, "rate stage: more passes than the bit-planes hold");
+        }
+        if (first > nb || count > nb - first) throw Error(J2K_HIP_ERR_PARAM, "rate stage: block range outside the blocks");
+        if (K > 128) throw Error(J2K_HIP_ERR_PARAM, "rate stage: more than 128 thresholds ahead");
+        if ((K || nscans) && !count) throw Error(J2K_HIP_ERR_PARAM, "rate stage: queries over an empty block range");
+        if ((K && (!ahead || !body)) || (nscans && (!scans || !taken || !bytes || !sums)))
+            throw Error(J2K_HIP_ERR_PARAM, "rate stage: a query without its arrays");
+        for (uint32_t i = 0; done && i < count; ++i)
+            if (done[i] > npasses[first + i]) throw Error(J2K_HIP_ERR_PARAM, "rate stage: more passes done than the block has");
+        for (uint32_t k = 1; k < K; ++k)
+            if (!(ahead[k] <= ahead[k - 1])) throw Error(J2K_HIP_ERR_PARAM, "rate stage: thresholds ahead must descend");
+        {
+            // a slot whose fetch is put off must still hold its scan at the end
+            bool held[3] = {false, false, false};
+            for (uint32_t i = 0; i < nscans; ++i) {
+                const j2k_hip_rate_scan &q = scans[i];
+                if (q.mode > J2K_HIP_RATE_SUMS_FETCH_LAST || (q.mode != J2K_HIP_RATE_SCAN && q.slot > 2))
+                    throw Error(J2K_HIP_ERR_PARAM, "rate stage: unknown scan mode or slot");
+                const uint32_t k = q.mode == J2K_HIP_RATE_SCAN ? 0u : q.slot;
+                if (held[k]) throw Error(J2K_HIP_ERR_PARAM, "rate stage: a scan into a slot whose fetch is still to come");
+                if (q.mode == J2K_HIP_RATE_SUMS_FETCH_LAST) held[k] = true;
+            }
+        }
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        e->geo_valid = false; e->seq_valid = false; e->band_valid = false; e->rc_weight_valid = false; // tables of the handle's last frame are overwritten
+        // the Tier-1 results where a frame's coder leaves them: meta = [numbps | npasses | ..], passes = [decisions | nmsedec | rate]
+        const size_t row = (size_t)kDevMaxPasses;
+        e->meta.ensure((4 * nb + 4) * sizeof(uint32_t));
+        e->passes.ensure(nb * row * 3 * sizeof(uint32_t));
+        uint32_t *meta = e->meta.as<uint32_t>();
+        uint32_t *pn = e->passes.as<uint32_t>();
+        HIP_CHECK(hipMemcpyAsync(meta, numbps, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(meta + nb, npasses, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(pn + nb * row, pass_dist, nb * row * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(pn + 2 * nb * row, pass_rate, nb * row * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HipRateDevice dev(e, nb, meta);
+        const RateArgs &ra = dev.a;
+        std::vector<uint8_t> wc(nb * sizeof(double) + nb); // the blocks' components behind their weights, as encode_begin stages them
+        std::memcpy(wc.data(), weight, nb * sizeof(double));
+        std::memcpy(wc.data() + nb * sizeof(double), comp, nb);
+        HIP_CHECK(hipMemcpyAsync(e->rc_weight.p, wc.data(), wc.size(), hipMemcpyHostToDevice, s));
+        // (filled first: what the kernel leaves alone -- the rows' entries beyond npasses -- comes back as 0xA5 bytes)
+        HIP_CHECK(hipMemsetAsync(ra.disto, 0xA5, nb * row * sizeof(double), s));
+        HIP_CHECK(hipMemsetAsync(ra.reach, 0xA5, nb * row * sizeof(float), s));
+        HIP_CHECK(hipMemsetAsync(e->rc_small.p, 0xA5, dev.lay.total, s));
+        launch_rate_prepare(ra, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(e->h_rc_bounds.p, ra.bounds, 3 * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(disto, ra.disto, nb * row * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(reach, ra.reach, nb * row * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        std::memcpy(bounds, dev.bmin(), nb * sizeof(double));
+        std::memcpy(bounds + nb, dev.bmax(), nb * sizeof(double));
+        std::memcpy(bounds + 2 * nb, dev.steepest(), nb * sizeof(double));
+        if (!K && !nscans) return;
+        dev.begin_layer(first, count, done);
+        if (K) dev.ahead(first, count, ahead, K, body);
+        auto keep = [&](uint32_t i, const Taken *t, const uint32_t *b) {
+            std::memcpy(taken + (size_t)i * count, t, (size_t)count * sizeof(Taken));
+            std::memcpy(bytes + (size_t)i * count, b, (size_t)count * sizeof(uint32_t));
+        };
+        for (uint32_t i = 0; i < nscans; ++i) {
+            const j2k_hip_rate_scan &q = scans[i];
+            const Taken *t = nullptr;
+            const uint32_t *b = nullptr;
+            if (q.mode == J2K_HIP_RATE_SCAN) {
+                dev.scan(first, count, q.thresh, &t, &b, sums + (size_t)i * kRateSums);
+                keep(i, t, b);
+                continue;
+            }
+            dev.scan_sums(first, count, q.thresh, (int)q.slot, sums + (size_t)i * kRateSums);
+            if (q.mode == J2K_HIP_RATE_SUMS_FETCH) { dev.fetch((int)q.slot, count, &t, &b); keep(i, t, b); }
+        }
+        for (uint32_t i = 0; i < nscans; ++i) {
+            if (scans[i].mode != J2K_HIP_RATE_SUMS_FETCH_LAST) continue;
+            const Taken *t = nullptr;
+            const uint32_t *b = nullptr;
+            dev.fetch((int)scans[i].slot, count, &t, &b);
+            keep(i, t, b);
+        }
+    });
+}
+
+// One launch_gather over pieces the caller supplies, its GatherArgs filled from the buffers and in the table order of
+// encode_end (block pieces: a CblkDev table, the blocks' lengths and cblk_dst) and of the decoder (segments alone).
+int j2k_hip_stage_gather(j2k_hip_encoder *e, const void *src, size_t src_bytes, const void *blob, size_t blob_bytes, void *dst,
+                         size_t dst_bytes, const j2k_hip_gather_piece *blocks, uint32_t nblocks, const j2k_hip_gather_piece *headers,
+                         uint32_t nheaders, const j2k_hip_gather_piece *segments, uint32_t nsegments)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        if ((src_bytes && !src) || (blob_bytes && !blob) || (dst_bytes && !dst) || (nblocks && !blocks) || (nheaders && !headers) ||
+            (nsegments && !segments))
+            throw Error(J2K_HIP_ERR_PARAM, "gather stage: a buffer or a piece list is NULL");
+        const size_t nbd = nblocks, nh = nheaders, nseg = nsegments;
+        if (nbd + nh + nseg > (size_t)INT32_MAX) throw Error(J2K_HIP_ERR_PARAM, "gather stage: too many pieces");
+        std::vector<std::pair<uint64_t, uint64_t>> spans; // destination [begin, end) of every piece that writes
+        auto piece = [&](const j2k_hip_gather_piece &p, size_t from_bytes) {
+            if (p.src > from_bytes || p.len > from_bytes - p.src) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a piece reads outside its source");
+            if (p.dst > dst_bytes || p.len > dst_bytes - p.dst) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a piece writes outside the destination");
+            if (p.len) spans.emplace_back(p.dst, p.dst + p.len);
+        };
+        for (size_t i = 0; i < nbd; ++i) {
+            if (blocks[i].src & 3) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a block's source is not 4-byte aligned");
+            piece(blocks[i], src_bytes);
+        }
+        for (size_t i = 0; i < nh; ++i) {
+            if (headers[i].src > UINT32_MAX) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a header's source offset needs more than 32 bits");
+            piece(headers[i], blob_bytes);
+        }
+        for (size_t i = 0; i < nseg; ++i) piece(segments[i], src_bytes);
+        std::sort(spans.begin(), spans.end());
+        for (size_t i = 1; i < spans.size(); ++i)
+            if (spans[i].first < spans[i - 1].second) throw Error(J2K_HIP_ERR_PARAM, "gather stage: destinations overlap");
+        if (!(nbd + nh + nseg)) return;
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        e->geo_valid = false; e->seq_valid = false; e->band_valid = false; // the block table is overwritten
+        // the plan's layout (encode_end): [blob][hdr_dst][cblk_dst][seg_dst][seg_src][hdr_src][hdr_len][seg_len]
+        const size_t blob_sz = round_up(blob_bytes + 8, 16);
+        const size_t plan_total = round_up(blob_sz + nh * (8 + 4 + 4) + nbd * 8 + nseg * (8 + 8 + 4) + 64, 64);
+        std::vector<uint8_t> hplan(plan_total, 0);
+        uint8_t *hp = hplan.data();
+        if (blob_bytes) std::memcpy(hp, blob, blob_bytes);
+        uint64_t *h_hdst = reinterpret_cast<uint64_t *>(hp + blob_sz);
+        uint64_t *h_cdst = h_hdst + nh;
+        uint64_t *h_sdst = h_cdst + nbd, *h_ssrc = h_sdst + nseg;
+        uint32_t *h_hsrc = reinterpret_cast<uint32_t *>(h_ssrc + nseg);
+        uint32_t *h_hlen = h_hsrc + nh, *h_slen = h_hlen + nh;
+        for (size_t i = 0; i < nh; ++i) { h_hdst[i] = headers[i].dst; h_hsrc[i] = (uint32_t)headers[i].src; h_hlen[i] = headers[i].len; }
+        for (size_t i = 0; i < nseg; ++i) { h_sdst[i] = segments[i].dst; h_ssrc[i] = segments[i].src; h_slen[i] = segments[i].len; }
+        std::vector<CblkDev> blks(std::max<size_t>(1, nbd));
+        std::vector<uint32_t> lens(std::max<size_t>(1, nbd));
+        for (size_t i = 0; i < nbd; ++i) { h_cdst[i] = blocks[i].dst; blks[i] = CblkDev{}; blks[i].out_off = blocks[i].src; lens[i] = blocks[i].len; }
+        e->plan.ensure(plan_total);
+        e->cs.ensure(dst_bytes + 64);
+        e->out.ensure(src_bytes + 64); // (as a frame's: a misaligned piece's last source word may end up to three bytes behind it)
+        e->blks.ensure(blks.size() * sizeof(CblkDev));
+        e->meta.ensure((4 * std::max<size_t>(1, nbd) + 4) * sizeof(uint32_t));
+        HIP_CHECK(hipMemcpyAsync(e->plan.p, hp, plan_total, hipMemcpyHostToDevice, s));
+        if (src_bytes) HIP_CHECK(hipMemcpyAsync(e->out.p, src, src_bytes, hipMemcpyHostToDevice, s));
+        if (dst_bytes) HIP_CHECK(hipMemcpyAsync(e->cs.p, dst, dst_bytes, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(e->blks.p, blks.data(), blks.size() * sizeof(CblkDev), hipMemcpyHostToDevice, s));
+        uint32_t *meta = e->meta.as<uint32_t>();
+        HIP_CHECK(hipMemcpyAsync(meta + 2 * nbd, lens.data(), lens.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        GatherArgs ga{};
+        uint8_t *dp = e->plan.as<uint8_t>();
+        ga.dst = e->cs.as<uint8_t>();
+        ga.blob = dp;
+        ga.hdr_dst = reinterpret_cast<const unsigned long long *>(dp + blob_sz);
+        ga.cblk_dst = ga.hdr_dst + nh;
+        ga.seg_dst = ga.cblk_dst + nbd; ga.seg_src = ga.seg_dst + nseg;
+        ga.hdr_src = reinterpret_cast<const unsigned int *>(ga.seg_src + nseg);
+        ga.hdr_len = ga.hdr_src + nh;
+        ga.seg_len = ga.hdr_len + nh;
+        ga.nhdr = (int)nh; ga.nseg = (int)nseg;
+        ga.out = e->out.as<uint8_t>(); ga.blks = e->blks.as<CblkDev>(); ga.len = meta + 2 * nbd; ga.nblks = (int)nbd;
+        launch_gather(ga, s);
+        HIP_CHECK(hipGetLastError());
+        if (dst_bytes) HIP_CHECK(hipMemcpyAsync(dst, e->cs.p, dst_bytes, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int j2k_hip_stage_pack_offsets(j2k_hip_encoder *e, const uint32_t *len, uint32_t n, uint64_t base, uint64_t *dst)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        if (!n) return;
+        if (!len || !dst || n > (uint32_t)INT32_MAX) throw Error(J2K_HIP_ERR_PARAM, "pack offsets stage: an array is NULL, or too many lengths");
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        e->meta.ensure(((size_t)n + 4) * sizeof(uint32_t));
+        e->pack_dst.ensure((size_t)n * sizeof(uint64_t));
+        e->band_valid = false; // (a band-pipelined call's destinations are overwritten)
+        HIP_CHECK(hipMemcpyAsync(e->meta.p, len, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        launch_pack_offsets(e->meta.as<unsigned>(), (int)n, base, e->pack_dst.as<unsigned long long>(), s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(dst, e->pack_dst.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 // native sinks for benchmarks (include/j2k_hip.h, diagnostics)
 size_t j2k_hip_debug_copy_sink(void *user, const void *buf, size_t n)
 {

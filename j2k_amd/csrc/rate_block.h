@@ -75,10 +75,14 @@ J2K_HD void rate_block_bounds(const uint32_t *rate, const double *disto, uint32_
     // Rounding to single precision and the factor are monotone, so they are applied to every piece's bound at once and the
     // maxima are taken on the results -- the same numbers as taking the maxima first, with nothing per pass to keep but
     // `reach` itself (the kernel's private memory is what limits how many of its waves the chip holds).
-    auto single = [](double bound) -> float { // margin 1e-3; the conversion may round down by 6e-8 of it, what single precision cannot hold rounds UP
-        if (!(bound > 0)) return 0.0f;
-        const float f = (float)(bound * 1.0011);
-        return f > FLT_MIN ? f : FLT_MIN;
+    // rate_block_choose takes a pass when thresh - slope < DBL_EPSILON, an absolute term: under 2.2e-16 a threshold takes steps
+    // with bytes whatever their slope, a step with bytes and no distortion among them (a significance pass that found nothing:
+    // its slope of 0 is then the bisection's lower end, and 128 halvings of a bracket whose candidates all fit come down
+    // there after some 70 rounds).  Every piece's bound carries the term, twice (the conversion may round down by 6e-8 of the
+    // sum); against a real frame's bounds (block_weight >= 0.5: slopes over 1e-10) it is a fraction of a unit in the last place
+    // of single precision.
+    auto single = [](double bound) -> float { // margin 1e-3; the conversion may round down by 6e-8 of it
+        return (float)((bound > 0 ? bound * 1.0011 : 0.0) + 2 * DBL_EPSILON);
     };
     {
         // forward: the bound of every step with bytes, known when the next such step (or the end) closes the gap behind it

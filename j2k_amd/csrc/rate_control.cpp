@@ -150,6 +150,7 @@ LayerAlloc allocate(const Geometry &geo, const std::vector<CblkResult> &res, con
     // with margin).  Why: a pass is taken when the run from the last pass taken up to it is steep enough; all shorter runs
     // from the same start were not, so the run's last piece must itself be that steep (mediant again) -- the last pass
     // taken at threshold t therefore lies in a piece whose bound reaches t.  Non-increasing in p; single precision.
+    // ("Steep enough" is thresh - slope < DBL_EPSILON: every piece's bound carries that absolute term, rate_block.h.)
     std::vector<float> reach(plain || dev ? 0 : pass0[nb]);
     auto weight = [&](size_t id) { return block_weight(cod, geo.cblks[id]); };
     // With a device a block's distortions are made the first time the host scans it, and those few thousand rows sit back to
