@@ -343,7 +343,6 @@ int lane_waves_resident()
 // a group's arenas (files, codewords, two plane sets, state / planes / masks, staged output) stay under this share of the
 // device memory that is free, counting what the handle's arenas hold already
 constexpr double kSeqMemoryShare = 0.5;
-unsigned plan_threads() { return std::max(1u, std::min(4u, std::thread::hardware_concurrency())); } // (encoder.cpp: the Tier-2 planner's)
 
 // One group: frames [first, first + nf) of the call, plans[0 .. nf) theirs.  file_uploaded: the (single) file is on its way to
 // d_file already and EV_START is recorded.  Adds to st.

@@ -45,8 +45,11 @@
 #include "bands.h"
 #include "cblk_style.h"
 #include "handle.h"
+#include "rate_device.h"
 
 using namespace j2k_hip;
+
+const char j2k_hip::J2K_T1ARGS_LAYOUT_TAG = 0; // (handle.h: the T1Args layout this file was built with)
 
 namespace {
 
@@ -118,12 +121,13 @@ bool same_coding(const Coding &a, const Coding &b)
            std::memcmp(a.cdx, b.cdx, sizeof a.cdx) == 0 && std::memcmp(a.cdy, b.cdy, sizeof a.cdy) == 0;
 }
 
+} // namespace
+
 // Decision-stream and codeword capacities of a code-block of `area` samples with up to Mb bit-planes under code-block style
 // `style`: one rule for the frames (prepare_geometry) and for the Tier-1 stage hooks.  A frame passes the band's own Mb; the
 // hooks know no band and pass 30, so a hook's capacities are a frame's or larger (two to three times at the usual depths):
 // the hooks show that the rule holds the codewords of Mb = 30, not that a frame's smaller Mb does.
-struct CblkCaps { size_t sym, out; };
-CblkCaps cblk_capacities(size_t area, uint32_t Mb, uint32_t style)
+CblkCaps j2k_hip::cblk_capacities(size_t area, uint32_t Mb, uint32_t style)
 {
     // <= 1.5 decisions per sample and bit-plane (ZC/MR + run-length overhead) + one sign each
     const size_t symcap = round_up(area * 3 * Mb / 2 + area + 64, 1024);
@@ -134,8 +138,6 @@ CblkCaps cblk_capacities(size_t area, uint32_t Mb, uint32_t style)
     const size_t style_room = style ? 8 * (size_t)(3 * Mb) : 0;
     return {symcap, round_up(symcap / 4 + 64 + style_room, 16)};
 }
-
-} // namespace
 
 // The working planes of one frame over the box [bx0, bx1) x [by0, by1) of the reference grid: one row stride for every
 // component (the box width rounded to 64 words: T1Args and DwtLevelArgs carry one stride), component c with the rows of its
@@ -155,19 +157,15 @@ PlaneLayout j2k_hip::plane_layout(const Coding &cod, int bx0, int by0, int bx1, 
     }
     return l;
 }
-namespace {
 
 // Build (or reuse) geometry, code-block table and DWT job lists; upload the device images.
-void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first, uint32_t tile_count)
+void j2k_hip::prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first, uint32_t tile_count)
 {
     if (e->geo_valid && same_coding(e->geo_cod, cod) && e->geo_first == tile_first && e->geo_count == tile_count) {
         e->geo.cod = cod; // comment / promote may differ
         return;
     }
-    e->geo_valid = false;
-    e->seq_valid = false;
-    e->band_valid = false;
-    e->rc_weight_valid = false;
+    invalidate_cached_tables(e);
     e->geo = build_geometry(cod, tile_first, tile_count);
     // bounding box of the requested tiles: everything the kernels touch lies inside it
     int bx0 = (int)cod.width, by0 = (int)cod.height, bx1 = 0, by1 = 0;
@@ -272,6 +270,7 @@ void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first
     e->geo_cod = cod; e->geo_first = tile_first; e->geo_count = tile_count;
     e->geo_valid = true;
 }
+namespace {
 
 // What an encode refuses about a channel view's sample type (J2K_HIP_ERR_PARAM, host code: before any device work).  A float
 // channel under promote_ae16 is the After Effects 15+1-bit world as floats: it stands for depth 16.
@@ -318,14 +317,13 @@ FrontendArgs j2k_hip::make_frontend_args(const Coding &cod, const j2k_hip_plane 
     }
     return fa;
 }
-namespace {
 
 // Does level 1 of the DWT take its samples straight from the frame (dwt_fused_kernel) -- the one place that decides it, for
 // an encode (in one piece or in bands) and for the stage hook alike?  After Effects layout (1, 3 or 4 channels out of one
 // interleaved pixel, equal depths): the front end -- Promote and both of CopyChannel's shift branches included -- runs inside
 // the level-1 DWT kernel and the planar intermediate is never written; any other arrangement of channel views is converted
 // by a pass of its own (frontend.hip).
-bool fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tuning &tn)
+bool j2k_hip::fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tuning &tn)
 {
     bool same_depth = true;
     for (uint32_t c = 1; c < cod.ncomp; ++c) same_depth = same_depth && fa.src_depth[c] == fa.src_depth[0];
@@ -334,8 +332,6 @@ bool fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tuning &tn)
         if (fa.sample_bytes[c] == 4) return false; // (... and integer samples: a float world is quantised by the front end's own pass)
     return !tn.no_fuse && cod.levels() >= 1 && fa.interleaved && same_depth && (cod.ncomp == 1 || cod.ncomp == 3 || cod.ncomp == 4);
 }
-
-} // namespace
 
 // The stand-alone front end of one frame into planes of row stride S words, component c at dst + comp_off[c]; fa: the frame's
 // channel views (make_frontend_args), its dst_x0 / dst_y0 the planes' origin.  Components of one size: one launch of
@@ -376,12 +372,10 @@ hipStream_t j2k_hip::coder_stream(j2k_hip_encoder *e, int i)
     return e->mqs[i];
 }
 
-namespace {
-
 #ifdef J2K_T1_COUNTERS
 // diagnostic build: the modeller's loop and path counters (kernels.h: kT1Counters) -- prints the totals of the launches since
 // the last call and hands the zeroed words to the next ones
-void t1_counters(T1Args &ta)
+void j2k_hip::t1_counters(T1Args &ta)
 {
     static unsigned long long *dbg = nullptr;
     if (!dbg) { HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&dbg), kT1Counters * 8)); }
@@ -411,7 +405,7 @@ void t1_counters(T1Args &ta)
 // Launch arguments of DWT level l (0 = full resolution) of frame f of the call: level l reads LL(l-1) and writes LL(l) to
 // the other ping-pong plane (the last level: to Z) and its HL/LH/HH bands to Z.
 // tile_row >= 0: the jobs of that tile row only (band-pipelined encode).
-DwtLevelArgs dwt_level_args(j2k_hip_encoder *e, const Coding &cod, const FrontendArgs &fa, bool fused, size_t f, int l, int tile_row = -1)
+DwtLevelArgs j2k_hip::dwt_level_args(j2k_hip_encoder *e, const Coding &cod, const FrontendArgs &fa, bool fused, size_t f, int l, int tile_row)
 {
     const int NL = (int)cod.levels();
     const size_t S = e->stride;
@@ -448,6 +442,7 @@ DwtLevelArgs dwt_level_args(j2k_hip_encoder *e, const Coding &cod, const Fronten
     }
     return da;
 }
+namespace {
 
 // The DWT launches of levels [l0, l1) of frame f, in order (one launch per level).
 void launch_dwt_levels(j2k_hip_encoder *e, const Coding &cod, const FrontendArgs &fa, bool fused, size_t f, int l0, int l1, hipStream_t s,
@@ -525,8 +520,6 @@ namespace {
 // nframes > 1 (image sequence, device frames only): planes = nframes consecutive sets of channels; the frames
 // share every launch of the context modeller and of the MQ coder, so their coder chains run side by side
 // instead of one after the other -- what a sequence of small frames needs.
-static RateArgs rate_args(j2k_hip_encoder *e, size_t nb, const uint32_t *meta, const int *pass_nmsedec, const unsigned *pass_rate);
-
 void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes,
                   bool planes_on_device, uint32_t tile_first, uint32_t tile_count, bool framed, uint32_t nframes = 1)
 {
@@ -578,11 +571,12 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     // nothing but kernel boundaries sits between the previous modeller, this frame's DWT and this frame's modeller
     const size_t nb1 = g.cblks.size();  // per frame
     const size_t nb = nb1 * F;          // in the Tier-1 launches
+    const T1Tables tt(nb);
     e->sym.ensure(e->sym_bytes * F + 1024);
     e->out.ensure(e->out_bytes * F + 64);
-    e->meta.ensure((4 * nb + 4) * sizeof(uint32_t));
-    e->passes.ensure(std::max<size_t>(1, nb) * kDevMaxPasses * 3 * sizeof(uint32_t));
-    HIP_CHECK(hipMemsetAsync(e->meta.as<uint32_t>() + 4 * nb, 0, sizeof(uint32_t), s));
+    e->meta.ensure(tt.meta_bytes());
+    e->passes.ensure(tt.passes_bytes());
+    HIP_CHECK(hipMemsetAsync(tt.err(e->meta.as<uint32_t>()), 0, sizeof(uint32_t), s));
 
     const bool overlap_mq = tn.overlap != 0;
     // the dense phases (DWT + modeller) of the frames in flight are chained: the bandwidth-bound launches keep the chip to themselves
@@ -668,11 +662,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     T1Args ta{};
     ta.coef = NL >= 1 ? e->Z.p : e->P.p; ta.stride = (long long)S;
     ta.blks = dblk; ta.nblks = (int)nb; ta.reversible = cod.reversible;
-    ta.sym = e->sym.as<uint8_t>(); ta.out = e->out.as<uint8_t>();
-    ta.numbps = meta; ta.npasses = meta + nb; ta.len = meta + 2 * nb; ta.nsym = meta + 3 * nb; ta.err = meta + 4 * nb;
-    ta.pass_nsym = e->passes.as<uint32_t>();
-    ta.pass_nmsedec = reinterpret_cast<int *>(e->passes.as<uint32_t>() + nb * kDevMaxPasses);
-    ta.pass_rate = e->passes.as<uint32_t>() + 2 * nb * kDevMaxPasses;
+    t1_arena_args(e, tt, ta);
     ta.mq_prio = tn.mq_prio ? 3 : 0;
     ta.sparse = tn.t1_sparse;
     ta.style = cod.cblk_style;
@@ -738,13 +728,13 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     HIP_CHECK(hipEventRecord(e->ev[EV_T1], s));
 
     // ---- per-block results to the host
-    e->h_meta.ensure((4 * nb + 4) * sizeof(uint32_t));
-    HIP_CHECK(hipMemcpyAsync(e->h_meta.p, meta, (4 * nb + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    e->h_meta.ensure(tt.meta_bytes());
+    HIP_CHECK(hipMemcpyAsync(e->h_meta.p, meta, tt.meta_words() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (rate_control && nb) { // per-pass byte counts (after the fix-ups) and distortion sums for the layer allocation
         T1Args tf = ta;
         tf.first = 0; tf.nblks = (int)nb;
         launch_t1_rate_fixup(tf, s);
-        e->h_passes.ensure(nb * kDevMaxPasses * 2 * sizeof(uint32_t));
+        e->h_passes.ensure(tt.h_passes_bytes());
         // The allocation's per-block work right here, behind the coder (rate.hip): distortions, slope ranges, bounds.  Byte
         // budgets only (fixed quality sums distortions in OpenJPEG's block order on the host), one frame per call.
         const int dev_min = tn.rate_dev == 0 ? 8192 : tn.rate_dev;
@@ -753,9 +743,9 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
         pd.rc_device = dev_min > 0 && cod.psnr.empty() && F == 1 && nb >= (size_t)dev_min && (!cod.max_comp_size || dev.inflight.load() <= 1);
         pd.rc_tables_pending = false;
         if (!(pd.rc_device && tn.overlap))
-            HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_nmsedec, nb * kDevMaxPasses * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_nmsedec, tt.h_passes_bytes(), hipMemcpyDeviceToHost, s));
         if (pd.rc_device) {
-            const RateArgs ra = rate_args(e, nb, meta, ta.pass_nmsedec, ta.pass_rate);
+            const RateArgs ra = rate_args(e, tt);
             if (!e->rc_weight_valid) {
                 // once per geometry; staged in the pinned buffer the bounds come back to (later, on the same stream)
                 const std::vector<double> w = rate_block_weights(g);
@@ -774,7 +764,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
                 hipStream_t side = coder_stream(e, 0);
                 HIP_CHECK(hipEventRecord(e->rc_fixed, s));
                 HIP_CHECK(hipStreamWaitEvent(side, e->rc_fixed, 0));
-                HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_nmsedec, nb * kDevMaxPasses * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, side));
+                HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_nmsedec, tt.h_passes_bytes(), hipMemcpyDeviceToHost, side));
                 HIP_CHECK(hipEventRecord(e->rc_tables, side));
                 pd.rc_tables_pending = true;
             }
@@ -786,8 +776,8 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
             T1Args tf = ta;
             tf.first = 0; tf.nblks = (int)nb;
             launch_t1_rate_fixup(tf, s);
-            e->h_passes.ensure(nb * kDevMaxPasses * sizeof(uint32_t));
-            HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_rate, nb * kDevMaxPasses * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            e->h_passes.ensure(tt.h_rates_bytes());
+            HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_rate, tt.h_rates_bytes(), hipMemcpyDeviceToHost, s));
         }
     }
     // The dense phase ends when the last modeller launch has drained: the next frame's DWT + modeller
@@ -803,145 +793,6 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     pd.F = F; pd.nb1 = nb1; pd.framed = framed; pd.rate_control = rate_control; pd.dwt_bytes = dwt_bytes;
     pd.meta = meta; pd.dblk = dblk; pd.nl = NL;
 }
-
-// ---- rate control on the device (rate.hip; rate_control.h: RateDevice)
-// rc_small, device and pinned host alike: [done nb][ahead 128 doubles][delta 4 x 128 x 8][three slots of scan results]
-struct RcLayout {
-    // a scan's results, three slots of them: [sums kRateSums x 8][bytes nb x 4][taken nb x 16]
-    size_t done, ahead, delta, slot0, slot_bytes, slot_taken, slot_stride, total;
-    explicit RcLayout(size_t nb)
-    {
-        done = 0;
-        ahead = round_up(nb, 256);
-        delta = ahead + 128 * sizeof(double);
-        slot0 = delta + 4 * 128 * sizeof(long long);
-        slot_bytes = kRateSums * sizeof(uint64_t);
-        slot_taken = slot_bytes + round_up(nb * sizeof(uint32_t), 256);
-        slot_stride = round_up(slot_taken + nb * sizeof(Taken), 256);
-        total = slot0 + 3 * slot_stride;
-    }
-    size_t slot(int k) const { return slot0 + (size_t)k * slot_stride; }
-};
-
-static RateArgs rate_args(j2k_hip_encoder *e, size_t nb, const uint32_t *meta, const int *pass_nmsedec, const unsigned *pass_rate)
-{
-    const RcLayout lay(nb);
-    e->rc_weight.ensure(nb * sizeof(double) + nb); // (the blocks' components behind their weights)
-    e->rc_disto.ensure(nb * kDevMaxPasses * sizeof(double));
-    e->rc_reach.ensure(nb * kDevMaxPasses * sizeof(float));
-    e->rc_bounds.ensure(3 * nb * sizeof(double));
-    e->rc_small.ensure(lay.total);
-    e->h_rc_bounds.ensure(3 * nb * sizeof(double));
-    e->h_rc_small.ensure(lay.total);
-    RateArgs a = {};
-    a.nblks = (unsigned)nb;
-    a.weight = e->rc_weight.as<double>();
-    a.comp_of = e->rc_weight.as<unsigned char>() + nb * sizeof(double);
-    a.numbps = meta; a.npasses = meta + nb;
-    a.pass_nmsedec = pass_nmsedec; a.pass_rate = pass_rate;
-    a.disto = e->rc_disto.as<double>(); a.reach = e->rc_reach.as<float>(); a.bounds = e->rc_bounds.as<double>();
-    uint8_t *sm = e->rc_small.as<uint8_t>();
-    a.done = sm + lay.done;
-    a.ahead = reinterpret_cast<const double *>(sm + lay.ahead);
-    a.delta = reinterpret_cast<long long *>(sm + lay.delta);
-    a.scan_sums = nullptr; a.scan_bytes = nullptr; a.scan_taken = nullptr; // (per launch: one of the slots)
-    return a;
-}
-
-// The bisection's calls into the device, one round trip each on the handle's stream (the prepare kernel and the copy of the
-// bounds were queued behind the coder by encode_begin and are through when encode_end has waited for the stream).
-struct HipRateDevice : RateDevice {
-    j2k_hip_encoder *e;
-    size_t nb;
-    RcLayout lay;
-    RateArgs a;
-    hipStream_t s;
-    uint8_t *hs, *ds;
-    HipRateDevice(j2k_hip_encoder *enc, size_t nblks, const uint32_t *meta)
-        : e(enc), nb(nblks), lay(nblks), s(enc->stream)
-    {
-        const uint32_t *pn = enc->passes.as<uint32_t>(); // [decisions | nmsedec | rate], each [nb][kDevMaxPasses]
-        a = rate_args(enc, nblks, meta, reinterpret_cast<const int *>(pn + nblks * kDevMaxPasses), pn + 2 * nblks * kDevMaxPasses);
-        hs = enc->h_rc_small.as<uint8_t>(); ds = enc->rc_small.as<uint8_t>();
-    }
-    const double *bmin() override { return e->h_rc_bounds.as<double>(); }
-    const double *bmax() override { return e->h_rc_bounds.as<double>() + nb; }
-    const double *steepest() override { return e->h_rc_bounds.as<double>() + 2 * nb; }
-    void begin_layer(uint32_t first, uint32_t count, const uint8_t *done) override
-    {
-        if (!done) { HIP_CHECK(hipMemsetAsync(ds + lay.done + first, 0, count, s)); return; }
-        std::memcpy(hs + lay.done + first, done, count);
-        HIP_CHECK(hipMemcpyAsync(ds + lay.done + first, hs + lay.done + first, count, hipMemcpyHostToDevice, s));
-    }
-    const bool trace = std::getenv("J2K_RATE_TRACE") != nullptr; // each round trip's time to stderr
-    struct Trace {
-        const char *what; bool on; double t0;
-        Trace(const char *w, bool o) : what(w), on(o), t0(o ? now_ms() : 0) {}
-        ~Trace() { if (on) std::fprintf(stderr, "rate device: %s %.3f ms\n", what, now_ms() - t0); }
-    };
-    void ahead(uint32_t first, uint32_t count, const double *ah, uint32_t K, uint64_t *body) override
-    {
-        Trace tr("ahead", trace);
-        if (K > 128) throw Error(J2K_HIP_ERR_PARAM, "internal: more than 128 thresholds ahead");
-        std::memcpy(hs + lay.ahead, ah, K * sizeof(double));
-        HIP_CHECK(hipMemcpyAsync(ds + lay.ahead, hs + lay.ahead, K * sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemsetAsync(ds + lay.delta, 0, 4 * 128 * sizeof(long long), s));
-        launch_rate_ahead(a, first, count, K, s);
-        HIP_CHECK(hipMemcpyAsync(hs + lay.delta, ds + lay.delta, 4 * 128 * sizeof(long long), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        const long long *d = reinterpret_cast<const long long *>(hs + lay.delta);
-        for (uint32_t c = 0; c < 4; ++c) {
-            long long run = 0;
-            for (uint32_t k = 0; k < K; ++k) { run += d[c * 128 + k]; body[(size_t)c * K + k] = (uint64_t)run; }
-        }
-    }
-    void launch_into(int k, uint32_t first, uint32_t count, double thresh)
-    {
-        RateArgs r = a;
-        uint8_t *d = ds + lay.slot(k);
-        r.scan_sums = reinterpret_cast<unsigned long long *>(d);
-        r.scan_bytes = reinterpret_cast<unsigned *>(d + lay.slot_bytes);
-        r.scan_taken = reinterpret_cast<Taken *>(d + lay.slot_taken);
-        HIP_CHECK(hipMemsetAsync(d, 0, kRateSums * sizeof(uint64_t), s));
-        launch_rate_scan(r, first, count, thresh, s);
-    }
-    void scan(uint32_t first, uint32_t count, double thresh, const Taken **taken, const uint32_t **bytes, uint64_t *sums) override
-    {
-        Trace tr("scan", trace);
-        launch_into(0, first, count, thresh);
-        // (the sums and the two result arrays lie back to back but for padding: one copy)
-        HIP_CHECK(hipMemcpyAsync(hs + lay.slot(0), ds + lay.slot(0), lay.slot_taken + (size_t)count * sizeof(Taken), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        std::memcpy(sums, hs + lay.slot(0), kRateSums * sizeof(uint64_t));
-        *bytes = reinterpret_cast<const uint32_t *>(hs + lay.slot(0) + lay.slot_bytes);
-        *taken = reinterpret_cast<const Taken *>(hs + lay.slot(0) + lay.slot_taken);
-    }
-    void scan_sums(uint32_t first, uint32_t count, double thresh, int slot, uint64_t *sums) override
-    {
-        Trace tr("scan, sums only", trace);
-        launch_into(slot, first, count, thresh);
-        HIP_CHECK(hipMemcpyAsync(hs + lay.slot(slot), ds + lay.slot(slot), kRateSums * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        std::memcpy(sums, hs + lay.slot(slot), kRateSums * sizeof(uint64_t));
-    }
-    void fetch(int slot, uint32_t count, const Taken **taken, const uint32_t **bytes) override
-    {
-        Trace tr("fetch", trace);
-        HIP_CHECK(hipMemcpyAsync(hs + lay.slot(slot) + lay.slot_bytes, ds + lay.slot(slot) + lay.slot_bytes,
-                                 (lay.slot_taken - lay.slot_bytes) + (size_t)count * sizeof(Taken), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        *bytes = reinterpret_cast<const uint32_t *>(hs + lay.slot(slot) + lay.slot_bytes);
-        *taken = reinterpret_cast<const Taken *>(hs + lay.slot(slot) + lay.slot_taken);
-    }
-    uint32_t min_scan() const override { return (uint32_t)(tuning().rate_dev_scan == 0 ? 512 : std::max(1, tuning().rate_dev_scan)); }
-    void need_tables() override
-    {
-        if (!e->pend.rc_tables_pending) return;
-        Trace tr("wait for the pass tables", trace);
-        HIP_CHECK(hipEventSynchronize(e->rc_tables));
-        e->pend.rc_tables_pending = false;
-    }
-};
 
 // Second half: waits for the Tier-1 results, plans the codestream on the host (Tier-2), assembles it in HBM.
 std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
@@ -969,28 +820,32 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
         HIP_CHECK(hipStreamSynchronize(s));
     }
     const double t_t2 = now_ms();
+    const T1Tables tt(nb);
     const uint32_t *hm = e->h_meta.as<uint32_t>();
-    if (hm[4 * nb] != 0)
-        throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 kernel reported error " + std::to_string(hm[4 * nb]) +
+    if (*tt.err(hm) != 0)
+        throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 kernel reported error " + std::to_string(*tt.err(hm)) +
                                               " (1: too many bit-planes, 2: decision buffer, 3: codeword buffer)");
     uint64_t nsym_total = 0;
-    for (size_t i = 0; i < nb; ++i) nsym_total += hm[3 * nb + i];
+    for (size_t i = 0; i < nb; ++i) nsym_total += tt.nsym(hm)[i];
     // bytes in front of the first tile-part: the main header and, for JP2, the boxes before it
     const size_t lead = main_header(cod).size() + jp2_file_header(cod, 0).size();
     std::vector<Tier2Plan> plans(F);
-    std::vector<size_t> plan_off(F), cs_off(F), blob_szs(F);
+    std::vector<GatherPlan> lays(F);
+    std::vector<size_t> plan_off(F), cs_off(F);
     size_t plan_total = 0, cs_total = 0;
     const size_t nbd = rate_control ? 0 : nb1; // per-block destinations or per-layer pieces
     {
         Range r("j2k_hip tier2 host");
         for (size_t f = 0; f < F; ++f) {
             std::vector<CblkResult> res(nb1);
-            for (size_t i = 0; i < nb1; ++i) res[i] = CblkResult{hm[f * nb1 + i], hm[nb + f * nb1 + i], hm[2 * nb + f * nb1 + i]};
-            if (cod.cblk_style) // (styled frames: h_passes holds the byte counts per pass alone, [nb][kDevMaxPasses])
-                for (size_t i = 0; i < nb1; ++i) res[i].rates = e->h_passes.as<uint32_t>() + (f * nb1 + i) * kDevMaxPasses;
+            const size_t b0 = f * nb1; // the frame's first block in the tables
+            for (size_t i = 0; i < nb1; ++i) res[i] = CblkResult{tt.numbps(hm)[b0 + i], tt.npasses(hm)[b0 + i], tt.len(hm)[b0 + i]};
+            if (cod.cblk_style) // (styled frames: h_passes holds the byte counts per pass alone)
+                for (size_t i = 0; i < nb1; ++i) res[i].rates = e->h_passes.as<uint32_t>() + tt.row(b0 + i);
             LayerAlloc alloc;
             if (rate_control) {
-                const uint32_t *hp = e->h_passes.as<uint32_t>(); // [nmsedec | rate], each [nb][kDevMaxPasses]
+                const uint32_t *hp = e->h_passes.as<uint32_t>(); // [nmsedec | rate]
+                const uint32_t *h_rate = tt.h_rate(hp) + tt.row(b0), *h_nmsedec = hp + tt.row(b0);
 #ifdef J2K_ALLOC_DUMP
                 // tools/alloc_probe.cpp works on real Tier-1 results: one frame's allocation inputs, written once
                 if (pd.rc_tables_pending) { HIP_CHECK(hipEventSynchronize(e->rc_tables)); pd.rc_tables_pending = false; }
@@ -1005,8 +860,8 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
                             for (size_t i = 0; i < nb1; ++i) {
                                 const uint32_t r3[3] = {res[i].numbps, res[i].npasses, res[i].len};
                                 std::fwrite(r3, 4, 3, fp);
-                                std::fwrite(hp + (nb + i) * kDevMaxPasses, 4, res[i].npasses, fp);
-                                std::fwrite(hp + i * kDevMaxPasses, 4, res[i].npasses, fp);
+                                std::fwrite(h_rate + tt.row(i), 4, res[i].npasses, fp);
+                                std::fwrite(h_nmsedec + tt.row(i), 4, res[i].npasses, fp);
                             }
                             std::fclose(fp);
                         }
@@ -1014,19 +869,18 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
                 }
 #endif
                 std::unique_ptr<HipRateDevice> rdev;
-                if (pd.rc_device) rdev.reset(new HipRateDevice(e, nb, meta));
+                if (pd.rc_device) rdev.reset(new HipRateDevice(e, tt));
                 const unsigned at = std::max(1u, std::min((unsigned)std::max(1, tuning().alloc_threads), std::thread::hardware_concurrency()));
                 if (nb1 >= 4096 && !(e->alloc_workers && e->alloc_workers->size() == at)) e->alloc_workers.reset(new Workers(at));
-                alloc = allocate_layers(g, res, hp + (nb + f * nb1) * kDevMaxPasses,
-                                        reinterpret_cast<const int32_t *>(hp + f * nb1 * kDevMaxPasses), lead, at, rdev.get(), e->alloc_workers.get());
+                alloc = allocate_layers(g, res, h_rate, reinterpret_cast<const int32_t *>(h_nmsedec), lead, at, rdev.get(), e->alloc_workers.get());
             }
             if (pd.rc_tables_pending) { HIP_CHECK(hipEventSynchronize(e->rc_tables)); pd.rc_tables_pending = false; } // (never read: still ours to wait for)
             // big frames: a few host threads write the packet headers of the (resolution, component) pairs side by side
-            if (nb1 >= 4096 && !e->t2_workers) e->t2_workers.reset(new Workers(std::max(1u, std::min(4u, std::thread::hardware_concurrency()))));
+            if (nb1 >= 4096 && !e->t2_workers) e->t2_workers.reset(new Workers(plan_threads()));
             plans[f] = plan_codestream(g, res, framed, framed, rate_control ? &alloc : nullptr, e->t2_workers.get());
-            blob_szs[f] = round_up(plans[f].blob.size() + 8, 16);
+            lays[f] = GatherPlan(plans[f].blob.size(), plans[f].hdr_segs.size(), nbd, plans[f].body_segs.size());
             plan_off[f] = plan_total;
-            plan_total += round_up(blob_szs[f] + plans[f].hdr_segs.size() * (8 + 4 + 4) + nbd * 8 + plans[f].body_segs.size() * (8 + 8 + 4) + 64, 64);
+            plan_total += lays[f].total;
             cs_off[f] = cs_total;
             cs_total += round_up(plans[f].total_len + 64, 256);
         }
@@ -1041,32 +895,20 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
     std::vector<GatherArgs> gas(F);
     for (size_t f = 0; f < F; ++f) {
         const Tier2Plan &plan = plans[f];
-        const size_t nh = plan.hdr_segs.size(), nseg = plan.body_segs.size(), blob_sz = blob_szs[f];
+        const size_t nh = plan.hdr_segs.size(), nseg = plan.body_segs.size();
         uint8_t *hp = e->h_plan.as<uint8_t>() + plan_off[f];
         std::memcpy(hp, plan.blob.data(), plan.blob.size());
-        uint64_t *h_hdst = reinterpret_cast<uint64_t *>(hp + blob_sz);
-        uint64_t *h_cdst = h_hdst + nh;
-        uint64_t *h_sdst = h_cdst + nbd, *h_ssrc = h_sdst + nseg;
-        uint32_t *h_hsrc = reinterpret_cast<uint32_t *>(h_ssrc + nseg);
-        uint32_t *h_hlen = h_hsrc + nh, *h_slen = h_hlen + nh;
-        for (size_t i = 0; i < nh; ++i) { h_hdst[i] = plan.hdr_segs[i].dst; h_hsrc[i] = plan.hdr_segs[i].src; h_hlen[i] = plan.hdr_segs[i].len; }
-        if (nbd) std::memcpy(h_cdst, plan.cblk_dst.data(), nbd * 8);
+        const GatherTables h = lays[f].tables(hp);
+        for (size_t i = 0; i < nh; ++i) { h.hdr_dst[i] = plan.hdr_segs[i].dst; h.hdr_src[i] = plan.hdr_segs[i].src; h.hdr_len[i] = plan.hdr_segs[i].len; }
+        if (nbd) std::memcpy(h.cblk_dst, plan.cblk_dst.data(), nbd * 8);
         for (size_t i = 0; i < nseg; ++i) {
             const BodySeg &b = plan.body_segs[i];
-            h_sdst[i] = b.dst; h_ssrc[i] = hblk[f * nb1 + b.cblk].out_off + b.off; h_slen[i] = b.len;
+            h.seg_dst[i] = b.dst; h.seg_src[i] = hblk[f * nb1 + b.cblk].out_off + b.off; h.seg_len[i] = b.len;
         }
         GatherArgs &ga = gas[f];
-        uint8_t *dp = e->plan.as<uint8_t>() + plan_off[f];
+        lays[f].fill(ga, e->plan.as<uint8_t>() + plan_off[f]);
         ga.dst = e->cs.as<uint8_t>() + cs_off[f];
-        ga.blob = dp;
-        ga.hdr_dst = reinterpret_cast<const unsigned long long *>(dp + blob_sz);
-        ga.cblk_dst = ga.hdr_dst + nh;
-        ga.seg_dst = ga.cblk_dst + nbd; ga.seg_src = ga.seg_dst + nseg;
-        ga.hdr_src = reinterpret_cast<const unsigned int *>(ga.seg_src + nseg);
-        ga.hdr_len = ga.hdr_src + nh;
-        ga.seg_len = ga.hdr_len + nh;
-        ga.nhdr = (int)nh; ga.nseg = (int)nseg;
-        ga.out = e->out.as<uint8_t>(); ga.blks = dblk + f * nb1; ga.len = meta + 2 * nb + f * nb1; ga.nblks = (int)nbd;
+        ga.out = e->out.as<uint8_t>(); ga.blks = dblk + f * nb1; ga.len = tt.len(meta) + f * nb1; ga.nblks = (int)nbd;
     }
     HIP_CHECK(hipMemcpyAsync(e->plan.p, e->h_plan.p, plan_total, hipMemcpyHostToDevice, s));
     for (size_t f = 0; f < F; ++f) launch_gather(gas[f], s);
@@ -1247,14 +1089,15 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     e->sym.ensure(e->sym_bytes + 1024);
     e->out.ensure(e->out_bytes + 64);
     e->cs.ensure(e->out_bytes + 64); // packing arena: stage k's codewords back to back from its first block's offset on
-    e->meta.ensure((4 * nb + 4) * sizeof(uint32_t));
-    e->passes.ensure(nb * kDevMaxPasses * 3 * sizeof(uint32_t));
-    e->h_meta.ensure((4 * nb + 4) * sizeof(uint32_t));
+    const T1Tables tt(nb);
+    e->meta.ensure(tt.meta_bytes());
+    e->passes.ensure(tt.passes_bytes());
+    e->h_meta.ensure(tt.meta_bytes());
     uint32_t *meta = e->meta.as<uint32_t>();
     e->gate_state.ensure((NG + (size_t)NS + 8) * sizeof(uint32_t));
     unsigned *const gate_ready = e->gate_state.as<unsigned>(), *const gate_done = gate_ready + NG, *const gate_abort = gate_done + NS;
     HIP_CHECK(hipEventRecord(e->ev[EV_START], s));
-    HIP_CHECK(hipMemsetAsync(meta + 4 * nb, 0, sizeof(uint32_t), s));
+    HIP_CHECK(hipMemsetAsync(tt.err(meta), 0, sizeof(uint32_t), s));
     HIP_CHECK(hipMemsetAsync(gate_ready, 0, (NG + (size_t)NS + 8) * sizeof(uint32_t), s));
     HIP_CHECK(hipEventRecord(e->gates_zeroed, s)); // (the counters are zero: the coder launch and the stages' wait kernels may be queued)
 
@@ -1270,11 +1113,7 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     T1Args ta{};
     ta.coef = e->Z.p; ta.stride = (long long)e->stride;
     ta.blks = e->blks_band.as<CblkDev>(); ta.nblks = (int)nb; ta.reversible = cod.reversible;
-    ta.sym = e->sym.as<uint8_t>(); ta.out = e->out.as<uint8_t>();
-    ta.numbps = meta; ta.npasses = meta + nb; ta.len = meta + 2 * nb; ta.nsym = meta + 3 * nb; ta.err = meta + 4 * nb;
-    ta.pass_nsym = e->passes.as<uint32_t>();
-    ta.pass_nmsedec = reinterpret_cast<int *>(e->passes.as<uint32_t>() + nb * kDevMaxPasses);
-    ta.pass_rate = e->passes.as<uint32_t>() + 2 * nb * kDevMaxPasses;
+    t1_arena_args(e, tt, ta);
     ta.mq_prio = tn.mq_prio ? 3 : 0;
     ta.sparse = tn.t1_sparse;
     ta.gate_groups = e->gate_groups.as<T1Args::GateGroup>(); ta.gate_group_of = e->gate_group_of.as<unsigned>();
@@ -1344,15 +1183,16 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
             ga.dst = e->cs.as<uint8_t>(); ga.out = e->out.as<uint8_t>(); ga.blks = ta.blks + st.blk_first;
             ga.cblk_dst = pd_dst; ga.len = ta.len + st.blk_first; ga.nblks = (int)st.blk_count;
             launch_gather(ga, e->dl_stream);
-            HIP_CHECK(hipMemcpy2DAsync(e->h_meta.as<uint32_t>() + st.blk_first, nb * sizeof(uint32_t), meta + st.blk_first, nb * sizeof(uint32_t),
-                                       st.blk_count * sizeof(uint32_t), 4, hipMemcpyDeviceToHost, e->dl_stream));
+            // (the stage's rows of the four columns: numbps() + blk_first on, a column apart)
+            HIP_CHECK(hipMemcpy2DAsync(tt.numbps(e->h_meta.as<uint32_t>()) + st.blk_first, tt.column_bytes(), tt.numbps(meta) + st.blk_first, tt.column_bytes(),
+                                       st.blk_count * sizeof(uint32_t), T1Tables::kColumns, hipMemcpyDeviceToHost, e->dl_stream));
         }
         HIP_CHECK(hipEventRecord(e->stage_done[k], e->dl_stream));
     }
 
 
     for (int k = 0; k < NS; ++k) HIP_CHECK(hipStreamWaitEvent(s, e->stage_done[k], 0));
-    HIP_CHECK(hipMemcpyAsync(e->h_meta.as<uint32_t>() + 4 * nb, meta + 4 * nb, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(tt.err(e->h_meta.as<uint32_t>()), tt.err(meta), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipEventRecord(e->ev[EV_T1], s));
 
     pd.active = true;
@@ -1393,6 +1233,7 @@ void encode_end_banded(j2k_hip_encoder *e, j2k_hip_write_fn write, void *user)
     const BandSchedule &S = e->band;
     const size_t nb = pd.nb1;
     const int NS = pd.stages, B = pd.bands;
+    const T1Tables tt(nb);
     const uint32_t *hm = e->h_meta.as<uint32_t>();
     // ---- every finished stage's codewords come down while the later stages are still being coded, and Tier-2 -- a thread of
     // its own, a few workers under it -- writes the packets of every resolution as soon as the stages that hold its blocks have
@@ -1410,7 +1251,7 @@ void encode_end_banded(j2k_hip_encoder *e, j2k_hip_write_fn write, void *user)
         cv.wait(lk, [&] { return failed || (done_mask & need) == need; });
         if (failed) throw Error(J2K_HIP_ERR_DEVICE, "the frame's stages did not complete");
     };
-    if (nb >= 4096 && !e->t2_workers) e->t2_workers.reset(new Workers(std::max(1u, std::min(4u, std::thread::hardware_concurrency()))));
+    if (nb >= 4096 && !e->t2_workers) e->t2_workers.reset(new Workers(plan_threads()));
     double t_t2 = 0, t_t2_end = 0;
     std::future<Tier2Plan> planner = std::async(std::launch::async, [&] {
         Range r("j2k_hip tier2 host");
@@ -1438,8 +1279,8 @@ void encode_end_banded(j2k_hip_encoder *e, j2k_hip_write_fn write, void *user)
                 const BandStage &st = S.stages[(size_t)k];
                 uint64_t tot = 0;
                 for (size_t n = st.blk_first; n < (size_t)st.blk_first + st.blk_count; ++n) {
-                    pack_off[n] = tot; tot += hm[2 * nb + n]; nsym_total += hm[3 * nb + n];
-                    res[S.perm[n]] = CblkResult{hm[n], hm[nb + n], hm[2 * nb + n]};
+                    pack_off[n] = tot; tot += tt.len(hm)[n]; nsym_total += tt.nsym(hm)[n];
+                    res[S.perm[n]] = CblkResult{tt.numbps(hm)[n], tt.npasses(hm)[n], tt.len(hm)[n]};
                 }
                 if (tot) {
                     if (tot > e->out_bytes) throw Error(J2K_HIP_ERR_OVERFLOW, "internal: a stage's codewords exceed the arena");
@@ -1461,9 +1302,9 @@ void encode_end_banded(j2k_hip_encoder *e, j2k_hip_write_fn write, void *user)
         abandon();
         throw;
     }
-    if (hm[4 * nb] != 0) {
+    if (*tt.err(hm) != 0) {
         abandon();
-        throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 kernel reported error " + std::to_string(hm[4 * nb]) +
+        throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 kernel reported error " + std::to_string(*tt.err(hm)) +
                                               " (1: too many bit-planes, 2: decision buffer, 3: codeword buffer)");
     }
     const Tier2Plan plan = planner.get();
@@ -1921,512 +1762,6 @@ int j2k_hip_file_header(const j2k_hip_params *params, uint64_t codestream_len, v
     } catch (...) {
         return J2K_HIP_ERR_PARAM;
     }
-}
-
-// ---------------------------------------------------------------------------------------- stages
-int j2k_hip_stage_frontend(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes_device, void *d_out)
-{
-    if (!e) return J2K_HIP_ERR_PARAM;
-    return guarded(e, [&] {
-        HIP_CHECK(hipSetDevice(e->device));
-        const Coding cod = normalise(params);
-        FrontendArgs fa = make_frontend_args(cod, planes_device, 0, 0, (int)cod.width, (int)cod.height);
-        if (cod.subsampled() || cod.rgb_to_sycc) {
-            // components of their own sizes: into planes of a common, aligned row stride as an encode has them, then dense to d_out
-            const PlaneLayout lay = plane_layout(cod, 0, 0, (int)cod.width, (int)cod.height);
-            e->P.ensure(lay.frame_elems * sizeof(int32_t));
-            run_frontend(cod, fa, e->P.as<int32_t>(), lay.comp_off, lay.stride, e->stream);
-            HIP_CHECK(hipGetLastError());
-            uint8_t *out = static_cast<uint8_t *>(d_out);
-            for (uint32_t c = 0; c < cod.ncomp; ++c) {
-                const size_t cw = (size_t)lay.cw[c], chh = (size_t)lay.ch[c];
-                HIP_CHECK(hipMemcpy2DAsync(out, cw * 4, e->P.as<int32_t>() + lay.comp_off[c], lay.stride * 4, cw * 4, chh, hipMemcpyDeviceToDevice, e->stream));
-                out += cw * chh * 4;
-            }
-            HIP_CHECK(hipStreamSynchronize(e->stream));
-            return;
-        }
-        for (uint32_t c = 0; c < cod.ncomp; ++c) fa.dst[c] = static_cast<int32_t *>(d_out) + (size_t)c * cod.width * cod.height;
-        fa.dst_stride = cod.width;
-        launch_frontend(fa, e->stream);
-        HIP_CHECK(hipStreamSynchronize(e->stream));
-    });
-}
-
-int j2k_hip_stage_dwt(j2k_hip_encoder *e, int reversible, uint32_t width, uint32_t height, uint32_t nplanes, uint32_t levels,
-                      uint32_t x0, uint32_t y0, const void *d_in, void *d_out, uint32_t repeat, double *ms_out)
-{
-    if (!e) return J2K_HIP_ERR_PARAM;
-    return guarded(e, [&] {
-        HIP_CHECK(hipSetDevice(e->device));
-        if (!width || !height || !nplanes || levels > 32) throw Error(J2K_HIP_ERR_PARAM, "bad DWT stage arguments");
-        const size_t plane = (size_t)width * height;
-        e->P.ensure(plane * nplanes * 4);
-        e->Q.ensure(plane * nplanes * 4);
-        std::vector<std::vector<DwtJob>> jobs(levels);
-        std::vector<int> mrw(levels, 0), mrh(levels, 0);
-        size_t total = 0;
-        for (uint32_t l = 0; l < levels; ++l)
-            for (uint32_t c = 0; c < nplanes; ++c) {
-                DwtJob j{};
-                const int ax0 = ceildivpow2((int)x0, (int)l), ax1 = ceildivpow2((int)(x0 + width), (int)l);
-                const int ay0 = ceildivpow2((int)y0, (int)l), ay1 = ceildivpow2((int)(y0 + height), (int)l);
-                j.rw = ax1 - ax0; j.rh = ay1 - ay0; j.casx = ax0 & 1; j.casy = ay0 & 1;
-                j.src_off = j.ll_off = j.z_off = (long long)(c * plane);
-                if (j.rw <= 0 || j.rh <= 0) continue;
-                jobs[l].push_back(j); mrw[l] = std::max(mrw[l], j.rw); mrh[l] = std::max(mrh[l], j.rh);
-                ++total;
-            }
-        e->jobs.ensure(std::max<size_t>(1, total) * sizeof(DwtJob));
-        size_t pos = 0;
-        for (auto &v : jobs) {
-            if (!v.empty()) HIP_CHECK(hipMemcpyAsync(e->jobs.as<DwtJob>() + pos, v.data(), v.size() * sizeof(DwtJob), hipMemcpyHostToDevice, e->stream));
-            pos += v.size();
-        }
-        e->geo_valid = false; e->seq_valid = false; // the job table was overwritten
-        if (levels == 0) HIP_CHECK(hipMemcpyAsync(d_out, d_in, plane * nplanes * 4, hipMemcpyDeviceToDevice, e->stream));
-        if (repeat == 0) repeat = 1;
-        HIP_CHECK(hipEventRecord(e->ev[EV_START], e->stream));
-        for (uint32_t r = 0; r < repeat; ++r) {
-            pos = 0;
-            for (uint32_t l = 0; l < levels; ++l) {
-                DwtLevelArgs da{};
-                da.src = l == 0 ? d_in : ((l & 1) ? e->Q.p : e->P.p); da.src_stride = width;
-                const bool last = l == levels - 1;
-                da.ll = last ? d_out : ((l & 1) ? e->P.p : e->Q.p); da.ll_stride = width;
-                da.z = d_out; da.z_stride = width;
-                da.jobs = e->jobs.as<DwtJob>() + pos; da.njobs = (int)jobs[l].size();
-                da.max_rw = mrw[l]; da.max_rh = mrh[l]; da.reversible = reversible;
-                launch_dwt_level(da, e->stream);
-                pos += jobs[l].size();
-            }
-        }
-        HIP_CHECK(hipEventRecord(e->ev[EV_DONE], e->stream));
-        HIP_CHECK(hipStreamSynchronize(e->stream));
-        float ms = 0;
-        HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_START], e->ev[EV_DONE]));
-        if (ms_out) *ms_out = ms / repeat;
-    });
-}
-
-// The front end and the DWT launches of an encode, and nothing behind them: encode_begin's own steps up to the last level
-// (device frames, one frame), with a level optionally launched in pieces over row-pair ranges.
-int j2k_hip_stage_transform(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes_device,
-                            const uint32_t *cuts, const uint32_t *ncuts, uint32_t ncut_levels, int descending, void *d_out)
-{
-    if (!e) return J2K_HIP_ERR_PARAM;
-    return guarded(e, [&] {
-        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
-        if (!planes_device || !d_out) throw Error(J2K_HIP_ERR_PARAM, "planes or d_out is NULL");
-        if (ncut_levels && (!ncuts || !cuts)) throw Error(J2K_HIP_ERR_PARAM, "cut points announced but not given");
-        HIP_CHECK(hipSetDevice(e->device));
-        const Tuning tn = tuning();
-        const Coding cod = normalise(params);
-        prepare_geometry(e, cod, 0, cod.ntiles());
-        // The handle's geometry is this call's now while last_fa still describes an earlier call's channels: nothing may
-        // replay them against it (j2k_hip_debug_dwt_time), so the next call builds its geometry afresh.
-        e->geo_valid = false; e->seq_valid = false; e->band_valid = false; e->rc_weight_valid = false;
-        const Geometry &g = e->geo;
-        hipStream_t s = e->stream;
-        const size_t S = e->stride;
-        const int NL = (int)cod.levels();
-        if (ncut_levels > (uint32_t)NL) throw Error(J2K_HIP_ERR_PARAM, "cut points for more levels than the transform has");
-        // row-pair ranges per level: [0, c_1), [c_1, c_2), .., [c_n, end)
-        std::vector<std::vector<int>> bounds((size_t)NL);
-        const uint32_t *cp = cuts;
-        for (int l = 0; l < NL; ++l) {
-            int npy = 0; // row pairs of the level's tallest job
-            for (const DwtJob &j : e->h_jobs[(size_t)l]) npy = std::max(npy, (j.rh + j.casy + 1) >> 1);
-            std::vector<int> &b = bounds[(size_t)l];
-            b.push_back(0);
-            for (uint32_t i = 0; (uint32_t)l < ncut_levels && i < ncuts[l]; ++i, ++cp) {
-                if (*cp >= (uint32_t)npy || (int)*cp <= b.back()) throw Error(J2K_HIP_ERR_PARAM, "cut points must increase and lie inside the level's row pairs");
-                b.push_back((int)*cp);
-            }
-            b.push_back(npy);
-        }
-        const int y0 = e->box_y0, x0 = e->box_x0;
-        int y1 = 0, x1 = 0;
-        for (const Tile &T : g.tiles) { y1 = std::max(y1, T.y1); x1 = std::max(x1, T.x1); }
-        FrontendArgs fa = make_frontend_args(cod, planes_device, x0, y0, x1, y1);
-        const bool fused = fuse_frontend(cod, fa, tn);
-        const size_t plane_bytes = e->frame_elems * sizeof(int32_t);
-        // (the planes are filled first: a word that no launch writes shows as 0xA5A5A5A5 instead of an earlier call's result)
-        if (!fused || NL >= 3) { e->P.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->P.p, 0xA5, plane_bytes, s)); }
-        if (NL >= 1) { e->Z.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->Z.p, 0xA5, plane_bytes, s)); }
-        if (NL >= 2) { e->Q.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->Q.p, 0xA5, plane_bytes, s)); }
-        if (!fused) {
-            fa.dst_x0 = x0; fa.dst_y0 = y0;
-            run_frontend(cod, fa, e->P.as<int32_t>(), e->comp_off, S, s);
-        }
-        for (int l = 0; l < NL; ++l) {
-            const std::vector<int> &b = bounds[(size_t)l];
-            const int n = (int)b.size() - 1;
-            for (int i = 0; i < n; ++i) {
-                const int k = descending ? n - 1 - i : i;
-                DwtLevelArgs da = dwt_level_args(e, cod, fa, fused, 0, l);
-                if (n > 1) { da.pair0 = b[(size_t)k]; da.pair1 = b[(size_t)k + 1]; }
-                launch_dwt_level(da, s);
-                HIP_CHECK(hipGetLastError());
-            }
-        }
-        // the coefficient planes without their stride padding (zero levels: the front end's output)
-        const uint8_t *from = NL >= 1 ? e->Z.as<uint8_t>() : e->P.as<uint8_t>();
-        uint8_t *out = static_cast<uint8_t *>(d_out);
-        for (uint32_t c = 0; c < cod.ncomp; ++c) { // (every component at its own size: the box on the component's grid)
-            const int sx = cod.cdx[c], sy = cod.cdy[c];
-            const size_t W = (size_t)((x1 + sx - 1) / sx - (x0 + sx - 1) / sx), H = (size_t)((y1 + sy - 1) / sy - (y0 + sy - 1) / sy);
-            HIP_CHECK(hipMemcpy2DAsync(out, W * 4, from + e->comp_off[c] * 4, S * 4, W * 4, H, hipMemcpyDeviceToDevice, s));
-            out += W * H * 4;
-        }
-        HIP_CHECK(hipStreamSynchronize(s));
-    });
-}
-
-// the three Tier-1 stage hooks are one function: pass_rate / pass_dist on request, a code-block style or none
-static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
-                           const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
-                           const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
-                           void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist, uint32_t cblk_style);
-
-int j2k_hip_stage_t1(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
-                     const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
-                     const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
-                     void *data, size_t data_cap)
-{
-    return j2k_hip_stage_t1_passes(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses,
-                                   length, offsets, data, data_cap, nullptr, nullptr);
-}
-
-int j2k_hip_stage_t1_passes(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
-                            const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
-                            const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
-                            void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist)
-{
-    return stage_t1_blocks(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses, length,
-                           offsets, data, data_cap, pass_rate, pass_dist, 0);
-}
-
-// No pass_dist here, and so no branch that refuses it under bypass: launch_t1_model picks the distortion instantiation
-// (want_dist) before it looks at the bypass bit, and a block modelled that way would hand the raw passes sign XOR
-// prediction.  A style excludes rate control in a frame too (geometry.cpp).
-int j2k_hip_stage_t1_styled(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
-                            const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
-                            const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
-                            void *data, size_t data_cap, uint32_t *pass_rate, uint32_t cblk_style)
-{
-    return stage_t1_blocks(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses, length,
-                           offsets, data, data_cap, pass_rate, nullptr, cblk_style);
-}
-
-static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
-                           const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
-                           const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
-                           void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist, uint32_t cblk_style)
-{
-    if (!e) return J2K_HIP_ERR_PARAM;
-    return guarded(e, [&] {
-        // the styles a frame refuses (geometry.cpp)
-        if (cblk_style & kStyleVcausal) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: vertically causal contexts (bit 8) are not written");
-        if (cblk_style & ~(uint32_t)(kStylesEncoded | kStyleVcausal)) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: unknown code-block style bits");
-        HIP_CHECK(hipSetDevice(e->device));
-        hipStream_t s = e->stream;
-        const size_t nb = nblocks;
-        std::vector<CblkDev> blks(nb);
-        size_t sym_off = 0, out_off = 0;
-        for (size_t i = 0; i < nb; ++i) {
-            if (bw[i] == 0 || bh[i] == 0 || bw[i] > 64 || bh[i] > 64 || orient[i] > 3) throw Error(J2K_HIP_ERR_PARAM, "bad code-block rectangle");
-            CblkDev d{};
-            d.coef_off = (unsigned long long)by[i] * stride + bx[i];
-            const size_t area = (size_t)bw[i] * bh[i];
-            const CblkCaps caps = cblk_capacities(area, 30, cblk_style); // (Mb = 30: no band is known here; a frame's are smaller)
-            const size_t symcap = caps.sym, outcap = caps.out;
-            d.sym_off = sym_off; d.sym_cap = (unsigned)symcap; d.out_off = out_off; d.out_cap = (unsigned)outcap;
-            d.stepsize = stepsize ? stepsize[i] : 1.0f;
-            d.w = (unsigned short)bw[i]; d.h = (unsigned short)bh[i]; d.orient = (unsigned char)orient[i]; d.Mb = 30;
-            sym_off += symcap; out_off += outcap;
-            blks[i] = d;
-        }
-        {
-            // The modeller rewrites every block of d_coef in place (scaled magnitudes, transposed bit-planes): two blocks that
-            // share a sample would read each other's scratch.  Sweep over the blocks sorted by their top row.
-            std::vector<uint32_t> order(nb);
-            for (uint32_t i = 0; i < nb; ++i) order[i] = i;
-            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return by[a] < by[b]; });
-            for (size_t i = 0; i < nb; ++i)
-                for (size_t j = i + 1; j < nb && by[order[j]] < by[order[i]] + bh[order[i]]; ++j) {
-                    const uint32_t a = order[i], b = order[j];
-                    if (bx[a] < bx[b] + bw[b] && bx[b] < bx[a] + bw[a]) throw Error(J2K_HIP_ERR_PARAM, "code-block rectangles overlap");
-                }
-            for (size_t i = 0; i < nb; ++i)
-                if ((uint64_t)bx[i] + bw[i] > stride) throw Error(J2K_HIP_ERR_PARAM, "code-block rectangle wider than the plane's stride");
-        }
-        e->geo_valid = false;
-        e->blks.ensure(std::max<size_t>(1, nb) * sizeof(CblkDev));
-        if (nb) HIP_CHECK(hipMemcpyAsync(e->blks.p, blks.data(), nb * sizeof(CblkDev), hipMemcpyHostToDevice, s));
-        e->sym.ensure(sym_off + 1024); e->out.ensure(out_off + 64);
-        e->meta.ensure((4 * nb + 4) * sizeof(uint32_t));
-        e->passes.ensure(std::max<size_t>(1, nb) * kDevMaxPasses * 3 * sizeof(uint32_t));
-        uint32_t *meta = e->meta.as<uint32_t>();
-        T1Args ta{};
-        ta.coef = d_coef; ta.stride = stride; ta.blks = e->blks.as<CblkDev>(); ta.nblks = (int)nb; ta.reversible = reversible;
-        ta.sym = e->sym.as<uint8_t>(); ta.out = e->out.as<uint8_t>();
-        ta.numbps = meta; ta.npasses = meta + nb; ta.len = meta + 2 * nb; ta.nsym = meta + 3 * nb; ta.err = meta + 4 * nb;
-        ta.pass_nsym = e->passes.as<uint32_t>();
-        ta.pass_nmsedec = reinterpret_cast<int *>(e->passes.as<uint32_t>() + nb * kDevMaxPasses);
-        ta.pass_rate = e->passes.as<uint32_t>() + 2 * nb * kDevMaxPasses;
-        ta.want_dist = pass_dist != nullptr; // the distortion sums cost LDS and issue slots: only on request
-        ta.sparse = tuning().t1_sparse;
-        ta.style = cblk_style;
-#ifdef J2K_T1_COUNTERS
-        t1_counters(ta);
-#endif
-        HIP_CHECK(hipMemsetAsync(ta.err, 0, sizeof(uint32_t), s));
-        launch_t1_model(ta, s);
-        launch_t1_mq(ta, s);
-        if (cblk_style) launch_t1_rate_fixup(ta, s); // as a styled frame has them: on the device, behind the styled coder
-        std::vector<uint32_t> hm(4 * nb + 1);
-        HIP_CHECK(hipMemcpyAsync(hm.data(), meta, hm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        if (hm[4 * nb]) throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 kernel reported error " + std::to_string(hm[4 * nb]));
-        size_t pos = 0;
-        for (size_t i = 0; i < nb; ++i) {
-            numbps[i] = hm[i]; npasses[i] = hm[nb + i]; length[i] = hm[2 * nb + i];
-            offsets[i] = pos;
-            if (pos + length[i] > data_cap) throw Error(J2K_HIP_ERR_OVERFLOW, "data buffer too small");
-            if (length[i]) HIP_CHECK(hipMemcpy(static_cast<uint8_t *>(data) + pos, e->out.as<uint8_t>() + blks[i].out_off, length[i], hipMemcpyDeviceToHost));
-            pos += length[i];
-        }
-        if (pass_rate || pass_dist) {
-            std::vector<uint32_t> hp(nb * kDevMaxPasses * 3);
-            HIP_CHECK(hipMemcpy(hp.data(), e->passes.p, hp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < nb; ++i) {
-                const uint32_t np = npasses[i];
-                uint32_t *rate = hp.data() + 2 * nb * kDevMaxPasses + i * kDevMaxPasses;
-                if (!cblk_style) {
-                    // the reference's fix-ups of the per-pass byte counts: an estimate never exceeds what
-                    // follows it, and a pass never ends on 0xFF  (under a style the kernel above has applied them)
-                    uint32_t last = length[i];
-                    for (uint32_t p = np; p > 0;) { --p; if (rate[p] > last) rate[p] = last; else last = rate[p]; }
-                    const uint8_t *bytes = static_cast<const uint8_t *>(data) + offsets[i];
-                    for (uint32_t p = 0; p < np; ++p)
-                        if (rate[p] > 0 && bytes[rate[p] - 1] == 0xff) --rate[p];
-                }
-                for (uint32_t p = 0; p < (uint32_t)kDevMaxPasses; ++p) {
-                    if (pass_rate) pass_rate[i * kDevMaxPasses + p] = p < np ? rate[p] : 0;
-                    if (pass_dist) pass_dist[i * kDevMaxPasses + p] = p < np ? (int32_t)hp[nb * kDevMaxPasses + i * kDevMaxPasses + p] : 0;
-                }
-            }
-        }
-    });
-}
-
-// The rate control's kernels alone (rate.hip), on tables the caller supplies, through the objects an encode drives them with:
-// rate_args lays out the device memory, launch_rate_prepare runs where encode_begin queues it, and a HipRateDevice over the
-// uploaded tables answers begin_layer / ahead / scan / scan_sums / fetch -- slot layout, copy sizes, memsets and the running
-// sums over `delta` included.
-int j2k_hip_stage_rate(j2k_hip_encoder *e, uint32_t nblocks, const double *weight, const uint8_t *comp, const uint32_t *numbps,
-                       const uint32_t *npasses, const uint32_t *pass_rate, const int32_t *pass_dist, double *disto, float *reach,
-                       double *bounds, uint32_t first, uint32_t count, const uint8_t *done, const double *ahead, uint32_t K,
-                       uint64_t *body, const j2k_hip_rate_scan *scans, uint32_t nscans, j2k_hip_rate_taken *taken, uint32_t *bytes,
-                       uint64_t *sums)
-{
-    if (!e) return J2K_HIP_ERR_PARAM;
-    return guarded(e, [&] {
-        static_assert(sizeof(j2k_hip_rate_taken) == sizeof(Taken), "the scan's records go out as they are");
-        static_assert(J2K_HIP_MAX_PASSES == kDevMaxPasses, "the header's row length is the tables'");
-        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
-        const size_t nb = nblocks;
-        if (!nb || !weight || !comp || !numbps || !npasses || !pass_rate || !pass_dist || !disto || !reach || !bounds)
-            throw Error(J2K_HIP_ERR_PARAM, "rate stage: no blocks, or a table is NULL");
-        for (size_t i = 0; i < nb; ++i) {
-            if (comp[i] > 3) throw Error(J2K_HIP_ERR_PARAM, "rate stage: component above 3");
-            if (numbps[i] > 31) throw Error(J2K_HIP_ERR_PARAM, "rate stage: more than 31 bit-planes");
-            if (npasses[i] > (uint32_t)kDevMaxPasses || (npasses[i] && npasses[i] + 2 > 3 * numbps[i]))
-                throw Error(J2K_HIP_ERR_PARAM, "rate stage: more passes than the bit-planes hold");
-        }
-        if (first > nb || count > nb - first) throw Error(J2K_HIP_ERR_PARAM, "rate stage: block range outside the blocks");
-        if (K > 128) throw Error(J2K_HIP_ERR_PARAM, "rate stage: more than 128 thresholds ahead");
-        if ((K || nscans) && !count) throw Error(J2K_HIP_ERR_PARAM, "rate stage: queries over an empty block range");
-        if ((K && (!ahead || !body)) || (nscans && (!scans || !taken || !bytes || !sums)))
-            throw Error(J2K_HIP_ERR_PARAM, "rate stage: a query without its arrays");
-        for (uint32_t i = 0; done && i < count; ++i)
-            if (done[i] > npasses[first + i]) throw Error(J2K_HIP_ERR_PARAM, "rate stage: more passes done than the block has");
-        for (uint32_t k = 1; k < K; ++k)
-            if (!(ahead[k] <= ahead[k - 1])) throw Error(J2K_HIP_ERR_PARAM, "rate stage: thresholds ahead must descend");
-        {
-            // a slot whose fetch is put off must still hold its scan at the end
-            bool held[3] = {false, false, false};
-            for (uint32_t i = 0; i < nscans; ++i) {
-                const j2k_hip_rate_scan &q = scans[i];
-                if (q.mode > J2K_HIP_RATE_SUMS_FETCH_LAST || (q.mode != J2K_HIP_RATE_SCAN && q.slot > 2))
-                    throw Error(J2K_HIP_ERR_PARAM, "rate stage: unknown scan mode or slot");
-                const uint32_t k = q.mode == J2K_HIP_RATE_SCAN ? 0u : q.slot;
-                if (held[k]) throw Error(J2K_HIP_ERR_PARAM, "rate stage: a scan into a slot whose fetch is still to come");
-                if (q.mode == J2K_HIP_RATE_SUMS_FETCH_LAST) held[k] = true;
-            }
-        }
-        HIP_CHECK(hipSetDevice(e->device));
-        hipStream_t s = e->stream;
-        e->geo_valid = false; e->seq_valid = false; e->band_valid = false; e->rc_weight_valid = false; // tables of the handle's last frame are overwritten
-        // the Tier-1 results where a frame's coder leaves them: meta = [numbps | npasses | ..], passes = [decisions | nmsedec | rate]
-        const size_t row = (size_t)kDevMaxPasses;
-        e->meta.ensure((4 * nb + 4) * sizeof(uint32_t));
-        e->passes.ensure(nb * row * 3 * sizeof(uint32_t));
-        uint32_t *meta = e->meta.as<uint32_t>();
-        uint32_t *pn = e->passes.as<uint32_t>();
-        HIP_CHECK(hipMemcpyAsync(meta, numbps, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(meta + nb, npasses, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(pn + nb * row, pass_dist, nb * row * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(pn + 2 * nb * row, pass_rate, nb * row * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        HipRateDevice dev(e, nb, meta);
-        const RateArgs &ra = dev.a;
-        std::vector<uint8_t> wc(nb * sizeof(double) + nb); // the blocks' components behind their weights, as encode_begin stages them
-        std::memcpy(wc.data(), weight, nb * sizeof(double));
-        std::memcpy(wc.data() + nb * sizeof(double), comp, nb);
-        HIP_CHECK(hipMemcpyAsync(e->rc_weight.p, wc.data(), wc.size(), hipMemcpyHostToDevice, s));
-        // (filled first: what the kernel leaves alone -- the rows' entries beyond npasses -- comes back as 0xA5 bytes)
-        HIP_CHECK(hipMemsetAsync(ra.disto, 0xA5, nb * row * sizeof(double), s));
-        HIP_CHECK(hipMemsetAsync(ra.reach, 0xA5, nb * row * sizeof(float), s));
-        HIP_CHECK(hipMemsetAsync(e->rc_small.p, 0xA5, dev.lay.total, s));
-        launch_rate_prepare(ra, s);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(e->h_rc_bounds.p, ra.bounds, 3 * nb * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(disto, ra.disto, nb * row * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(reach, ra.reach, nb * row * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        std::memcpy(bounds, dev.bmin(), nb * sizeof(double));
-        std::memcpy(bounds + nb, dev.bmax(), nb * sizeof(double));
-        std::memcpy(bounds + 2 * nb, dev.steepest(), nb * sizeof(double));
-        if (!K && !nscans) return;
-        dev.begin_layer(first, count, done);
-        if (K) dev.ahead(first, count, ahead, K, body);
-        auto keep = [&](uint32_t i, const Taken *t, const uint32_t *b) {
-            std::memcpy(taken + (size_t)i * count, t, (size_t)count * sizeof(Taken));
-            std::memcpy(bytes + (size_t)i * count, b, (size_t)count * sizeof(uint32_t));
-        };
-        for (uint32_t i = 0; i < nscans; ++i) {
-            const j2k_hip_rate_scan &q = scans[i];
-            const Taken *t = nullptr;
-            const uint32_t *b = nullptr;
-            if (q.mode == J2K_HIP_RATE_SCAN) {
-                dev.scan(first, count, q.thresh, &t, &b, sums + (size_t)i * kRateSums);
-                keep(i, t, b);
-                continue;
-            }
-            dev.scan_sums(first, count, q.thresh, (int)q.slot, sums + (size_t)i * kRateSums);
-            if (q.mode == J2K_HIP_RATE_SUMS_FETCH) { dev.fetch((int)q.slot, count, &t, &b); keep(i, t, b); }
-        }
-        for (uint32_t i = 0; i < nscans; ++i) {
-            if (scans[i].mode != J2K_HIP_RATE_SUMS_FETCH_LAST) continue;
-            const Taken *t = nullptr;
-            const uint32_t *b = nullptr;
-            dev.fetch((int)scans[i].slot, count, &t, &b);
-            keep(i, t, b);
-        }
-    });
-}
-
-// One launch_gather over pieces the caller supplies, its GatherArgs filled from the buffers and in the table order of
-// encode_end (block pieces: a CblkDev table, the blocks' lengths and cblk_dst) and of the decoder (segments alone).
-int j2k_hip_stage_gather(j2k_hip_encoder *e, const void *src, size_t src_bytes, const void *blob, size_t blob_bytes, void *dst,
-                         size_t dst_bytes, const j2k_hip_gather_piece *blocks, uint32_t nblocks, const j2k_hip_gather_piece *headers,
-                         uint32_t nheaders, const j2k_hip_gather_piece *segments, uint32_t nsegments)
-{
-    if (!e) return J2K_HIP_ERR_PARAM;
-    return guarded(e, [&] {
-        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
-        if ((src_bytes && !src) || (blob_bytes && !blob) || (dst_bytes && !dst) || (nblocks && !blocks) || (nheaders && !headers) ||
-            (nsegments && !segments))
-            throw Error(J2K_HIP_ERR_PARAM, "gather stage: a buffer or a piece list is NULL");
-        const size_t nbd = nblocks, nh = nheaders, nseg = nsegments;
-        if (nbd + nh + nseg > (size_t)INT32_MAX) throw Error(J2K_HIP_ERR_PARAM, "gather stage: too many pieces");
-        std::vector<std::pair<uint64_t, uint64_t>> spans; // destination [begin, end) of every piece that writes
-        auto piece = [&](const j2k_hip_gather_piece &p, size_t from_bytes) {
-            if (p.src > from_bytes || p.len > from_bytes - p.src) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a piece reads outside its source");
-            if (p.dst > dst_bytes || p.len > dst_bytes - p.dst) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a piece writes outside the destination");
-            if (p.len) spans.emplace_back(p.dst, p.dst + p.len);
-        };
-        for (size_t i = 0; i < nbd; ++i) {
-            if (blocks[i].src & 3) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a block's source is not 4-byte aligned");
-            piece(blocks[i], src_bytes);
-        }
-        for (size_t i = 0; i < nh; ++i) {
-            if (headers[i].src > UINT32_MAX) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a header's source offset needs more than 32 bits");
-            piece(headers[i], blob_bytes);
-        }
-        for (size_t i = 0; i < nseg; ++i) piece(segments[i], src_bytes);
-        std::sort(spans.begin(), spans.end());
-        for (size_t i = 1; i < spans.size(); ++i)
-            if (spans[i].first < spans[i - 1].second) throw Error(J2K_HIP_ERR_PARAM, "gather stage: destinations overlap");
-        if (!(nbd + nh + nseg)) return;
-        HIP_CHECK(hipSetDevice(e->device));
-        hipStream_t s = e->stream;
-        e->geo_valid = false; e->seq_valid = false; e->band_valid = false; // the block table is overwritten
-        // the plan's layout (encode_end): [blob][hdr_dst][cblk_dst][seg_dst][seg_src][hdr_src][hdr_len][seg_len]
-        const size_t blob_sz = round_up(blob_bytes + 8, 16);
-        const size_t plan_total = round_up(blob_sz + nh * (8 + 4 + 4) + nbd * 8 + nseg * (8 + 8 + 4) + 64, 64);
-        std::vector<uint8_t> hplan(plan_total, 0);
-        uint8_t *hp = hplan.data();
-        if (blob_bytes) std::memcpy(hp, blob, blob_bytes);
-        uint64_t *h_hdst = reinterpret_cast<uint64_t *>(hp + blob_sz);
-        uint64_t *h_cdst = h_hdst + nh;
-        uint64_t *h_sdst = h_cdst + nbd, *h_ssrc = h_sdst + nseg;
-        uint32_t *h_hsrc = reinterpret_cast<uint32_t *>(h_ssrc + nseg);
-        uint32_t *h_hlen = h_hsrc + nh, *h_slen = h_hlen + nh;
-        for (size_t i = 0; i < nh; ++i) { h_hdst[i] = headers[i].dst; h_hsrc[i] = (uint32_t)headers[i].src; h_hlen[i] = headers[i].len; }
-        for (size_t i = 0; i < nseg; ++i) { h_sdst[i] = segments[i].dst; h_ssrc[i] = segments[i].src; h_slen[i] = segments[i].len; }
-        std::vector<CblkDev> blks(std::max<size_t>(1, nbd));
-        std::vector<uint32_t> lens(std::max<size_t>(1, nbd));
-        for (size_t i = 0; i < nbd; ++i) { h_cdst[i] = blocks[i].dst; blks[i] = CblkDev{}; blks[i].out_off = blocks[i].src; lens[i] = blocks[i].len; }
-        e->plan.ensure(plan_total);
-        e->cs.ensure(dst_bytes + 64);
-        e->out.ensure(src_bytes + 64); // (as a frame's: a misaligned piece's last source word may end up to three bytes behind it)
-        e->blks.ensure(blks.size() * sizeof(CblkDev));
-        e->meta.ensure((4 * std::max<size_t>(1, nbd) + 4) * sizeof(uint32_t));
-        HIP_CHECK(hipMemcpyAsync(e->plan.p, hp, plan_total, hipMemcpyHostToDevice, s));
-        if (src_bytes) HIP_CHECK(hipMemcpyAsync(e->out.p, src, src_bytes, hipMemcpyHostToDevice, s));
-        if (dst_bytes) HIP_CHECK(hipMemcpyAsync(e->cs.p, dst, dst_bytes, hipMemcpyHostToDevice, s));
-        HIP_CHECK(hipMemcpyAsync(e->blks.p, blks.data(), blks.size() * sizeof(CblkDev), hipMemcpyHostToDevice, s));
-        uint32_t *meta = e->meta.as<uint32_t>();
-        HIP_CHECK(hipMemcpyAsync(meta + 2 * nbd, lens.data(), lens.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        GatherArgs ga{};
-        uint8_t *dp = e->plan.as<uint8_t>();
-        ga.dst = e->cs.as<uint8_t>();
-        ga.blob = dp;
-        ga.hdr_dst = reinterpret_cast<const unsigned long long *>(dp + blob_sz);
-        ga.cblk_dst = ga.hdr_dst + nh;
-        ga.seg_dst = ga.cblk_dst + nbd; ga.seg_src = ga.seg_dst + nseg;
-        ga.hdr_src = reinterpret_cast<const unsigned int *>(ga.seg_src + nseg);
-        ga.hdr_len = ga.hdr_src + nh;
-        ga.seg_len = ga.hdr_len + nh;
-        ga.nhdr = (int)nh; ga.nseg = (int)nseg;
-        ga.out = e->out.as<uint8_t>(); ga.blks = e->blks.as<CblkDev>(); ga.len = meta + 2 * nbd; ga.nblks = (int)nbd;
-        launch_gather(ga, s);
-        HIP_CHECK(hipGetLastError());
-        if (dst_bytes) HIP_CHECK(hipMemcpyAsync(dst, e->cs.p, dst_bytes, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-    });
-}
-
-int j2k_hip_stage_pack_offsets(j2k_hip_encoder *e, const uint32_t *len, uint32_t n, uint64_t base, uint64_t *dst)
-{
-    if (!e) return J2K_HIP_ERR_PARAM;
-    return guarded(e, [&] {
-        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
-        if (!n) return;
-        if (!len || !dst || n > (uint32_t)INT32_MAX) throw Error(J2K_HIP_ERR_PARAM, "pack offsets stage: an array is NULL, or too many lengths");
-        HIP_CHECK(hipSetDevice(e->device));
-        hipStream_t s = e->stream;
-        e->meta.ensure(((size_t)n + 4) * sizeof(uint32_t));
-        e->pack_dst.ensure((size_t)n * sizeof(uint64_t));
-        e->band_valid = false; // (a band-pipelined call's destinations are overwritten)
-        HIP_CHECK(hipMemcpyAsync(e->meta.p, len, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        launch_pack_offsets(e->meta.as<unsigned>(), (int)n, base, e->pack_dst.as<unsigned long long>(), s);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(dst, e->pack_dst.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-    });
 }
 
 // native sinks for benchmarks (include/j2k_hip.h, diagnostics)

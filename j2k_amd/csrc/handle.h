@@ -1,5 +1,6 @@
 // handle.h -- the codec handle (j2k_hip_encoder of include/j2k_hip.h) and the small helpers its users share:
-// encoder.cpp (encode path, lifetime) and decoder.cpp (decode path).  Internal to libj2k_hip.
+// encoder.cpp (encode path, lifetime), stage_hooks.cpp (the encode kernels' stage hooks) and decoder.cpp (decode path).
+// Internal to libj2k_hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,12 +11,14 @@
 #include <future>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "bands.h"
 #include "common.h"
 #include "geometry.h"
 #include "kernels.h"
+#include "table_layout.h"
 
 namespace j2k_hip {
 
@@ -70,7 +73,10 @@ struct PinnedBuf {
     template <typename T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
-inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static_assert(kMaxPasses == kDevMaxPasses, "table_layout.h and the Tier-1 kernels agree on the passes per block");
+
+// host threads of a Tier-2 planner (encode: the packet headers of a big frame; decode: the packets of a file)
+inline unsigned plan_threads() { return std::max(1u, std::min(4u, std::thread::hardware_concurrency())); }
 
 // the HIP runtime's number of hardware queues (its own environment knob GPU_MAX_HW_QUEUES, read once; 4 unless the host raised
 // it): streams beyond it share queues and wait for each other
@@ -215,6 +221,38 @@ FrontendArgs make_frontend_args(const Coding &cod, const j2k_hip_plane *planes, 
 void run_frontend(const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t comp_off[4], size_t S, hipStream_t s);
 // ... and a host frame's rows [y0, y1) into the handle's input arena, queued on s: dplanes[c].base = the device copy of planes[c]'s
 void upload_planes(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_plane *planes, int y0, int y1, j2k_hip_plane dplanes[4], hipStream_t s);
+
+// What an encode and the stage hooks of its kernels (stage_hooks.cpp) share, defined in encoder.cpp:
+// geometry, code-block table and DWT job lists of the handle, built or reused, with their device images ...
+void prepare_geometry(j2k_hip_encoder *e, const Coding &cod, uint32_t tile_first, uint32_t tile_count);
+// ... the decision-stream and codeword capacities of a code-block ...
+struct CblkCaps { size_t sym, out; };
+CblkCaps cblk_capacities(size_t area, uint32_t Mb, uint32_t style);
+// ... whether level 1 of the DWT takes its samples straight from the frame, and the launch arguments of DWT level l of frame f ...
+bool fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tuning &tn);
+DwtLevelArgs dwt_level_args(j2k_hip_encoder *e, const Coding &cod, const FrontendArgs &fa, bool fused, size_t f, int l, int tile_row = -1);
+#ifdef J2K_T1_COUNTERS
+void t1_counters(T1Args &ta);
+#endif
+// T1Args has a member more in a J2K_T1_COUNTERS / J2K_MQ_TIMES build (kernels.h), so the files that fill one must be built
+// alike.  Each refers to a tag named after its layout (through t1_arena_args) and encoder.cpp defines its own: a library
+// whose encoder.cpp and stage_hooks.cpp disagree does not link.  (The kernels' side is the build recipe's: tools/README.md.)
+#if defined(J2K_T1_COUNTERS) || defined(J2K_MQ_TIMES)
+#define J2K_T1ARGS_LAYOUT_TAG t1args_layout_with_dbg
+#else
+#define J2K_T1ARGS_LAYOUT_TAG t1args_layout_plain
+#endif
+extern const char J2K_T1ARGS_LAYOUT_TAG __attribute__((visibility("hidden")));
+// ... and where the Tier-1 kernels read and write in the handle's arenas: decisions, codewords, and the result tables of t.nb blocks
+inline void t1_arena_args(const j2k_hip_encoder *e, const T1Tables &t, T1Args &ta)
+{
+    asm volatile("" : : "r"(&J2K_T1ARGS_LAYOUT_TAG)); // (the reference to the tag: an address in a register)
+    ta.sym = e->sym.as<uint8_t>(); ta.out = e->out.as<uint8_t>();
+    t.fill(ta, e->meta.as<uint32_t>(), e->passes.as<uint32_t>());
+}
+// The tables an encode keeps from call to call (geometry, sequence and band block tables, rate weights) are rebuilt by the next
+// one: for every stage hook that overwrites an arena of the handle.
+inline void invalidate_cached_tables(j2k_hip_encoder *e) { e->geo_valid = e->seq_valid = e->band_valid = e->rc_weight_valid = false; }
 
 // After a failure nothing of a handle may stay in flight (the next call reuses every arena): waits for its streams.
 void drain(j2k_hip_encoder *e);

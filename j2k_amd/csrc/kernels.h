@@ -1,4 +1,4 @@
-// kernels.h -- launch interface of the gfx950 kernels (defined in *.hip, called by encoder.cpp).
+// kernels.h -- launch interface of the gfx950 kernels (defined in *.hip; called by encoder.cpp, stage_hooks.cpp, decoder.cpp, compare.cpp).
 // Every launcher is asynchronous on the given stream and allocates nothing.
 #pragma once
 

@@ -1,0 +1,506 @@
+// stage_hooks.cpp -- the stage hooks of the encode path (include/j2k_hip.h: j2k_hip_stage_*): single kernels, or a few of them,
+// driven on buffers the caller supplies, for the tests that pin the kernels down in isolation.  They run on a handle's stream and
+// arenas and through what an encode runs them with (handle.h, table_layout.h, rate_device.h): a table layout has one definition.
+// Every hook that overwrites an arena of the handle leaves the tables an encode caches to be rebuilt (invalidate_cached_tables).
+// The decode path's hooks are in decoder.cpp.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "cblk_style.h"
+#include "handle.h"
+#include "rate_device.h"
+
+using namespace j2k_hip;
+
+// the three Tier-1 stage hooks are one function: pass_rate / pass_dist on request, a code-block style or none
+static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                           const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
+                           const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
+                           void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist, uint32_t cblk_style)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        // the styles a frame refuses (geometry.cpp)
+        if (cblk_style & kStyleVcausal) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: vertically causal contexts (bit 8) are not written");
+        if (cblk_style & ~(uint32_t)(kStylesEncoded | kStyleVcausal)) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: unknown code-block style bits");
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t nb = nblocks;
+        std::vector<CblkDev> blks(nb);
+        size_t sym_off = 0, out_off = 0;
+        for (size_t i = 0; i < nb; ++i) {
+            if (bw[i] == 0 || bh[i] == 0 || bw[i] > 64 || bh[i] > 64 || orient[i] > 3) throw Error(J2K_HIP_ERR_PARAM, "bad code-block rectangle");
+            CblkDev d{};
+            d.coef_off = (unsigned long long)by[i] * stride + bx[i];
+            const size_t area = (size_t)bw[i] * bh[i];
+            const CblkCaps caps = cblk_capacities(area, 30, cblk_style); // (Mb = 30: no band is known here; a frame's are smaller)
+            const size_t symcap = caps.sym, outcap = caps.out;
+            d.sym_off = sym_off; d.sym_cap = (unsigned)symcap; d.out_off = out_off; d.out_cap = (unsigned)outcap;
+            d.stepsize = stepsize ? stepsize[i] : 1.0f;
+            d.w = (unsigned short)bw[i]; d.h = (unsigned short)bh[i]; d.orient = (unsigned char)orient[i]; d.Mb = 30;
+            sym_off += symcap; out_off += outcap;
+            blks[i] = d;
+        }
+        {
+            // The modeller rewrites every block of d_coef in place (scaled magnitudes, transposed bit-planes): two blocks that
+            // share a sample would read each other's scratch.  Sweep over the blocks sorted by their top row.
+            std::vector<uint32_t> order(nb);
+            for (uint32_t i = 0; i < nb; ++i) order[i] = i;
+            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return by[a] < by[b]; });
+            for (size_t i = 0; i < nb; ++i)
+                for (size_t j = i + 1; j < nb && by[order[j]] < by[order[i]] + bh[order[i]]; ++j) {
+                    const uint32_t a = order[i], b = order[j];
+                    if (bx[a] < bx[b] + bw[b] && bx[b] < bx[a] + bw[a]) throw Error(J2K_HIP_ERR_PARAM, "code-block rectangles overlap");
+                }
+            for (size_t i = 0; i < nb; ++i)
+                if ((uint64_t)bx[i] + bw[i] > stride) throw Error(J2K_HIP_ERR_PARAM, "code-block rectangle wider than the plane's stride");
+        }
+        invalidate_cached_tables(e); // the block table and the Tier-1 results of the handle's last frame are overwritten
+        const T1Tables tt(nb);
+        e->blks.ensure(std::max<size_t>(1, nb) * sizeof(CblkDev));
+        if (nb) HIP_CHECK(hipMemcpyAsync(e->blks.p, blks.data(), nb * sizeof(CblkDev), hipMemcpyHostToDevice, s));
+        e->sym.ensure(sym_off + 1024); e->out.ensure(out_off + 64);
+        e->meta.ensure(tt.meta_bytes());
+        e->passes.ensure(tt.passes_bytes());
+        T1Args ta{};
+        ta.coef = d_coef; ta.stride = stride; ta.blks = e->blks.as<CblkDev>(); ta.nblks = (int)nb; ta.reversible = reversible;
+        t1_arena_args(e, tt, ta);
+        ta.want_dist = pass_dist != nullptr; // the distortion sums cost LDS and issue slots: only on request
+        ta.sparse = tuning().t1_sparse;
+        ta.style = cblk_style;
+#ifdef J2K_T1_COUNTERS
+        t1_counters(ta);
+#endif
+        HIP_CHECK(hipMemsetAsync(ta.err, 0, sizeof(uint32_t), s));
+        launch_t1_model(ta, s);
+        launch_t1_mq(ta, s);
+        if (cblk_style) launch_t1_rate_fixup(ta, s); // as a styled frame has them: on the device, behind the styled coder
+        std::vector<uint32_t> hm(tt.meta_words());
+        HIP_CHECK(hipMemcpyAsync(hm.data(), e->meta.p, hm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (*tt.err(hm.data())) throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 kernel reported error " + std::to_string(*tt.err(hm.data())));
+        size_t pos = 0;
+        for (size_t i = 0; i < nb; ++i) {
+            numbps[i] = tt.numbps(hm.data())[i]; npasses[i] = tt.npasses(hm.data())[i]; length[i] = tt.len(hm.data())[i];
+            offsets[i] = pos;
+            if (pos + length[i] > data_cap) throw Error(J2K_HIP_ERR_OVERFLOW, "data buffer too small");
+            if (length[i]) HIP_CHECK(hipMemcpy(static_cast<uint8_t *>(data) + pos, e->out.as<uint8_t>() + blks[i].out_off, length[i], hipMemcpyDeviceToHost));
+            pos += length[i];
+        }
+        if (pass_rate || pass_dist) {
+            std::vector<uint32_t> hp(tt.passes_words());
+            HIP_CHECK(hipMemcpy(hp.data(), e->passes.p, hp.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < nb; ++i) {
+                const uint32_t np = npasses[i];
+                uint32_t *rate = tt.pass_rate(hp.data()) + tt.row(i);
+                const uint32_t *nmsedec = tt.pass_nmsedec(hp.data()) + tt.row(i);
+                if (!cblk_style) {
+                    // the reference's fix-ups of the per-pass byte counts: an estimate never exceeds what
+                    // follows it, and a pass never ends on 0xFF  (under a style the kernel above has applied them)
+                    uint32_t last = length[i];
+                    for (uint32_t p = np; p > 0;) { --p; if (rate[p] > last) rate[p] = last; else last = rate[p]; }
+                    const uint8_t *bytes = static_cast<const uint8_t *>(data) + offsets[i];
+                    for (uint32_t p = 0; p < np; ++p)
+                        if (rate[p] > 0 && bytes[rate[p] - 1] == 0xff) --rate[p];
+                }
+                for (uint32_t p = 0; p < (uint32_t)kDevMaxPasses; ++p) {
+                    if (pass_rate) pass_rate[tt.row(i) + p] = p < np ? rate[p] : 0;
+                    if (pass_dist) pass_dist[tt.row(i) + p] = p < np ? (int32_t)nmsedec[p] : 0;
+                }
+            }
+        }
+    });
+}
+
+extern "C" {
+
+int j2k_hip_stage_frontend(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes_device, void *d_out)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        HIP_CHECK(hipSetDevice(e->device));
+        const Coding cod = normalise(params);
+        FrontendArgs fa = make_frontend_args(cod, planes_device, 0, 0, (int)cod.width, (int)cod.height);
+        if (cod.subsampled() || cod.rgb_to_sycc) {
+            // components of their own sizes: into planes of a common, aligned row stride as an encode has them, then dense to d_out
+            const PlaneLayout lay = plane_layout(cod, 0, 0, (int)cod.width, (int)cod.height);
+            e->P.ensure(lay.frame_elems * sizeof(int32_t));
+            run_frontend(cod, fa, e->P.as<int32_t>(), lay.comp_off, lay.stride, e->stream);
+            HIP_CHECK(hipGetLastError());
+            uint8_t *out = static_cast<uint8_t *>(d_out);
+            for (uint32_t c = 0; c < cod.ncomp; ++c) {
+                const size_t cw = (size_t)lay.cw[c], chh = (size_t)lay.ch[c];
+                HIP_CHECK(hipMemcpy2DAsync(out, cw * 4, e->P.as<int32_t>() + lay.comp_off[c], lay.stride * 4, cw * 4, chh, hipMemcpyDeviceToDevice, e->stream));
+                out += cw * chh * 4;
+            }
+            HIP_CHECK(hipStreamSynchronize(e->stream));
+            return;
+        }
+        for (uint32_t c = 0; c < cod.ncomp; ++c) fa.dst[c] = static_cast<int32_t *>(d_out) + (size_t)c * cod.width * cod.height;
+        fa.dst_stride = cod.width;
+        launch_frontend(fa, e->stream);
+        HIP_CHECK(hipStreamSynchronize(e->stream));
+    });
+}
+
+int j2k_hip_stage_dwt(j2k_hip_encoder *e, int reversible, uint32_t width, uint32_t height, uint32_t nplanes, uint32_t levels,
+                      uint32_t x0, uint32_t y0, const void *d_in, void *d_out, uint32_t repeat, double *ms_out)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        HIP_CHECK(hipSetDevice(e->device));
+        if (!width || !height || !nplanes || levels > 32) throw Error(J2K_HIP_ERR_PARAM, "bad DWT stage arguments");
+        const size_t plane = (size_t)width * height;
+        e->P.ensure(plane * nplanes * 4);
+        e->Q.ensure(plane * nplanes * 4);
+        std::vector<std::vector<DwtJob>> jobs(levels);
+        std::vector<int> mrw(levels, 0), mrh(levels, 0);
+        size_t total = 0;
+        for (uint32_t l = 0; l < levels; ++l)
+            for (uint32_t c = 0; c < nplanes; ++c) {
+                DwtJob j{};
+                const int ax0 = ceildivpow2((int)x0, (int)l), ax1 = ceildivpow2((int)(x0 + width), (int)l);
+                const int ay0 = ceildivpow2((int)y0, (int)l), ay1 = ceildivpow2((int)(y0 + height), (int)l);
+                j.rw = ax1 - ax0; j.rh = ay1 - ay0; j.casx = ax0 & 1; j.casy = ay0 & 1;
+                j.src_off = j.ll_off = j.z_off = (long long)(c * plane);
+                if (j.rw <= 0 || j.rh <= 0) continue;
+                jobs[l].push_back(j); mrw[l] = std::max(mrw[l], j.rw); mrh[l] = std::max(mrh[l], j.rh);
+                ++total;
+            }
+        e->jobs.ensure(std::max<size_t>(1, total) * sizeof(DwtJob));
+        size_t pos = 0;
+        for (auto &v : jobs) {
+            if (!v.empty()) HIP_CHECK(hipMemcpyAsync(e->jobs.as<DwtJob>() + pos, v.data(), v.size() * sizeof(DwtJob), hipMemcpyHostToDevice, e->stream));
+            pos += v.size();
+        }
+        invalidate_cached_tables(e); // the job table was overwritten
+        if (levels == 0) HIP_CHECK(hipMemcpyAsync(d_out, d_in, plane * nplanes * 4, hipMemcpyDeviceToDevice, e->stream));
+        if (repeat == 0) repeat = 1;
+        HIP_CHECK(hipEventRecord(e->ev[EV_START], e->stream));
+        for (uint32_t r = 0; r < repeat; ++r) {
+            pos = 0;
+            for (uint32_t l = 0; l < levels; ++l) {
+                DwtLevelArgs da{};
+                da.src = l == 0 ? d_in : ((l & 1) ? e->Q.p : e->P.p); da.src_stride = width;
+                const bool last = l == levels - 1;
+                da.ll = last ? d_out : ((l & 1) ? e->P.p : e->Q.p); da.ll_stride = width;
+                da.z = d_out; da.z_stride = width;
+                da.jobs = e->jobs.as<DwtJob>() + pos; da.njobs = (int)jobs[l].size();
+                da.max_rw = mrw[l]; da.max_rh = mrh[l]; da.reversible = reversible;
+                launch_dwt_level(da, e->stream);
+                pos += jobs[l].size();
+            }
+        }
+        HIP_CHECK(hipEventRecord(e->ev[EV_DONE], e->stream));
+        HIP_CHECK(hipStreamSynchronize(e->stream));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, e->ev[EV_START], e->ev[EV_DONE]));
+        if (ms_out) *ms_out = ms / repeat;
+    });
+}
+
+// The front end and the DWT launches of an encode, and nothing behind them: encode_begin's own steps up to the last level
+// (device frames, one frame), with a level optionally launched in pieces over row-pair ranges.
+int j2k_hip_stage_transform(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes_device,
+                            const uint32_t *cuts, const uint32_t *ncuts, uint32_t ncut_levels, int descending, void *d_out)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        if (!planes_device || !d_out) throw Error(J2K_HIP_ERR_PARAM, "planes or d_out is NULL");
+        if (ncut_levels && (!ncuts || !cuts)) throw Error(J2K_HIP_ERR_PARAM, "cut points announced but not given");
+        HIP_CHECK(hipSetDevice(e->device));
+        const Tuning tn = tuning();
+        const Coding cod = normalise(params);
+        prepare_geometry(e, cod, 0, cod.ntiles());
+        // The handle's geometry is this call's now while last_fa still describes an earlier call's channels: nothing may
+        // replay them against it (j2k_hip_debug_dwt_time), so the next call builds its geometry afresh.
+        invalidate_cached_tables(e);
+        const Geometry &g = e->geo;
+        hipStream_t s = e->stream;
+        const size_t S = e->stride;
+        const int NL = (int)cod.levels();
+        if (ncut_levels > (uint32_t)NL) throw Error(J2K_HIP_ERR_PARAM, "cut points for more levels than the transform has");
+        // row-pair ranges per level: [0, c_1), [c_1, c_2), .., [c_n, end)
+        std::vector<std::vector<int>> bounds((size_t)NL);
+        const uint32_t *cp = cuts;
+        for (int l = 0; l < NL; ++l) {
+            int npy = 0; // row pairs of the level's tallest job
+            for (const DwtJob &j : e->h_jobs[(size_t)l]) npy = std::max(npy, (j.rh + j.casy + 1) >> 1);
+            std::vector<int> &b = bounds[(size_t)l];
+            b.push_back(0);
+            for (uint32_t i = 0; (uint32_t)l < ncut_levels && i < ncuts[l]; ++i, ++cp) {
+                if (*cp >= (uint32_t)npy || (int)*cp <= b.back()) throw Error(J2K_HIP_ERR_PARAM, "cut points must increase and lie inside the level's row pairs");
+                b.push_back((int)*cp);
+            }
+            b.push_back(npy);
+        }
+        const int y0 = e->box_y0, x0 = e->box_x0;
+        int y1 = 0, x1 = 0;
+        for (const Tile &T : g.tiles) { y1 = std::max(y1, T.y1); x1 = std::max(x1, T.x1); }
+        FrontendArgs fa = make_frontend_args(cod, planes_device, x0, y0, x1, y1);
+        const bool fused = fuse_frontend(cod, fa, tn);
+        const size_t plane_bytes = e->frame_elems * sizeof(int32_t);
+        // (the planes are filled first: a word that no launch writes shows as 0xA5A5A5A5 instead of an earlier call's result)
+        if (!fused || NL >= 3) { e->P.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->P.p, 0xA5, plane_bytes, s)); }
+        if (NL >= 1) { e->Z.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->Z.p, 0xA5, plane_bytes, s)); }
+        if (NL >= 2) { e->Q.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->Q.p, 0xA5, plane_bytes, s)); }
+        if (!fused) {
+            fa.dst_x0 = x0; fa.dst_y0 = y0;
+            run_frontend(cod, fa, e->P.as<int32_t>(), e->comp_off, S, s);
+        }
+        for (int l = 0; l < NL; ++l) {
+            const std::vector<int> &b = bounds[(size_t)l];
+            const int n = (int)b.size() - 1;
+            for (int i = 0; i < n; ++i) {
+                const int k = descending ? n - 1 - i : i;
+                DwtLevelArgs da = dwt_level_args(e, cod, fa, fused, 0, l);
+                if (n > 1) { da.pair0 = b[(size_t)k]; da.pair1 = b[(size_t)k + 1]; }
+                launch_dwt_level(da, s);
+                HIP_CHECK(hipGetLastError());
+            }
+        }
+        // the coefficient planes without their stride padding (zero levels: the front end's output)
+        const uint8_t *from = NL >= 1 ? e->Z.as<uint8_t>() : e->P.as<uint8_t>();
+        uint8_t *out = static_cast<uint8_t *>(d_out);
+        for (uint32_t c = 0; c < cod.ncomp; ++c) { // (every component at its own size: the box on the component's grid)
+            const int sx = cod.cdx[c], sy = cod.cdy[c];
+            const size_t W = (size_t)((x1 + sx - 1) / sx - (x0 + sx - 1) / sx), H = (size_t)((y1 + sy - 1) / sy - (y0 + sy - 1) / sy);
+            HIP_CHECK(hipMemcpy2DAsync(out, W * 4, from + e->comp_off[c] * 4, S * 4, W * 4, H, hipMemcpyDeviceToDevice, s));
+            out += W * H * 4;
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int j2k_hip_stage_t1(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                     const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
+                     const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
+                     void *data, size_t data_cap)
+{
+    return j2k_hip_stage_t1_passes(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses,
+                                   length, offsets, data, data_cap, nullptr, nullptr);
+}
+
+int j2k_hip_stage_t1_passes(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                            const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
+                            const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
+                            void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist)
+{
+    return stage_t1_blocks(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses, length,
+                           offsets, data, data_cap, pass_rate, pass_dist, 0);
+}
+
+// No pass_dist here, and so no branch that refuses it under bypass: launch_t1_model picks the distortion instantiation
+// (want_dist) before it looks at the bypass bit, and a block modelled that way would hand the raw passes sign XOR
+// prediction.  A style excludes rate control in a frame too (geometry.cpp).
+int j2k_hip_stage_t1_styled(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                            const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
+                            const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
+                            void *data, size_t data_cap, uint32_t *pass_rate, uint32_t cblk_style)
+{
+    return stage_t1_blocks(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses, length,
+                           offsets, data, data_cap, pass_rate, nullptr, cblk_style);
+}
+
+// The rate control's kernels alone (rate.hip), on tables the caller supplies, through the objects an encode drives them with:
+// the tables go where T1Tables puts a frame's, rate_args lays out the device memory, launch_rate_prepare runs where encode_begin
+// queues it, and a HipRateDevice over the uploaded tables answers begin_layer / ahead / scan / scan_sums / fetch -- slot layout,
+// copy sizes, memsets and the running sums over `delta` included.  The layouts are the encode's by construction: each has one
+// definition (table_layout.h, rate_device.h).
+int j2k_hip_stage_rate(j2k_hip_encoder *e, uint32_t nblocks, const double *weight, const uint8_t *comp, const uint32_t *numbps,
+                       const uint32_t *npasses, const uint32_t *pass_rate, const int32_t *pass_dist, double *disto, float *reach,
+                       double *bounds, uint32_t first, uint32_t count, const uint8_t *done, const double *ahead, uint32_t K,
+                       uint64_t *body, const j2k_hip_rate_scan *scans, uint32_t nscans, j2k_hip_rate_taken *taken, uint32_t *bytes,
+                       uint64_t *sums)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        static_assert(sizeof(j2k_hip_rate_taken) == sizeof(Taken), "the scan's records go out as they are");
+        static_assert(J2K_HIP_MAX_PASSES == kDevMaxPasses, "the header's row length is the tables'");
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        const size_t nb = nblocks;
+        if (!nb || !weight || !comp || !numbps || !npasses || !pass_rate || !pass_dist || !disto || !reach || !bounds)
+            throw Error(J2K_HIP_ERR_PARAM, "rate stage: no blocks, or a table is NULL");
+        for (size_t i = 0; i < nb; ++i) {
+            if (comp[i] > 3) throw Error(J2K_HIP_ERR_PARAM, "rate stage: component above 3");
+            if (numbps[i] > 31) throw Error(J2K_HIP_ERR_PARAM, "rate stage: more than 31 bit-planes");
+            if (npasses[i] > (uint32_t)kDevMaxPasses || (npasses[i] && npasses[i] + 2 > 3 * numbps[i]))
+                throw Error(J2K_HIP_ERR_PARAM, "rate stage: more passes than the bit-planes hold");
+        }
+        if (first > nb || count > nb - first) throw Error(J2K_HIP_ERR_PARAM, "rate stage: block range outside the blocks");
+        if (K > 128) throw Error(J2K_HIP_ERR_PARAM, "rate stage: more than 128 thresholds ahead");
+        if ((K || nscans) && !count) throw Error(J2K_HIP_ERR_PARAM, "rate stage: queries over an empty block range");
+        if ((K && (!ahead || !body)) || (nscans && (!scans || !taken || !bytes || !sums)))
+            throw Error(J2K_HIP_ERR_PARAM, "rate stage: a query without its arrays");
+        for (uint32_t i = 0; done && i < count; ++i)
+            if (done[i] > npasses[first + i]) throw Error(J2K_HIP_ERR_PARAM, "rate stage: more passes done than the block has");
+        for (uint32_t k = 1; k < K; ++k)
+            if (!(ahead[k] <= ahead[k - 1])) throw Error(J2K_HIP_ERR_PARAM, "rate stage: thresholds ahead must descend");
+        {
+            // a slot whose fetch is put off must still hold its scan at the end
+            bool held[3] = {false, false, false};
+            for (uint32_t i = 0; i < nscans; ++i) {
+                const j2k_hip_rate_scan &q = scans[i];
+                if (q.mode > J2K_HIP_RATE_SUMS_FETCH_LAST || (q.mode != J2K_HIP_RATE_SCAN && q.slot > 2))
+                    throw Error(J2K_HIP_ERR_PARAM, "rate stage: unknown scan mode or slot");
+                const uint32_t k = q.mode == J2K_HIP_RATE_SCAN ? 0u : q.slot;
+                if (held[k]) throw Error(J2K_HIP_ERR_PARAM, "rate stage: a scan into a slot whose fetch is still to come");
+                if (q.mode == J2K_HIP_RATE_SUMS_FETCH_LAST) held[k] = true;
+            }
+        }
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        invalidate_cached_tables(e); // tables of the handle's last frame are overwritten
+        // the Tier-1 results where a frame's coder leaves them
+        const T1Tables tt(nb);
+        const size_t rows = tt.row(nb);
+        e->meta.ensure(tt.meta_bytes());
+        e->passes.ensure(tt.passes_bytes());
+        uint32_t *meta = e->meta.as<uint32_t>();
+        uint32_t *pn = e->passes.as<uint32_t>();
+        HIP_CHECK(hipMemcpyAsync(tt.numbps(meta), numbps, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.npasses(meta), npasses, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.pass_nmsedec(pn), pass_dist, rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.pass_rate(pn), pass_rate, rows * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HipRateDevice dev(e, tt);
+        const RateArgs &ra = dev.a;
+        std::vector<uint8_t> wc(nb * sizeof(double) + nb); // the blocks' components behind their weights, as encode_begin stages them
+        std::memcpy(wc.data(), weight, nb * sizeof(double));
+        std::memcpy(wc.data() + nb * sizeof(double), comp, nb);
+        HIP_CHECK(hipMemcpyAsync(e->rc_weight.p, wc.data(), wc.size(), hipMemcpyHostToDevice, s));
+        // (filled first: what the kernel leaves alone -- the rows' entries beyond npasses -- comes back as 0xA5 bytes)
+        HIP_CHECK(hipMemsetAsync(ra.disto, 0xA5, rows * sizeof(double), s));
+        HIP_CHECK(hipMemsetAsync(ra.reach, 0xA5, rows * sizeof(float), s));
+        HIP_CHECK(hipMemsetAsync(e->rc_small.p, 0xA5, dev.lay.total, s));
+        launch_rate_prepare(ra, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(e->h_rc_bounds.p, ra.bounds, 3 * nb * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(disto, ra.disto, rows * sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(reach, ra.reach, rows * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        std::memcpy(bounds, dev.bmin(), nb * sizeof(double));
+        std::memcpy(bounds + nb, dev.bmax(), nb * sizeof(double));
+        std::memcpy(bounds + 2 * nb, dev.steepest(), nb * sizeof(double));
+        if (!K && !nscans) return;
+        dev.begin_layer(first, count, done);
+        if (K) dev.ahead(first, count, ahead, K, body);
+        auto keep = [&](uint32_t i, const Taken *t, const uint32_t *b) {
+            std::memcpy(taken + (size_t)i * count, t, (size_t)count * sizeof(Taken));
+            std::memcpy(bytes + (size_t)i * count, b, (size_t)count * sizeof(uint32_t));
+        };
+        for (uint32_t i = 0; i < nscans; ++i) {
+            const j2k_hip_rate_scan &q = scans[i];
+            const Taken *t = nullptr;
+            const uint32_t *b = nullptr;
+            if (q.mode == J2K_HIP_RATE_SCAN) {
+                dev.scan(first, count, q.thresh, &t, &b, sums + (size_t)i * kRateSums);
+                keep(i, t, b);
+                continue;
+            }
+            dev.scan_sums(first, count, q.thresh, (int)q.slot, sums + (size_t)i * kRateSums);
+            if (q.mode == J2K_HIP_RATE_SUMS_FETCH) { dev.fetch((int)q.slot, count, &t, &b); keep(i, t, b); }
+        }
+        for (uint32_t i = 0; i < nscans; ++i) {
+            if (scans[i].mode != J2K_HIP_RATE_SUMS_FETCH_LAST) continue;
+            const Taken *t = nullptr;
+            const uint32_t *b = nullptr;
+            dev.fetch((int)scans[i].slot, count, &t, &b);
+            keep(i, t, b);
+        }
+    });
+}
+
+// One launch_gather over pieces the caller supplies: the plan is laid out and its GatherArgs filled by the GatherPlan an encode
+// uses (table_layout.h) -- encode_end's table order by construction -- with block pieces as a CblkDev table, the blocks' lengths
+// in the `len` column of T1Tables and cblk_dst, as a frame has them, and segments alone as the decoder has them.
+int j2k_hip_stage_gather(j2k_hip_encoder *e, const void *src, size_t src_bytes, const void *blob, size_t blob_bytes, void *dst,
+                         size_t dst_bytes, const j2k_hip_gather_piece *blocks, uint32_t nblocks, const j2k_hip_gather_piece *headers,
+                         uint32_t nheaders, const j2k_hip_gather_piece *segments, uint32_t nsegments)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        if ((src_bytes && !src) || (blob_bytes && !blob) || (dst_bytes && !dst) || (nblocks && !blocks) || (nheaders && !headers) ||
+            (nsegments && !segments))
+            throw Error(J2K_HIP_ERR_PARAM, "gather stage: a buffer or a piece list is NULL");
+        const size_t nbd = nblocks, nh = nheaders, nseg = nsegments;
+        if (nbd + nh + nseg > (size_t)INT32_MAX) throw Error(J2K_HIP_ERR_PARAM, "gather stage: too many pieces");
+        std::vector<std::pair<uint64_t, uint64_t>> spans; // destination [begin, end) of every piece that writes
+        auto piece = [&](const j2k_hip_gather_piece &p, size_t from_bytes) {
+            if (p.src > from_bytes || p.len > from_bytes - p.src) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a piece reads outside its source");
+            if (p.dst > dst_bytes || p.len > dst_bytes - p.dst) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a piece writes outside the destination");
+            if (p.len) spans.emplace_back(p.dst, p.dst + p.len);
+        };
+        for (size_t i = 0; i < nbd; ++i) {
+            if (blocks[i].src & 3) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a block's source is not 4-byte aligned");
+            piece(blocks[i], src_bytes);
+        }
+        for (size_t i = 0; i < nh; ++i) {
+            if (headers[i].src > UINT32_MAX) throw Error(J2K_HIP_ERR_PARAM, "gather stage: a header's source offset needs more than 32 bits");
+            piece(headers[i], blob_bytes);
+        }
+        for (size_t i = 0; i < nseg; ++i) piece(segments[i], src_bytes);
+        std::sort(spans.begin(), spans.end());
+        for (size_t i = 1; i < spans.size(); ++i)
+            if (spans[i].first < spans[i - 1].second) throw Error(J2K_HIP_ERR_PARAM, "gather stage: destinations overlap");
+        if (!(nbd + nh + nseg)) return;
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        invalidate_cached_tables(e); // the block table is overwritten
+        const GatherPlan lay(blob_bytes, nh, nbd, nseg);
+        std::vector<uint8_t> hplan(lay.total, 0);
+        if (blob_bytes) std::memcpy(hplan.data(), blob, blob_bytes);
+        const GatherTables h = lay.tables(hplan.data());
+        for (size_t i = 0; i < nh; ++i) { h.hdr_dst[i] = headers[i].dst; h.hdr_src[i] = (uint32_t)headers[i].src; h.hdr_len[i] = headers[i].len; }
+        for (size_t i = 0; i < nseg; ++i) { h.seg_dst[i] = segments[i].dst; h.seg_src[i] = segments[i].src; h.seg_len[i] = segments[i].len; }
+        std::vector<CblkDev> blks(std::max<size_t>(1, nbd));
+        std::vector<uint32_t> lens(std::max<size_t>(1, nbd));
+        for (size_t i = 0; i < nbd; ++i) { h.cblk_dst[i] = blocks[i].dst; blks[i] = CblkDev{}; blks[i].out_off = blocks[i].src; lens[i] = blocks[i].len; }
+        const T1Tables tt(nbd);
+        e->plan.ensure(lay.total);
+        e->cs.ensure(dst_bytes + 64);
+        e->out.ensure(src_bytes + 64); // (as a frame's: a misaligned piece's last source word may end up to three bytes behind it)
+        e->blks.ensure(blks.size() * sizeof(CblkDev));
+        e->meta.ensure(tt.meta_bytes());
+        HIP_CHECK(hipMemcpyAsync(e->plan.p, hplan.data(), lay.total, hipMemcpyHostToDevice, s));
+        if (src_bytes) HIP_CHECK(hipMemcpyAsync(e->out.p, src, src_bytes, hipMemcpyHostToDevice, s));
+        if (dst_bytes) HIP_CHECK(hipMemcpyAsync(e->cs.p, dst, dst_bytes, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(e->blks.p, blks.data(), blks.size() * sizeof(CblkDev), hipMemcpyHostToDevice, s));
+        uint32_t *len = tt.len(e->meta.as<uint32_t>());
+        HIP_CHECK(hipMemcpyAsync(len, lens.data(), lens.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        GatherArgs ga{};
+        lay.fill(ga, e->plan.as<uint8_t>());
+        ga.dst = e->cs.as<uint8_t>();
+        ga.out = e->out.as<uint8_t>(); ga.blks = e->blks.as<CblkDev>(); ga.len = len; ga.nblks = (int)nbd;
+        launch_gather(ga, s);
+        HIP_CHECK(hipGetLastError());
+        if (dst_bytes) HIP_CHECK(hipMemcpyAsync(dst, e->cs.p, dst_bytes, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+int j2k_hip_stage_pack_offsets(j2k_hip_encoder *e, const uint32_t *len, uint32_t n, uint64_t base, uint64_t *dst)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        if (!n) return;
+        if (!len || !dst || n > (uint32_t)INT32_MAX) throw Error(J2K_HIP_ERR_PARAM, "pack offsets stage: an array is NULL, or too many lengths");
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        e->meta.ensure(((size_t)n + 4) * sizeof(uint32_t));
+        e->pack_dst.ensure((size_t)n * sizeof(uint64_t));
+        invalidate_cached_tables(e); // (a band-pipelined call's destinations are overwritten)
+        HIP_CHECK(hipMemcpyAsync(e->meta.p, len, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        launch_pack_offsets(e->meta.as<unsigned>(), (int)n, base, e->pack_dst.as<unsigned long long>(), s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(dst, e->pack_dst.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+} // extern "C"
