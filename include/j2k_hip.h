@@ -161,6 +161,36 @@ typedef struct j2k_hip_params {
      * J2K_HIP_ABI_VERSION is still 9: fields were appended, no function changed; struct_size is the guard. */
     uint32_t comp_sub_x[4], comp_sub_y[4];
     uint32_t rgb_to_sycc;
+    /* ---- cinema colour: R'G'B' to X'Y'Z' code values in the front end (a DCI frame holds 12-bit X'Y'Z': CIE XYZ normalised to
+     * 48 cd/m2 out of 52.37, under a 1/2.6 power).  0 = off: every byte, launch and statistic is what it was without the field.
+     * Otherwise channels 0..2 are R, G, B of the full image and say how they are coded:
+     *     1  sRGB (IEC 61966-2-1 piecewise curve, Rec.709 primaries, D65)
+     *     2  Rec.709 primaries under a pure 2.4 power (BT.1886)
+     *     3  Rec.709 primaries, linear light
+     * A fourth channel (alpha) takes the ordinary path (Promote, depth conversion, DC shift).  A pixel, to the rounding:
+     *   1. v = the integer sample of d bits, d = the plane's `depth` (after Promote where promote_ae16 applies; a float plane:
+     *      the integer j2k_hip_plane's rule makes of it); a stored sample above 2^d - 1 counts as 2^d - 1.
+     *      l = lin[v],  lin[v] = (float)EOTF((double)v / (2^d - 1)), a table of 2^d binary32 values computed on the host in double:
+     *      EOTF_1(x) = x <= 0.04045 ? x / 12.92 : pow((x + 0.055) / 1.055, 2.4),  EOTF_2(x) = pow(x, 2.4),  EOTF_3(x) = x.
+     *   2. M_ij = (float)((double)m_ij * (48.0 / 52.37)), m = the sRGB -> XYZ (D65) matrix, no chromatic adaptation (DCI practice):
+     *          0.4124564 0.3575761 0.1804375 / 0.2126729 0.7151522 0.0721750 / 0.0193339 0.1191920 0.9503041
+     *      X = fadd(fadd(fmul(M00, r), fmul(M01, g)), fmul(M02, b)): every product and sum rounded to binary32 on its own,
+     *      nothing contracted to an FMA; Y and Z alike from rows 1 and 2.
+     *   3. top = 2^depth - 1 (params.depth), thr[c] = (float)pow(((double)c - 0.5) / top, 2.6) for c = 1..top (strictly increasing
+     *      in binary32 for every depth); the code is the number of c with thr[c] <= X -- round-to-nearest of top * X^(1/2.6),
+     *      decided on thresholds: no transcendental function decides a code on the device.
+     *   The code minus the DC shift is the component sample (the 9/7 path: the same integer as a float); with `ycc` the RCT / ICT
+     *   follows as for any three components.  j2k_hip_xyz_tables hands out lin, thr and M as the kernel gets them.
+     * J2K_HIP_ERR_PARAM, the text naming rgb_to_xyz: a value above 3; fewer than 3 channels; rgb_to_sycc with it; a comp_sub
+     * factor other than 1.  It combines with everything else: dci_profile, layer_rates / layer_psnr, ycc, cblk_style, tiles
+     * inside one call, the JP2 wrapper, float planes, promote_ae16.  The main header and the file header do not depend on it.
+     * Entry points: as for rgb_to_sycc -- every entry point that takes planes but the tile-sharded ones, which refuse it with
+     * J2K_HIP_ERR_PARAM before any device work.  The front end runs as a pass of its own (never fused into DWT level 1, never
+     * band-pipelined: j2k_hip_stats.bands = 0).
+     * J2K_HIP_ABI_VERSION is still 9: the field was appended, no function changed; struct_size is the guard.  Where the struct
+     * ended in alignment padding (LP64: 4 bytes behind rgb_to_sycc) the field takes that padding and sizeof does not move: a
+     * caller of the older header that zero-initialises the whole struct, as the header has always asked for, passes 0. */
+    uint32_t rgb_to_xyz;
 } j2k_hip_params;
 
 enum { J2K_HIP_CBLK_BYPASS = 1, J2K_HIP_CBLK_RESET = 2, J2K_HIP_CBLK_TERMALL = 4, J2K_HIP_CBLK_VCAUSAL = 8 /* decode only */,
@@ -557,7 +587,8 @@ int j2k_hip_decode_get_max_layers(const j2k_hip_encoder *enc, uint32_t *max_laye
  * ceil(width / sub_x) x ceil(height / sub_y) samples:
  *   S_c(x, y)  the unsigned integer of params->depth bits that the encode's front end makes of the planes, before the DC shift
  *              and before any RCT / ICT: promote_ae16, the float quantisation of j2k_hip_plane, CopyChannel's depth conversion,
- *              and with rgb_to_sycc the integer Y / Cb / Cr formula of j2k_hip_params with its decimation;
+ *              and with rgb_to_sycc the integer Y / Cb / Cr formula of j2k_hip_params with its decimation; with rgb_to_xyz
+ *              the X'Y'Z' code of j2k_hip_params for channels 0..2 (a fourth channel as without it);
  *   D_c(x, y)  what j2k_hip_decode delivers for component c at the file's own depth; for a sub-sampled component the delivered
  *              sample at (x * sub_x, y * sub_y) (the decode replicates: that is the component's own sample);
  *   e = D - S, per sample.
@@ -573,7 +604,7 @@ int j2k_hip_decode_get_max_layers(const j2k_hip_encoder *enc, uint32_t *max_laye
  * J2K_HIP_ERR_UNSUPPORTED and a malformed one J2K_HIP_ERR_PARAM, both with j2k_hip_read_info's texts; a file cut short
  * compares what decodes; a handle with an encode pending refuses as j2k_hip_decode does.  Only the fields of `params` that
  * define the source samples and the geometry count -- width, height, channels, depth, promote_ae16, comp_sub_x / _y,
- * rgb_to_sycc; the coding fields (wavelet, ycc, layers, tiles, precincts, style, rates, profile, wrapper) are not read.
+ * rgb_to_sycc, rgb_to_xyz; the coding fields (wavelet, ycc, layers, tiles, precincts, style, rates, profile, wrapper) are not read.
  * j2k_hip_compare: planes in host memory.  j2k_hip_compare_device: planes[i].base are device pointers and the image never
  * crosses the bus.  j2k_hip_compare_check: the agreement test above alone -- no handle, no device, the text through
  * j2k_hip_last_error(NULL); both calls run it first.
@@ -591,10 +622,19 @@ int j2k_hip_compare(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2
 int j2k_hip_compare_device(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes, const void *file,
                            size_t len, j2k_hip_diff *diffs, uint32_t ndiffs);
 
+/* --- the tables of rgb_to_xyz -------------------------------------------------------------------------
+ * What the cinema colour front end (j2k_hip_params.rgb_to_xyz) looks its values up in, as the kernel gets them: no handle and
+ * no device needed.  source = 1..3 as rgb_to_xyz; lin receives 2^src_depth values (lin[v]), thr 2^dst_depth - 1 values
+ * (thr[c - 1] = the threshold of code c, c = 1 .. 2^dst_depth - 1), matrix the nine M_ij row by row.  A NULL output is
+ * skipped.  J2K_HIP_ERR_PARAM for a source outside 1..3 or a depth outside 1..16.
+ * J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
+int j2k_hip_xyz_tables(uint32_t source, uint32_t src_depth, uint32_t dst_depth, float *lin, float *thr, float matrix[9]);
+
 /* --- stage-level entry points (parity tests and roofline measurement call these) -----------------
  * A1+A2+A4+A5: front end only. d_out = channels planes of width*height 32-bit words (int32 for
  * reversible, float32 bit patterns otherwise), row stride = width.  With sub-sampled components (comp_sub_x / _y,
- * rgb_to_sycc) the components follow one another, each dense at its own size ceil(width / sub_x) x ceil(height / sub_y). */
+ * rgb_to_sycc) the components follow one another, each dense at its own size ceil(width / sub_x) x ceil(height / sub_y).
+ * rgb_to_xyz is honoured: channels 0..2 come out as X'Y'Z' codes minus the DC shift (then the RCT / ICT with ycc). */
 int j2k_hip_stage_frontend(j2k_hip_encoder *enc, const j2k_hip_params *params,
                            const j2k_hip_plane *planes_device, void *d_out);
 /* A6: forward DWT of `nplanes` planes of width*height 32-bit words (row stride = width), in the

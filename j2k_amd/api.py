@@ -42,7 +42,8 @@ class Params(C.Structure):
                 ("num_precincts", C.c_uint32), ("precinct_w", C.c_uint32 * 33), ("precinct_h", C.c_uint32 * 33),
                 ("dci_profile", C.c_uint32), ("max_cs_size", C.c_uint32), ("max_comp_size", C.c_uint32),
                 ("cblk_style", C.c_uint32),
-                ("comp_sub_x", C.c_uint32 * 4), ("comp_sub_y", C.c_uint32 * 4), ("rgb_to_sycc", C.c_uint32)]
+                ("comp_sub_x", C.c_uint32 * 4), ("comp_sub_y", C.c_uint32 * 4), ("rgb_to_sycc", C.c_uint32),
+                ("rgb_to_xyz", C.c_uint32)]
 
 
 class Plane(C.Structure):
@@ -94,7 +95,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_tiles", "j2k_hip_device_count", "j2k_hip_encode_batch",
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
-           "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
+           "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_xyz_tables", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
            "j2k_hip_stage_t1_styled", "j2k_hip_stage_transform",
            "j2k_hip_stage_rate", "j2k_hip_stage_gather", "j2k_hip_stage_pack_offsets",
            "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_t1_decode_styled", "j2k_hip_stage_decode_output",
@@ -225,6 +226,8 @@ def load_library():
     L.j2k_hip_main_header.argtypes = [C.POINTER(Params), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.POINTER(C.c_uint32)]
     L.j2k_hip_file_header.argtypes = [C.POINTER(Params), C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    if hasattr(L, "j2k_hip_xyz_tables"):  # (an earlier build loaded through J2K_HIP_LIB for an A/B run has none)
+        L.j2k_hip_xyz_tables.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.j2k_hip_stage_frontend.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Plane), C.c_void_p]
     L.j2k_hip_stage_dwt.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
@@ -357,11 +360,12 @@ def make_params(width, height, channels, depth, reversible=True, ycc=False, laye
                 num_resolutions=6, cblk=(64, 64), promote=False, comment="", jp2=False, color_space=0,
                 alpha_channel=-1, alpha_premultiplied=False, icc=None, rates=None, psnr=None, progression=0,
                 pixel_aspect=None, dpi=0.0, precincts=None, dci_profile=0, max_cs_size=0, max_comp_size=0, cblk_style=0,
-                sub=None, rgb_to_sycc=False):
+                sub=None, rgb_to_sycc=False, rgb_to_xyz=0):
     """comment: None -> library default COM, "" -> no COM segment.  jp2/color_space/alpha_channel/icc describe
     the JP2 file wrapper (color_space in OPJ_COLOR_SPACE numbering: 1 sRGB, 2 grey, 3 sYCC).
     sub = [(dx, dy), ...]: the sub-sampling factors of the components (SIZ XRsiz / YRsiz), one pair per channel; rgb_to_sycc:
-    the planes are R, G, B[, A] of the full image and the library makes Y, Cb, Cr[, A] at those factors."""
+    the planes are R, G, B[, A] of the full image and the library makes Y, Cb, Cr[, A] at those factors.  rgb_to_xyz: channels
+    0..2 are R'G'B' (1 sRGB, 2 Rec.709 under a 2.4 power, 3 linear Rec.709) and the library makes cinema X'Y'Z' codes of them."""
     p = Params()
     p.struct_size = C.sizeof(Params)
     p.width, p.height, p.channels, p.depth = width, height, channels, depth
@@ -379,6 +383,7 @@ def make_params(width, height, channels, depth, reversible=True, ycc=False, laye
         for c, (dx, dy) in enumerate(sub):
             p.comp_sub_x[c], p.comp_sub_y[c] = dx, dy
     p.rgb_to_sycc = int(rgb_to_sycc)
+    p.rgb_to_xyz = int(rgb_to_xyz)
     p.cblk_style = cblk_style  # COD SPcod code-block style: 1 bypass, 2 reset, 4 termall, 16 pterm, 32 segsym, in any combination
     if precincts:  # [(w, h), ...] highest resolution first (OpenJPEG's -c / res_spec semantics)
         p.num_precincts = len(precincts)
@@ -407,6 +412,20 @@ def main_header(params: Params) -> bytes:
     if rc != 0:
         raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
     return buf.raw[:n.value]
+
+
+def xyz_tables(source: int, src_depth: int, dst_depth: int):
+    """The tables of rgb_to_xyz as the kernel gets them (j2k_hip_xyz_tables; no device needed): (lin, thr, matrix) -- lin[v]
+    the linear light of a src_depth-bit sample, thr[c - 1] the threshold of code c of dst_depth bits, matrix 3 x 3, all float32."""
+    L = load_library()
+    if not (1 <= src_depth <= 16 and 1 <= dst_depth <= 16):  # (the sizes of the arrays below)
+        raise J2kHipError(1, "rgb_to_xyz tables: the depths must be 1..16")
+    lin, thr = np.zeros(1 << src_depth, np.float32), np.zeros((1 << dst_depth) - 1, np.float32)
+    m = np.zeros(9, np.float32)
+    rc = L.j2k_hip_xyz_tables(source, src_depth, dst_depth, lin.ctypes.data, thr.ctypes.data if thr.size else None, m.ctypes.data)
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+    return lin, thr, m.reshape(3, 3)
 
 
 def file_header(params: Params, codestream_len: int) -> bytes:

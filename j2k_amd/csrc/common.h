@@ -38,6 +38,9 @@ struct Coding {
     uint32_t cblk_style = 0;
     // encode: the planes are R, G, B[, A] of the full image and the front end makes Y, Cb, Cr[, A] at the components' own sizes
     bool rgb_to_sycc = false;
+    // encode: channels 0..2 are R'G'B' and the front end makes cinema X'Y'Z' code values of them (0 = off; 1 sRGB, 2 Rec.709 under
+    // a 2.4 power, 3 linear Rec.709; xyz_tables.h)
+    uint32_t rgb_to_xyz = 0;
     uint32_t dci_tileparts() const { return dci == 4 ? 6u : (dci == 3 ? 3u : 1u); }
     // per component: sub-sampling factors on the reference grid (decode: whatever SIZ holds; encode: comp_sub_x / _y, 1, 2 or 4, the
     // reference's own encode call never sub-samples), and -- decode only, the encode path writes one unsigned depth -- precision, signedness

@@ -10,7 +10,8 @@
 // of them in one launch.  Sub-sampled components given as planes of their own (comp_sub_x / _y) are read straight too, one
 // launch per component, as the front end runs them.  rgb_to_sycc is the exception: the existing Y Cb Cr front-end kernel runs
 // into the handle's working planes (as for a reversible frame: integers) and the compare reads those -- its decimation keeps
-// one definition.  The decoded image is never downloaded.
+// one definition.  rgb_to_xyz likewise: the X'Y'Z' front-end kernel (its tables on the handle) writes the codes the compare reads.
+// The decoded image is never downloaded.
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -36,7 +37,7 @@ Source source_of(const j2k_hip_params *p)
     q.width = p->width; q.height = p->height; q.channels = p->channels; q.depth = p->depth;
     q.promote_ae16 = p->promote_ae16;
     for (int c = 0; c < 4; ++c) { q.comp_sub_x[c] = p->comp_sub_x[c]; q.comp_sub_y[c] = p->comp_sub_y[c]; }
-    q.rgb_to_sycc = p->rgb_to_sycc;
+    q.rgb_to_sycc = p->rgb_to_sycc; q.rgb_to_xyz = p->rgb_to_xyz;
     q.reversible = 1; q.num_resolutions = 1; q.comment = ""; // (integers out of the Y Cb Cr front end; no limit from a wavelet)
     Source s;
     s.cod = normalise(&q);
@@ -113,11 +114,11 @@ void reduce(j2k_hip_encoder *e, const Source &src, const j2k_hip_plane *dplanes,
     auto decoded = [&](CompareArgs &a, int k, uint32_t c) {
         a.dec[k] = D.plane[c]; a.dec_stride[k] = D.stride[c]; a.dec_sx[k] = D.sx[c]; a.dec_sy[k] = D.sy[c]; a.slot[k] = (int)c;
     };
-    if (cod.rgb_to_sycc) {
-        // Y, Cb, Cr[, A] by the front end's own kernel into the working planes; components of one grid share a launch
+    if (cod.rgb_to_sycc || cod.rgb_to_xyz) {
+        // Y, Cb, Cr[, A] -- or X', Y', Z'[, A] -- by the front end's own kernel into the working planes; components of one grid share a launch
         const PlaneLayout lay = plane_layout(cod, 0, 0, (int)cod.width, (int)cod.height);
         e->P.ensure(lay.frame_elems * sizeof(int32_t));
-        run_frontend(cod, fa, e->P.as<int32_t>(), lay.comp_off, lay.stride, s);
+        run_frontend(e, cod, fa, e->P.as<int32_t>(), lay.comp_off, lay.stride, s);
         HIP_CHECK(hipGetLastError());
         bool done[4] = {false, false, false, false};
         for (uint32_t c = 0; c < cod.ncomp; ++c) {

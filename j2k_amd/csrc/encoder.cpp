@@ -26,6 +26,7 @@
 #include <condition_variable>
 #include <functional>
 #include <future>
+#include <limits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,6 +47,7 @@
 #include "cblk_style.h"
 #include "handle.h"
 #include "rate_device.h"
+#include "xyz_tables.h"
 
 using namespace j2k_hip;
 
@@ -328,6 +330,7 @@ bool j2k_hip::fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tun
     bool same_depth = true;
     for (uint32_t c = 1; c < cod.ncomp; ++c) same_depth = same_depth && fa.src_depth[c] == fa.src_depth[0];
     if (cod.subsampled() || cod.rgb_to_sycc) return false; // (the fused kernel keeps its contract: components of one size, straight from the samples)
+    if (cod.rgb_to_xyz) return false; // (... and no colour conversion but the RCT / ICT: X'Y'Z' is made by the front end's own pass)
     for (uint32_t c = 0; c < cod.ncomp; ++c)
         if (fa.sample_bytes[c] == 4) return false; // (... and integer samples: a float world is quantised by the front end's own pass)
     return !tn.no_fuse && cod.levels() >= 1 && fa.interleaved && same_depth && (cod.ncomp == 1 || cod.ncomp == 3 || cod.ncomp == 4);
@@ -337,10 +340,40 @@ bool j2k_hip::fuse_frontend(const Coding &cod, const FrontendArgs &fa, const Tun
 // channel views (make_frontend_args), its dst_x0 / dst_y0 the planes' origin.  Components of one size: one launch of
 // frontend_kernel.  rgb_to_sycc: the channels are R, G, B[, A] of the whole image, one launch of the Y Cb Cr kernel writes every
 // component at its own size.  Sub-sampled planes given as they are: every component is a frame of its own -- one launch each.
-void j2k_hip::run_frontend(const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t comp_off[4], size_t S, hipStream_t s)
+namespace {
+
+// A table of the X'Y'Z' front end on the device: the handle's copy, made and uploaded on s where the handle has none yet
+// (source 0: the thresholds of destination depth `depth`, padded with +infinity to a multiple of four words).
+const float *xyz_device_table(j2k_hip_encoder *e, uint32_t source, uint32_t depth, hipStream_t s)
+{
+    for (const auto &t : e->xyz_tables)
+        if (t->source == source && t->depth == depth) return t->dev.as<float>();
+    auto t = std::make_unique<j2k_hip_encoder::XyzTable>();
+    t->source = source; t->depth = depth;
+    if (source) t->host = xyz_lin_table(source, depth);
+    else {
+        t->host = xyz_thr_table(depth);
+        t->host.resize(std::max<size_t>((size_t)1 << depth, 4), std::numeric_limits<float>::infinity());
+    }
+    t->dev.ensure(t->host.size() * sizeof(float));
+    HIP_CHECK(hipMemcpyAsync(t->dev.p, t->host.data(), t->host.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    e->xyz_tables.push_back(std::move(t));
+    return e->xyz_tables.back()->dev.as<float>();
+}
+
+} // namespace
+
+void j2k_hip::run_frontend(j2k_hip_encoder *e, const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t comp_off[4], size_t S, hipStream_t s)
 {
     fa.dst_stride = (long long)S;
     for (uint32_t c = 0; c < cod.ncomp; ++c) fa.dst[c] = dst + comp_off[c];
+    if (cod.rgb_to_xyz) {
+        for (int c = 0; c < 3; ++c) fa.xyz_lin[c] = xyz_device_table(e, cod.rgb_to_xyz, (uint32_t)fa.src_depth[c], s);
+        fa.xyz_thr = xyz_device_table(e, 0, cod.prec, s);
+        xyz_matrix(fa.xyz_m);
+        launch_frontend_xyz(fa, s);
+        return;
+    }
     if (cod.rgb_to_sycc) { launch_frontend_sycc(fa, cod.cdx[1], cod.cdy[1], s); return; }
     if (!cod.subsampled()) { launch_frontend(fa, s); return; }
     for (uint32_t c = 0; c < cod.ncomp; ++c) {
@@ -605,7 +638,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     FrontendArgs fa = f == 0 ? fa0 : make_frontend_args(cod, dplanes, x0, y0, x1, y1);
     if (!fused) {
         fa.dst_x0 = x0; fa.dst_y0 = y0;
-        run_frontend(cod, fa, reinterpret_cast<int32_t *>(e->P.as<uint8_t>() + f * plane_bytes), e->comp_off, S, s);
+        run_frontend(e, cod, fa, reinterpret_cast<int32_t *>(e->P.as<uint8_t>() + f * plane_bytes), e->comp_off, S, s);
     }
     if (f == 0) e->last_fa = fa;
     if (f == 0) HIP_CHECK(hipEventRecord(e->ev[EV_FRONT], s));
@@ -997,7 +1030,7 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     const int NL = (int)cod.levels();
     // (a code-block style: its coder is not the gated two-wave kernel this path is built around)
     if (tn.bands < 0 || NL < 1 || tn.no_fuse || cod.rate_control() || cod.dci || cod.cblk_style || g.cblks.empty()) return false;
-    if (cod.subsampled() || cod.rgb_to_sycc) return false; // (components of their own sizes run the unfused path, in one piece)
+    if (cod.subsampled() || cod.rgb_to_sycc || cod.rgb_to_xyz) return false; // (components of their own sizes and X'Y'Z' frames run the unfused path, in one piece)
     // Other encode calls in progress on the device (a host that renders on several threads, or pipelines handles with _begin /
     // _end): their frames overlap as wholes -- one frame's upload beside another's coder chains -- and ten more coder launches
     // per frame only get in each other's way (three handles from one thread: 31 -> 50 ms per frame).  The bands are for the call
@@ -1490,6 +1523,7 @@ void j2k_hip_destroy(j2k_hip_encoder *e)
     for (auto &v : e->stage_done) if (v) (void)hipEventDestroy(v);
     for (auto &v : e->stage_dl) if (v) (void)hipEventDestroy(v);
     for (auto &b : e->h_stage_cs) b.release();
+    e->xyz_tables.clear(); // (the streams are drained: no upload of a table is in flight)
     DeviceShared &dev = g_dev[(e->device >= 0 && e->device < kMaxDevices) ? e->device : 0];
     if (e->k1_done) {
         std::lock_guard<std::mutex> lk(dev.dense);
@@ -1755,6 +1789,22 @@ int j2k_hip_file_header(const j2k_hip_params *params, uint64_t codestream_len, v
             if (h.size() > cap) return J2K_HIP_ERR_OVERFLOW;
             if (!h.empty()) std::memcpy(out, h.data(), h.size());
         }
+        return J2K_HIP_OK;
+    } catch (const Error &x) {
+        create_error() = x.what();
+        return x.code;
+    } catch (...) {
+        return J2K_HIP_ERR_PARAM;
+    }
+}
+
+int j2k_hip_xyz_tables(uint32_t source, uint32_t src_depth, uint32_t dst_depth, float *lin, float *thr, float matrix[9])
+{
+    try {
+        if (!xyz_tables_valid(source, src_depth, dst_depth)) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_xyz tables: source must be 1..3, the depths 1..16");
+        if (lin) { const std::vector<float> t = xyz_lin_table(source, src_depth); std::memcpy(lin, t.data(), t.size() * sizeof(float)); }
+        if (thr) { const std::vector<float> t = xyz_thr_table(dst_depth); std::memcpy(thr, t.data(), t.size() * sizeof(float)); }
+        if (matrix) xyz_matrix(matrix);
         return J2K_HIP_OK;
     } catch (const Error &x) {
         create_error() = x.what();

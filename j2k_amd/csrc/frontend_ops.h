@@ -50,20 +50,11 @@ __device__ __forceinline__ int fe_sample(const FrontendArgs &a, int c, unsigned 
     return (int)depth_convert(raw, a.src_depth[c], a.prec);
 }
 
-// raw[c] = sample of codec channel c as stored (a float sample: as quantised, Promote included); out[c] = component value after promote, depth
-// conversion, DC shift and colour transform (int for the reversible path, float otherwise).
+// s[c] = DC-shifted sample of component c; out[c] = the component value after the colour transform (RCT for the reversible
+// path, ICT otherwise) on components 0..2 when a.mct is set: the one text of both transforms (fe_convert, the X'Y'Z' front end).
 template <bool REV, typename T>
-__device__ __forceinline__ void fe_convert(const FrontendArgs &a, const unsigned raw[4], T out[4])
+__device__ __forceinline__ void fe_colour(const FrontendArgs &a, int s[4], T out[4])
 {
-    int s[4] = {0, 0, 0, 0};
-    const int dc = 1 << (a.prec - 1);
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-        if (c < a.ncomp) {
-            unsigned t = raw[c];
-            if (a.promote && a.sample_bytes[c] == 2) t = promote16(t);
-            s[c] = (int)depth_convert(t, a.src_depth[c], a.prec) - dc;
-        }
     if constexpr (REV) {
         if (a.mct) {
             const int r = s[0], g = s[1], b = s[2];
@@ -88,6 +79,23 @@ __device__ __forceinline__ void fe_convert(const FrontendArgs &a, const unsigned
 #pragma unroll
         for (int c = 0; c < 4; ++c) out[c] = f[c];
     }
+}
+
+// raw[c] = sample of codec channel c as stored (a float sample: as quantised, Promote included); out[c] = component value after promote, depth
+// conversion, DC shift and colour transform (int for the reversible path, float otherwise).
+template <bool REV, typename T>
+__device__ __forceinline__ void fe_convert(const FrontendArgs &a, const unsigned raw[4], T out[4])
+{
+    int s[4] = {0, 0, 0, 0};
+    const int dc = 1 << (a.prec - 1);
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+        if (c < a.ncomp) {
+            unsigned t = raw[c];
+            if (a.promote && a.sample_bytes[c] == 2) t = promote16(t);
+            s[c] = (int)depth_convert(t, a.src_depth[c], a.prec) - dc;
+        }
+    fe_colour<REV, T>(a, s, out);
 }
 
 // the samples of codec channels 0..ncomp-1 from one interleaved pixel (After Effects layout)

@@ -129,6 +129,14 @@ Coding normalise(const j2k_hip_params *p)
         if (i >= c.ncomp) { if (sx != 1 || sy != 1) throw Error(J2K_HIP_ERR_PARAM, "comp_sub_x / comp_sub_y: a factor for a channel that does not exist"); continue; }
         c.cdx[i] = (uint8_t)sx; c.cdy[i] = (uint8_t)sy;
     }
+    // cinema colour: R'G'B' -> X'Y'Z' code values in the front end (three full-size components of the image's own grid)
+    if (p->rgb_to_xyz) {
+        if (p->rgb_to_xyz > 3) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_xyz must be 0, 1 (sRGB), 2 (Rec.709 under a 2.4 power) or 3 (linear Rec.709)");
+        if (c.ncomp < 3) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_xyz needs 3 or 4 channels (R, G, B[, A])");
+        if (p->rgb_to_sycc) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_xyz cannot be combined with rgb_to_sycc: one colour conversion per frame");
+        if (c.subsampled()) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_xyz cannot be combined with comp_sub_x / comp_sub_y: every factor must be 1");
+        c.rgb_to_xyz = p->rgb_to_xyz;
+    }
     if (p->rgb_to_sycc > 1) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_sycc must be 0 or 1");
     c.rgb_to_sycc = p->rgb_to_sycc != 0;
     if (c.subsampled() || c.rgb_to_sycc) {
@@ -174,6 +182,7 @@ void refuse_subsampled_tiles(const Coding &cod)
 {
     if (cod.subsampled() || cod.rgb_to_sycc)
         throw Error(J2K_HIP_ERR_PARAM, "comp_sub / rgb_to_sycc: sub-sampled components are not written by the tile-sharded entry points");
+    if (cod.rgb_to_xyz) throw Error(J2K_HIP_ERR_PARAM, "rgb_to_xyz: the X'Y'Z' front end is not run by the tile-sharded entry points");
 }
 
 // L2 norms of the synthesis basis vectors, as tabulated for the 5/3 and 9/7 kernels (used by

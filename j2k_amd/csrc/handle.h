@@ -207,6 +207,11 @@ struct j2k_hip_encoder {
     // compare (compare.cpp): the decoded components as dense 16-bit planes, the accumulators, and their host image
     j2k_hip::DevBuf cmp_dec, cmp_acc;
     j2k_hip::PinnedBuf h_cmp;
+    // cinema colour (rgb_to_xyz; xyz_tables.h): the tables a frame needs, uploaded on first use and kept with the handle --
+    // linear light by (source, sample depth), thresholds by destination depth (source = 0).  `host` stays alive while its
+    // upload may still be in flight.
+    struct XyzTable { uint32_t source, depth; std::vector<float> host; j2k_hip::DevBuf dev; };
+    std::vector<std::unique_ptr<XyzTable>> xyz_tables;
 };
 
 namespace j2k_hip {
@@ -218,7 +223,8 @@ PlaneLayout plane_layout(const Coding &cod, int bx0, int by0, int bx1, int by1);
 // ... FrontendArgs from channel views whose `base` pointers are device pointers (checks the views) ...
 FrontendArgs make_frontend_args(const Coding &cod, const j2k_hip_plane *planes, int x0, int y0, int x1, int y1);
 // ... the stand-alone front end of one frame into planes of row stride S words, component c at dst + comp_off[c] ...
-void run_frontend(const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t comp_off[4], size_t S, hipStream_t s);
+// (rgb_to_xyz: the handle's tables, uploaded on s ahead of the launch where they are new)
+void run_frontend(j2k_hip_encoder *e, const Coding &cod, FrontendArgs fa, int32_t *dst, const size_t comp_off[4], size_t S, hipStream_t s);
 // ... and a host frame's rows [y0, y1) into the handle's input arena, queued on s: dplanes[c].base = the device copy of planes[c]'s
 void upload_planes(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_plane *planes, int y0, int y1, j2k_hip_plane dplanes[4], hipStream_t s);
 

@@ -77,6 +77,10 @@ struct FrontendArgs {
     int chan_off[4];
     void *dst[4];        // int32 (reversible) or float planes
     long long dst_stride; // words per row
+    // launch_frontend_xyz only (j2k_hip_params.rgb_to_xyz; null / zero everywhere else): the tables of xyz_tables.h on the device
+    const float *xyz_lin[3]; // per channel R, G, B: 2^src_depth[c] values, linear light of a stored sample
+    const float *xyz_thr;    // max(2^prec, 4) words: the 2^prec - 1 thresholds of codes 1 .. top, then +infinity; 16-byte aligned
+    float xyz_m[9];          // R G B -> X Y Z, row by row
 };
 void launch_frontend(const FrontendArgs &a, hipStream_t s);
 // RGB -> Y Cb Cr with chroma decimation (j2k_hip_params.rgb_to_sycc): the channels are R, G, B[, A] of the whole image
@@ -84,6 +88,10 @@ void launch_frontend(const FrontendArgs &a, hipStream_t s);
 // (Cb, Cr) ceil(width / sub_x) x ceil(y1 / sub_y), all at dst_stride (even) words per row, DC-shifted; (sub_x, sub_y) one of
 // (1,1), (2,1), (2,2).  mct is ignored.
 void launch_frontend_sycc(const FrontendArgs &a, int sub_x, int sub_y, hipStream_t s);
+// R'G'B' -> X'Y'Z' code values (j2k_hip_params.rgb_to_xyz): channels 0..2 are R, G, B; a fourth passes through as in
+// launch_frontend.  Same region and destination conventions as launch_frontend; a.xyz_* set.  prec <= 12: the thresholds are
+// searched in LDS, deeper ones in global memory.
+void launch_frontend_xyz(const FrontendArgs &a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Compare (compare.hip; include/j2k_hip.h: j2k_hip_compare): error sums of decoded samples against the source samples the

@@ -124,11 +124,11 @@ int j2k_hip_stage_frontend(j2k_hip_encoder *e, const j2k_hip_params *params, con
         HIP_CHECK(hipSetDevice(e->device));
         const Coding cod = normalise(params);
         FrontendArgs fa = make_frontend_args(cod, planes_device, 0, 0, (int)cod.width, (int)cod.height);
-        if (cod.subsampled() || cod.rgb_to_sycc) {
-            // components of their own sizes: into planes of a common, aligned row stride as an encode has them, then dense to d_out
+        if (cod.subsampled() || cod.rgb_to_sycc || cod.rgb_to_xyz) {
+            // components of their own sizes, and X'Y'Z' (run_frontend holds its tables): into planes of a common, aligned row stride as an encode has them, then dense to d_out
             const PlaneLayout lay = plane_layout(cod, 0, 0, (int)cod.width, (int)cod.height);
             e->P.ensure(lay.frame_elems * sizeof(int32_t));
-            run_frontend(cod, fa, e->P.as<int32_t>(), lay.comp_off, lay.stride, e->stream);
+            run_frontend(e, cod, fa, e->P.as<int32_t>(), lay.comp_off, lay.stride, e->stream);
             HIP_CHECK(hipGetLastError());
             uint8_t *out = static_cast<uint8_t *>(d_out);
             for (uint32_t c = 0; c < cod.ncomp; ++c) {
@@ -250,7 +250,7 @@ int j2k_hip_stage_transform(j2k_hip_encoder *e, const j2k_hip_params *params, co
         if (NL >= 2) { e->Q.ensure(plane_bytes); HIP_CHECK(hipMemsetAsync(e->Q.p, 0xA5, plane_bytes, s)); }
         if (!fused) {
             fa.dst_x0 = x0; fa.dst_y0 = y0;
-            run_frontend(cod, fa, e->P.as<int32_t>(), e->comp_off, S, s);
+            run_frontend(e, cod, fa, e->P.as<int32_t>(), e->comp_off, S, s);
         }
         for (int l = 0; l < NL; ++l) {
             const std::vector<int> &b = bounds[(size_t)l];

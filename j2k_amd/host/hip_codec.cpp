@@ -363,6 +363,11 @@ bool map_frame(HipCodec::Mode mode, unsigned options, const FileInfo &info, cons
     }
 
     CompressionMethod method = info.settings.method;
+    // CinemaXYZ: a cinema frame of three channels inside the largest container is written as 12-bit X'Y'Z' code values made from
+    // the world's R'G'B' (sRGB) by the front end, whatever the world's depth -- the transform is the depth conversion
+    const bool xyz = mode == HipCodec::HonourSettings && (options & HipCodec::CinemaXYZ) && method == CINEMA && buffer.channels == 3 &&
+                     info.width <= 4096 && info.height <= 2160;
+    if (xyz) { p.rgb_to_xyz = 1; p.depth = 12; }
     if (mode == HipCodec::HonourSettings && method == CINEMA) {
         // settings.method == CINEMA (aftereffects/j2k.cpp:639-646, :817-830): fileSize is then the budget of one frame
         // in KiB (the DCI data rate divided by the frame rate).  Frames beyond 4096 x 2160 fall back to lossless like
@@ -374,7 +379,7 @@ bool map_frame(HipCodec::Mode mode, unsigned options, const FileInfo &info, cons
         // the profile flag (Rsiz 0, one tile-part), cut to the budget by the rate allocation.
         const bool k4 = info.settings.dciProfile == DCI_4K;
         if (info.width > 4096 || info.height > 2160) { method = LOSSLESS; p.reversible = 1; }
-        else if (buffer.channels == 3 && info.depth == 12 && info.width <= (k4 ? 4096u : 2048u) && info.height <= (k4 ? 2160u : 1080u)) {
+        else if (buffer.channels == 3 && p.depth == 12 && info.width <= (k4 ? 4096u : 2048u) && info.height <= (k4 ? 2160u : 1080u)) {
             p.dci_profile = k4 ? 4 : 3;
             p.num_resolutions = k4 ? 7 : 6;
             while (p.num_resolutions > 1 && ((info.width >> (p.num_resolutions - 1)) == 0 || (info.height >> (p.num_resolutions - 1)) == 0)) --p.num_resolutions;
@@ -398,7 +403,7 @@ bool map_frame(HipCodec::Mode mode, unsigned options, const FileInfo &info, cons
         // its WriteFile never hands it to OpenJPEG (:707).  Expressed the way OpenJPEG takes targets: one
         // compression ratio per layer (tcp_rates, cp_disto_alloc); the last layer meets the file size, every
         // earlier layer halves the bytes of the next one.
-        const double raw = (double)info.width * info.height * buffer.channels * info.depth / 8.0;
+        const double raw = (double)info.width * info.height * buffer.channels * p.depth / 8.0;
         const double final_ratio = raw / ((double)info.settings.fileSize * 1024.0);
         unsigned L = p.layers ? p.layers : 1;
         if (L > J2K_CODEC_MAX_LAYERS) L = J2K_CODEC_MAX_LAYERS;
@@ -425,13 +430,17 @@ bool map_frame(HipCodec::Mode mode, unsigned options, const FileInfo &info, cons
         p.promote_ae16 = all16 ? 1 : 0;
     }
 
-    if (mode == HipCodec::HonourSettings && (options & (HipCodec::Chroma422 | HipCodec::Chroma420)) && buffer.channels >= 3 && !p.dci_profile) {
+    if (mode == HipCodec::HonourSettings && (options & (HipCodec::Chroma422 | HipCodec::Chroma420)) && buffer.channels >= 3 && !p.dci_profile && !xyz) {
         // Y Cb Cr with sub-sampled chroma out of the world's R, G, B: the front end converts and decimates (j2k_hip.h)
         p.rgb_to_sycc = 1; p.ycc = 0;
         p.comp_sub_x[1] = p.comp_sub_x[2] = 2;
         p.comp_sub_y[1] = p.comp_sub_y[2] = (options & HipCodec::Chroma420) ? 2 : 1;
         p.color_space = J2K_HIP_CS_SYCC; // (reaches the file with the JP2 wrapper only)
         p.icc_profile = NULL; p.icc_profile_len = 0; // (a profile of the RGB world does not describe Y Cb Cr)
+    }
+    if (xyz) { // (X'Y'Z' is no enumerated colour space of the JP2 wrapper, and a profile of the R'G'B' world does not describe it)
+        p.color_space = J2K_HIP_CS_UNSPECIFIED;
+        p.icc_profile = NULL; p.icc_profile_len = 0;
     }
     return true;
 }

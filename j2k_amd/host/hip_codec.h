@@ -31,7 +31,13 @@ class HipCodec : public Codec {
     //   what broadcast and proxy JPEG 2000 use -- made from the world's R, G, B on the GPU while the samples are loaded
     //   (j2k_hip_params.rgb_to_sycc; settings.ycc is not used, an alpha channel stays full size).  The colour space written
     //   is sYCC: with FileInfo.format JP2 the colr box says so and ReadRGBA returns R, G, B again.  Both bits: 4:2:0.
-    enum Options { NoOptions = 0, PromoteAE16 = 1, DemoteAE16 = 2, Chroma422 = 4, Chroma420 = 8 };
+    //   CinemaXYZ (HonourSettings, settings.method CINEMA, buffers of 3 channels of 8-bit, 16-bit or float samples within
+    //   4096 x 2160; ignored otherwise): the world's R, G, B are sRGB and WriteFile writes what a DCI frame holds -- 12-bit
+    //   X'Y'Z' code values, made on the GPU while the samples are loaded (j2k_hip_params.rgb_to_xyz = 1, depth 12 whatever
+    //   FileInfo.depth says: the transform is the depth conversion).  The real profile (dci_profile 3 / 4) is then reached
+    //   for any world depth when the frame fits the container.  No ICC profile is written and the colour space is
+    //   unspecified.  Compare takes the same mapping.  With Chroma422 / Chroma420 as well, CinemaXYZ wins on such a frame.
+    enum Options { NoOptions = 0, PromoteAE16 = 1, DemoteAE16 = 2, Chroma422 = 4, Chroma420 = 8, CinemaXYZ = 16 };
 
     // device: HIP device ordinal, or -1 = the host threads that call this codec take the devices in turn
     explicit HipCodec(Mode mode = ReferenceLiteral, int device = -1, unsigned options = NoOptions);

@@ -303,12 +303,46 @@ long j2k_host_test_write(const unsigned char *frame, unsigned width, unsigned he
                                   out, out_cap, err, err_cap);
 }
 
+} // extern "C"
+
+namespace {
+long write_frame(const unsigned char *frame, unsigned width, unsigned height, long rowbytes, int pixel_size,
+                 int channels, int depth, int reversible, int ycc, int layers, int tile_size, int honour,
+                 long max_write, int format, int color_space, const void *icc, unsigned long icc_len,
+                 int alpha_kind, unsigned extra_options, unsigned char *out, unsigned long out_cap, char *err, unsigned long err_cap);
+}
+
+extern "C" {
+
 // Same with the file-level fields of FileInfo: format (j2k::Format), color_space (j2k::ColorSpace), ICC
 // profile, alpha_kind (j2k::Alpha, or -1 = STRAIGHT for 4 channels / NO_ALPHA otherwise).
 long j2k_host_test_write_ex(const unsigned char *frame, unsigned width, unsigned height, long rowbytes, int pixel_size,
                             int channels, int depth, int reversible, int ycc, int layers, int tile_size, int honour,
                             long max_write, int format, int color_space, const void *icc, unsigned long icc_len,
                             int alpha_kind, unsigned char *out, unsigned long out_cap, char *err, unsigned long err_cap)
+{
+    return write_frame(frame, width, height, rowbytes, pixel_size, channels, depth, reversible, ycc, layers, tile_size, honour, max_write,
+                       format, color_space, icc, icc_len, alpha_kind, 0u, out, out_cap, err, err_cap);
+}
+
+// j2k_host_test_write with HipCodec options given by the caller (HipCodec::Options bits, e.g. CinemaXYZ = 16) on top of the
+// environment's knobs.
+long j2k_host_test_write_options(const unsigned char *frame, unsigned width, unsigned height, long rowbytes, int pixel_size,
+                                 int channels, int depth, int reversible, int ycc, int layers, int tile_size, int honour,
+                                 unsigned options, unsigned char *out, unsigned long out_cap, char *err, unsigned long err_cap)
+{
+    return write_frame(frame, width, height, rowbytes, pixel_size, channels, depth, reversible, ycc, layers, tile_size, honour, -1,
+                       j2k::UNKNOWN_FORMAT, j2k::UNKNOWN_COLOR_SPACE, NULL, 0, -1, options, out, out_cap, err, err_cap);
+}
+
+} // extern "C"
+
+namespace {
+
+long write_frame(const unsigned char *frame, unsigned width, unsigned height, long rowbytes, int pixel_size,
+                 int channels, int depth, int reversible, int ycc, int layers, int tile_size, int honour,
+                 long max_write, int format, int color_space, const void *icc, unsigned long icc_len,
+                 int alpha_kind, unsigned extra_options, unsigned char *out, unsigned long out_cap, char *err, unsigned long err_cap)
 {
     using namespace j2k;
     // WorldToBuffer: channel i of (A,R,G,B) starts at byte i*pixelSize
@@ -356,7 +390,7 @@ long j2k_host_test_write_ex(const unsigned char *frame, unsigned width, unsigned
     MemoryOutputFile file;
     if (max_write >= 0) file.max_write = (size_t)max_write;
     const bool promote = std::getenv("J2K_HOST_TEST_PROMOTE") != NULL; // test knob: the world holds 15+1-bit samples
-    unsigned options = promote ? HipCodec::PromoteAE16 : HipCodec::NoOptions;
+    unsigned options = (promote ? HipCodec::PromoteAE16 : HipCodec::NoOptions) | extra_options;
     if (const char *ch = std::getenv("J2K_HOST_TEST_CHROMA")) // test knob: 422 | 420 -> HipCodec::Chroma422 / Chroma420
         options |= std::atoi(ch) == 420 ? HipCodec::Chroma420 : (std::atoi(ch) == 422 ? HipCodec::Chroma422 : 0u);
     HipCodec hip(honour ? HipCodec::HonourSettings : HipCodec::ReferenceLiteral, -1, options);
@@ -374,6 +408,10 @@ long j2k_host_test_write_ex(const unsigned char *frame, unsigned width, unsigned
     if (out && file.data.size() <= out_cap) std::memcpy(out, file.data.data(), file.data.size());
     return (long)file.data.size();
 }
+
+} // namespace
+
+extern "C" {
 
 // HipCodec::Compare of `file` against the A,R,G,B world `frame` (as in j2k_host_test_write: HonourSettings, the PROMOTE and
 // CHROMA knobs, FileInfo of width x height x channels at `depth` bits; the coding settings do not matter).  ints_out = 7 values
