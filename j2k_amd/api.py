@@ -990,12 +990,13 @@ class Encoder:
         return [d.as_dict() for d in diffs]
 
     # -- stages -----------------------------------------------------------------------------------
-    def stage_frontend(self, frame: np.ndarray, layout: dict, params: Params) -> np.ndarray:
+    def stage_frontend(self, frame: np.ndarray, layout: dict, params: Params, depth_bits: int | None = None) -> np.ndarray:
+        """j2k_hip_stage_frontend of an AE frame; depth_bits: Channel.depth of its samples (default: what the layout says)."""
         d_in = self.upload(frame)
         n = params.channels * params.width * params.height
         d_out = self.malloc(4 * n)
         try:
-            planes = planes_from_layout(d_in, layout, params.channels)
+            planes = planes_from_layout(d_in, layout, params.channels, depth_bits)
             self._check(self.L.j2k_hip_stage_frontend(self.h, C.byref(params), planes, d_out))
             raw = self.d2h(d_out, 4 * n)
         finally:

@@ -25,6 +25,7 @@ from collections import OrderedDict, namedtuple
 
 import numpy as np
 
+import depth_cases
 from j2k_amd import synth
 
 # kernels.h: the defaults every test restores
@@ -43,14 +44,8 @@ def kid(kn: dict) -> str:
 
 # ------------------------------------------------------------------------------------------------ inputs
 def convert(v, src_depth, prec):
-    """CopyChannel in numpy: right shift, or left shift with bit replication (src_depth >= 8, shift <= src_depth)."""
-    s = prec - src_depth
-    if s == 0:
-        return v
-    if s < 0:
-        return v >> -s
-    assert src_depth >= 8 and s <= src_depth
-    return (v << s) | (v >> (src_depth - s))
+    """CopyChannel in numpy, any pair of depths: the test tree's one copy of it (depth_cases.convert)."""
+    return depth_cases.convert(v, src_depth, prec)
 
 
 def promote(v):
