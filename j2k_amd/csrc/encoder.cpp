@@ -720,6 +720,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     ta.yield_word = (dwt_word && tn.mq_yield && tn.overlap) ? dwt_word + 32 : nullptr;
     const bool rate_control = cod.rate_control();
     ta.want_dist = rate_control ? 1 : 0; // per-pass distortion sums: only the rate control needs them
+    ta.want_rates = rate_control ? 1 : 0; // and the two-wave coder's per-pass byte counts (a styled frame's come from the other coder)
     {
         // The MQ coder is a long serial chain per block that occupies <1 wave per SIMD, the context
         // modeller is issue-bound: run them side by side.  Blocks are cut into groups (packet order
@@ -1149,6 +1150,7 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     t1_arena_args(e, tt, ta);
     ta.mq_prio = tn.mq_prio ? 3 : 0;
     ta.sparse = tn.t1_sparse;
+    ta.want_rates = 0; // (a band-pipelined call never runs under rate control: no per-pass byte counts)
     ta.gate_groups = e->gate_groups.as<T1Args::GateGroup>(); ta.gate_group_of = e->gate_group_of.as<unsigned>();
     ta.gate_ready = gate_ready; ta.gate_done = gate_done; ta.gate_abort = gate_abort;
     ta.gate_budget = 1u << 21; // polls of ~4 us: eight seconds, then the workgroup gives up (error 4)

@@ -189,6 +189,7 @@ struct T1Args {
     int first;
     int reversible;
     int want_dist;                      // also produce pass_nmsedec (rate control); 0 = skip that work
+    int want_rates;                     // t1_mq2: also produce pass_rate (rate control, the stage hook on request); 0 = the coder keeps no per-pass counts
     int mq_prio;                        // issue priority of the MQ coder waves: 0 = as launched, 1..3 = s_setprio level (the knob mq_prio = 1 asks for 3)
     int model_prio;                     // the same for the modeller's waves (0 everywhere but in a band-pipelined call's last stages)
     int sparse;                         // t1_model: the sample-wise path of sparse significance / cleanup passes (the knob t1_sparse)

@@ -69,6 +69,7 @@ static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uin
         ta.coef = d_coef; ta.stride = stride; ta.blks = e->blks.as<CblkDev>(); ta.nblks = (int)nb; ta.reversible = reversible;
         t1_arena_args(e, tt, ta);
         ta.want_dist = pass_dist != nullptr; // the distortion sums cost LDS and issue slots: only on request
+        ta.want_rates = pass_rate || pass_dist; // the coder's per-pass byte counts: whenever the pass tables are read back
         ta.sparse = tuning().t1_sparse;
         ta.style = cblk_style;
 #ifdef J2K_T1_COUNTERS

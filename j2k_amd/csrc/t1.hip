@@ -137,6 +137,39 @@ struct PackSel {
 };
 __constant__ PackSel kPackSel = PackSel();
 
+// Two bit-planes' row nibbles of a stripe as decision-byte bits at once: entry a | b << 4 holds bit r of a at bit 0 and bit r of
+// b at bit 1 of byte r -- spread4(a) | spread4(b) << 1 without the two multiplies.  The dense stripes take their zero-coding and
+// sign bytes from it two planes at a time, the refinement rounds theirs.  The plain variants of the modeller hold a copy in LDS.
+struct PairTab {
+    unsigned v[256];
+    constexpr PairTab() : v()
+    {
+        for (unsigned e = 0; e < 256; ++e) {
+            unsigned t = 0;
+            for (unsigned r = 0; r < 4; ++r) t |= (((e >> r) & 1u) | (((e >> (4 + r)) & 1u) << 1)) << (8 * r);
+            v[e] = t;
+        }
+    }
+};
+constexpr bool pair_tab_ok()
+{
+    const PairTab t;
+    for (unsigned a = 0; a < 16; ++a)
+        for (unsigned b = 0; b < 16; ++b)
+            if (t.v[a | (b << 4)] != (spread4(a) | (spread4(b) << 1))) return false;
+    return true;
+}
+static_assert(pair_tab_ok(), "PairTab: entry a | b << 4 must be spread4(a) | spread4(b) << 1 for all 256 nibble pairs");
+__constant__ PairTab kPairTab = PairTab();
+// The table's index bytes of one 32-row half for a plane pair (x, y): byte k of `even` is the entry number of stripe 2 k, of
+// `odd` that of stripe 2 k + 1 (x's nibble below y's)
+__device__ __forceinline__ void pair_index(unsigned x, unsigned y, unsigned &even, unsigned &odd)
+{
+    constexpr unsigned M = 0x0f0f0f0fu;
+    even = (x & M) | ((y << 4) & ~M);
+    odd = ((x >> 4) & M) | (y & ~M);
+}
+
 // one butterfly stage of the 32 x 32 bit-matrix transpose held in 32 registers (m[p] bit r <- m[r] bit p after the five
 // stages J = 16, 8, 4, 2, 1)
 template <int J, unsigned MASK>
@@ -190,6 +223,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
     // the selector table kPackSel in LDS (with DIST the distortion window leaves no room for its 2 KiB at 7 waves per
     // SIMD: that variant reads it from constant memory)
     __shared__ u64 sel_tab[DIST ? 1 : 256];
+    // PairTab in LDS beside it, for the same reason not with DIST: that variant keeps the multiplies.  (Read per lane from
+    // constant memory the table cost more than it saved: every look-up is a gather over up to sixteen cache lines.)
+    constexpr bool kPairTabs = !DIST;
+    __shared__ unsigned pair_tab[kPairTabs ? 256 : 1];
+    const auto pair_entry = [&](unsigned e) -> unsigned { return pair_tab[e]; };
 
     const int b = a.first + (int)blockIdx.x;
     const int lane = threadIdx.x;
@@ -201,7 +239,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
     // the stage starts zeroed and stays so beyond what is pending (decisions are ORed into it)
     for (int i = lane; i < kStageBytes / 16; i += 64) reinterpret_cast<uint4 *>(stage)[i] = make_uint4(0, 0, 0, 0);
     if constexpr (!DIST)
-        for (int e = lane; e < 256; e += 64) sel_tab[e] = kPackSel.v[e];
+        for (int e = lane; e < 256; e += 64) { sel_tab[e] = kPackSel.v[e]; pair_tab[e] = kPairTab.v[e]; }
 
     // ---- A7: load the block (coalesced rows), scale to sign-magnitude with 6 fractional bits
     u64 chi = 0;
@@ -328,9 +366,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
         fill += total;
         if (fill - flushed >= kFlush) {
             __builtin_amdgcn_wave_barrier();
-            const uint4 v = *reinterpret_cast<const uint4 *>(&stage[lane * 16]);
-            const uint4 r = *reinterpret_cast<const uint4 *>(&stage[kFlush + min(lane, 39) * 16]); // 40 x 16 B cover the burst
-            if (flushed + kFlush <= symcap) *reinterpret_cast<uint4 *>(symout + flushed + lane * 16) = v;
+            // (the lane number through an empty asm: its multiples and the lane's address in the stream are formed here, once per
+            //  flush, and not kept in four registers through every loop of the kernel)
+            int ln = lane;
+            asm volatile("" : "+v"(ln));
+            const uint4 v = *reinterpret_cast<const uint4 *>(&stage[ln * 16]);
+            const uint4 r = *reinterpret_cast<const uint4 *>(&stage[kFlush + min(ln, 39) * 16]); // 40 x 16 B cover the burst
+            if (flushed + kFlush <= symcap) *reinterpret_cast<uint4 *>(symout + flushed + ln * 16) = v;
             else overflow = true;
             flushed += kFlush;
             __builtin_amdgcn_wave_barrier();
@@ -339,10 +381,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
             unsigned z;
             asm volatile("v_mov_b32 %0, 0" : "=v"(z));
             const uint4 zero = make_uint4(z, z, z, z);
-            if (lane < 40) {
-                *reinterpret_cast<uint4 *>(&stage[lane * 16]) = r;
-                *reinterpret_cast<uint4 *>(&stage[kFlush + lane * 16]) = zero;
-            } else *reinterpret_cast<uint4 *>(&stage[lane * 16]) = zero;
+            if (ln < 40) {
+                *reinterpret_cast<uint4 *>(&stage[ln * 16]) = r;
+                *reinterpret_cast<uint4 *>(&stage[kFlush + ln * 16]) = zero;
+            } else *reinterpret_cast<uint4 *>(&stage[ln * 16]) = zero;
             __builtin_amdgcn_wave_barrier();
         }
     };
@@ -487,6 +529,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                     auto hf = [&](u64 m) { return half ? (unsigned)(m >> 32) : (unsigned)m; };
                     const unsigned refh = hf(ref64), nbh = hf(nb64), muh = hf(mu), bitsh = hf(bits);
                     const int rows = min(4 * ns_eff - 32 * half, 32);
+                    // a round's two stripes are an even and an odd one: byte sl / 8 of the two index words
+                    unsigned bn[2] = {0, 0};
+                    if constexpr (kPairTabs) pair_index(bitsh, nbh, bn[0], bn[1]);
                     for (int sl = 0; sl < rows; sl += 8) {
                         const unsigned ref8 = __builtin_amdgcn_ubfe(refh, (unsigned)sl, 8u); // rows of both stripes refined in this pass
                         if (!__any(ref8 != 0)) { DCNT(5); continue; }
@@ -498,8 +543,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                             const unsigned ref4 = k ? ref8 >> 4 : ref8 & 0xfu;
                             const unsigned at = (unsigned)(sl + 4 * k);
                             const unsigned sel = (unsigned)(DIST ? kPackSel.v[ref4] : sel_tab[ref4]);
-                            const unsigned W = 0x1c1c1c1cu + (spread4(__builtin_amdgcn_ubfe(nbh, at, 4u)) << 1) + (spread4(__builtin_amdgcn_ubfe(muh, at, 4u)) << 2) +
-                                               spread4(__builtin_amdgcn_ubfe(bitsh, at, 4u));
+                            unsigned W;
+                            if constexpr (kPairTabs)
+                                W = 0x1c1c1c1cu + pair_entry(__builtin_amdgcn_ubfe(bn[k], (unsigned)sl, 8u)) + (pair_entry(__builtin_amdgcn_ubfe(muh, at, 4u)) << 2);
+                            else
+                                W = 0x1c1c1c1cu + (spread4(__builtin_amdgcn_ubfe(nbh, at, 4u)) << 1) + (spread4(__builtin_amdgcn_ubfe(muh, at, 4u)) << 2) +
+                                    spread4(__builtin_amdgcn_ubfe(bitsh, at, 4u));
                             pk[k] = __builtin_amdgcn_perm(0u, W, sel);
                             cnt[k] = (unsigned)__builtin_popcount(ref4);
                         }
@@ -735,6 +784,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                     continue;
                 }
                 DCNT(pt == 0 ? 12 : 13);
+                // PairTab's index bytes of this half for the zero-coding bytes, even and odd stripes: (bit, zb0) and (zb1, zb2).  Formed
+                // here, behind the sample-wise path, and only for a half with a stripe that is no fill: neither pays for them.  (The sign
+                // planes keep their form and are indexed stripe by stripe: their four index words as well are more than 72 registers
+                // hold, and pi went to scratch in every pass.  With DIST the stripes keep the multiplies: see kPairTabs.)
+                unsigned zi0e = 0, zi0o = 0, zi1e = 0, zi1o = 0;
+                if (kPairTabs && fills != active) {
+                    pair_index(bitsh, zb0, zi0e, zi0o);
+                    pair_index(zb1, zb2, zi1e, zi1o);
+                }
                 while (active) {
                     const int sl = __builtin_ctz(active) & ~3; // first row of the stripe inside the half
                     active &= active - 1;
@@ -747,7 +805,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                         continue;
                     }
                     DCNT(pt == 0 ? 0 : 2);
-                    const unsigned bits4 = (bitsh >> sl) & 0xfu;
                     const unsigned N = (Nh >> sl) & 0xfu;
                     unsigned Vz = (Vh >> sl) & 0xfu;
                     unsigned pc = 0, rlsym = 0; // run-length prefix of this lane (cleanup): 0, 1 (RL) or 3 (RL, UNI, UNI) decisions
@@ -770,12 +827,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(J2K_MODEL_WA
                     unsigned total;
                     const unsigned base = reserve(cnt, std::integral_constant<int, 10>(), total);
                     unsigned zsym = 0, ssym = 0; // decision bytes of the four rows: zero coding / sign
-                    if (__any(Vz != 0)) // (context << 1) | bit
-                        zsym = (spread4((zb0 >> sl) & 0xfu) << 1) | (spread4((zb1 >> sl) & 0xfu) << 2) | (spread4((zb2 >> sl) & 0xfu) << 3) |
-                               (spread4((zb3 >> sl) & 0xfu) << 4) | spread4(bits4);
-                    if (__any(N != 0))
-                        ssym = 0x12121212u + (spread4((sb0 >> sl) & 0xfu) << 1) + (spread4((sb1 >> sl) & 0xfu) << 2) +
-                               (spread4((sb2 >> sl) & 0xfu) << 3) + spread4((sd >> sl) & 0xfu);
+                    const auto nib = [&](unsigned plane) { return __builtin_amdgcn_ubfe(plane, (unsigned)sl, 4u); };
+                    if constexpr (kPairTabs) {
+                        // The stripe's index byte: byte sl / 8 of the even or the odd word, picked by one v_perm whose selector is formed
+                        // on the scalar unit (bytes 0..3: the second operand, 4..7: the first; 0x0c: a zero byte)
+                        const unsigned pick = 0x0c0c0c00u | ((unsigned)sl >> 3) | ((unsigned)sl & 4u);
+                        if (__any(Vz != 0)) // (context << 1) | bit
+                            zsym = pair_entry(__builtin_amdgcn_perm(zi0o, zi0e, pick)) | (pair_entry(__builtin_amdgcn_perm(zi1o, zi1e, pick)) << 2) |
+                                   (spread4(nib(zb3)) << 4);
+                        if (__any(N != 0))
+                            ssym = 0x12121212u + pair_entry(nib(sd) | (nib(sb0) << 4)) + (pair_entry(nib(sb1) | (nib(sb2) << 4)) << 2);
+                    } else {
+                        if (__any(Vz != 0))
+                            zsym = (spread4(nib(zb0)) << 1) | (spread4(nib(zb1)) << 2) | (spread4(nib(zb2)) << 3) | (spread4(nib(zb3)) << 4) | spread4(nib(bitsh));
+                        if (__any(N != 0))
+                            ssym = 0x12121212u + (spread4(nib(sb0)) << 1) + (spread4(nib(sb1)) << 2) + (spread4(nib(sb2)) << 3) + spread4(nib(sd));
+                    }
                     {
                         // The lane's bytes in coding order, [RL][UNI][UNI] then row by row [ZC][sign], packed in registers:
                         // one v_perm per output word picks the present rows' bytes out of zsym / ssym, the run-length prefix
@@ -859,6 +926,10 @@ __device__ __forceinline__ unsigned ctx_word2(unsigned qe, unsigned idx, unsigne
 #define J2K_MQ2_RING 128
 #endif
 constexpr unsigned kRing = J2K_MQ2_RING;
+// RATES: the consumer also keeps the byte count at the end of every coding pass (pass_rate: rate control, and the stage hook on
+// request).  A plain frame reads none of them: without the parameter the consumer has no pass-end tests, one copy of its
+// decision loop, and neither loads pass_nsym nor stores pass_rate.  Codeword, lengths, flush, errors and gates are the same.
+template <bool RATES>
 __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
 {
     __shared__ unsigned ctxs[19 * 64];
@@ -1040,7 +1111,8 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
         asm("" : "+v"(pos)); // (one register for the pointer: left to itself the compiler forms it a second time for the next store)
     };
     unsigned cur_pass = 0;
-    unsigned next_end = npasses ? pass_nsym[0] : 0xffffffffu;
+    unsigned next_end = 0xffffffffu;
+    if constexpr (RATES) next_end = npasses ? pass_nsym[0] : 0xffffffffu;
     auto close_passes = [&](unsigned i) {
         while (cur_pass < npasses && i == next_end) {
             pass_rate[cur_pass] = (unsigned)(nbytes() + 3);
@@ -1057,7 +1129,8 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
 #endif
         if (c >= 1) {
             const unsigned base = (c - 1) * 16;
-            int rel = (int)min(next_end - base, 64u);
+            int rel = 64;
+            if constexpr (RATES) rel = (int)min(next_end - base, 64u);
             // four decisions; CHECK = a coding pass of some lane ends among them (its byte count is taken then)
             auto four = [&](auto check, const unsigned (&e)[4], const int g) {
                 constexpr bool ENDS = decltype(check)::value;
@@ -1099,13 +1172,17 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
             };
             // the sixteen decisions of the chunk.  Pass ends are looked for group by group: with 64 lanes nearly every chunk has one
             // somewhere, but four groups in five have none, and their decisions go without the test.
-            const bool ends_here = __any(rel <= 16);
+            // (Without RATES there is nothing to look for: one copy of the decisions, no test.)
+            bool ends_here = false;
+            if constexpr (RATES) ends_here = __any(rel <= 16);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const uint4 q = queue[(c - 1) & 1][g][lane];
                 const unsigned e[4] = {q.x, q.y, q.z, q.w};
-                if (ends_here && __any(rel > 4 * g && rel <= 4 * g + 4)) four(std::true_type(), e, g);
-                else four(std::false_type(), e, g);
+                if constexpr (RATES) {
+                    if (ends_here && __any(rel > 4 * g && rel <= 4 * g + 4)) four(std::true_type(), e, g);
+                    else four(std::false_type(), e, g);
+                } else four(std::false_type(), e, g);
             }
             // Codeword bytes leave the stage in 16-byte units, every lane's at once: when some lane has 64 waiting, all lanes send
             // the whole units they have.  (Each lane on its own -- 64 bytes whenever it had them -- ran this code in five chunks
@@ -1149,7 +1226,7 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
     const bool fin = live && npasses;
     const unsigned A = finalA[lane]; // written by the producer before the last barrier
     if (fin) {
-        close_passes(nsym);
+        if constexpr (RATES) close_passes(nsym);
         const unsigned tempc = C + A;
         C |= 0xffffu;
         if (C >= tempc) C -= 0x8000u;
@@ -1166,7 +1243,7 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
             if ((unsigned)(o + 4) <= cb.out_cap) *reinterpret_cast<unsigned *>(out + o) = *reinterpret_cast<const unsigned *>(ostage_b + dbase + (o - flushed));
             else overflow = true;
         }
-        pass_rate[npasses - 1] = (unsigned)nb;
+        if constexpr (RATES) pass_rate[npasses - 1] = (unsigned)nb;
         a.len[b] = (unsigned)nb;
         if (overflow) a.err[0] = 3u;
     } else if (live) {
@@ -1273,7 +1350,8 @@ void launch_t1_mq_gated(const T1Args &a, int group_first, int group_count, hipSt
     if (group_count <= 0 || !a.gate_groups) return;
     T1Args g = a;
     g.first = group_first; // (gated: `first` is the first workgroup's index into gate_groups / gate_ready)
-    hipLaunchKernelGGL(t1_mq2_kernel, dim3((unsigned)group_count), dim3(128), 0, s, g);
+    if (g.want_rates) hipLaunchKernelGGL(t1_mq2_kernel<true>, dim3((unsigned)group_count), dim3(128), 0, s, g);
+    else hipLaunchKernelGGL(t1_mq2_kernel<false>, dim3((unsigned)group_count), dim3(128), 0, s, g);
 }
 
 void launch_t1_mq(const T1Args &a, hipStream_t s)
@@ -1281,7 +1359,9 @@ void launch_t1_mq(const T1Args &a, hipStream_t s)
     const int n = a.nblks - a.first;
     if (n <= 0) return;
     if (a.style) { launch_t1_mq_styled(a, s); return; } // (a termination at a pass boundary needs interval and code register together)
-    hipLaunchKernelGGL(t1_mq2_kernel, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, s, a);
+    // want_rates: per-pass byte counts (rate control, the stage hook on request); a plain frame's consumer keeps none
+    if (a.want_rates) hipLaunchKernelGGL(t1_mq2_kernel<true>, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, s, a);
+    else hipLaunchKernelGGL(t1_mq2_kernel<false>, dim3((unsigned)((n + 63) / 64)), dim3(128), 0, s, a);
 }
 
 } // namespace j2k_hip
