@@ -144,6 +144,15 @@ EXT = {
     "m2_150x130_5comp12_97_tile64_2layers": (150, 130, 5, 12, 94, dict(numres=3, reversible=False, tile=(64, 64), rates=[20.0, 5.0])),
     "ua_200x150_grey8_53_cblk128x32": (200, 150, 1, 8, 70, dict(numres=3, cblk=(128, 32))),  # legal (xcb + ycb <= 12), beyond the 64 x 64 of this decoder
     "u9_256_rgb8_53_precincts_lrcp_tile100": (256, 256, 3, 8, 69, dict(numres=4, mct=True, precincts=[(64, 64), (64, 64), (32, 32), (16, 16)], tile=(100, 100))),
+    # small precincts and code-blocks under the position-driven orders (tests/small_block_cases.py; the oracle's encoder takes
+    # precincts with LRCP / RLCP / RPCL only).  They stop at 8-sample precincts: below that libopenjp2 2.4.0's encoder answers
+    # "Cannot encode tile" or "Size of code block data exceeds system limits" for most frames
+    "k1_67x45_rgb8_53_pcrl_prec8_cblk4": (67, 45, 3, 8, 95, dict(numres=3, mct=True, precincts=[(8, 8)], cblk=(4, 4), prog=3)),
+    "k2_67x45_rgb8_53_cprl_prec8_cblk4": (67, 45, 3, 8, 95, dict(numres=3, mct=True, precincts=[(8, 8)], cblk=(4, 4), prog=4)),
+    "k3_67x45_rgb8_53_pcrl_prec16x8_cblk8x4": (67, 45, 3, 8, 96, dict(numres=3, mct=True, precincts=[(16, 8)], cblk=(8, 4), prog=3)),
+    "k4_67x45_rgb8_53_cprl_prec16x8_cblk8x4": (67, 45, 3, 8, 96, dict(numres=3, mct=True, precincts=[(16, 8)], cblk=(8, 4), prog=4)),
+    "k5_67x45_rgb8_53_pcrl_prec32_8_cblk64": (67, 45, 3, 8, 97, dict(numres=3, mct=True, precincts=[(32, 32), (8, 8)], cblk=(64, 64), prog=3)),
+    "k6_67x45_rgb8_53_cprl_prec32_8_cblk64": (67, 45, 3, 8, 97, dict(numres=3, mct=True, precincts=[(32, 32), (8, 8)], cblk=(64, 64), prog=4)),
 }
 
 
