@@ -643,6 +643,19 @@ int j2k_hip_stage_frontend(j2k_hip_encoder *enc, const j2k_hip_params *params,
 int j2k_hip_stage_dwt(j2k_hip_encoder *enc, int reversible, uint32_t width, uint32_t height,
                       uint32_t nplanes, uint32_t levels, uint32_t x0, uint32_t y0, const void *d_in,
                       void *d_out, uint32_t repeat, double *ms);
+/* The region form of j2k_hip_stage_dwt (the mirror of the region form of j2k_hip_stage_idwt, whose j2k_hip_idwt_region it
+ * takes): every plane holds `nregions` sub-rectangles (x, y, w, h), each transformed on its own into a Mallat layout of its
+ * own with its own origin (x0, y0) -- the tiles of a tiled component.  Per level every (plane, region) is one job of the same
+ * launch: sizes, lifting parities and word offsets differ from job to job, and the launch is sized by the largest.  A region
+ * of which nothing is left at a level (a single odd-phase sample is all high-pass) takes no part from there on.  The regions
+ * must be non-empty, lie inside the plane and not overlap, nregions >= 1, levels <= 32, no encode pending on the handle:
+ * J2K_HIP_ERR_PARAM otherwise.  d_in is preserved; d_out receives the coefficients, and the words outside every region are
+ * copied from d_in.  The handle's cached geometry is dropped: the next encode builds it again.
+ * J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
+struct j2k_hip_idwt_region;
+int j2k_hip_stage_dwt_regions(j2k_hip_encoder *enc, int reversible, uint32_t width, uint32_t height,
+                              uint32_t nplanes, uint32_t levels, const struct j2k_hip_idwt_region *regions,
+                              uint32_t nregions, const void *d_in, void *d_out);
 /* A1..A6 as an encode runs them: the front end and every DWT launch of j2k_hip_encode_device for these parameters and
  * channel views (device pointers) -- the same geometry and job tables, the same choice between the fused level-1 kernel and
  * the stand-alone front end, the same launch shapes under the tuning knobs -- and nothing behind them: no Tier-1 launch,

@@ -95,7 +95,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_tiles", "j2k_hip_device_count", "j2k_hip_encode_batch",
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
-           "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_xyz_tables", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
+           "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_xyz_tables", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_dwt_regions", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
            "j2k_hip_stage_t1_styled", "j2k_hip_stage_transform",
            "j2k_hip_stage_rate", "j2k_hip_stage_gather", "j2k_hip_stage_pack_offsets",
            "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_t1_decode_styled", "j2k_hip_stage_decode_output",
@@ -231,6 +231,9 @@ def load_library():
     L.j2k_hip_stage_frontend.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Plane), C.c_void_p]
     L.j2k_hip_stage_dwt.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                     C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
+    if hasattr(L, "j2k_hip_stage_dwt_regions"):  # (an earlier build loaded through J2K_HIP_LIB for an A/B run has none)
+        L.j2k_hip_stage_dwt_regions.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.POINTER(IdwtRegion), C.c_uint32, C.c_void_p, C.c_void_p]
     U32P = C.POINTER(C.c_uint32)
     L.j2k_hip_stage_transform.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Plane), U32P, U32P, C.c_uint32, C.c_int, C.c_void_p]
     L.j2k_hip_stage_t1.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, U32P, U32P, U32P, U32P, U32P,
@@ -1053,6 +1056,27 @@ class Encoder:
             self.free(d_in)
             self.free(d_out)
         return raw.view(dt).reshape(n, h, w), ms.value
+
+    def stage_dwt_regions(self, planes: np.ndarray, levels: int, reversible: bool, regions):
+        """The region form of stage_dwt (j2k_hip_stage_dwt_regions): planes (n, h, w) int32 / float32, regions
+        [(x, y, w, h, x0, y0)] sub-rectangles of every plane, each transformed on its own with its own origin, every
+        (plane, region) a job of the same launch per level.  Returns the planes; words outside every region stay."""
+        dt = np.int32 if reversible else np.float32
+        planes = np.ascontiguousarray(planes, dtype=dt)
+        n, h, w = planes.shape
+        nr = len(regions)
+        rg = (IdwtRegion * max(nr, 1))()
+        for i in range(nr):
+            rg[i].x, rg[i].y, rg[i].w, rg[i].h, rg[i].x0, rg[i].y0 = regions[i]
+        d_in = self.upload(planes)
+        d_out = self.malloc(max(planes.nbytes, 16))
+        try:
+            self._check(self.L.j2k_hip_stage_dwt_regions(self.h, int(reversible), w, h, n, levels, rg, nr, d_in, d_out))
+            raw = self.d2h(d_out, planes.nbytes)
+        finally:
+            self.free(d_in)
+            self.free(d_out)
+        return raw.view(dt).reshape(n, h, w)
 
     def stage_t1(self, coef: np.ndarray, rects, orients, stepsizes, reversible: bool, want_passes: bool = False, style=None):
         """coef: (H, W) int32/float32 plane; rects: list of (x, y, w, h). Returns list of dicts.  style (a code-block style,

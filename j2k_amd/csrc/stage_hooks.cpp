@@ -203,6 +203,69 @@ int j2k_hip_stage_dwt(j2k_hip_encoder *e, int reversible, uint32_t width, uint32
     });
 }
 
+// j2k_hip_stage_dwt with jobs of different sizes, origins and offsets in one launch per level: every (plane, region) is a
+// DwtJob of its own, as every tile-component of a frame is (the mirror of the region form of j2k_hip_stage_idwt).
+int j2k_hip_stage_dwt_regions(j2k_hip_encoder *e, int reversible, uint32_t width, uint32_t height, uint32_t nplanes, uint32_t levels,
+                              const j2k_hip_idwt_region *regions, uint32_t nregions, const void *d_in, void *d_out)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        if (!width || !height || !nplanes || levels > 32 || !d_in || !d_out || !regions || !nregions)
+            throw Error(J2K_HIP_ERR_PARAM, "bad DWT region stage arguments");
+        const j2k_hip_idwt_region *rg = regions;
+        for (uint32_t i = 0; i < nregions; ++i) {
+            if (!rg[i].w || !rg[i].h || (uint64_t)rg[i].x + rg[i].w > width || (uint64_t)rg[i].y + rg[i].h > height ||
+                (uint64_t)rg[i].x0 + rg[i].w > 0x7fffffffu || (uint64_t)rg[i].y0 + rg[i].h > 0x7fffffffu)
+                throw Error(J2K_HIP_ERR_PARAM, "DWT region empty or outside the plane");
+            for (uint32_t j = 0; j < i; ++j)
+                if (rg[i].x < rg[j].x + rg[j].w && rg[j].x < rg[i].x + rg[i].w && rg[i].y < rg[j].y + rg[j].h && rg[j].y < rg[i].y + rg[i].h)
+                    throw Error(J2K_HIP_ERR_PARAM, "DWT regions overlap");
+        }
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        const size_t plane = (size_t)width * height, bytes = plane * nplanes * 4;
+        e->P.ensure(bytes);
+        e->Q.ensure(bytes);
+        std::vector<DwtJob> jobs;
+        std::vector<size_t> first(levels + 1, 0);
+        std::vector<int> mrw(levels, 0), mrh(levels, 0);
+        for (uint32_t l = 0; l < levels; ++l) {
+            first[l] = jobs.size();
+            for (uint32_t c = 0; c < nplanes; ++c)
+                for (uint32_t i = 0; i < nregions; ++i) {
+                    DwtJob j{};
+                    const int ax0 = ceildivpow2((int)rg[i].x0, (int)l), ax1 = ceildivpow2((int)(rg[i].x0 + rg[i].w), (int)l);
+                    const int ay0 = ceildivpow2((int)rg[i].y0, (int)l), ay1 = ceildivpow2((int)(rg[i].y0 + rg[i].h), (int)l);
+                    j.rw = ax1 - ax0; j.rh = ay1 - ay0; j.casx = ax0 & 1; j.casy = ay0 & 1;
+                    if (j.rw <= 0 || j.rh <= 0) continue; // (a single odd-phase sample is all high-pass: nothing is left of it)
+                    j.src_off = j.ll_off = j.z_off = (long long)(c * plane) + (long long)rg[i].y * width + rg[i].x;
+                    jobs.push_back(j); mrw[l] = std::max(mrw[l], j.rw); mrh[l] = std::max(mrh[l], j.rh);
+                }
+        }
+        first[levels] = jobs.size();
+        invalidate_cached_tables(e); // the job table and the planes are overwritten
+        HIP_CHECK(hipMemcpyAsync(d_out, d_in, bytes, hipMemcpyDeviceToDevice, s)); // words outside every region stay
+        if (!jobs.empty()) {
+            e->jobs.ensure(jobs.size() * sizeof(DwtJob));
+            HIP_CHECK(hipMemcpyAsync(e->jobs.p, jobs.data(), jobs.size() * sizeof(DwtJob), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s)); // `jobs` is a pageable host vector
+        }
+        for (uint32_t l = 0; l < levels; ++l) {
+            DwtLevelArgs da{};
+            da.src = l == 0 ? d_in : ((l & 1) ? e->Q.p : e->P.p); da.src_stride = width;
+            const bool last = l == levels - 1;
+            da.ll = last ? d_out : ((l & 1) ? e->P.p : e->Q.p); da.ll_stride = width;
+            da.z = d_out; da.z_stride = width;
+            da.jobs = e->jobs.as<DwtJob>() + first[l]; da.njobs = (int)(first[l + 1] - first[l]);
+            da.max_rw = mrw[l]; da.max_rh = mrh[l]; da.reversible = reversible;
+            launch_dwt_level(da, s);
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 // The front end and the DWT launches of an encode, and nothing behind them: encode_begin's own steps up to the last level
 // (device frames, one frame), with a level optionally launched in pieces over row-pair ranges.
 int j2k_hip_stage_transform(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes_device,

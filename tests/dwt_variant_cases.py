@@ -8,6 +8,8 @@ reference(oracle, case) composes the oracle exactly as test_gpu_parity.py::test_
 Promote in numpy where asked, j2ko_dc_mct), then transforms every tile-component rectangle on its own with the tile's
 origin as the lifting phase and pastes the result back: the dense (ncomp, H, W) array the hook returns.
 
+knobs(), run_hook() and check() are the GPU tests' calls (test_dwt_variants.py, test_dwt_sweep.py): one copy of them.
+
 The launch model (level_launch, fused_launch) repeats the wave-uniform decisions of dwt.hip in a few lines of Python, so
 that the CPU tests can assert that a case still reaches the path its name claims.  It mirrors, by the names in dwt.hip:
   Geo<PAIRS>                    valid pairs 124 / 60, halo lanes 1 / 2
@@ -20,10 +22,12 @@ that the CPU tests can assert that a case still reaches the path its name claims
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from collections import OrderedDict, namedtuple
 
 import numpy as np
+import pytest
 
 import depth_cases
 from j2k_amd import synth
@@ -184,6 +188,42 @@ def difference(case: Case, kn: dict, got: np.ndarray, ref: np.ndarray, extra: st
     return (f"{case.name} [{kid(kn)}] {extra}: {len(bad)} of {g.size} words differ, first at (component {c}, y {y}, x {x}) in tile "
             f"{tiles(case).index(t)} {t}, sub-band {subband(case, (t[0] + origin[0], t[1] + origin[1], t[2] + origin[0], t[3] + origin[1]), x - t[0], y - t[1])}: got {got[c, y, x]!r} (0x{int(g[c, y, x]) & 0xffffffff:08x}), "
             f"reference {ref[c, y, x]!r} (0x{int(r[c, y, x]) & 0xffffffff:08x})")
+
+
+# ------------------------------------------------------------------------------------------------ the GPU tests' calls
+def _api():
+    from j2k_amd import api
+    return api
+
+
+@contextlib.contextmanager
+def knobs(kn: dict):
+    """The tuning knobs of kn for the calls inside, the defaults again behind them."""
+    api = _api()
+    try:
+        for k, v in kn.items():
+            api.tune(k, v)
+        yield
+    finally:
+        for k in kn:
+            api.tune(k, DEFAULTS[k])
+
+
+def run_hook(enc, case, kn, cuts=None, descending=False):
+    api = _api()
+    inp = make_input(case)
+    p = api.make_params(case.w, case.h, case.nc, case.prec, reversible=case.rev, ycc=case.mct, promote=case.promote,
+                        num_resolutions=case.levels + 1, tile_size=case.tile)
+    with knobs(kn):
+        return enc.stage_transform(inp.buf, plane_views(api, inp.chans), p, cuts, descending)
+
+
+def check(oracle, enc, case, kn, cuts=None, descending=False):
+    got = run_hook(enc, case, kn, cuts, descending)
+    extra = "" if cuts is None else f"cuts {cuts} {'descending' if descending else 'ascending'}"
+    msg = difference(case, kn, got, reference(oracle, case), extra)
+    if msg:
+        pytest.fail(msg, pytrace=False)
 
 
 # ------------------------------------------------------------------------------------------------ launch model

@@ -24,13 +24,12 @@ test_level_kernel_cases_... assert this table from the launch model):
 An untiled frame narrower or lower than 2^levels is refused by the encoder, as by the reference: 1 x 40, 40 x 1 and
 their like run as the edge tiles of small tiled frames (dwt_variant_cases.fused_shapes), at even and at odd origins.
 """
-import contextlib
-
 import numpy as np
 import pytest
 
 import dwt_variant_cases as V
 from conftest import golden_case
+from dwt_variant_cases import check, knobs, run_hook  # (shared with test_dwt_sweep.py)
 from j2k_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -47,35 +46,6 @@ def enc():
 def _api():
     from j2k_amd import api
     return api
-
-
-@contextlib.contextmanager
-def knobs(kn: dict):
-    api = _api()
-    try:
-        for k, v in kn.items():
-            api.tune(k, v)
-        yield
-    finally:
-        for k in kn:
-            api.tune(k, V.DEFAULTS[k])
-
-
-def run_hook(enc, case, kn, cuts=None, descending=False):
-    api = _api()
-    inp = V.make_input(case)
-    p = api.make_params(case.w, case.h, case.nc, case.prec, reversible=case.rev, ycc=case.mct, promote=case.promote,
-                        num_resolutions=case.levels + 1, tile_size=case.tile)
-    with knobs(kn):
-        return enc.stage_transform(inp.buf, V.plane_views(api, inp.chans), p, cuts, descending)
-
-
-def check(oracle, enc, case, kn, cuts=None, descending=False):
-    got = run_hook(enc, case, kn, cuts, descending)
-    extra = "" if cuts is None else f"cuts {cuts} {'descending' if descending else 'ascending'}"
-    msg = V.difference(case, kn, got, V.reference(oracle, case), extra)
-    if msg:
-        pytest.fail(msg, pytrace=False)
 
 
 # ------------------------------------------------------------------------------------------------ the fused level-1 kernel

@@ -319,15 +319,21 @@ def test_tiled_encode_behind_the_ycc_front_end(api, enc, oracle, chroma, tile, p
 
 # ------------------------------------------------------------------------------------------------ host planes of their own
 def _apart(arrays):
-    """Copies of the arrays that are allocations of their own, megabytes of other allocations between them."""
-    out, spacers = [], []
-    for a in arrays:
-        spacers.append(np.full(3 << 20, 7, np.uint8))
-        out.append(np.array(a, copy=True, order="C"))
-    lo = min(a.ctypes.data for a in out)
-    hi = max(a.ctypes.data + a.nbytes for a in out)
-    assert hi - lo > sum(a.nbytes for a in out) + (1 << 20), "the planes were not allocated apart"
-    return out, spacers
+    """Copies of the arrays that are allocations of their own, megabytes of other allocations between them.  The allocator puts
+    a copy where it finds room, and holes that earlier tests' arrays left in the heap may take the small copies side by side
+    while the spacers go elsewhere: such an attempt is kept alive (it fills the holes) and the copies are made again."""
+    kept = []
+    for _ in range(32):
+        out, spacers = [], []
+        for a in arrays:
+            spacers.append(np.full(3 << 20, 7, np.uint8))
+            out.append(np.array(a, copy=True, order="C"))
+        lo = min(a.ctypes.data for a in out)
+        hi = max(a.ctypes.data + a.nbytes for a in out)
+        if hi - lo > sum(a.nbytes for a in out) + (1 << 20):
+            return out, spacers + kept
+        kept += out + spacers
+    raise AssertionError("the planes were not allocated apart")
 
 
 def test_separately_allocated_component_planes(api, enc):
