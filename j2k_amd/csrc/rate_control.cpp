@@ -132,6 +132,9 @@ LayerAlloc allocate(const Geometry &geo, const std::vector<CblkResult> &res, con
     // (not when small tiles are dealt to the host threads whole: the device is driven from one thread)
     const bool tiles_side_by_side = geo.tiles.size() > 1 && biggest < 4096 && workers.size() > 1;
     RateDevice *const dev = (plain || quality || tiles_side_by_side) ? nullptr : dev_in;
+    // A device that is not used has still been sent for the pass tables, and everything below reads them: asked for here, on
+    // the calling thread, before the first look and before any worker runs.  (A device that is used is asked as late as possible.)
+    if (dev_in && !dev) dev_in->need_tables();
     std::vector<size_t> pass0(nb + 1, 0);
     for (size_t id = 0; id < nb; ++id) pass0[id + 1] = pass0[id] + res[id].npasses;
     std::unique_ptr<double[]> disto_holder(new double[pass0[nb] + 1]); // (not zeroed: with a device most of it is never touched)

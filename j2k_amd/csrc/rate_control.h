@@ -57,7 +57,9 @@ struct RateDevice {
     virtual void fetch(int slot, uint32_t count, const Taken **taken, const uint32_t **bytes) = 0;
     // rounds with fewer open blocks than this are scanned on the host
     virtual uint32_t min_scan() const = 0;
-    // called before the host reads pass_rate / pass_nmsedec for the first time (they may still be on their way from the device)
+    // called before the host reads pass_rate / pass_nmsedec for the first time (they may still be on their way from the device).
+    // Also called, once and at the start, when the allocation decides not to use the device it was given (tiles dealt whole to
+    // the host threads, fixed quality): it reads the tables all the same.  Always on the thread that called allocate_layers.
     virtual void need_tables() {}
 };
 // a block's weight without the bit-plane (MCT norm x band norm x step size, multiplied in OpenJPEG's order): what the device is given

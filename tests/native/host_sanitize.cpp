@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <set>
+#include <thread>
 
 using namespace j2k_hip;
 
@@ -28,6 +29,134 @@ static void header_bits_case()
             CHECK(rate_block_header_bits(np, np ? len : 0u) == packet_block_bits(np, np ? len : 0u));
         }
     std::printf("ok header bits formula\n");
+}
+
+// synthetic Tier-1 results: plausible bit-planes, passes, non-decreasing byte counts, distortion sums
+static void synth_tables(const Geometry &g, uint32_t seed, std::vector<CblkResult> &res, std::vector<uint32_t> &rate, std::vector<int32_t> &nmse)
+{
+    const size_t nb = g.cblks.size();
+    res.assign(nb, CblkResult());
+    rate.assign(nb * kMaxPasses, 0);
+    nmse.assign(nb * kMaxPasses, 0);
+    uint32_t s = seed;
+    for (size_t i = 0; i < nb; ++i) {
+        const Cblk &c = g.cblks[i];
+        const uint32_t bps = lcg(s) % (c.Mb + 1u);
+        res[i].numbps = bps;
+        res[i].npasses = bps ? 3 * bps - 2 : 0;
+        uint32_t acc = 0;
+        for (uint32_t k = 0; k < res[i].npasses; ++k) {
+            acc += lcg(s) % (1 + (uint32_t)c.w * c.h / 8);
+            rate[i * kMaxPasses + k] = acc;
+            nmse[i * kMaxPasses + k] = (int32_t)(lcg(s) % 100000);
+        }
+        res[i].len = res[i].npasses ? acc : 0;
+    }
+}
+
+// The pass tables arriving late, as they do from the device (encoder.cpp: a copy on a side stream, RateDevice::need_tables
+// waits for it).  Every call goes to the host stand-in, which is built over the true tables; the tables handed to
+// allocate_layers are this wrapper's own and hold decoys until need_tables() is called: tables made the same way from another
+// seed for the same pass counts (monotone and plausible, nothing reads out of bounds, but another allocation comes of them).
+// A read before need_tables() therefore shows as an allocation that differs from the plain procedure's on the true tables.
+// (need_tables() writes the tables with no lock: under ThreadSanitizer a worker reading them at that time is a report.)
+struct LateTables : RateDevice {
+    const std::unique_ptr<RateDevice> inner;
+    const std::vector<uint32_t> &true_rate;
+    const std::vector<int32_t> &true_nmse;
+    std::vector<uint32_t> rate; // what allocate_layers is given
+    std::vector<int32_t> nmse;
+    unsigned table_calls = 0, device_calls = 0; // need_tables / the calls that do a device's work
+    LateTables(const Geometry &g, const std::vector<CblkResult> &res, const std::vector<uint32_t> &r, const std::vector<int32_t> &n, uint32_t min_scan, uint32_t decoy_seed)
+        : inner(make_host_rate_device(g, res, r.data(), n.data(), min_scan)), true_rate(r), true_nmse(n), rate(r.size(), 0), nmse(n.size(), 0)
+    {
+        uint32_t s = decoy_seed;
+        for (size_t i = 0; i < g.cblks.size(); ++i) {
+            const Cblk &c = g.cblks[i];
+            uint32_t acc = 0;
+            for (uint32_t k = 0; k < res[i].npasses; ++k) {
+                acc += lcg(s) % (1 + (uint32_t)c.w * c.h / 8);
+                rate[i * kMaxPasses + k] = acc;
+                nmse[i * kMaxPasses + k] = (int32_t)(lcg(s) % 100000);
+            }
+        }
+    }
+    const double *bmin() override { return inner->bmin(); }
+    const double *bmax() override { return inner->bmax(); }
+    const double *steepest() override { return inner->steepest(); }
+    void begin_layer(uint32_t first, uint32_t count, const uint8_t *done) override { ++device_calls; inner->begin_layer(first, count, done); }
+    void ahead(uint32_t first, uint32_t count, const double *ah, uint32_t K, uint64_t *body) override { ++device_calls; inner->ahead(first, count, ah, K, body); }
+    void scan(uint32_t first, uint32_t count, double thresh, const Taken **taken, const uint32_t **bytes, uint64_t *sums) override
+    {
+        ++device_calls; inner->scan(first, count, thresh, taken, bytes, sums);
+    }
+    void scan_sums(uint32_t first, uint32_t count, double thresh, int slot, uint64_t *sums) override { ++device_calls; inner->scan_sums(first, count, thresh, slot, sums); }
+    void fetch(int slot, uint32_t count, const Taken **taken, const uint32_t **bytes) override { ++device_calls; inner->fetch(slot, count, taken, bytes); }
+    uint32_t min_scan() const override { return inner->min_scan(); }
+    void need_tables() override
+    {
+        ++table_calls;
+        std::copy(true_rate.begin(), true_rate.end(), rate.begin());
+        std::copy(true_nmse.begin(), true_nmse.end(), nmse.begin());
+        inner->need_tables();
+    }
+};
+
+// allocate_layers with late tables against the plain procedure on the true ones; returns the number of need_tables calls
+// (device_calls, optional: how many calls did a device's work -- none when the allocation has dropped the device)
+static unsigned late_alloc(const Geometry &g, const std::vector<CblkResult> &res, const std::vector<uint32_t> &rate, const std::vector<int32_t> &nmse, size_t lead,
+                           const LayerAlloc &want, uint32_t min_scan, unsigned max_threads, uint32_t seed, unsigned *device_calls = nullptr)
+{
+    LateTables late(g, res, rate, nmse, min_scan, seed * 2654435761u + 12345u);
+    const LayerAlloc got = allocate_layers(g, res, late.rate.data(), late.nmse.data(), lead, max_threads, &late);
+    CHECK(got.layers == want.layers && got.np == want.np && got.len == want.len && got.off == want.off);
+    CHECK(late.table_calls >= 1);
+    CHECK(late.rate == rate && late.nmse == nmse);
+    if (device_calls) *device_calls = late.device_calls;
+    return late.table_calls;
+}
+
+// A small rate-controlled frame (8-bit, code-blocks of cb x cb) through allocate_layers with late tables, at both settings of
+// min_scan.  dealt: the frame is one whose tiles are dealt whole to the allocation's threads when it has more than one (several
+// tiles of under 4096 blocks, 2048 blocks or more in all): the allocation then drops the device, and it must still ask for the
+// tables.  That needs two hardware threads; with one the device is kept, and the line says so.
+static void late_case(const char *what, uint32_t nc, bool rev, uint32_t tile, std::vector<float> rates, bool psnr, unsigned max_threads, bool dealt, uint32_t seed)
+{
+    j2k_hip_params p = {};
+    p.struct_size = sizeof(p);
+    p.width = 256; p.height = 256; p.channels = nc; p.depth = 8; p.reversible = rev; p.ycc = nc >= 3;
+    p.num_resolutions = 4; p.tile_size = tile; p.cblk_w = 8; p.cblk_h = 8;
+    p.layers = (uint32_t)rates.size();
+    if (psnr) p.layer_psnr = rates.data();
+    else p.layer_rates = rates.data();
+    p.comment = "sanitize";
+    const Coding cod = normalise(&p);
+    const Geometry g = build_geometry(cod, 0, cod.ntiles());
+    const size_t nb = g.cblks.size();
+    CHECK(cod.rate_control() && nb >= 2048);
+    size_t biggest = 0;
+    for (const Tile &T : g.tiles) biggest = std::max<size_t>(biggest, T.num_cblks);
+    CHECK(biggest < 4096 && (g.tiles.size() > 1) == (tile != 0));
+    std::vector<CblkResult> res;
+    std::vector<uint32_t> rate;
+    std::vector<int32_t> nmse;
+    synth_tables(g, seed, res, rate, nmse);
+    const size_t lead = main_header(cod).size();
+    const LayerAlloc want = allocate_layers_plain(g, res, rate.data(), nmse.data(), lead);
+    const unsigned hw = std::thread::hardware_concurrency();
+    const bool threads = std::min(max_threads, hw) > 1; // (as the allocation counts its threads)
+    unsigned calls[2] = {0, 0}, dev_calls[2] = {0, 0};
+    int k = 0;
+    for (uint32_t min_scan : {0u, 64u}) {
+        calls[k] = late_alloc(g, res, rate, nmse, lead, want, min_scan, max_threads, seed, &dev_calls[k]);
+        // the device is dropped exactly when tiles are dealt to threads, or for fixed quality: otherwise this is not the path meant
+        CHECK((dev_calls[k] == 0) == ((dealt && threads) || psnr));
+        ++k;
+    }
+    const char *path = psnr ? "fixed quality, device dropped" : !dealt ? "device kept" : threads ? "tiles dealt to threads, device dropped"
+                       : max_threads > 1 ? "ONE HARDWARE THREAD, tiles not dealt to threads: device kept" : "one thread asked for, tiles not dealt to threads: device kept";
+    std::printf("ok late tables, %s: c%u %s tile%u layers%u, %zu blocks in %zu tiles, max_threads %u, %s; need_tables calls %u and %u, hardware_concurrency %u\n", what,
+                nc, rev ? "5/3" : "9/7", tile, cod.layers, nb, g.tiles.size(), max_threads, path, calls[0], calls[1], hw);
 }
 
 static void one_case(uint32_t w, uint32_t h, uint32_t nc, uint32_t prec, bool rev, uint32_t numres, uint32_t tile, uint32_t cb,
@@ -49,24 +178,10 @@ static void one_case(uint32_t w, uint32_t h, uint32_t nc, uint32_t prec, bool re
     const Geometry g = build_geometry(cod, 0, cod.ntiles());
     const size_t nb = g.cblks.size();
     CHECK(nb > 0);
-    // synthetic Tier-1 results: plausible bit-planes, passes, non-decreasing byte counts, distortion sums
-    std::vector<CblkResult> res(nb);
-    std::vector<uint32_t> rate(nb * kMaxPasses, 0);
-    std::vector<int32_t> nmse(nb * kMaxPasses, 0);
-    uint32_t s = seed;
-    for (size_t i = 0; i < nb; ++i) {
-        const Cblk &c = g.cblks[i];
-        const uint32_t bps = lcg(s) % (c.Mb + 1u);
-        res[i].numbps = bps;
-        res[i].npasses = bps ? 3 * bps - 2 : 0;
-        uint32_t acc = 0;
-        for (uint32_t k = 0; k < res[i].npasses; ++k) {
-            acc += lcg(s) % (1 + (uint32_t)c.w * c.h / 8);
-            rate[i * kMaxPasses + k] = acc;
-            nmse[i * kMaxPasses + k] = (int32_t)(lcg(s) % 100000);
-        }
-        res[i].len = res[i].npasses ? acc : 0;
-    }
+    std::vector<CblkResult> res;
+    std::vector<uint32_t> rate;
+    std::vector<int32_t> nmse;
+    synth_tables(g, seed, res, rate, nmse);
     LayerAlloc al;
     const bool rc = cod.rate_control();
     const size_t lead = main_header(cod).size() + jp2_file_header(cod, 0).size();
@@ -76,12 +191,8 @@ static void one_case(uint32_t w, uint32_t h, uint32_t nc, uint32_t prec, bool re
             const LayerAlloc want = allocate_layers_plain(g, res, rate.data(), nmse.data(), lead);
             CHECK(al.layers == want.layers && al.np == want.np && al.len == want.len && al.off == want.off);
             // and with the per-block work behind the RateDevice interface (the host standing in for rate.hip): every scan, or
-            // only the rounds with many open blocks
-            for (uint32_t min_scan : {0u, 64u}) {
-                const std::unique_ptr<RateDevice> dev = make_host_rate_device(g, res, rate.data(), nmse.data(), min_scan);
-                const LayerAlloc got = allocate_layers(g, res, rate.data(), nmse.data(), lead, 4, dev.get());
-                CHECK(got.np == want.np && got.len == want.len && got.off == want.off);
-            }
+            // only the rounds with many open blocks -- with the pass tables arriving late (LateTables above)
+            for (uint32_t min_scan : {0u, 64u}) late_alloc(g, res, rate, nmse, lead, want, min_scan, 4, seed);
         }
         for (size_t i = 0; i < nb; ++i) { // every pass assigned at most once, pieces contiguous
             uint32_t np = 0, off = 0;
@@ -332,6 +443,12 @@ int main()
     one_case(4096, 2160, 3, 12, false, 7, 0, 32, {}, false, 18, J2K_HIP_CPRL, false, 4, 0, 0);
     one_case(998, 540, 3, 12, false, 6, 0, 32, {}, false, 19, J2K_HIP_CPRL, false, 4, 90000, 40000);
     one_case(640, 360, 3, 12, false, 5, 0, 32, {}, false, 20, J2K_HIP_CPRL, false, 3, 30000, 8000);
+    // the pass tables arriving late on small frames: 3072 blocks (4 components: 4096) of 8 x 8 in 256 x 256, whole or in four tiles
+    late_case("tiled, four threads", 3, false, 128, {40.f, 10.f}, false, 4, true, 31);
+    late_case("tiled, one thread", 3, false, 128, {40.f, 10.f}, false, 1, true, 31);
+    late_case("untiled, three layers", 3, false, 0, {40.f, 20.f, 10.f}, false, 4, false, 32); // (a later layer's first lawful read: the bytes of the layers before)
+    late_case("tiled, four components", 4, true, 128, {40.f, 10.f}, false, 4, true, 33);
+    late_case("tiled, fixed quality", 3, false, 128, {30.f, 40.f}, true, 4, true, 34);
     // many small rate-controlled cases (random byte counts with runs of byte-less passes, random distortions): the fast
     // allocation against the plain procedure, see one_case
     for (uint32_t k = 0; k < 30; ++k) {
