@@ -634,12 +634,14 @@ int j2k_hip_xyz_tables(uint32_t source, uint32_t src_depth, uint32_t dst_depth, 
  * A1+A2+A4+A5: front end only. d_out = channels planes of width*height 32-bit words (int32 for
  * reversible, float32 bit patterns otherwise), row stride = width.  With sub-sampled components (comp_sub_x / _y,
  * rgb_to_sycc) the components follow one another, each dense at its own size ceil(width / sub_x) x ceil(height / sub_y).
- * rgb_to_xyz is honoured: channels 0..2 come out as X'Y'Z' codes minus the DC shift (then the RCT / ICT with ycc). */
+ * rgb_to_xyz is honoured: channels 0..2 come out as X'Y'Z' codes minus the DC shift (then the RCT / ICT with ycc).
+ * An encode pending on the handle (j2k_hip_encode_begin without its _end): J2K_HIP_ERR_PARAM, nothing of the handle is touched. */
 int j2k_hip_stage_frontend(j2k_hip_encoder *enc, const j2k_hip_params *params,
                            const j2k_hip_plane *planes_device, void *d_out);
 /* A6: forward DWT of `nplanes` planes of width*height 32-bit words (row stride = width), in the
  * Mallat layout of the oracle, origin (x0,y0).  d_in is preserved; d_out receives the result.
- * `repeat` > 1 re-runs the transform (for timing); *ms (optional) = mean device time per run. */
+ * `repeat` > 1 re-runs the transform (for timing); *ms (optional) = mean device time per run.
+ * An encode pending on the handle: J2K_HIP_ERR_PARAM, its job table and planes stay as they are. */
 int j2k_hip_stage_dwt(j2k_hip_encoder *enc, int reversible, uint32_t width, uint32_t height,
                       uint32_t nplanes, uint32_t levels, uint32_t x0, uint32_t y0, const void *d_in,
                       void *d_out, uint32_t repeat, double *ms);
@@ -678,7 +680,9 @@ int j2k_hip_stage_transform(j2k_hip_encoder *enc, const j2k_hip_params *params, 
  * words). Block i = rectangle (bx[i],by[i],bw[i],bh[i]), orientation orient[i], band step size
  * stepsize[i] (ignored when reversible).  Outputs (host): numbps[i], npasses[i], length[i] and the
  * concatenated codewords in `data` (offsets[i] = start of block i).  Rectangles must not overlap:
- * the kernel rewrites each block of d_coef in place as scaled magnitudes (d_coef is scratch). */
+ * the kernel rewrites each block of d_coef in place as scaled magnitudes (d_coef is scratch).
+ * An encode pending on the handle: J2K_HIP_ERR_PARAM (j2k_hip_stage_t1_passes and _styled alike) -- the pending frame's
+ * coder streams still read the block table and the Tier-1 arenas this call would overwrite. */
 int j2k_hip_stage_t1(j2k_hip_encoder *enc, int reversible, void *d_coef, uint32_t stride,
                      uint32_t nblocks, const uint32_t *bx, const uint32_t *by, const uint32_t *bw,
                      const uint32_t *bh, const uint32_t *orient, const float *stepsize,

@@ -681,6 +681,15 @@ class Encoder:
                                                        C.byref(dptr), C.byref(n), None, 0))
         return self.d2h(dptr.value, n.value).tobytes()
 
+    def encode_tiles_host(self, planes, params: Params, tile_first: int, tile_count: int) -> bytes:
+        """j2k_hip_encode_tiles: the tile-parts of a tile range from host memory.  planes: a Plane array of any channel views
+        (planes_from_layout, planes_from_arrays, bottom-up rows); only the rows of the range's tiles are read."""
+        cap = 4 * params.width * params.height * params.channels + (1 << 20)
+        out = np.empty(cap, dtype=np.uint8)
+        n = C.c_size_t()
+        self._check(self.L.j2k_hip_encode_tiles(self.h, C.byref(params), planes, tile_first, tile_count, out.ctypes.data, cap, C.byref(n)))
+        return out[:n.value].tobytes()
+
     # -- decode -----------------------------------------------------------------------------------
     def decode_planar(self, data: bytes, subsample: int = 1, sample_bits: int | None = None, depth: int | None = None,
                       channels: int | None = None, out: np.ndarray | None = None) -> np.ndarray:

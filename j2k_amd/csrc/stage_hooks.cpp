@@ -23,6 +23,8 @@ static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uin
 {
     if (!e) return J2K_HIP_ERR_PARAM;
     return guarded(e, [&] {
+        // (the coder streams of a pending frame still read blks / sym / out / meta: nothing of the handle is touched)
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
         // the styles a frame refuses (geometry.cpp)
         if (cblk_style & kStyleVcausal) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: vertically causal contexts (bit 8) are not written");
         if (cblk_style & ~(uint32_t)(kStylesEncoded | kStyleVcausal)) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: unknown code-block style bits");
@@ -122,6 +124,7 @@ int j2k_hip_stage_frontend(j2k_hip_encoder *e, const j2k_hip_params *params, con
 {
     if (!e) return J2K_HIP_ERR_PARAM;
     return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
         HIP_CHECK(hipSetDevice(e->device));
         const Coding cod = normalise(params);
         FrontendArgs fa = make_frontend_args(cod, planes_device, 0, 0, (int)cod.width, (int)cod.height);
@@ -152,6 +155,7 @@ int j2k_hip_stage_dwt(j2k_hip_encoder *e, int reversible, uint32_t width, uint32
 {
     if (!e) return J2K_HIP_ERR_PARAM;
     return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
         HIP_CHECK(hipSetDevice(e->device));
         if (!width || !height || !nplanes || levels > 32) throw Error(J2K_HIP_ERR_PARAM, "bad DWT stage arguments");
         const size_t plane = (size_t)width * height;

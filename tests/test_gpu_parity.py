@@ -874,6 +874,38 @@ def test_begin_without_end_and_end_without_begin_fail_cleanly(enc, golden):
     assert enc.encode_host(frame, lay, p) == cs
 
 
+def test_stage_hooks_refuse_while_a_begin_is_pending(enc, golden):
+    """The front-end, DWT and Tier-1 hooks overwrite the block table, the job table, the planes and the Tier-1 arenas that the
+    coder streams of a pending frame still read: each refuses as every other hook does, and the handle it drained stays exact."""
+    api = _api()
+    g, pl, _, cs = golden_case(golden, "g3_300x200_rgb8_53_rct")
+    frame, lay = synth.ae_frame(pl, g["prec"])
+    p = _params_from_golden(g)
+    small, slay = synth.ae_frame(synth.planes(64, 48, 3, 8, 5), 8)
+    sp = api.make_params(64, 48, 3, 8)
+    coef = np.zeros((64, 128), dtype=np.int32)
+    coef[::3, ::5] = 77
+    rects, ori, steps = [(0, 0, 64, 64), (64, 0, 64, 64)], [0, 1], [1.0, 1.0]
+    hooks = {
+        "frontend": lambda: enc.stage_frontend(small, slay, sp),
+        "dwt": lambda: enc.stage_dwt(np.zeros((2, 40, 56), np.int32), 2, True),
+        "t1": lambda: enc.stage_t1(coef, rects, ori, steps, True),
+        "t1_passes": lambda: enc.stage_t1(coef, rects, ori, steps, True, want_passes=True),
+        "t1_styled": lambda: enc.stage_t1(coef, rects, ori, steps, True, style=5),
+    }
+    for name, hook in hooks.items():
+        enc.encode_begin_host(frame, lay, p)
+        with pytest.raises(api.J2kHipError, match="the previous j2k_hip_encode_begin on this handle has not been finished") as ei:
+            hook()
+        assert ei.value.code == 1, name  # J2K_HIP_ERR_PARAM
+        # the refused hook has drained the handle: no frame is pending, and the next one is exact
+        with pytest.raises(api.J2kHipError, match="no encode in progress"):
+            enc.encode_end()
+        assert enc.encode_host(frame, lay, p) == cs, name
+        hook()  # ... and with nothing pending the hook runs
+    assert enc.encode_host(frame, lay, p) == cs
+
+
 def _ae16_planes(w, h, nc, seed):
     """After Effects "15+1-bit" samples: 0..32768 inclusive (reference: src/aftereffects/FrameSeq.cpp:311-314)."""
     pl = synth.planes(w, h, nc, 15, seed, "A")
