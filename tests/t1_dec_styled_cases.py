@@ -236,6 +236,66 @@ def spoiled_raw_cases(oracle, style):
     return out
 
 
+DAMAGE_MQ_KINDS = ["marker90", "markerc3", "markerff", "ff8f", "flip", "ff_last", "ff_last_00"]
+_dmq_cache = {}
+
+
+def _damaged_mq(oracle, style):
+    """[(damaged case, clean case, kind, indices of the segments touched)]"""
+    if style in _dmq_cache:
+        return _dmq_cache[style]
+    assert style & 5
+    out = []
+    six = six_blocks()
+    for r, w, h, o in _small(oracle, style, [six[0], six[1], six[4]]):  # the blocks with many and long segments
+        full = make_case(r, w, h, o, style, 1.0)
+        at, p, mq = 0, 0, []  # (index, offset, length, the next segment is MQ-coded and holds a byte) of the MQ-coded segments
+        spans = []
+        for n, k in full["segs"]:
+            spans.append((at, n, not (style & 1 and p >= 10 and (p - 1) % 3 != 2)))
+            at, p = at + n, p + k
+        for i, (a, n, is_mq) in enumerate(spans):
+            if is_mq and n >= 1:
+                mq.append((i, a, n, i + 1 < len(spans) and spans[i + 1][2] and spans[i + 1][1] >= 1))
+        assert len(mq) >= 2 and mq[0][0] == 0
+        for kind in DAMAGE_MQ_KINDS:
+            for half in (0, 1):  # the segments in turn: segment 0 (no restart before it) is in the first half alone
+                data, touched = bytearray(full["data"]), []
+                for j, (i, a, n, next_mq) in enumerate(mq[half::2]):
+                    if kind in ("ff_last", "ff_last_00"):
+                        if kind == "ff_last_00" and not next_mq:
+                            continue
+                        data[a + n - 1] = 0xFF  # the segment's last byte, directly before the next segment's first byte
+                        if kind == "ff_last_00":
+                            data[a + n] = 0x00  # (not a marker: a decoder that looked at it would take seven bits of it)
+                        touched.append(i)
+                        continue
+                    off = min(1, n - 2) if j % 2 == 0 else n // 2 - 1  # near the segment's start, and half way into it
+                    if off >= 0 and off + 2 <= n:
+                        if kind == "flip":
+                            data[a + off] ^= 1 << (off % 8)
+                        else:
+                            data[a + off:a + off + 2] = {"marker90": b"\xff\x90", "markerc3": b"\xff\xc3", "markerff": b"\xff\xff", "ff8f": b"\xff\x8f"}[kind]
+                        touched.append(i)
+                if touched and bytes(data) != full["data"]:
+                    out.append((dsc.variant(full, data=bytes(data)), full, kind, sorted(set(touched))))
+    _dmq_cache[style] = out
+    return out
+
+
+def damaged_mq_cases(oracle, style):
+    """MQ-coded segments with bytes no encoder writes, as a damaged file has them (raw segments: spoiled_raw_cases): a marker
+    inside a terminated segment, 0xFF 0x8F, a flipped bit, 0xFF as a segment's last byte directly before the next
+    segment's first byte -- in the block's first segment and in segments that follow an MQ restart.  The segment table is
+    the clean case's."""
+    return [c for c, _, _, _ in _damaged_mq(oracle, style)]
+
+
+def damaged_mq_info(oracle, style):
+    """Per case of damaged_mq_cases: (the clean case, the kind of damage, the segments touched)."""
+    return [(clean, kind, touched) for _, clean, kind, touched in _damaged_mq(oracle, style)]
+
+
 _file_cache = {}
 
 
@@ -302,6 +362,8 @@ for _s in LASTPASS_STYLES:
     GROUPS[f"cutshort-{_s}"] = (lambda s: lambda oracle: [(True, s, cutshort_cases(oracle, s))])(_s)
 for _s in SPOILED_STYLES:
     GROUPS[f"spoiled-raw-{_s}"] = (lambda s: lambda oracle: [(True, s, spoiled_raw_cases(oracle, s))])(_s)
+for _s in LASTPASS_STYLES:
+    GROUPS[f"damaged-mq-{_s}"] = (lambda s: lambda oracle: [(True, s, damaged_mq_cases(oracle, s))])(_s)
 for _n in FILE_NAMES:
     GROUPS[f"file-{_n}"] = (lambda n: lambda oracle: [file_batch(oracle, n)])(_n)
 GROUPS["manyplanes"] = manyplanes_batches

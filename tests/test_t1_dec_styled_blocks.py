@@ -1,6 +1,6 @@
 """GPU: the lane-per-block Tier-1 decode kernel under code-block styles, block by block, through
 j2k_hip_stage_t1_decode_styled.  Every group of t1_dec_styled_cases.py: both families of t1_styled_families.py under their
-styles, every last pass, codewords and segment tables cut short, damaged raw segments, every block of the styled files of
+styles, every last pass, codewords and segment tables cut short, damaged raw and MQ-coded segments, every block of the styled files of
 libopenjp2 under the file's own style, many bit-planes with and without a region-of-interest shift, orders and group
 sizes.  Expected words are the oracle's styled block decoder's on the same bytes and the same segment table, laid into a
 plane whose other words must stay as they were.  Bit-exact.  test_t1_lane_styled_host.py runs the same cases through the

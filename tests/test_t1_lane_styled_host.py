@@ -1,8 +1,8 @@
 """CPU: the lane-per-block Tier-1 decoder (j2k_amd/csrc/t1_dec_lane.h) under code-block styles, as a stand-alone host program
 with one lane (tests/native/t1_lane_styled_host.cpp) built with the address and undefined-behaviour sanitizers and run as a
 child process.  Every group of cases that test_t1_dec_styled_blocks.py sends to the GPU goes through it here: the families
-of t1_styled_families.py under their styles, every last pass, codewords and segment tables cut short, damaged raw
-segments, every block of the styled files of libopenjp2 (the vertically causal ones among them), many bit-planes, and the
+of t1_styled_families.py under their styles, every last pass, codewords and segment tables cut short, damaged raw and
+MQ-coded segments, every block of the styled files of libopenjp2 (the vertically causal ones among them), many bit-planes, and the
 orders.  Expected samples are the oracle's styled block decoder's.  A second build without the ring's refill on the beat
 (-DT1L_TEST_NO_REFILL) runs the long raw segments through the slow byte path.  The sanitizers' runtimes are linked into
 the program; its environment is the test's own, unchanged."""
@@ -57,7 +57,8 @@ def test_lane_decoder_on_the_host_matches_the_styled_oracle(program, oracle, tmp
     _check(program, oracle, tmp_path, tc.group(oracle, name))
 
 
-@pytest.mark.parametrize("name", ["small-1", "small-5", "small-55", "lastpass-1", "cutshort-5", "spoiled-raw-1", "manyplanes"])
+@pytest.mark.parametrize("name", ["small-1", "small-5", "small-55", "lastpass-1", "cutshort-5", "spoiled-raw-1", "damaged-mq-4", "damaged-mq-5",
+                                  "manyplanes"])
 def test_slow_byte_path_reads_long_raw_segments_the_same(program_no_refill, oracle, tmp_path, name):
     batches = tc.group(oracle, name)
     assert any(n > 64 for _, s, cases in batches for c in cases for n, _ in c["segs"])  # a segment longer than the ring
