@@ -580,6 +580,46 @@ int j2k_hip_decode_rgba_sequence_device(j2k_hip_encoder *enc, const j2k_hip_file
 int j2k_hip_decode_set_max_layers(j2k_hip_encoder *enc, uint32_t max_layers);
 int j2k_hip_decode_get_max_layers(const j2k_hip_encoder *enc, uint32_t *max_layers);
 
+/* --- cinema frames to R'G'B': X'Y'Z' code values to RGB in the RGBA output kernel ---------------------------
+ * A DCI codestream carries no colour space, so j2k_hip_rgba_mode classifies a cinema frame as plain RGB and the RGBA calls
+ * deliver its X'Y'Z' code values as R, G, B.  xyz_to_rgb, a property of the handle like max_layers (sticky until set again,
+ * initially 0), makes j2k_hip_decode_rgba[_device] and j2k_hip_decode_rgba_sequence[_device] -- region and subsample
+ * included -- convert them in the output kernel: the inverse of j2k_hip_params.rgb_to_xyz.  target:
+ *     0  off: every byte and launch is what it was without the setting
+ *     1  sRGB (IEC 61966-2-1 piecewise curve, Rec.709 primaries, D65)
+ *     2  Rec.709 primaries under a pure 2.4 power (BT.1886)
+ *     3  Rec.709 primaries, linear light
+ * -- the three codings of rgb_to_xyz, with its EOTF_1..3.  It applies to mode J2K_HIP_RGBA_RGB only.  A destination pixel, to
+ * the rounding:
+ *   1. c_i (i = 0..2) = the component sample at the component's own precision P: what j2k_hip_decode delivers at depth P
+ *      (replication of sub-sampled components, inverse RCT / ICT, DC shift, clamp to 0 .. 2^P - 1), NOT converted to the
+ *      destination's depth first.  Components 0..2 must be unsigned and share P (1..16).
+ *      l_i = dl[c_i],  dl[c] = (float)pow((double)c / (2^P - 1), 2.6), a table of 2^P binary32 values computed on the host in double.
+ *   2. N_ij = (float)((double)n_ij * (52.37 / 48.0)), n = the XYZ -> linear Rec.709 (D65) matrix, no chromatic adaptation:
+ *          3.2404542 -1.5371385 -0.4985314 / -0.9692660 1.8760108 0.0415560 / 0.0556434 -0.2040259 1.0572252
+ *      r = fadd(fadd(fmul(N00, l_X), fmul(N01, l_Y)), fmul(N02, l_Z)): every product and sum rounded to binary32 on its own,
+ *      nothing contracted to an FMA; g and b alike from rows 1 and 2.
+ *   3. D = the destination's depth, top = 2^D - 1, othr[k] = (float)EOTF_target(((double)k - 0.5) / top) for k = 1..top (strictly
+ *      increasing in binary32 for every target and depth); the channel is the number of k with othr[k] <= r -- round-to-nearest
+ *      of top * OETF(r), decided on thresholds: no transcendental function decides a code on the device.  A negative r (a
+ *      colour outside the Rec.709 gamut) gives 0, r >= othr[top] gives top.
+ *   4. Everything else is the RGB mode's: a fourth component is A through the depth conversion, without one A is filled with
+ *      top; demote_ae16 and the float store ((float)v / (2^D - 1)) follow as without the setting.
+ * j2k_hip_xyz_inverse_tables hands out dl, othr and N as the kernel gets them.  The way there and back is not the identity:
+ * 12-bit codes under a 2.6 power are coarser in the dark than an 8-bit sRGB or 2.4 code (DESIGN.md has the measured errors).
+ * J2K_HIP_ERR_PARAM, the text naming xyz_to_rgb, nothing changed: a target above 3; enc == NULL (the text through
+ * j2k_hip_last_error(NULL)); between j2k_hip_encode_begin_borrowed and its _end.  With the setting non-zero the RGBA calls
+ * refuse, with J2K_HIP_ERR_PARAM naming xyz_to_rgb, before any device work and with nothing written: a file whose mode is GREY,
+ * PALETTE or SYCC; components 0..2 that are signed or of unlike precision.  The planar decode calls and j2k_hip_compare ignore
+ * the setting.
+ * j2k_hip_read_profile: Rsiz of the codestream's SIZ segment, from the headers alone (no handle, no device; failures as
+ * j2k_hip_read_info's): 3 and 4 are the 2K and 4K digital cinema profiles -- the one mark a DCI frame carries, for a host
+ * that wants to convert such files only.  Nothing decodes by it.
+ * J2K_HIP_ABI_VERSION is still 9: functions were added, none changed. */
+int j2k_hip_decode_set_xyz_to_rgb(j2k_hip_encoder *enc, uint32_t target);
+int j2k_hip_decode_get_xyz_to_rgb(const j2k_hip_encoder *enc, uint32_t *target);
+int j2k_hip_read_profile(const void *file, size_t len, uint32_t *rsiz);
+
 /* --- compare a file with its source frame ------------------------------------------------------------
  * What did a file lose?  The source frame is given exactly as j2k_hip_encode takes it (params + planes), the file is decoded
  * as j2k_hip_decode decodes it (subsample 1, the handle's max_layers), and both stay on the device: only the file goes up and
@@ -629,6 +669,11 @@ int j2k_hip_compare_device(j2k_hip_encoder *enc, const j2k_hip_params *params, c
  * skipped.  J2K_HIP_ERR_PARAM for a source outside 1..3 or a depth outside 1..16.
  * J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
 int j2k_hip_xyz_tables(uint32_t source, uint32_t src_depth, uint32_t dst_depth, float *lin, float *thr, float matrix[9]);
+/* The tables of the way back (j2k_hip_decode_set_xyz_to_rgb), alike: target = 1..3; dl receives 2^comp_depth values (dl[c]), othr
+ * 2^dst_depth - 1 values (othr[k - 1] = the threshold of code k, k = 1 .. 2^dst_depth - 1), matrix the nine N_ij row by row.  A
+ * NULL output is skipped.  J2K_HIP_ERR_PARAM for a target outside 1..3 or a depth outside 1..16.
+ * J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
+int j2k_hip_xyz_inverse_tables(uint32_t target, uint32_t comp_depth, uint32_t dst_depth, float *dl, float *othr, float matrix[9]);
 
 /* --- stage-level entry points (parity tests and roofline measurement call these) -----------------
  * A1+A2+A4+A5: front end only. d_out = channels planes of width*height 32-bit words (int32 for
@@ -822,6 +867,13 @@ int j2k_hip_stage_rgba_output(j2k_hip_encoder *enc, int reversible, int mct, uin
                               const void *d_comp, size_t comp_words, uint32_t stride,
                               const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf, size_t buf_bytes,
                               const j2k_hip_rgba_dst *dst, const j2k_hip_rgba_stage *stage);
+/* ... and with the X'Y'Z' -> R'G'B' conversion of j2k_hip_decode_set_xyz_to_rgb: xyz_to_rgb = 0..3 (0: the call above), the
+ * kernel's arguments filled by the same function as for a decode.  Refused with J2K_HIP_ERR_PARAM, the text naming xyz_to_rgb: a
+ * value above 3, a mode other than RGB, components 0..2 of unlike precision.  The handle's own setting is not read. */
+int j2k_hip_stage_rgba_output_xyz(j2k_hip_encoder *enc, int reversible, int mct, uint32_t width, uint32_t height,
+                                  const void *d_comp, size_t comp_words, uint32_t stride,
+                                  const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf, size_t buf_bytes,
+                                  const j2k_hip_rgba_dst *dst, const j2k_hip_rgba_stage *stage, uint32_t xyz_to_rgb);
 
 /* The compare's reduction alone (compare_kernel), with no file involved: the source planes (device pointers, as for
  * j2k_hip_compare_device) against decoded component planes that the caller supplies.  d_decoded (device) holds `channels` planes

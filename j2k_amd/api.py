@@ -91,6 +91,8 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_decode_sequence_check", "j2k_hip_decode_sequence", "j2k_hip_decode_sequence_device",
            "j2k_hip_decode_rgba_sequence", "j2k_hip_decode_rgba_sequence_device", "j2k_hip_debug_decode_kernels",
            "j2k_hip_decode_set_max_layers", "j2k_hip_decode_get_max_layers", "j2k_hip_debug_decode_work",
+           "j2k_hip_decode_set_xyz_to_rgb", "j2k_hip_decode_get_xyz_to_rgb", "j2k_hip_xyz_inverse_tables", "j2k_hip_read_profile",
+           "j2k_hip_stage_rgba_output_xyz",
            "j2k_hip_compare_check", "j2k_hip_compare", "j2k_hip_compare_device", "j2k_hip_stage_compare",
            "j2k_hip_encode_tiles", "j2k_hip_device_count", "j2k_hip_encode_batch",
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
@@ -267,6 +269,12 @@ def load_library():
     L.j2k_hip_debug_decode_work.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.j2k_hip_decode_set_max_layers.argtypes = [C.c_void_p, C.c_uint32]
     L.j2k_hip_decode_get_max_layers.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+    if hasattr(L, "j2k_hip_decode_set_xyz_to_rgb"):  # (an earlier build loaded through J2K_HIP_LIB for an A/B run has none)
+        L.j2k_hip_decode_set_xyz_to_rgb.argtypes = [C.c_void_p, C.c_uint32]
+        L.j2k_hip_decode_get_xyz_to_rgb.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.j2k_hip_xyz_inverse_tables.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.j2k_hip_read_profile.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.j2k_hip_stage_rgba_output_xyz.argtypes = L.j2k_hip_stage_rgba_output.argtypes + [C.c_uint32]
     L.j2k_hip_compare_check.argtypes = [C.POINTER(Params), C.c_void_p, C.c_size_t]
     L.j2k_hip_compare.argtypes = [C.c_void_p, C.POINTER(Params), C.POINTER(Plane), C.c_void_p, C.c_size_t, C.POINTER(Diff), C.c_uint32]
     L.j2k_hip_compare_device.argtypes = L.j2k_hip_compare.argtypes
@@ -429,6 +437,31 @@ def xyz_tables(source: int, src_depth: int, dst_depth: int):
     if rc != 0:
         raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
     return lin, thr, m.reshape(3, 3)
+
+
+def xyz_inverse_tables(target: int, comp_depth: int, dst_depth: int):
+    """The tables of xyz_to_rgb as the kernel gets them (j2k_hip_xyz_inverse_tables; no device needed): (dl, othr, matrix) --
+    dl[c] of 2^comp_depth values, othr[k - 1] = the threshold of code k, the 3 x 3 matrix, all float32."""
+    L = load_library()
+    if not (1 <= comp_depth <= 16 and 1 <= dst_depth <= 16):
+        raise J2kHipError(1, "xyz_to_rgb tables: the depths must be 1..16")
+    dl, othr = np.zeros(1 << comp_depth, np.float32), np.zeros((1 << dst_depth) - 1, np.float32)
+    m = np.zeros(9, np.float32)
+    rc = L.j2k_hip_xyz_inverse_tables(target, comp_depth, dst_depth, dl.ctypes.data, othr.ctypes.data if othr.size else None, m.ctypes.data)
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+    return dl, othr, m.reshape(3, 3)
+
+
+def read_profile(data: bytes) -> int:
+    """Rsiz of the codestream's SIZ segment (j2k_hip_read_profile; header only): 3 / 4 = the 2K / 4K digital cinema profiles."""
+    L = load_library()
+    v = C.c_uint32()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    rc = L.j2k_hip_read_profile(buf.ctypes.data, len(data), C.byref(v))
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+    return v.value
 
 
 def file_header(params: Params, codestream_len: int) -> bytes:
@@ -929,6 +962,16 @@ class Encoder:
         self._check(self.L.j2k_hip_decode_get_max_layers(self.h, C.byref(v)))
         return v.value
 
+    def set_xyz_to_rgb(self, target: int):
+        """j2k_hip_decode_set_xyz_to_rgb: the RGBA decode calls on this handle convert X'Y'Z' code values to R'G'B' of `target`
+        (0 = off, 1 sRGB, 2 Rec.709 under a 2.4 power, 3 Rec.709 linear); sticky until set again."""
+        self._check(self.L.j2k_hip_decode_set_xyz_to_rgb(self.h, target))
+
+    def xyz_to_rgb(self) -> int:
+        v = C.c_uint32()
+        self._check(self.L.j2k_hip_decode_get_xyz_to_rgb(self.h, C.byref(v)))
+        return v.value
+
     def decode_work(self) -> tuple:
         """(coding passes, codeword bytes) handed to Tier-1 by the last decode call, summed over the frames of a sequence call."""
         a, b = C.c_uint64(), C.c_uint64()
@@ -1337,11 +1380,12 @@ class Encoder:
 
     def stage_rgba_output(self, comps, precs, subs, width: int, height: int, reversible: bool, mct: bool, mode: int, chans, buf: np.ndarray,
                           demote: bool = False, lut=None, lut_rgb=(0, 1, 2), org=(0, 0), stride: int | None = None,
-                          gap: int = 0x7fc0dead) -> np.ndarray:
+                          gap: int = 0x7fc0dead, xyz_to_rgb: int | None = None) -> np.ndarray:
         """The RGBA output stage alone (j2k_hip_stage_rgba_output).  comps, precs, subs, stride, gap as in stage_decode_output,
         each plane of ceil((org_y + height) / sub_y) x ceil((org_x + width) / sub_x) samples.  chans: the dicts of
         stage_decode_output for R, G, B and A in this order; A may be None (no alpha destination).  lut: (entries, columns)
-        uint8 palette, lut_rgb the columns R, G, B take.  Returns the whole buffer as the kernel left it."""
+        uint8 palette, lut_rgb the columns R, G, B take.  xyz_to_rgb (0..3): through j2k_hip_stage_rgba_output_xyz, with the
+        X'Y'Z' -> R'G'B' conversion of that target.  Returns the whole buffer as the kernel left it."""
         dt = np.int32 if reversible else np.float32
         planes = [np.ascontiguousarray(c).view(np.uint32) if np.asarray(c).dtype == np.uint32 else
                   np.ascontiguousarray(c, dtype=dt).view(np.uint32) for c in comps]
@@ -1373,8 +1417,12 @@ class Encoder:
         d_comp = self.upload(words)
         d_buf = self.upload(buf)
         try:
-            self._check(self.L.j2k_hip_stage_rgba_output(self.h, int(reversible), int(mct), width, height, d_comp, words.size, stride,
-                                                         oc, len(planes), d_buf, buf.nbytes, C.byref(dst), C.byref(st)))
+            if xyz_to_rgb is None:
+                self._check(self.L.j2k_hip_stage_rgba_output(self.h, int(reversible), int(mct), width, height, d_comp, words.size, stride,
+                                                             oc, len(planes), d_buf, buf.nbytes, C.byref(dst), C.byref(st)))
+            else:
+                self._check(self.L.j2k_hip_stage_rgba_output_xyz(self.h, int(reversible), int(mct), width, height, d_comp, words.size, stride,
+                                                                 oc, len(planes), d_buf, buf.nbytes, C.byref(dst), C.byref(st), xyz_to_rgb))
             return self.d2h(d_buf, buf.nbytes)
         finally:
             self.free(d_comp)

@@ -180,6 +180,7 @@ void parse_main_header(const uint8_t *d, size_t len, FileHeader &H)
         switch (m) {
         case 0xff51: {
             if (L < 41) bad("SIZ too short");
+            H.rsiz = be16(s);
             const uint32_t Xsiz = be32(s + 2), Ysiz = be32(s + 6);
             c.img_x0 = be32(s + 10); c.img_y0 = be32(s + 14);
             c.tile_w = be32(s + 18); c.tile_h = be32(s + 22);

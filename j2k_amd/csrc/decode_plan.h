@@ -15,6 +15,7 @@ namespace j2k_hip {
 
 struct FileHeader {
     Coding cod;                 // width, height, ncomp, prec, reversible, mct, layers, numres, cbw/cbh, prog, tiles
+    uint32_t rsiz = 0;          // SIZ Rsiz, the codestream's capabilities (3 / 4: the 2K / 4K digital cinema profiles); nothing decodes by it
     bool sop = false, eph = false;
     std::vector<uint8_t> ppm;   // packed packet headers of the main header (PPM, A.7.4): the Ippm bytes of all segments in Zppm order
     uint8_t roishift[Coding::kMaxComps] = {}; // RGN (A.6.3): the component's region of interest by MAXSHIFT (H.1)

@@ -16,11 +16,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <future>
+#include <limits>
 #include <thread>
 
 #include "decode_plan.h"
 #include "decode_seq.h"
 #include "handle.h"
+#include "xyz_tables.h"
 
 using namespace j2k_hip;
 
@@ -37,6 +39,37 @@ struct Decoding {
     Decoding(const Decoding &) = delete;
     Decoding &operator=(const Decoding &) = delete;
 };
+// A table of the X'Y'Z' -> R'G'B' output stage on the device (j2k_hip_decode_set_xyz_to_rgb): the handle's copy, made and
+// uploaded on s where the handle has none yet.  target 0: code -> linear light of component depth `depth`; 1..3: the thresholds
+// of that target at destination depth `depth`, padded with +infinity.  Both hold max(2^depth, 4) words (whole float4s).
+const float *xyz_inverse_device_table(j2k_hip_encoder *e, uint32_t target, uint32_t depth, hipStream_t s)
+{
+    for (const auto &t : e->xyz_inverse_tables)
+        if (t->source == target && t->depth == depth) return t->dev.as<float>();
+    auto t = std::make_unique<j2k_hip_encoder::XyzTable>();
+    t->source = target; t->depth = depth;
+    const size_t words = std::max<size_t>((size_t)1 << depth, 4);
+    if (target) {
+        t->host = xyz_othr_table(target, depth);
+        t->host.resize(words, std::numeric_limits<float>::infinity());
+    } else {
+        t->host = xyz_delin_table(depth);
+        t->host.resize(words, 0.0f);
+    }
+    t->dev.ensure(words * sizeof(float));
+    HIP_CHECK(hipMemcpyAsync(t->dev.p, t->host.data(), words * sizeof(float), hipMemcpyHostToDevice, s));
+    e->xyz_inverse_tables.push_back(std::move(t));
+    return e->xyz_inverse_tables.back()->dev.as<float>();
+}
+// ... and what decode_rgba_args leaves to the owner of the tables: their device addresses and the matrix
+void add_xyz_to_rgb(j2k_hip_encoder *e, DecRgbaArgs &a, hipStream_t s)
+{
+    if (!a.xyz_to_rgb) return;
+    a.xyz_dl = xyz_inverse_device_table(e, 0, (uint32_t)a.cprec[0], s);
+    a.xyz_othr = xyz_inverse_device_table(e, (uint32_t)a.xyz_to_rgb, (uint32_t)a.depth, s);
+    xyz_inverse_matrix(a.xyz_n);
+}
+
 // rows [0, rows) split over a few host threads (strided per-sample copies of a large frame)
 template <typename F> void parallel_rows(int rows, size_t work, F &&fn)
 {
@@ -429,8 +462,9 @@ void decode_group(j2k_hip_encoder *e, const DecodeCall &call, const Shape &S, De
             for (int c = 0; c < oas[f].nout; ++c) ch[c]->base = oas[f].dst[c];
             RgbaComp rc[4] = {};
             for (int c = 0; c < cls.ncomp; ++c) rc[c] = RgbaComp{ocs[(size_t)f * 4 + c].plane, ocs[(size_t)f * 4 + c].prec, ocs[(size_t)f * 4 + c].sub_x, ocs[(size_t)f * 4 + c].sub_y};
-            ras[f] = decode_rgba_args(cod.reversible, cod.mct, out_w, out_h, (long long)stride, rc, cls, d, nplanes == 4, org_x, org_y);
+            ras[f] = decode_rgba_args(cod.reversible, cod.mct, out_w, out_h, (long long)stride, rc, cls, d, nplanes == 4, org_x, org_y, e->dec_xyz_to_rgb);
         }
+        add_xyz_to_rgb(e, ras[0], s); // (the launch reads frame 0's arguments; the tables go up on s ahead of it)
         for (uint32_t f = 1; f < nf; ++f) // one record form for the launch: the packed one only where every frame has it, slots alike
             if (!ras[f].packed || std::memcmp(ras[f].slot, ras[0].slot, sizeof ras[0].slot) != 0) ras[0].packed = 0;
     }
@@ -810,7 +844,10 @@ void decode_frames(j2k_hip_encoder *e, const DecodeCall &call)
             FileHeader early;
             try {
                 early = parse_headers(bytes_of(f), call.files[f].len);
-                if (call.rgba) (void)classify_rgba(early); // (a file the fused path does not take: J2K_HIP_ERR_UNSUPPORTED, nothing written)
+                if (call.rgba) { // (a file the fused path does not take: J2K_HIP_ERR_UNSUPPORTED, nothing written)
+                    const RgbaClass k = classify_rgba(early);
+                    if (e->dec_xyz_to_rgb) check_xyz_to_rgb(early, k);
+                }
             } catch (const Error &x) {
                 if (call.seq) throw FrameError(x.code, f, x.what());
                 throw;
@@ -1207,6 +1244,66 @@ int j2k_hip_decode_get_max_layers(const j2k_hip_encoder *e, uint32_t *max_layers
     });
 }
 
+int j2k_hip_decode_set_xyz_to_rgb(j2k_hip_encoder *e, uint32_t target)
+{
+    if (!e) {
+        create_error() = "xyz_to_rgb: no handle";
+        return J2K_HIP_ERR_PARAM;
+    }
+    const int rc = guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "xyz_to_rgb: an encode is in progress on this handle");
+        if (target > 3) throw Error(J2K_HIP_ERR_PARAM, "xyz_to_rgb must be 0..3 (off, sRGB, Rec.709 under a 2.4 power, Rec.709 linear)");
+        e->dec_xyz_to_rgb = target;
+    });
+    if (rc != J2K_HIP_OK && refused_handle() == e) // (a pending j2k_hip_encode_begin_borrowed: refused before the handle is touched)
+        refused_text() = "xyz_to_rgb: an encode is in progress on this handle (j2k_hip_encode_begin_borrowed without its _end)";
+    return rc;
+}
+
+int j2k_hip_decode_get_xyz_to_rgb(const j2k_hip_encoder *e, uint32_t *target)
+{
+    if (!e) {
+        create_error() = "xyz_to_rgb: no handle";
+        return J2K_HIP_ERR_PARAM;
+    }
+    return guarded(const_cast<j2k_hip_encoder *>(e), [&] {
+        if (!target) throw Error(J2K_HIP_ERR_PARAM, "no place for xyz_to_rgb");
+        *target = e->dec_xyz_to_rgb;
+    });
+}
+
+int j2k_hip_xyz_inverse_tables(uint32_t target, uint32_t comp_depth, uint32_t dst_depth, float *dl, float *othr, float matrix[9])
+{
+    try {
+        if (!xyz_inverse_valid(target, comp_depth, dst_depth)) throw Error(J2K_HIP_ERR_PARAM, "xyz_to_rgb tables: target must be 1..3, the depths 1..16");
+        if (dl) { const std::vector<float> t = xyz_delin_table(comp_depth); std::memcpy(dl, t.data(), t.size() * sizeof(float)); }
+        if (othr) { const std::vector<float> t = xyz_othr_table(target, dst_depth); std::memcpy(othr, t.data(), t.size() * sizeof(float)); }
+        if (matrix) xyz_inverse_matrix(matrix);
+        return J2K_HIP_OK;
+    } catch (const Error &x) {
+        create_error() = x.what();
+        return x.code;
+    } catch (const std::exception &x) {
+        create_error() = x.what();
+        return J2K_HIP_ERR_PARAM;
+    }
+}
+
+int j2k_hip_read_profile(const void *file, size_t len, uint32_t *rsiz)
+{
+    if (!rsiz) return J2K_HIP_ERR_PARAM;
+    try {
+        *rsiz = parse_headers(static_cast<const uint8_t *>(file), len).rsiz;
+        return J2K_HIP_OK;
+    } catch (const Error &x) {
+        create_error() = x.what();
+        return x.code;
+    } catch (const std::exception &x) {
+        create_error() = x.what();
+        return J2K_HIP_ERR_PARAM;
+    }
+}
+
 int j2k_hip_region_footprint(int reversible, uint32_t width, uint32_t height, uint32_t levels, uint32_t x0, uint32_t y0,
                              const j2k_hip_rect *window, j2k_hip_rect *rects, uint32_t nrects)
 {
@@ -1389,6 +1486,13 @@ int j2k_hip_stage_rgba_output(j2k_hip_encoder *e, int reversible, int mct, uint3
                               size_t comp_words, uint32_t stride, const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf,
                               size_t buf_bytes, const j2k_hip_rgba_dst *dst, const j2k_hip_rgba_stage *stage)
 {
+    return j2k_hip_stage_rgba_output_xyz(e, reversible, mct, width, height, d_comp, comp_words, stride, comps, ncomp, d_buf, buf_bytes, dst, stage, 0);
+}
+
+int j2k_hip_stage_rgba_output_xyz(j2k_hip_encoder *e, int reversible, int mct, uint32_t width, uint32_t height, const void *d_comp,
+                                  size_t comp_words, uint32_t stride, const j2k_hip_outcomp *comps, uint32_t ncomp, void *d_buf,
+                                  size_t buf_bytes, const j2k_hip_rgba_dst *dst, const j2k_hip_rgba_stage *stage, uint32_t xyz_to_rgb)
+{
     if (!e) return J2K_HIP_ERR_PARAM;
     return guarded(e, [&] {
         if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "an encode is in progress on this handle");
@@ -1437,8 +1541,9 @@ int j2k_hip_stage_rgba_output(j2k_hip_encoder *e, int reversible, int mct, uint3
             if (sb == 2 && ((reinterpret_cast<uintptr_t>(p.base) & 1) || (w > 1 && (p.colbytes & 1)) || (h > 1 && (p.rowbytes & 1))))
                 throw Error(J2K_HIP_ERR_PARAM, "16-bit destination channel at an odd address");
         }
-        const DecRgbaArgs ra = decode_rgba_args(reversible != 0, mct != 0, (int)width, (int)height, (long long)stride, rc, cls, d, alpha,
-                                                (int)stage->org_x, (int)stage->org_y);
+        DecRgbaArgs ra = decode_rgba_args(reversible != 0, mct != 0, (int)width, (int)height, (long long)stride, rc, cls, d, alpha,
+                                          (int)stage->org_x, (int)stage->org_y, xyz_to_rgb);
+        add_xyz_to_rgb(e, ra, s);
         launch_decode_rgba(ra, s);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(s));

@@ -1426,6 +1426,11 @@ const j2k_hip_encoder *&j2k_hip::refused_handle()
     thread_local const j2k_hip_encoder *h = nullptr;
     return h;
 }
+const char *&j2k_hip::refused_text()
+{
+    thread_local const char *t = nullptr;
+    return t;
+}
 
 // After a failure nothing of this handle may stay in flight: the next call reuses every arena.
 void j2k_hip::drain(j2k_hip_encoder *e)
@@ -1526,6 +1531,7 @@ void j2k_hip_destroy(j2k_hip_encoder *e)
     for (auto &v : e->stage_dl) if (v) (void)hipEventDestroy(v);
     for (auto &b : e->h_stage_cs) b.release();
     e->xyz_tables.clear(); // (the streams are drained: no upload of a table is in flight)
+    e->xyz_inverse_tables.clear();
     DeviceShared &dev = g_dev[(e->device >= 0 && e->device < kMaxDevices) ? e->device : 0];
     if (e->k1_done) {
         std::lock_guard<std::mutex> lk(dev.dense);
@@ -1553,6 +1559,7 @@ const char *j2k_hip_last_error(const j2k_hip_encoder *e)
 {
     if (!e) return create_error().c_str();
     // (while the deferred half runs, the handle's error text is the worker's to write: nobody else reads it)
+    if (refused_handle() == e && refused_text()) return refused_text();
     if (refused_handle() == e || (e->begin_async.load() && !begin_worker_thread()))
         return "an encode is in progress on this handle (j2k_hip_encode_begin_borrowed without its _end)";
     return e->err.c_str();

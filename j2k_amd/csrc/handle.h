@@ -212,6 +212,11 @@ struct j2k_hip_encoder {
     // upload may still be in flight.
     struct XyzTable { uint32_t source, depth; std::vector<float> host; j2k_hip::DevBuf dev; };
     std::vector<std::unique_ptr<XyzTable>> xyz_tables;
+    // ... and the way back in the decode's RGBA output stage (j2k_hip_decode_set_xyz_to_rgb): the setting, and its tables, kept
+    // alike -- thresholds by (target, destination depth), code -> linear light by component depth (source = 0: it is the same
+    // for every target).  Both are padded to max(2^depth, 4) words, the thresholds with +infinity.
+    uint32_t dec_xyz_to_rgb = 0;
+    std::vector<std::unique_ptr<XyzTable>> xyz_inverse_tables;
 };
 
 namespace j2k_hip {
@@ -269,13 +274,15 @@ hipStream_t coder_stream(j2k_hip_encoder *e, int i);
 // remembered per calling thread and j2k_hip_last_error answers it.
 bool begin_worker_thread();
 const j2k_hip_encoder *&refused_handle();
+// ... with a text of the refused call's own where it has one (null: the general text); a static string, per calling thread
+const char *&refused_text();
 // text of the last failure of a call without a handle (j2k_hip_create, header-only entry points), per thread
 std::string &create_error();
 
 // Runs f(), turning every exception into a status code + the handle's error text: nothing is thrown across the C ABI.
 template <typename F> int guarded(j2k_hip_encoder *e, F &&f)
 {
-    if (e && e->begin_async.load() && !begin_worker_thread()) { refused_handle() = e; return J2K_HIP_ERR_PARAM; }
+    if (e && e->begin_async.load() && !begin_worker_thread()) { refused_handle() = e; refused_text() = nullptr; return J2K_HIP_ERR_PARAM; }
     refused_handle() = nullptr;
     try {
         f();

@@ -376,7 +376,9 @@ void launch_decode_output(const DecOutArgs &a, hipStream_t s);
 // The same stage straight to R, G, B, A (rgba_out.hip): the component samples as above, then the file's mode (RGB, grey,
 // palette, sYCC), the alpha fill and Demote, stored as one record per pixel where the four channels form one.  DecRgbaArgs
 // and its preconditions are in rgba_plan.h (no HIP types: the function that fills it, decode_rgba_args, is host code that
-// is also built and run on its own).
+// is also built and run on its own).  a.xyz_to_rgb != 0 (mode RGB; a.xyz_dl, a.xyz_othr and a.xyz_n set): R, G, B are made from
+// X'Y'Z' code values by table, matrix and threshold search (j2k_hip_decode_set_xyz_to_rgb); component and destination depth
+// <= 12: both tables are copied into LDS and the grid is kept at about the workgroups the chip holds, like launch_frontend_xyz's.
 void launch_decode_rgba(const DecRgbaArgs &a, hipStream_t s);
 
 // Both output stages for the frames of a sequence decode in one launch (decode_output_seq_kernel, idwt.hip;

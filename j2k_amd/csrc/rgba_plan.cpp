@@ -81,6 +81,16 @@ RgbaClass classify_rgba(const FileHeader &H)
     throw Error(J2K_HIP_ERR_UNSUPPORTED, "no conversion to RGBA for " + where);
 }
 
+void check_xyz_to_rgb(const FileHeader &H, const RgbaClass &cls)
+{
+    if (cls.mode != J2K_HIP_RGBA_RGB) throw Error(J2K_HIP_ERR_PARAM, "xyz_to_rgb: only a file of mode RGB holds X'Y'Z' code values");
+    const Coding &c = H.cod;
+    for (int k = 0; k < 3; ++k) {
+        if (c.csgnd[k]) throw Error(J2K_HIP_ERR_PARAM, "xyz_to_rgb: component " + std::to_string(k) + " is signed");
+        if (c.cprec[k] != c.cprec[0]) throw Error(J2K_HIP_ERR_PARAM, "xyz_to_rgb: components 0..2 of unlike precision");
+    }
+}
+
 void check_rgba_dst(const j2k_hip_rgba_dst &dst, bool alpha)
 {
     if (dst.struct_size != sizeof(j2k_hip_rgba_dst)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_rgba_dst.struct_size mismatch (ABI drift)");
@@ -95,7 +105,7 @@ void check_rgba_dst(const j2k_hip_rgba_dst &dst, bool alpha)
 }
 
 DecRgbaArgs decode_rgba_args(bool reversible, bool mct, int width, int height, long long stride, const RgbaComp *comps,
-                             const RgbaClass &cls, const j2k_hip_rgba_dst &dst, bool alpha, int org_x, int org_y)
+                             const RgbaClass &cls, const j2k_hip_rgba_dst &dst, bool alpha, int org_x, int org_y, uint32_t xyz_to_rgb)
 {
     check_rgba_dst(dst, alpha);
     (void)rgba_class(cls.mode, (uint32_t)cls.ncomp); // (a class made by hand)
@@ -110,7 +120,12 @@ DecRgbaArgs decode_rgba_args(bool reversible, bool mct, int width, int height, l
         for (int c = 1; c < 3; ++c)
             if (comps[c].prec != comps[0].prec || comps[c].sub_x != comps[0].sub_x || comps[c].sub_y != comps[0].sub_y)
                 throw Error(J2K_HIP_ERR_PARAM, "component transform on components of unlike precision or sub-sampling");
+    if (xyz_to_rgb > 3) throw Error(J2K_HIP_ERR_PARAM, "xyz_to_rgb must be 0..3");
+    if (xyz_to_rgb && cls.mode != J2K_HIP_RGBA_RGB) throw Error(J2K_HIP_ERR_PARAM, "xyz_to_rgb: only the RGB mode holds X'Y'Z' code values");
+    if (xyz_to_rgb && (comps[1].prec != comps[0].prec || comps[2].prec != comps[0].prec))
+        throw Error(J2K_HIP_ERR_PARAM, "xyz_to_rgb: components 0..2 of unlike precision");
     DecRgbaArgs a{};
+    a.xyz_to_rgb = (int)xyz_to_rgb;
     a.stride = stride; a.ncomp = cls.ncomp; a.width = width; a.height = height;
     a.reversible = reversible; a.mct = mct; a.org_x = org_x; a.org_y = org_y;
     for (int c = 0; c < 4; ++c) { a.cprec[c] = (int)comps[0].prec; a.sub_x[c] = a.sub_y[c] = 1; }

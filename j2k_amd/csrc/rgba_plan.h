@@ -30,7 +30,7 @@ RgbaClass classify_rgba(const FileHeader &H);
 // Arguments of decode_rgba_kernel (rgba_out.hip).  Per destination pixel: the component samples as decode_output_kernel
 // produces them, the mode's arithmetic, the alpha fill, Demote, and either one store of the pixel's record (packed) or one
 // store per given channel.
-struct DecRgbaArgs {
+struct DecRgbaCore {
     const void *comp[4]; long long stride; // decoded components (int32 or float32 words)
     int ncomp, width, height, reversible, mct;
     int cprec[4], sub_x[4], sub_y[4];
@@ -46,6 +46,14 @@ struct DecRgbaArgs {
     int dst_w[4], dst_h[4];
     uint32_t lut_size, lut[256];           // palette entry = R | G << 8 | B << 16; entries from lut_size on are 0
 };
+// ... and, behind them, what the X'Y'Z' -> R'G'B' variants read (j2k_hip_decode_set_xyz_to_rgb; xyz_tables.h).  The kernels
+// without the conversion take DecRgbaCore as their argument, so their argument layout is what it was before these existed.
+struct DecRgbaArgs : DecRgbaCore {
+    int xyz_to_rgb;        // 0: off (nothing below is read); 1..3: the target coding, mode RGB only
+    const float *xyz_dl;   // max(2^cprec[0], 4) words: code -> linear light; 16-byte aligned
+    const float *xyz_othr; // max(2^depth, 4) words: the 2^depth - 1 thresholds of codes 1 .. top, then +infinity; 16-byte aligned
+    float xyz_n[9];        // X Y Z -> R G B, row by row
+};
 // Preconditions (not checked on the device; decode_rgba_args below is the one place that fills the struct):
 //   * mode RGB: ncomp 3 or 4, alpha_comp 3 or -1; GREY: ncomp 1 or 2, alpha_comp 1 or -1; PALETTE: ncomp 1, alpha_comp -1,
 //     lut_size <= 256; SYCC: ncomp 3, alpha_comp -1; alpha_comp < ncomp.  With mct, ncomp >= 3 and components 0..2 share
@@ -57,7 +65,9 @@ struct DecRgbaArgs {
 //   * dst_w[c] <= width, dst_h[c] <= height; dst[c] + y * rowbytes[c] + x * colbytes[c] is writable for x < dst_w[c],
 //     y < dst_h[c] and aligned to sample_bytes (general form: dst[0..2] given, dst[3] may be nullptr);
 //   * packed: slot[] is a permutation of 0..3, pix and pix_rowbytes are multiples of 4 * sample_bytes, and every record of
-//     dst_w[0] x dst_h[0] is writable.
+//     dst_w[0] x dst_h[0] is writable;
+//   * xyz_to_rgb != 0: mode RGB, cprec[0] == cprec[1] == cprec[2] (every component sample is an index into xyz_dl: the clamp
+//     of component_samples keeps it below 2^cprec), and both tables on the device.
 
 struct RgbaComp { const void *plane; uint32_t prec, sub_x, sub_y; };
 // What j2k_hip_decode_rgba refuses about its destination before anything else happens (J2K_HIP_ERR_PARAM): a struct of
@@ -69,7 +79,14 @@ void check_rgba_dst(const j2k_hip_rgba_dst &dst, bool alpha);
 // addresses in .base; ch[3] is read only with `alpha`.  Chooses the packed form when the four channels are the four samples
 // of one pixel record (all given; colbytes == 4 * sample_bytes; equal rowbytes, a multiple of the record; equal extents;
 // bases a permutation of p + {0,1,2,3} * sample_bytes with p aligned to the record), the general form otherwise.
+// xyz_to_rgb (0..3): the conversion of j2k_hip_decode_set_xyz_to_rgb; non-zero is refused (J2K_HIP_ERR_PARAM, the text naming
+// xyz_to_rgb) for every mode but RGB and for components 0..2 of unlike precision.  The tables' device addresses and the
+// matrix are the caller's to add (they belong to the handle).
 DecRgbaArgs decode_rgba_args(bool reversible, bool mct, int width, int height, long long stride, const RgbaComp *comps,
-                             const RgbaClass &cls, const j2k_hip_rgba_dst &dst, bool alpha, int org_x = 0, int org_y = 0);
+                             const RgbaClass &cls, const j2k_hip_rgba_dst &dst, bool alpha, int org_x = 0, int org_y = 0,
+                             uint32_t xyz_to_rgb = 0);
+// What a non-zero xyz_to_rgb refuses about a file, from the header alone (J2K_HIP_ERR_PARAM, the text naming xyz_to_rgb): a
+// mode other than RGB, components 0..2 that are signed or of unlike precision.
+void check_xyz_to_rgb(const FileHeader &H, const RgbaClass &cls);
 
 } // namespace j2k_hip

@@ -41,6 +41,35 @@ void xyz_matrix(float M[9])
     for (int i = 0; i < 9; ++i) M[i] = (float)(m[i] * k);
 }
 
+bool xyz_inverse_valid(uint32_t target, uint32_t comp_depth, uint32_t dst_depth)
+{
+    return xyz_tables_valid(target, comp_depth, dst_depth); // (the same three codings, the same depths)
+}
+
+std::vector<float> xyz_delin_table(uint32_t comp_depth)
+{
+    const uint32_t n = 1u << comp_depth;
+    const double top = (double)(n - 1);
+    std::vector<float> dl(n);
+    for (uint32_t c = 0; c < n; ++c) dl[c] = (float)std::pow((double)c / top, 2.6);
+    return dl;
+}
+
+std::vector<float> xyz_othr_table(uint32_t target, uint32_t dst_depth)
+{
+    const uint32_t top = (1u << dst_depth) - 1;
+    std::vector<float> othr(top);
+    for (uint32_t k = 1; k <= top; ++k) othr[k - 1] = (float)eotf(target, ((double)k - 0.5) / (double)top);
+    return othr;
+}
+
+void xyz_inverse_matrix(float N[9])
+{
+    static const double n[9] = {3.2404542, -1.5371385, -0.4985314, -0.9692660, 1.8760108, 0.0415560, 0.0556434, -0.2040259, 1.0572252};
+    const double k = 52.37 / 48.0;
+    for (int i = 0; i < 9; ++i) N[i] = (float)(n[i] * k);
+}
+
 uint32_t xyz_code(const float *thr, uint32_t n, float x)
 {
     uint32_t lo = 0, hi = n; // thr[i] <= x for i < lo, thr[i] > x for i >= hi

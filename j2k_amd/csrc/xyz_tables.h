@@ -22,4 +22,16 @@ void xyz_matrix(float M[9]);
 // The code of a linear value: how many thresholds are <= x (0 .. n).  The definition the kernel's search has to equal.
 uint32_t xyz_code(const float *thr, uint32_t n, float x);
 
+// The way back, for the decode's RGBA output stage (j2k_hip_decode_set_xyz_to_rgb; include/j2k_hip.h has the definition):
+// X'Y'Z' code -> linear light, the X Y Z -> R G B matrix scaled to 52.37 / 48, and the thresholds that decide the R'G'B' code of
+// target 1..3 (the codings of `source` above).  j2k_hip_xyz_inverse_tables hands out the same values.
+// target 1..3, depths 1..16
+bool xyz_inverse_valid(uint32_t target, uint32_t comp_depth, uint32_t dst_depth);
+// dl[c] = (float)pow((double)c / (2^P - 1), 2.6), c = 0 .. 2^P - 1
+std::vector<float> xyz_delin_table(uint32_t comp_depth);
+// othr[k - 1] = (float)EOTF_target(((double)k - 0.5) / top), k = 1 .. top = 2^depth - 1: strictly increasing
+std::vector<float> xyz_othr_table(uint32_t target, uint32_t dst_depth);
+// N[3 * i + j] = (float)(n_ij * (52.37 / 48.0)), n = XYZ -> linear Rec.709 (D65), row i = R, G, B
+void xyz_inverse_matrix(float N[9]);
+
 } // namespace j2k_hip

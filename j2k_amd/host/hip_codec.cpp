@@ -20,6 +20,11 @@ extern "C" int j2k_hip_compare_check(const j2k_hip_params *params, const void *f
 extern "C" int j2k_hip_compare(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes, const void *file, size_t len,
                                j2k_hip_diff *diffs, uint32_t ndiffs) __attribute__((weak));
 
+// ... and the X'Y'Z' -> R'G'B' conversion of the RGBA read: asking a library without it for a conversion is an error, never a
+// quiet read of the code values (apply_read_cinema).
+extern "C" int j2k_hip_decode_set_xyz_to_rgb(j2k_hip_encoder *enc, uint32_t target) __attribute__((weak));
+extern "C" int j2k_hip_read_profile(const void *file, size_t len, uint32_t *rsiz) __attribute__((weak));
+
 namespace j2k {
 namespace {
 
@@ -40,7 +45,7 @@ size_t sink_write(void *user, const void *buf, size_t n)
 
 } // namespace
 
-HipCodec::HipCodec(Mode mode, int device, unsigned options) : _mode(mode), _device(device), _options(options), _fallback(NULL), _read_layers(0) {}
+HipCodec::HipCodec(Mode mode, int device, unsigned options) : _mode(mode), _device(device), _options(options), _fallback(NULL), _read_layers(0), _read_xyz(0), _read_xyz_profile_only(true) {}
 HipCodec::~HipCodec() {}
 
 const char *HipCodec::LastError() { return t_enc.error.c_str(); }
@@ -117,6 +122,17 @@ void apply_read_layers(j2k_hip_encoder *h, unsigned layers)
         throw Exception("Error reading file");
     }
     if (j2k_hip_decode_set_max_layers(h, layers) != J2K_HIP_OK) { t_enc.error = j2k_hip_last_error(h); throw Exception("Error reading file"); }
+}
+
+// SetReadCinemaColour, alike: the handle's setting is the object's for this read (0 for a file that is not to be converted).
+void apply_read_cinema(j2k_hip_encoder *h, unsigned target)
+{
+    if (j2k_hip_decode_set_xyz_to_rgb == NULL) {
+        if (target == 0) return;
+        t_enc.error = "this libj2k_hip has no j2k_hip_decode_set_xyz_to_rgb: SetReadCinemaColour needs a newer library";
+        throw Exception("Error reading file");
+    }
+    if (j2k_hip_decode_set_xyz_to_rgb(h, target) != J2K_HIP_OK) { t_enc.error = j2k_hip_last_error(h); throw Exception("Error reading file"); }
 }
 
 } // namespace
@@ -300,6 +316,16 @@ bool HipCodec::ReadRGBA(InputFile &file, const Channel &r, const Channel &g, con
     j2k_hip_encoder *h = thread_handle(_device);
     if (!h) throw Exception("Error reading file");
     apply_read_layers(h, _read_layers);
+    unsigned xyz = _read_xyz;
+    if (xyz && _read_xyz_profile_only) { // convert only what says it is a cinema frame
+        uint32_t rsiz = 0;
+        if (j2k_hip_read_profile == NULL || j2k_hip_read_profile(data.data(), data.size(), &rsiz) != J2K_HIP_OK) {
+            t_enc.error = j2k_hip_read_profile == NULL ? "this libj2k_hip has no j2k_hip_read_profile: SetReadCinemaColour needs a newer library" : j2k_hip_last_error(NULL);
+            throw Exception("Error reading file");
+        }
+        if (rsiz != 3 && rsiz != 4) xyz = 0;
+    }
+    apply_read_cinema(h, xyz);
     const int rc = j2k_hip_decode_rgba(h, data.data(), data.size(), subsample ? subsample : 1, NULL, &dst);
     if (rc != J2K_HIP_OK) {
         t_enc.error = j2k_hip_last_error(h);

@@ -113,6 +113,16 @@ class HipCodec : public Codec {
     void SetReadLayers(unsigned layers) { _read_layers = layers; }
     unsigned ReadLayers() const { return _read_layers; }
 
+    // Cinema frames to R'G'B' (the read side of the CinemaXYZ options): a digital-cinema codestream holds X'Y'Z' code values and
+    // names no colour space, so ReadRGBA hands them over as R, G, B.  target 1..3 (sRGB / Rec.709 under a 2.4 power / Rec.709
+    // linear, as CinemaXYZ's sources; 0, the initial value: today's behaviour) makes ReadRGBA convert them in its output
+    // kernel (include/j2k_hip.h: j2k_hip_decode_set_xyz_to_rgb).  profileFilesOnly: only files that carry the one mark a DCI
+    // frame has -- Rsiz 3 or 4 in SIZ (j2k_hip_read_profile) -- are converted, every other file is read as without the setting;
+    // false: every file ReadRGBA takes as RGB is converted, and one it takes as grey, palette or sYCC throws.  A target above 3
+    // throws at the read.  ReadFile, ReadFiles and Compare are planar reads and do not convert.
+    void SetReadCinemaColour(unsigned target, bool profileFilesOnly = true) { _read_xyz = target; _read_xyz_profile_only = profileFilesOnly; }
+    unsigned ReadCinemaColour() const { return _read_xyz; }
+
     // text of the last failure on the calling thread (the exception itself carries the reference's
     // fixed message)
     static const char *LastError();
@@ -123,6 +133,8 @@ class HipCodec : public Codec {
     unsigned _options;
     Codec *_fallback;
     unsigned _read_layers;
+    unsigned _read_xyz;
+    bool _read_xyz_profile_only;
 };
 
 } // namespace j2k

@@ -76,10 +76,15 @@ class RecordingCodec : public j2k::Codec {
     virtual void WriteFile(j2k::OutputFile &, const j2k::FileInfo &, const j2k::Buffer &, j2k::Progress *) { throw j2k::Exception("read only"); }
 };
 
-// test knob of the read hooks: HipCodec::SetReadLayers
+// test knobs of the read hooks: HipCodec::SetReadLayers, and HipCodec::SetReadCinemaColour (J2K_HOST_TEST_READ_CINEMA = the
+// target; J2K_HOST_TEST_READ_CINEMA_ALL set to anything but 0: profileFilesOnly = false)
 void read_knobs(j2k::HipCodec &hip)
 {
     if (const char *l = std::getenv("J2K_HOST_TEST_READ_LAYERS")) hip.SetReadLayers((unsigned)std::atoi(l));
+    if (const char *t = std::getenv("J2K_HOST_TEST_READ_CINEMA")) {
+        const char *all = std::getenv("J2K_HOST_TEST_READ_CINEMA_ALL");
+        hip.SetReadCinemaColour((unsigned)std::atoi(t), !(all && std::atoi(all) != 0));
+    }
 }
 
 } // namespace
