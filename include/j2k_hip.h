@@ -429,7 +429,15 @@ typedef struct j2k_hip_outplane {
 } j2k_hip_outplane;
 /* Decode at 1/subsample of the size (subsample = 1, 2, 4 ...: cp_reduce = log2(subsample), :501): the image of
  * ceil(width / subsample) x ceil(height / subsample) goes to the top-left of the destination channels.
- * planes[i] receives codestream component i (after the inverse colour transform: R,G,B[,A]). */
+ * planes[i] receives codestream component i (after the inverse colour transform: R,G,B[,A]).
+ * A file cut short (its write was aborted) decodes what is there, in every decode entry point and in j2k_hip_compare:
+ *  - a cut inside a tile-part: the whole code-block contributions that arrived are decoded -- a packet whose header or
+ *    whose body is cut keeps the contributions in front of the cut -- and everything else of the tile is zero coefficients
+ *    (libopenjp2 2.4 / 2.5 refuse such a file: "Tile part length size inconsistent with stream length");
+ *  - whole tile-parts missing, with or without an EOC: decoded as libopenjp2 decodes them.  The samples of a tile of which
+ *    no tile-part arrived are component value 0 (not the mid level a tile of zero coefficients decodes to), and every
+ *    conversion behind it -- signed offset, depth, colour, palette, float -- runs on that 0;
+ *  - a cut in front of the first SOD, or inside a later tile-part's SOT .. SOD: J2K_HIP_ERR_PARAM. */
 int j2k_hip_decode(j2k_hip_encoder *enc, const void *file, size_t len, uint32_t subsample,
                    const j2k_hip_outplane *planes, uint32_t nplanes);
 /* Same with destination channels in device memory (planes[i].base are device pointers). */
@@ -527,7 +535,8 @@ int j2k_hip_decode_rgba_device(j2k_hip_encoder *enc, const void *file, size_t le
  * Output: frame f goes to planes[f * nplanes + i] (i < nplanes) or dsts[f], and every destination receives exactly what
  * j2k_hip_decode_region / j2k_hip_decode_rgba with the same subsample, region and destination would have written for
  * files[f] -- region == NULL: the whole image; sub-sampled, signed and mixed-depth components, palettes, code-block styles,
- * files cut short and the first four of sixteen components included.  Only channel samples are written.  Destinations of
+ * files cut short (j2k_hip_decode: a missing tile is component value 0 in its own frame, whatever its neighbours hold) and
+ * the first four of sixteen components included.  Only channel samples are written.  Destinations of
  * different frames may be pieces of one buffer but must not overlap.  Channel i has the same sample_bits and depth in every
  * frame (RGBA: also the same demote_ae16, and an alpha destination in all frames or in none); bases, strides and extents are
  * each frame's own.

@@ -517,9 +517,10 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const u
     std::vector<uint8_t> joined; // a tile whose packets are spread over several tile-parts is parsed from a joined copy
     const uint32_t top_res = cod.numres - 1 - reduce;
 
+    P.tile_arrived.assign(g.tiles.size(), 1);
     for (const Tile &T : g.tiles) {
         const std::vector<Span> &spans = tile_spans[T.index];
-        if (spans.empty()) continue;
+        if (spans.empty()) { P.tile_arrived[(size_t)(&T - g.tiles.data())] = 0; ++P.tiles_missing; continue; }
         const uint8_t *base = d + spans[0].off;
         size_t blen = spans[0].len;
         std::vector<std::pair<size_t, size_t>> map; // joined offset -> file offset (per span), only when joined

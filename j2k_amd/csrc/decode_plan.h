@@ -114,6 +114,11 @@ struct DecodePlan {
     // 0 .. numres - 1 - reduce; empty where the window misses the tile-component.  Blocks outside them are not in `blocks`.
     bool windowed = false;
     std::vector<std::vector<ResFootprint>> windows;
+    // a file cut short: tile_arrived[t] (geo.tiles order) = the file holds a tile-part of the tile (its SOT .. SOD at least);
+    // tiles_missing = how many do not.  The samples of such a tile are component value 0 (libopenjp2 leaves its image buffer as
+    // it allocated it), not what a tile of zero coefficients decodes to; a tile that arrived with packets missing is the latter.
+    std::vector<uint8_t> tile_arrived;
+    uint32_t tiles_missing = 0;
 };
 
 // Tier-2 of the whole file for a decode at resolution `reduce` (0 = full size).  window (optional): x, y, w, h in pixels of

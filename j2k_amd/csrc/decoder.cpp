@@ -484,6 +484,35 @@ void decode_group(j2k_hip_encoder *e, const DecodeCall &call, const Shape &S, De
         if (call.rgba) { D.pix = ras[f].pix; D.pix_rowbytes = ras[f].pix_rowbytes; }
     }
 
+    // ---- a file cut short: the tiles for which no tile-part arrived.  Their samples are component value 0 (decode_plan.h), so
+    // behind the inverse DWT their rectangles of the planes get the word the output stage turns into 0: minus the DC level it
+    // adds.  A signed component's 0 is a zero coefficient already (the output stage adds the offset the host's conversion
+    // wants), and behind the inverse component transform components 1 and 2 are differences: zero.  The rectangles are the
+    // inverse DWT's jobs of the top resolution.  Complete files: no job, no launch.
+    std::vector<FillJob> fills;
+    int fill_w = 0, fill_h = 0;
+    for (uint32_t f = 0; f < nf; ++f) {
+        if (!plans[f].tiles_missing) continue;
+        for (size_t t = 0; t < g.tiles.size(); ++t) {
+            if (plans[f].tile_arrived[t]) continue;
+            for (uint32_t c = 0; c < nd; ++c) {
+                if (cod.csgnd[c] || (cod.mct && (c == 1 || c == 2))) continue;
+                const TileComp &TC = g.tiles[t].comps[c];
+                const Resolution &Rs = TC.res[R];
+                FillJob j{};
+                j.w = Rs.x1 - Rs.x0; j.h = Rs.y1 - Rs.y0;
+                if (j.w <= 0 || j.h <= 0) continue;
+                j.off = (long long)(f * frame_words) + (long long)c * (long long)plane_elems +
+                        (long long)(ceildivpow2(TC.y0, (int)reduce) - S.poy[c]) * (long long)stride + (ceildivpow2(TC.x0, (int)reduce) - S.pox[c]);
+                const int dc = 1 << (cod.cprec[c] - 1);
+                if (cod.reversible) j.word = (unsigned)-dc;
+                else { const float v = -(float)dc; std::memcpy(&j.word, &v, sizeof v); }
+                fills.push_back(j);
+                fill_w = std::max(fill_w, j.w); fill_h = std::max(fill_h, j.h);
+            }
+        }
+    }
+
     // ---- tables to the device
     const size_t nb = M.blocks.size(), nseg = M.segs.size();
     // Tier-1 kernel.  A lane per block (t1_dec_lane.h): all its waves are resident at once, so the launch lasts as long as
@@ -565,12 +594,13 @@ void decode_group(j2k_hip_encoder *e, const DecodeCall &call, const Shape &S, De
     const size_t nl = nb - nheavy;
     std::vector<DecGroupDev> groups(lanes ? (nl + 63) / 64 : 0);
 
-    // one pinned table: block table | groups | seg dst | seg src | seg len | codeword segments | frame descriptors
+    // one pinned table: block table | groups | seg dst | seg src | seg len | codeword segments | frame descriptors | fill jobs
     const size_t grp_base = round_up(nb * sizeof(DecBlkDev), 16);
     const size_t seg_base = grp_base + round_up(groups.size() * sizeof(DecGroupDev), 16);
     const size_t cwseg_base = round_up(seg_base + nseg * (8 + 8 + 4), 16);
     const size_t desc_base = round_up(cwseg_base + M.cwsegs.size() * sizeof(uint32_t), 16);
-    const size_t tab_bytes = desc_base + desc.size() * sizeof(DecSeqFrameDev) + 64;
+    const size_t fill_base = round_up(desc_base + desc.size() * sizeof(DecSeqFrameDev), 16);
+    const size_t tab_bytes = fill_base + fills.size() * sizeof(FillJob) + 64;
     e->h_dtab.ensure(tab_bytes);
     e->d_dblk.ensure(tab_bytes);
     uint8_t *ht = e->h_dtab.as<uint8_t>();
@@ -619,6 +649,7 @@ void decode_group(j2k_hip_encoder *e, const DecodeCall &call, const Shape &S, De
     for (size_t i = 0; i < nseg; ++i) { h_sdst[i] = M.segs[i].dst; h_ssrc[i] = M.segs[i].src; h_slen[i] = M.segs[i].len; }
     if (!M.cwsegs.empty()) std::memcpy(ht + cwseg_base, M.cwsegs.data(), M.cwsegs.size() * sizeof(uint32_t));
     if (!desc.empty()) std::memcpy(ht + desc_base, desc.data(), desc.size() * sizeof(DecSeqFrameDev));
+    if (!fills.empty()) std::memcpy(ht + fill_base, fills.data(), fills.size() * sizeof(FillJob));
     HIP_CHECK(hipMemcpyAsync(e->d_dblk.p, ht, tab_bytes, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipEventRecord(e->ev[EV_UPLOAD], s));
 
@@ -763,6 +794,10 @@ void decode_group(j2k_hip_encoder *e, const DecodeCall &call, const Shape &S, De
             launch_idwt_level(ia, s);
             HIP_CHECK(hipGetLastError());
         }
+    }
+    if (!fills.empty()) { // tiles that never arrived (above): whole or windowed, the planes' layout is the same
+        launch_fill_rects(e->Z.p, (long long)stride, reinterpret_cast<const FillJob *>(e->d_dblk.as<uint8_t>() + fill_base), (int)fills.size(), fill_w, fill_h, s);
+        HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(hipEventRecord(e->ev[EV_DWT], s));
 

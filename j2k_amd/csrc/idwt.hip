@@ -335,6 +335,18 @@ __global__ __launch_bounds__(256) void decode_output_seq_kernel(DecOutArgs a, co
     }
 }
 
+// kernels.h: FillJob.  Jobs by blockIdx.z, a job's rows by blockIdx.y, 256 columns a workgroup; every index is checked
+// against the job's own size, so a grid sized by the largest job writes nothing outside a smaller one.
+__global__ __launch_bounds__(256) void fill_rects_kernel(unsigned *__restrict__ a, long long stride, const FillJob *__restrict__ jobs, int njobs)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    for (int j = blockIdx.z; j < njobs; j += gridDim.z) {
+        const FillJob J = jobs[j];
+        if (x >= J.w) continue;
+        for (int y = blockIdx.y; y < J.h; y += gridDim.y) a[J.off + (long long)y * stride + x] = J.word;
+    }
+}
+
 bool float_channels(const DecOutArgs &a)
 {
     for (int c = 0; c < a.nout && c < a.ncomp; ++c)
@@ -343,6 +355,13 @@ bool float_channels(const DecOutArgs &a)
 }
 
 } // namespace
+
+void launch_fill_rects(void *a, long long stride, const FillJob *jobs, int njobs, int max_w, int max_h, hipStream_t s)
+{
+    if (njobs <= 0 || max_w <= 0 || max_h <= 0) return;
+    const dim3 grid((unsigned)((max_w + 255) / 256), (unsigned)std::min(max_h, 64), (unsigned)std::min(njobs, 65535));
+    hipLaunchKernelGGL(fill_rects_kernel, grid, dim3(256), 0, s, static_cast<unsigned *>(a), stride, jobs, njobs);
+}
 
 void launch_idwt_level(const IdwtArgs &a, hipStream_t s)
 {

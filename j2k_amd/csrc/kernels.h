@@ -348,6 +348,17 @@ struct IdwtWinArgs {
 void idwt_window_items(const IdwtWinJob &j, int &h_items, int &v_items);
 void launch_idwt_window_level(const IdwtWinArgs &a, hipStream_t s);
 
+// Rectangles of the component planes set to one word each, between the inverse DWT and the output stage: the tiles of a file
+// cut short for which no tile-part arrived (decode_plan.h: DecodePlan::tile_arrived).  The word is the one the output stage
+// turns into component value 0, so every conversion behind it runs as it does for a decoded 0.  jobs: device memory.
+struct FillJob {
+    long long off;     // element offset of the rectangle's top-left in the planes
+    int w, h;
+    unsigned word;
+    unsigned pad;
+};
+void launch_fill_rects(void *a, long long stride, const FillJob *jobs, int njobs, int max_w, int max_h, hipStream_t s);
+
 // Inverse component transform, DC level shift, clamp, and Codec::CopyBuffer towards the destination channels
 // (reference: src/common/j2k_codec.cpp:222-427): writes only the samples of the destination channels.
 struct DecOutArgs {
