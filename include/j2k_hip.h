@@ -35,7 +35,10 @@ enum {
     J2K_HIP_ERR_PARAM = 1,    /* bad argument / unsupported coding parameter               */
     J2K_HIP_ERR_DEVICE = 2,   /* HIP runtime error (message holds hipGetErrorString)        */
     J2K_HIP_ERR_MEMORY = 3,   /* host or device allocation failed                            */
-    J2K_HIP_ERR_OVERFLOW = 4, /* an internal or caller buffer was too small                  */
+    J2K_HIP_ERR_OVERFLOW = 4, /* an internal or caller buffer was too small -- or, from an encode, "code-block has more
+                               * bit-planes than its sub-band signals (guard bits exceeded)": a coefficient of the frame
+                               * outgrew the Mb = exponent + guard bits - 1 bit-planes its sub-band's QCD entry allows (two
+                               * guard bits).  The frame is refused, never written wrongly           */
     J2K_HIP_ERR_SINK = 5,     /* the sink's write callback reported a short write            */
     J2K_HIP_ERR_UNSUPPORTED = 6 /* decode only: a well-formed file that uses a JPEG 2000 feature this decoder does
                                  * not implement (the text names it).  A host that has another reader -- the
@@ -278,6 +281,14 @@ const char *j2k_hip_last_error(const j2k_hip_encoder *enc); /* never NULL; enc m
  * RGBAoutputFile's channelMap, reference: src/common/j2k_rgba_file.cpp:763-813). */
 int j2k_hip_encode(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes,
                    j2k_hip_write_fn write, void *user);
+/* When an encode fails.  The sink sees the file's first byte only after the whole file has been planned (host Tier-2), in
+ * the one-piece and in the band-pipelined path alike: a failure up to there -- every J2K_HIP_ERR_OVERFLOW of a frame that
+ * exceeds its guard bits, every Tier-1 error -- returns its code with NOT ONE BYTE handed to the sink, and the buffer
+ * and device entry points write neither their output pointers nor *len / *out_len nor a byte of the caller's buffer (the
+ * caller's values stand; nothing is a file's length).  Only J2K_HIP_ERR_SINK (a short write), a device error during the
+ * download and a caller buffer too small for the planned file (J2K_HIP_ERR_OVERFLOW with the file's length reported) come
+ * later: what a sink holds then is a prefix of the file and is to be discarded.  After any failure the handle is
+ * drained -- nothing pending, nothing in flight -- and takes the next frame, of the same geometry or another. */
 
 /* The same call cut in two, for a host that pipelines the frames of an image sequence from ONE thread over
  * several handles (the reference's frame loop, src/aftereffects/FrameSeq.cpp:1211-1372, calls WriteFile once
@@ -931,6 +942,20 @@ int j2k_hip_get_dwt_level_ms(const j2k_hip_encoder *enc, double *ms, int cap);
  * is read once at first use).  Knobs move work between streams, CUs and launch shapes; no knob changes an
  * output byte.  Returns J2K_HIP_ERR_PARAM for an unknown key. */
 int j2k_hip_debug_tune(const char *key, int value);
+/* Host-only hooks for the tests (no handle, no device; the error text through j2k_hip_last_error(NULL)).
+ * j2k_hip_debug_cblk_capacities: the slot a frame gives a code-block of `area` samples in a sub-band of Mb bit-planes under
+ * cblk_style -- bytes of decisions and of codewords (the one rule, cblk_capacities).
+ * j2k_hip_debug_blocks: the code-blocks of a frame of `params` in the order of the encoder's tables (Tier-2 packet order),
+ * ten words each: tile, component, resolution, band inside the resolution, orientation, x, y (in the component's Mallat
+ * plane), width, height, Mb.  *nblocks receives their number (rows == NULL: only that); J2K_HIP_ERR_OVERFLOW when cap is
+ * less.
+ * j2k_hip_debug_tier2: host Tier-2 alone on per-block results in that order (no code-block style): pricer == 0 plans the
+ * codestream (*total_len = its length), pricer != 0 constructs the rate control's TilePricer of every tile.  Returns what
+ * an encode whose Tier-1 reported these results returns. */
+int j2k_hip_debug_cblk_capacities(uint32_t area, uint32_t Mb, uint32_t cblk_style, uint64_t *decisions, uint64_t *codeword);
+int j2k_hip_debug_blocks(const j2k_hip_params *params, uint32_t *rows, size_t cap, size_t *nblocks);
+int j2k_hip_debug_tier2(const j2k_hip_params *params, const uint32_t *numbps, const uint32_t *npasses, const uint32_t *length,
+                        size_t nblocks, int pricer, uint64_t *total_len);
 /* The knob's current value through *value (tests restore what they change). */
 int j2k_hip_debug_get_tune(const char *key, int *value);
 /* Waves per SIMD the fused front end + level-1 DWT kernel reaches by its register count AS BUILT (read from the code object;

@@ -102,7 +102,8 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_stage_rate", "j2k_hip_stage_gather", "j2k_hip_stage_pack_offsets",
            "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_t1_decode_styled", "j2k_hip_stage_decode_output",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
-           "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink"]
+           "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink",
+           "j2k_hip_debug_cblk_capacities", "j2k_hip_debug_blocks", "j2k_hip_debug_tier2"]
 
 class IdwtRegion(C.Structure):
     """include/j2k_hip.h: j2k_hip_idwt_region."""
@@ -286,6 +287,10 @@ def load_library():
     L.j2k_hip_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.j2k_hip_memcpy_d2h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.j2k_hip_synchronize.argtypes = [C.c_void_p]
+    if hasattr(L, "j2k_hip_debug_tier2"):  # (an earlier build loaded through J2K_HIP_LIB for an A/B run has none)
+        L.j2k_hip_debug_cblk_capacities.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.j2k_hip_debug_blocks.argtypes = [C.POINTER(Params), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.j2k_hip_debug_tier2.argtypes = [C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 
@@ -462,6 +467,46 @@ def read_profile(data: bytes) -> int:
     if rc != 0:
         raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
     return v.value
+
+
+def cblk_capacities(area: int, Mb: int, cblk_style: int = 0):
+    """(decision bytes, codeword bytes) of the slot a frame gives a code-block (j2k_hip_debug_cblk_capacities; no device needed)."""
+    L = load_library()
+    sym, out = C.c_uint64(), C.c_uint64()
+    rc = L.j2k_hip_debug_cblk_capacities(area, Mb, cblk_style, C.byref(sym), C.byref(out))
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+    return sym.value, out.value
+
+
+BLOCK_COLUMNS = ("tile", "comp", "res", "band", "orient", "x", "y", "w", "h", "Mb")
+
+
+def frame_blocks(params: Params) -> np.ndarray:
+    """The code-blocks of a frame in the order of the encoder's tables, (n, 10) uint32 with the columns BLOCK_COLUMNS
+    (j2k_hip_debug_blocks; no device needed)."""
+    L = load_library()
+    n = C.c_size_t()
+    rc = L.j2k_hip_debug_blocks(C.byref(params), None, 0, C.byref(n))
+    rows = np.zeros((n.value, len(BLOCK_COLUMNS)), np.uint32)
+    if rc == 0:
+        rc = L.j2k_hip_debug_blocks(C.byref(params), rows.ctypes.data, n.value, C.byref(n))
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+    return rows
+
+
+def host_tier2(params: Params, numbps, npasses, length, pricer: bool = False) -> int:
+    """Host Tier-2 alone on per-block results in frame_blocks order (j2k_hip_debug_tier2; no device needed): the planned
+    codestream's length, or with pricer the rate control's TilePricer of every tile (0).  Raises what an encode would."""
+    L = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.uint32) for v in (numbps, npasses, length)]
+    assert a[0].shape == a[1].shape == a[2].shape and a[0].ndim == 1
+    total = C.c_uint64()
+    rc = L.j2k_hip_debug_tier2(C.byref(params), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[0].size, int(pricer), C.byref(total))
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+    return total.value
 
 
 def file_header(params: Params, codestream_len: int) -> bytes:

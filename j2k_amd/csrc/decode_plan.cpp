@@ -642,7 +642,12 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const u
                     BlockState &bs = st[t.id];
                     // A block of numbps bit-planes (a region-of-interest shift included) has 3 numbps - 2 coding passes at most: more is a
                     // malformed file, rejected here -- the device tables are sized by this bound and nothing downstream clamps silently.
-                    if (bs.seen_passes + t.np > (uint32_t)kMaxPasses + 13 || (bs.numbps && bs.seen_passes + t.np > 3 * bs.numbps - 2))
+                    // One exception, blocks of one codeword segment only: libopenjp2 writes a block that outgrew its guard bits
+                    // with zero-bit-plane count 0 and all its 3 (Mb + 1) - 2 passes, and its decoder -- like the
+                    // oracle's -- stops at the last bit-plane whatever the header promised.  Up to three passes beyond the bound
+                    // are read the same way here: t1dec_passes (decode_plan.h) drops them, the segment's bytes stay whole.
+                    const uint32_t slack = multiseg ? 0u : 3u;
+                    if (bs.seen_passes + t.np > (uint32_t)kMaxPasses + 13 || (bs.numbps && bs.seen_passes + t.np > 3 * bs.numbps - 2 + slack))
                         bad("code-block with more coding passes than its bit-planes allow");
                     bs.seen_passes += t.np;
                     if (l >= keep_layers) { p += t.len; continue; } // a dropped layer: parsed, its bytes skipped
@@ -719,7 +724,7 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const u
         if (!bs.included || !t1dec_passes(bs.numbps, bs.npasses) || g.cblks[id].res > top_res || g.cblks[id].comp >= 4) continue; // (components beyond the fourth are parsed, not decoded)
         if (window && !wanted(g.cblks[id])) continue; // no DecBlock, no gather segments, no arena bytes
         DecBlock db;
-        db.cblk = id; db.numbps = bs.numbps; db.npasses = bs.npasses;
+        db.cblk = id; db.numbps = bs.numbps; db.npasses = t1dec_passes(bs.numbps, bs.npasses); // (the passes beyond the last bit-plane dropped: the parse's exception)
         db.roishift = H.roishift[g.cblks[id].comp];
         db.cw_off = arena; db.cw_len = (uint32_t)bs.bytes;
         uint64_t dst = arena;

@@ -129,6 +129,9 @@ bool same_coding(const Coding &a, const Coding &b)
 // `style`: one rule for the frames (prepare_geometry) and for the Tier-1 stage hooks.  A frame passes the band's own Mb; the
 // hooks know no band and pass 30, so a hook's capacities are a frame's or larger (two to three times at the usual depths):
 // the hooks show that the rule holds the codewords of Mb = 30, not that a frame's smaller Mb does.
+// A frame's block can come with Mb + 1 bit-planes (a frame beyond its guard bits): the slots of Mb hold its
+// decisions and codeword all the same (tests/test_guard_bits_refs.py, on the oracle's decision streams), so such a frame ends
+// in Tier-2's J2K_HIP_ERR_OVERFLOW and not in a Tier-1 capacity error.
 CblkCaps j2k_hip::cblk_capacities(size_t area, uint32_t Mb, uint32_t style)
 {
     // <= 1.5 decisions per sample and bit-plane (ZC/MR + run-length overhead) + one sign each

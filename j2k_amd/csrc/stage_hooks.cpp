@@ -12,6 +12,7 @@
 #include "cblk_style.h"
 #include "handle.h"
 #include "rate_device.h"
+#include "tier2.h"
 
 using namespace j2k_hip;
 
@@ -568,6 +569,74 @@ int j2k_hip_stage_pack_offsets(j2k_hip_encoder *e, const uint32_t *len, uint32_t
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(dst, e->pack_dst.p, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
+} // extern "C"
+
+// ---- host-only hooks (no handle, no device): a frame's code-block table and host Tier-2 on block results the caller supplies
+namespace {
+template <typename F> int host_guarded(F &&f)
+{
+    try {
+        f();
+        return J2K_HIP_OK;
+    } catch (const Error &x) {
+        create_error() = x.what();
+        return x.code;
+    } catch (const std::exception &x) {
+        create_error() = x.what();
+        return J2K_HIP_ERR_PARAM;
+    }
+}
+} // namespace
+
+extern "C" {
+
+int j2k_hip_debug_cblk_capacities(uint32_t area, uint32_t Mb, uint32_t cblk_style, uint64_t *decisions, uint64_t *codeword)
+{
+    return host_guarded([&] {
+        if (!area || area > 4096 || Mb > 37) throw Error(J2K_HIP_ERR_PARAM, "code-block capacities: area must be 1..4096, Mb at most 37");
+        const CblkCaps caps = cblk_capacities(area, Mb, cblk_style);
+        if (decisions) *decisions = caps.sym;
+        if (codeword) *codeword = caps.out;
+    });
+}
+
+int j2k_hip_debug_blocks(const j2k_hip_params *params, uint32_t *rows, size_t cap, size_t *nblocks)
+{
+    return host_guarded([&] {
+        const Coding cod = normalise(params);
+        const Geometry g = build_geometry(cod, 0, cod.ntiles());
+        if (nblocks) *nblocks = g.cblks.size();
+        if (!rows) return;
+        if (g.cblks.size() > cap) throw Error(J2K_HIP_ERR_OVERFLOW, "block table too small");
+        for (size_t i = 0; i < g.cblks.size(); ++i) {
+            const Cblk &c = g.cblks[i];
+            const uint32_t r[10] = {c.tile, c.comp, c.res, c.band, c.orient, c.px, c.py, c.w, c.h, c.Mb};
+            std::memcpy(rows + 10 * i, r, sizeof r);
+        }
+    });
+}
+
+int j2k_hip_debug_tier2(const j2k_hip_params *params, const uint32_t *numbps, const uint32_t *npasses, const uint32_t *length,
+                        size_t nblocks, int pricer, uint64_t *total_len)
+{
+    return host_guarded([&] {
+        if (!numbps || !npasses || !length) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 hook: an array is NULL");
+        const Coding cod = normalise(params);
+        if (cod.cblk_style) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 hook: no code-block style (a styled block needs its per-pass byte counts)");
+        const Geometry g = build_geometry(cod, 0, cod.ntiles());
+        if (nblocks != g.cblks.size()) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 hook: the frame has " + std::to_string(g.cblks.size()) + " code-blocks");
+        std::vector<CblkResult> res(nblocks);
+        for (size_t i = 0; i < nblocks; ++i) res[i] = CblkResult{numbps[i], npasses[i], length[i]};
+        uint64_t total = 0;
+        if (pricer) {
+            for (const Tile &T : g.tiles) { TilePricer tp(g, T, res); total += tp.committed(); }
+        } else {
+            total = plan_codestream(g, res, true, true).total_len;
+        }
+        if (total_len) *total_len = total;
     });
 }
 
