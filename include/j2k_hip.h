@@ -38,7 +38,8 @@ enum {
     J2K_HIP_ERR_OVERFLOW = 4, /* an internal or caller buffer was too small -- or, from an encode, "code-block has more
                                * bit-planes than its sub-band signals (guard bits exceeded)": a coefficient of the frame
                                * outgrew the Mb = exponent + guard bits - 1 bit-planes its sub-band's QCD entry allows (two
-                               * guard bits).  The frame is refused, never written wrongly           */
+                               * guard bits unless j2k_hip_params.guard_bits says otherwise).  The
+                               * frame is refused, never written wrongly                                                  */
     J2K_HIP_ERR_SINK = 5,     /* the sink's write callback reported a short write            */
     J2K_HIP_ERR_UNSUPPORTED = 6 /* decode only: a well-formed file that uses a JPEG 2000 feature this decoder does
                                  * not implement (the text names it).  A host that has another reader -- the
@@ -194,7 +195,43 @@ typedef struct j2k_hip_params {
      * ended in alignment padding (LP64: 4 bytes behind rgb_to_sycc) the field takes that padding and sizeof does not move: a
      * caller of the older header that zero-initialises the whole struct, as the header has always asked for, passes 0. */
     uint32_t rgb_to_xyz;
+    /* ---- guard bits (T.800 A.6.4 Sqcd, E.1: a sub-band signals Mb = exponent + guard bits - 1 bit-planes).  A lossless frame
+     * under the reversible colour transform can hold code-blocks of Mb + 1 bit-planes at two guard bits;
+     * libopenjp2 writes such a frame wrongly, this library refuses it -- or, asked to, writes it with the guard bits it needs.
+     *     0                    two guard bits, what libopenjp2 writes: every byte, launch and statistic is what it was without
+     *                          the field; a frame beyond them is J2K_HIP_ERR_OVERFLOW.
+     *     1 .. 7               that many guard bits, strictly: Sqcd = style | g << 5, every band signals exponent + g - 1
+     *                          bit-planes (the code-block slots grow with them), a frame beyond them is refused alike.  2 writes
+     *                          the bytes of 0.
+     *     J2K_HIP_GUARD_AUTO | floor (floor 0 .. 7, 0 = 2)
+     *                          the smallest G >= floor at which no code-block has more bit-planes than its band signals:
+     *                          G = max(floor, max over the blocks of numbps - exponent(band) + 1), one G for the file (QCD is a
+     *                          main-header marker segment).  A frame in range at floor 2 is written byte for byte as with 0, at
+     *                          no launch, copy or wait more (j2k_hip_stats.bands is what it is without the field).  A frame
+     *                          beyond the floor is planned once more on the host from the Tier-1 results it has -- packet
+     *                          headers, QCD, tile-part lengths, and under layer_rates the layer allocation, on the host and on
+     *                          the device path alike -- and no kernel of the front end, the DWT or Tier-1 runs again: a block's
+     *                          decisions, passes and codeword do not depend on the guard bits.  More than 7, or more bit-planes
+     *                          than the reader takes, is J2K_HIP_ERR_OVERFLOW as with 0.
+     * What stays an error in every mode: a Tier-1 slot overflow -- the kernels' own "Tier-1 kernel reported error" (too many
+     * bit-planes for the pass tables, decision buffer, codeword buffer) -- is J2K_HIP_ERR_OVERFLOW and never a short block.
+     * J2K_HIP_ERR_PARAM, the text naming guard_bits, before any device work: any other value; a count that gives a sub-band
+     * more than the 30 bit-planes this library's own reader accepts in a code-block; a non-zero value with dci_profile (the
+     * profile is pinned to libopenjp2's bytes); J2K_HIP_GUARD_AUTO on the entry points that take or make a header without a
+     * frame -- j2k_hip_main_header, j2k_hip_encode_tiles, _encode_tiles_device, _encode_tiles_distributed (rank 0 writes the
+     * header before any tile is coded); a fixed count is fine there.
+     * Entry points: every one that writes a file -- j2k_hip_encode, _encode_to_buffer, _encode_begin / _end,
+     * _encode_begin_borrowed, _encode_device, _encode_sequence_device (each frame its own G), _encode_batch -- and the
+     * tile-sharded ones with a fixed count.  The band-pipelined call writes at the floor while its stages come down and, where a
+     * stage's block exceeds it, plans the frame again once all stages are in: the sink sees nothing before the plan is final.
+     * j2k_hip_encode_get_guard_bits reports what the handle's last file got.  The read side takes the count from the file.
+     * J2K_HIP_ABI_VERSION is still 9: the field was appended and functions were added, none changed.  struct_size is the guard:
+     * sizeof(j2k_hip_params) of this header, or the size the struct had before the field (it ended behind rgb_to_xyz), which
+     * reads as guard_bits 0. */
+    uint32_t guard_bits;
 } j2k_hip_params;
+
+#define J2K_HIP_GUARD_AUTO 0x100u /* OR-ed with the floor, 0 .. 7 (0 = 2) */
 
 enum { J2K_HIP_CBLK_BYPASS = 1, J2K_HIP_CBLK_RESET = 2, J2K_HIP_CBLK_TERMALL = 4, J2K_HIP_CBLK_VCAUSAL = 8 /* decode only */,
        J2K_HIP_CBLK_PTERM = 16, J2K_HIP_CBLK_SEGSYM = 32 };
@@ -326,6 +363,16 @@ int j2k_hip_encode_device(j2k_hip_encoder *enc, const j2k_hip_params *params,
 int j2k_hip_encode_sequence_device(j2k_hip_encoder *enc, const j2k_hip_params *params,
                                    const j2k_hip_plane *planes, uint32_t nframes,
                                    const void **d_codestreams, size_t *lens);
+
+/* Guard bits (j2k_hip_params.guard_bits).  j2k_hip_encode_get_guard_bits: the count in the QCD of the last file the handle
+ * wrote -- of a sequence call its last frame's -- and 0 before any; a failed call leaves it alone.
+ * j2k_hip_guard_bits_needed: host only, no handle (error text through j2k_hip_last_error(NULL)): the rule the encoder uses,
+ * on per-block bit-plane counts in j2k_hip_debug_blocks order -- *g = max(floor, max over the blocks of numbps[i] -
+ * exponent(band of block i) + 1), the floor being the count `params` ask for (0 = 2, J2K_HIP_GUARD_AUTO | floor alike).
+ * J2K_HIP_ERR_OVERFLOW with the guard-bits text where that is more than 7 or gives a band more bit-planes than the reader
+ * takes; J2K_HIP_ERR_PARAM where nblocks is not the frame's number of code-blocks. */
+int j2k_hip_encode_get_guard_bits(const j2k_hip_encoder *enc, uint32_t *g);
+int j2k_hip_guard_bits_needed(const j2k_hip_params *params, const uint32_t *numbps, size_t nblocks, uint32_t *g);
 
 /* --- tile-sharded encode (multi-GPU) -----------------------------------------------
  * Encode only tiles [tile_first, tile_first+tile_count) of the image (raster tile index, Isot).
@@ -951,7 +998,12 @@ int j2k_hip_debug_tune(const char *key, int value);
  * less.
  * j2k_hip_debug_tier2: host Tier-2 alone on per-block results in that order (no code-block style): pricer == 0 plans the
  * codestream (*total_len = its length), pricer != 0 constructs the rate control's TilePricer of every tile.  Returns what
- * an encode whose Tier-1 reported these results returns. */
+ * an encode whose Tier-1 reported these results returns.  Both honour params.guard_bits: the Mb column moves with the count,
+ * and under J2K_HIP_GUARD_AUTO the hook plans (or prices) at the floor and, on an excess, once more at the count found --
+ * the encoder's own plan, excess, re-plan path.  j2k_hip_debug_tier2_guard is j2k_hip_debug_tier2 that also reports the
+ * count the plan was made with through *guard_bits. */
+int j2k_hip_debug_tier2_guard(const j2k_hip_params *params, const uint32_t *numbps, const uint32_t *npasses, const uint32_t *length,
+                              size_t nblocks, int pricer, uint64_t *total_len, uint32_t *guard_bits);
 int j2k_hip_debug_cblk_capacities(uint32_t area, uint32_t Mb, uint32_t cblk_style, uint64_t *decisions, uint64_t *codeword);
 int j2k_hip_debug_blocks(const j2k_hip_params *params, uint32_t *rows, size_t cap, size_t *nblocks);
 int j2k_hip_debug_tier2(const j2k_hip_params *params, const uint32_t *numbps, const uint32_t *npasses, const uint32_t *length,

@@ -43,7 +43,10 @@ class Params(C.Structure):
                 ("dci_profile", C.c_uint32), ("max_cs_size", C.c_uint32), ("max_comp_size", C.c_uint32),
                 ("cblk_style", C.c_uint32),
                 ("comp_sub_x", C.c_uint32 * 4), ("comp_sub_y", C.c_uint32 * 4), ("rgb_to_sycc", C.c_uint32),
-                ("rgb_to_xyz", C.c_uint32)]
+                ("rgb_to_xyz", C.c_uint32), ("guard_bits", C.c_uint32)]
+
+
+GUARD_AUTO = 0x100  # J2K_HIP_GUARD_AUTO: OR-ed with a floor of 0..7 (0 = 2)
 
 
 class Plane(C.Structure):
@@ -103,7 +106,8 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_t1_decode_styled", "j2k_hip_stage_decode_output",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink",
-           "j2k_hip_debug_cblk_capacities", "j2k_hip_debug_blocks", "j2k_hip_debug_tier2"]
+           "j2k_hip_debug_cblk_capacities", "j2k_hip_debug_blocks", "j2k_hip_debug_tier2",
+           "j2k_hip_encode_get_guard_bits", "j2k_hip_guard_bits_needed", "j2k_hip_debug_tier2_guard"]
 
 class IdwtRegion(C.Structure):
     """include/j2k_hip.h: j2k_hip_idwt_region."""
@@ -291,6 +295,10 @@ def load_library():
         L.j2k_hip_debug_cblk_capacities.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.j2k_hip_debug_blocks.argtypes = [C.POINTER(Params), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         L.j2k_hip_debug_tier2.argtypes = [C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
+    if hasattr(L, "j2k_hip_guard_bits_needed"):
+        L.j2k_hip_encode_get_guard_bits.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        L.j2k_hip_guard_bits_needed.argtypes = [C.POINTER(Params), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.j2k_hip_debug_tier2_guard.argtypes = L.j2k_hip_debug_tier2.argtypes + [C.POINTER(C.c_uint32)]
     _lib = L
     return L
 
@@ -376,12 +384,13 @@ def make_params(width, height, channels, depth, reversible=True, ycc=False, laye
                 num_resolutions=6, cblk=(64, 64), promote=False, comment="", jp2=False, color_space=0,
                 alpha_channel=-1, alpha_premultiplied=False, icc=None, rates=None, psnr=None, progression=0,
                 pixel_aspect=None, dpi=0.0, precincts=None, dci_profile=0, max_cs_size=0, max_comp_size=0, cblk_style=0,
-                sub=None, rgb_to_sycc=False, rgb_to_xyz=0):
+                sub=None, rgb_to_sycc=False, rgb_to_xyz=0, guard_bits=0):
     """comment: None -> library default COM, "" -> no COM segment.  jp2/color_space/alpha_channel/icc describe
     the JP2 file wrapper (color_space in OPJ_COLOR_SPACE numbering: 1 sRGB, 2 grey, 3 sYCC).
     sub = [(dx, dy), ...]: the sub-sampling factors of the components (SIZ XRsiz / YRsiz), one pair per channel; rgb_to_sycc:
     the planes are R, G, B[, A] of the full image and the library makes Y, Cb, Cr[, A] at those factors.  rgb_to_xyz: channels
-    0..2 are R'G'B' (1 sRGB, 2 Rec.709 under a 2.4 power, 3 linear Rec.709) and the library makes cinema X'Y'Z' codes of them."""
+    0..2 are R'G'B' (1 sRGB, 2 Rec.709 under a 2.4 power, 3 linear Rec.709) and the library makes cinema X'Y'Z' codes of them.
+    guard_bits: 0 = two, strictly; 1..7 = that many, strictly; GUARD_AUTO | floor = as many as the frame needs, the floor at least."""
     p = Params()
     p.struct_size = C.sizeof(Params)
     p.width, p.height, p.channels, p.depth = width, height, channels, depth
@@ -400,6 +409,7 @@ def make_params(width, height, channels, depth, reversible=True, ycc=False, laye
             p.comp_sub_x[c], p.comp_sub_y[c] = dx, dy
     p.rgb_to_sycc = int(rgb_to_sycc)
     p.rgb_to_xyz = int(rgb_to_xyz)
+    p.guard_bits = int(guard_bits)
     p.cblk_style = cblk_style  # COD SPcod code-block style: 1 bypass, 2 reset, 4 termall, 16 pterm, 32 segsym, in any combination
     if precincts:  # [(w, h), ...] highest resolution first (OpenJPEG's -c / res_spec semantics)
         p.num_precincts = len(precincts)
@@ -496,17 +506,34 @@ def frame_blocks(params: Params) -> np.ndarray:
     return rows
 
 
-def host_tier2(params: Params, numbps, npasses, length, pricer: bool = False) -> int:
+def host_tier2(params: Params, numbps, npasses, length, pricer: bool = False, with_guard: bool = False):
     """Host Tier-2 alone on per-block results in frame_blocks order (j2k_hip_debug_tier2; no device needed): the planned
-    codestream's length, or with pricer the rate control's TilePricer of every tile (0).  Raises what an encode would."""
+    codestream's length, or with pricer the rate control's TilePricer of every tile (0).  Raises what an encode would.
+    with_guard: (that, the guard bits the plan was made with) -- params.guard_bits is honoured, GUARD_AUTO included."""
     L = load_library()
     a = [np.ascontiguousarray(v, dtype=np.uint32) for v in (numbps, npasses, length)]
     assert a[0].shape == a[1].shape == a[2].shape and a[0].ndim == 1
-    total = C.c_uint64()
-    rc = L.j2k_hip_debug_tier2(C.byref(params), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[0].size, int(pricer), C.byref(total))
+    total, guard = C.c_uint64(), C.c_uint32()
+    if with_guard:
+        rc = L.j2k_hip_debug_tier2_guard(C.byref(params), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[0].size, int(pricer),
+                                         C.byref(total), C.byref(guard))
+    else:
+        rc = L.j2k_hip_debug_tier2(C.byref(params), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[0].size, int(pricer), C.byref(total))
     if rc != 0:
         raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
-    return total.value
+    return (total.value, guard.value) if with_guard else total.value
+
+
+def guard_bits_needed(params: Params, numbps) -> int:
+    """The smallest guard-bit count at or above the one `params` ask for that holds blocks of `numbps` bit-planes, frame_blocks
+    order (j2k_hip_guard_bits_needed; no device needed): the rule an encode under GUARD_AUTO uses."""
+    L = load_library()
+    a = np.ascontiguousarray(numbps, dtype=np.uint32)
+    g = C.c_uint32()
+    rc = L.j2k_hip_guard_bits_needed(C.byref(params), a.ctypes.data, a.size, C.byref(g))
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+    return g.value
 
 
 def file_header(params: Params, codestream_len: int) -> bytes:
@@ -1033,6 +1060,12 @@ class Encoder:
         s = Stats()
         self._check(self.L.j2k_hip_get_stats(self.h, C.byref(s)))
         return s.as_dict()
+
+    def guard_bits(self) -> int:
+        """Guard bits in the QCD of the last file this handle wrote (j2k_hip_encode_get_guard_bits); 0 before any."""
+        g = C.c_uint32()
+        self._check(self.L.j2k_hip_encode_get_guard_bits(self.h, C.byref(g)))
+        return g.value
 
     def dwt_time(self, first: int, count: int, repeat: int = 20) -> float:
         """Mean device time (ms) of the DWT launches of levels [first, first+count) of the last encode, replayed back to back."""

@@ -4,7 +4,9 @@
 // encode entry point fixes (reference: src/common/j2k_openjpeg_codec.cpp:627-719).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <functional>
 #include <stdexcept>
 #include <string>
@@ -20,8 +22,29 @@ struct Error : std::runtime_error {
 };
 
 constexpr int kFracBits = 6;     // T1 fractional bits below bit-plane 0 (T1_NMSEDEC_FRACBITS)
-constexpr int kGuardBits = 2;    // QCD guard bits
+constexpr int kGuardBits = 2;    // QCD guard bits unless the parameters say otherwise (Coding::guard)
+constexpr int kMaxGuardBits = 7; // ... and the most the three bits of Sqcd hold
 constexpr int kMaxPasses = 96;   // 3*Mb-2 with Mb <= 32
+constexpr int kMaxBitplanes = 30; // the most bit-planes the reader takes in a code-block (decode_plan.cpp; libopenjp2's limit)
+
+// A code-block has more bit-planes than its sub-band signals: the J2K_HIP_ERR_OVERFLOW of a frame beyond its guard bits, thrown
+// by host Tier-2 where it meets a negative zero-bit-plane count.  A type of its own so that a caller under J2K_HIP_GUARD_AUTO
+// can tell it from every other overflow and plan the frame again with the guard bits it needs.
+struct GuardExcess : Error {
+    GuardExcess() : Error(J2K_HIP_ERR_OVERFLOW, "code-block has more bit-planes than its sub-band signals (guard bits exceeded)") {}
+};
+
+// struct_size of j2k_hip_params before guard_bits was appended: such a caller passes guard_bits 0
+constexpr size_t kParamsSizeBeforeGuardBits = offsetof(j2k_hip_params, guard_bits);
+inline bool params_size_ok(const j2k_hip_params *p) { return p->struct_size == sizeof(j2k_hip_params) || p->struct_size == kParamsSizeBeforeGuardBits; }
+// the caller's struct widened to this library's layout (what lies beyond its struct_size is not read)
+inline j2k_hip_params widened(const j2k_hip_params *p)
+{
+    j2k_hip_params q = {};
+    std::memcpy(&q, p, p->struct_size == kParamsSizeBeforeGuardBits ? kParamsSizeBeforeGuardBits : sizeof q);
+    q.struct_size = sizeof q;
+    return q;
+}
 constexpr int kPrecinctExp = 15; // maximal precincts (PPx = PPy = 15): the default, no SPcod precinct bytes
 
 struct Coding {
@@ -41,6 +64,10 @@ struct Coding {
     // encode: channels 0..2 are R'G'B' and the front end makes cinema X'Y'Z' code values of them (0 = off; 1 sRGB, 2 Rec.709 under
     // a 2.4 power, 3 linear Rec.709; xyz_tables.h)
     uint32_t rgb_to_xyz = 0;
+    // encode: QCD guard bits (every band signals expn + guard - 1 bit-planes).  guard_auto: `guard` is the floor, and a frame whose
+    // blocks outgrow it is planned again with the smallest count that holds them (j2k_hip_params.guard_bits)
+    uint32_t guard = kGuardBits;
+    bool guard_auto = false;
     uint32_t dci_tileparts() const { return dci == 4 ? 6u : (dci == 3 ? 3u : 1u); }
     // per component: sub-sampling factors on the reference grid (decode: whatever SIZ holds; encode: comp_sub_x / _y, 1, 2 or 4, the
     // reference's own encode call never sub-samples), and -- decode only, the encode path writes one unsigned depth -- precision, signedness
@@ -83,6 +110,8 @@ struct Coding {
 // Validates exactly what the reference path would reject (OpenJPEG setup/validation errors) plus
 // the limits of this implementation; throws Error(J2K_HIP_ERR_PARAM, ...).
 Coding normalise(const j2k_hip_params *p);
+// Why `guard` guard bits cannot be written for these parameters (null: they can)
+const char *guard_bits_refusal(const Coding &c, uint32_t guard);
 // The tile-sharded entry points do not write sub-sampled components (a tile range whose origin is no multiple of the factors):
 // throws Error(J2K_HIP_ERR_PARAM, ...) for such parameters.  Host code: called before any device work.
 void refuse_subsampled_tiles(const Coding &cod);

@@ -31,7 +31,7 @@ struct Source {
 Source source_of(const j2k_hip_params *p)
 {
     if (!p) throw Error(J2K_HIP_ERR_PARAM, "params is NULL");
-    if (p->struct_size != sizeof(j2k_hip_params)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_params.struct_size mismatch (ABI drift)");
+    if (!params_size_ok(p)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_params.struct_size mismatch (ABI drift)");
     j2k_hip_params q{};
     q.struct_size = sizeof(q);
     q.width = p->width; q.height = p->height; q.channels = p->channels; q.depth = p->depth;

@@ -587,7 +587,7 @@ DecodePlan plan_decode(const uint8_t *file, size_t len, uint32_t reduce, const u
                                 // (a region of interest by MAXSHIFT adds its shift to the planes that are coded: H.1, libopenjp2's bpno_plus_one)
                                 if (band_bps + 1 - i < 0) bad("code-block with an impossible number of bit-planes");
                                 const int nb = band_bps + 1 - i + (int)H.roishift[c];
-                                if (nb > 30) { if (H.roishift[c]) unsupported("region-of-interest shift beyond 30 bit-planes"); bad("code-block with an impossible number of bit-planes"); } // (libopenjp2: bpno_plus_one >= 31 is an error)
+                                if (nb > kMaxBitplanes) { if (H.roishift[c]) unsupported("region-of-interest shift beyond 30 bit-planes"); bad("code-block with an impossible number of bit-planes"); } // (libopenjp2: bpno_plus_one >= 31 is an error)
                                 bs.numbps = (uint32_t)nb; bs.lenbits = 3; bs.included = true;
                             }
                             if (l >= keep_layers && !bs.cut) { // the block's first dropped contribution: freeze what is kept

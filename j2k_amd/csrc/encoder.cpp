@@ -120,6 +120,7 @@ bool same_coding(const Coding &a, const Coding &b)
            a.cbw == b.cbw && a.cbh == b.cbh && a.tile_w == b.tile_w && a.tile_h == b.tile_h &&
            std::memcmp(a.ppx, b.ppx, sizeof a.ppx) == 0 && std::memcmp(a.ppy, b.ppy, sizeof a.ppy) == 0 && a.prog == b.prog &&
            a.cblk_style == b.cblk_style && // (a style changes the codeword capacities)
+           a.guard == b.guard && // (... and so do the guard bits, through every band's Mb)
            std::memcmp(a.cdx, b.cdx, sizeof a.cdx) == 0 && std::memcmp(a.cdy, b.cdy, sizeof a.cdy) == 0;
 }
 
@@ -131,7 +132,8 @@ bool same_coding(const Coding &a, const Coding &b)
 // the hooks show that the rule holds the codewords of Mb = 30, not that a frame's smaller Mb does.
 // A frame's block can come with Mb + 1 bit-planes (a frame beyond its guard bits): the slots of Mb hold its
 // decisions and codeword all the same (tests/test_guard_bits_refs.py, on the oracle's decision streams), so such a frame ends
-// in Tier-2's J2K_HIP_ERR_OVERFLOW and not in a Tier-1 capacity error.
+// in Tier-2's J2K_HIP_ERR_OVERFLOW and not in a Tier-1 capacity error -- or, under J2K_HIP_GUARD_AUTO, is planned again with
+// more guard bits from the very slots it was coded into.  A fixed guard-bit count above two raises Mb and the slots with it.
 CblkCaps j2k_hip::cblk_capacities(size_t area, uint32_t Mb, uint32_t style)
 {
     // <= 1.5 decisions per sample and bit-plane (ZC/MR + run-length overhead) + one sign each
@@ -570,6 +572,8 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     if (F > 1 && (!planes_on_device || !framed)) throw Error(J2K_HIP_ERR_PARAM, "frame sequences take whole frames resident on the device");
     const Coding cod = normalise(params); // (before the device is touched: what is refused for its parameters costs no device work)
     if (!framed) refuse_subsampled_tiles(cod);
+    if (!framed && cod.guard_auto) // (rank 0 writes the main header, QCD in it, before any tile is coded)
+        throw Error(J2K_HIP_ERR_PARAM, "guard_bits: J2K_HIP_GUARD_AUTO is not taken by the tile-sharded entry points (the main header is made without the frame); give a fixed count");
     for (size_t i = 0; i < F * cod.ncomp; ++i) check_plane(cod, planes[i]);
     HIP_CHECK(hipSetDevice(e->device));
     const Tuning tn = tuning(); // one consistent snapshot per call
@@ -871,6 +875,7 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
     std::vector<size_t> plan_off(F), cs_off(F);
     size_t plan_total = 0, cs_total = 0;
     const size_t nbd = rate_control ? 0 : nb1; // per-block destinations or per-layer pieces
+    uint32_t guard = cod.guard; // of the frame planned last
     {
         Range r("j2k_hip tier2 host");
         for (size_t f = 0; f < F; ++f) {
@@ -879,42 +884,55 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
             for (size_t i = 0; i < nb1; ++i) res[i] = CblkResult{tt.numbps(hm)[b0 + i], tt.npasses(hm)[b0 + i], tt.len(hm)[b0 + i]};
             if (cod.cblk_style) // (styled frames: h_passes holds the byte counts per pass alone)
                 for (size_t i = 0; i < nb1; ++i) res[i].rates = e->h_passes.as<uint32_t>() + tt.row(b0 + i);
-            LayerAlloc alloc;
-            if (rate_control) {
-                const uint32_t *hp = e->h_passes.as<uint32_t>(); // [nmsedec | rate]
-                const uint32_t *h_rate = tt.h_rate(hp) + tt.row(b0), *h_nmsedec = hp + tt.row(b0);
+            // the frame's plan under the guard bits of `gg`: the layer allocation (its header bits hold the zero-bit-plane
+            // counts), then the codestream
+            auto plan_frame = [&](const Geometry &gg) -> Tier2Plan {
+                LayerAlloc alloc;
+                if (rate_control) {
+                    const uint32_t *hp = e->h_passes.as<uint32_t>(); // [nmsedec | rate]
+                    const uint32_t *h_rate = tt.h_rate(hp) + tt.row(b0), *h_nmsedec = hp + tt.row(b0);
 #ifdef J2K_ALLOC_DUMP
-                // tools/alloc_probe.cpp works on real Tier-1 results: one frame's allocation inputs, written once
-                if (pd.rc_tables_pending) { HIP_CHECK(hipEventSynchronize(e->rc_tables)); pd.rc_tables_pending = false; }
-                if (const char *path = std::getenv("J2K_ALLOC_DUMP")) {
-                    static bool dumped = false;
-                    if (!dumped && f == 0) {
-                        dumped = true;
-                        if (FILE *fp = std::fopen(path, "wb")) {
-                            const uint32_t head[10] = {(uint32_t)nb1, (uint32_t)kDevMaxPasses, cod.width, cod.height, cod.ncomp, cod.prec,
-                                                       cod.reversible ? 1u : 0u, cod.numres, 1u << cod.cbw, 1u << cod.cbh};
-                            std::fwrite(head, 4, 10, fp);
-                            for (size_t i = 0; i < nb1; ++i) {
-                                const uint32_t r3[3] = {res[i].numbps, res[i].npasses, res[i].len};
-                                std::fwrite(r3, 4, 3, fp);
-                                std::fwrite(h_rate + tt.row(i), 4, res[i].npasses, fp);
-                                std::fwrite(h_nmsedec + tt.row(i), 4, res[i].npasses, fp);
+                    // tools/alloc_probe.cpp works on real Tier-1 results: one frame's allocation inputs, written once
+                    if (pd.rc_tables_pending) { HIP_CHECK(hipEventSynchronize(e->rc_tables)); pd.rc_tables_pending = false; }
+                    if (const char *path = std::getenv("J2K_ALLOC_DUMP")) {
+                        static bool dumped = false;
+                        if (!dumped && f == 0) {
+                            dumped = true;
+                            if (FILE *fp = std::fopen(path, "wb")) {
+                                const uint32_t head[10] = {(uint32_t)nb1, (uint32_t)kDevMaxPasses, cod.width, cod.height, cod.ncomp, cod.prec,
+                                                           cod.reversible ? 1u : 0u, cod.numres, 1u << cod.cbw, 1u << cod.cbh};
+                                std::fwrite(head, 4, 10, fp);
+                                for (size_t i = 0; i < nb1; ++i) {
+                                    const uint32_t r3[3] = {res[i].numbps, res[i].npasses, res[i].len};
+                                    std::fwrite(r3, 4, 3, fp);
+                                    std::fwrite(h_rate + tt.row(i), 4, res[i].npasses, fp);
+                                    std::fwrite(h_nmsedec + tt.row(i), 4, res[i].npasses, fp);
+                                }
+                                std::fclose(fp);
                             }
-                            std::fclose(fp);
                         }
                     }
-                }
 #endif
-                std::unique_ptr<HipRateDevice> rdev;
-                if (pd.rc_device) rdev.reset(new HipRateDevice(e, tt));
-                const unsigned at = std::max(1u, std::min((unsigned)std::max(1, tuning().alloc_threads), std::thread::hardware_concurrency()));
-                if (nb1 >= 4096 && !(e->alloc_workers && e->alloc_workers->size() == at)) e->alloc_workers.reset(new Workers(at));
-                alloc = allocate_layers(g, res, h_rate, reinterpret_cast<const int32_t *>(h_nmsedec), lead, at, rdev.get(), e->alloc_workers.get());
+                    std::unique_ptr<HipRateDevice> rdev;
+                    if (pd.rc_device) rdev.reset(new HipRateDevice(e, tt));
+                    const unsigned at = std::max(1u, std::min((unsigned)std::max(1, tuning().alloc_threads), std::thread::hardware_concurrency()));
+                    if (nb1 >= 4096 && !(e->alloc_workers && e->alloc_workers->size() == at)) e->alloc_workers.reset(new Workers(at));
+                    alloc = allocate_layers(gg, res, h_rate, reinterpret_cast<const int32_t *>(h_nmsedec), lead, at, rdev.get(), e->alloc_workers.get());
+                }
+                if (pd.rc_tables_pending) { HIP_CHECK(hipEventSynchronize(e->rc_tables)); pd.rc_tables_pending = false; } // (never read: still ours to wait for)
+                // big frames: a few host threads write the packet headers of the (resolution, component) pairs side by side
+                if (nb1 >= 4096 && !e->t2_workers) e->t2_workers.reset(new Workers(plan_threads()));
+                return plan_codestream(gg, res, framed, framed, rate_control ? &alloc : nullptr, e->t2_workers.get());
+            };
+            // Planned at the guard bits the parameters give.  A block beyond them (GuardExcess) is the call's error -- or, under
+            // J2K_HIP_GUARD_AUTO, the same Tier-1 results are planned once more with the count they need: host work alone
+            guard = cod.guard;
+            try { plans[f] = plan_frame(g); }
+            catch (const GuardExcess &) {
+                if (!cod.guard_auto) throw;
+                guard = guard_bits_needed(g, res);
+                plans[f] = plan_frame(with_guard_bits(g, guard));
             }
-            if (pd.rc_tables_pending) { HIP_CHECK(hipEventSynchronize(e->rc_tables)); pd.rc_tables_pending = false; } // (never read: still ours to wait for)
-            // big frames: a few host threads write the packet headers of the (resolution, component) pairs side by side
-            if (nb1 >= 4096 && !e->t2_workers) e->t2_workers.reset(new Workers(plan_threads()));
-            plans[f] = plan_codestream(g, res, framed, framed, rate_control ? &alloc : nullptr, e->t2_workers.get());
             lays[f] = GatherPlan(plans[f].blob.size(), plans[f].hdr_segs.size(), nbd, plans[f].body_segs.size());
             plan_off[f] = plan_total;
             plan_total += lays[f].total;
@@ -985,6 +1003,7 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
     st.ms_after_upload = st.ms_total - st.ms_upload;
     std::vector<EncodeOut> outs(F);
     for (size_t f = 0; f < F; ++f) { outs[f].d_cs = e->cs.as<uint8_t>() + cs_off[f]; outs[f].len = (size_t)plans[f].total_len; }
+    if (framed) e->last_guard = guard;
     return outs;
 }
 
@@ -1345,7 +1364,20 @@ void encode_end_banded(j2k_hip_encoder *e, j2k_hip_write_fn write, void *user)
         throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 kernel reported error " + std::to_string(*tt.err(hm)) +
                                               " (1: too many bit-planes, 2: decision buffer, 3: codeword buffer)");
     }
-    const Tier2Plan plan = planner.get();
+    // The planner wrote at the guard bits the parameters give, optimistically.  A block beyond them ended it (GuardExcess): the
+    // call's error -- or, under J2K_HIP_GUARD_AUTO, what it wrote is dropped and the frame is planned again with the count its
+    // blocks need, now that every stage is in (their codewords are in host memory or on their way; no kernel runs again, and
+    // the sink has seen nothing yet)
+    Tier2Plan plan;
+    uint32_t guard = g.cod.guard;
+    try { plan = planner.get(); }
+    catch (const GuardExcess &) {
+        if (!g.cod.guard_auto) throw;
+        Range r("j2k_hip tier2 host, guard bits");
+        guard = guard_bits_needed(g, res);
+        plan = plan_codestream(with_guard_bits(g, guard), res, true, true, nullptr, e->t2_workers.get());
+        t_t2_end = now_ms();
+    }
     // ---- the file as pieces of host memory in file order: header pieces out of the plan's blob, runs of code-blocks out of
     // the stages' buffers
     struct Piece { uint64_t dst; const uint8_t *src; uint64_t len; int stage; };
@@ -1408,6 +1440,7 @@ void encode_end_banded(j2k_hip_encoder *e, j2k_hip_write_fn write, void *user)
     st.ms_assemble = t_end - t_t2_end;
     st.ms_after_upload = t_end - pd.t_uploaded;
     st.ms_total = t_end - pd.t_begin;
+    e->last_guard = guard;
 }
 
 std::vector<EncodeOut> encode_impl(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes,
@@ -1725,7 +1758,7 @@ int j2k_hip_encode_begin_borrowed(j2k_hip_encoder *e, const j2k_hip_params *para
         if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
         if (!params || !planes) throw Error(J2K_HIP_ERR_PARAM, "params / planes is NULL");
         const Coding cod = normalise(params);
-        e->begin_params = *params;
+        e->begin_params = widened(params);
         for (uint32_t c = 0; c < cod.ncomp && c < 4; ++c) e->begin_planes[c] = planes[c];
     });
     if (rc != J2K_HIP_OK) return rc;
@@ -1775,6 +1808,8 @@ int j2k_hip_main_header(const j2k_hip_params *params, void *out, size_t cap, siz
 {
     try {
         const Coding cod = normalise(params);
+        if (cod.guard_auto) // (QCD holds the count, and it is the frame that decides it)
+            throw Error(J2K_HIP_ERR_PARAM, "guard_bits: J2K_HIP_GUARD_AUTO needs a frame; a header made without one takes a fixed count");
         const std::vector<uint8_t> h = main_header(cod);
         if (len) *len = h.size();
         if (num_tiles) *num_tiles = cod.ntiles();
@@ -1882,6 +1917,13 @@ int j2k_hip_debug_dwt_time(j2k_hip_encoder *e, uint32_t first, uint32_t count, u
         HIP_CHECK(hipEventElapsedTime(&t, e->ev[EV_START], e->ev[EV_DONE]));
         if (ms) *ms = t / repeat;
     });
+}
+
+int j2k_hip_encode_get_guard_bits(const j2k_hip_encoder *e, uint32_t *g)
+{
+    if (!e || !g) return J2K_HIP_ERR_PARAM;
+    *g = e->last_guard;
+    return J2K_HIP_OK;
 }
 
 int j2k_hip_get_stats(const j2k_hip_encoder *e, j2k_hip_stats *stats)

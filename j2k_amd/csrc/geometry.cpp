@@ -13,8 +13,7 @@ namespace j2k_hip {
 Coding normalise(const j2k_hip_params *p)
 {
     if (!p) throw Error(J2K_HIP_ERR_PARAM, "params is NULL");
-    if (p->struct_size != sizeof(j2k_hip_params))
-        throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_params.struct_size mismatch (ABI drift)");
+    if (!params_size_ok(p)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_params.struct_size mismatch (ABI drift)");
     Coding c;
     c.width = p->width; c.height = p->height; c.ncomp = p->channels; c.prec = p->depth;
     if (c.width == 0 || c.height == 0) throw Error(J2K_HIP_ERR_PARAM, "empty image");
@@ -175,7 +174,29 @@ Coding normalise(const j2k_hip_params *p)
     if ((c.aspect_num == 0) != (c.aspect_den == 0)) throw Error(J2K_HIP_ERR_PARAM, "pixel aspect needs both a numerator and a denominator");
     if (!(p->dpi >= 0.0f) || p->dpi > 1e6f) throw Error(J2K_HIP_ERR_PARAM, "dpi must be finite and >= 0");
     c.dpi = p->dpi;
+    // guard bits: a fixed count, or a floor under J2K_HIP_GUARD_AUTO (a caller of the layout before the field: 0)
+    if (const uint32_t gb = p->struct_size == sizeof(j2k_hip_params) ? p->guard_bits : 0u) {
+        if ((gb & ~(uint32_t)J2K_HIP_GUARD_AUTO) > (uint32_t)kMaxGuardBits)
+            throw Error(J2K_HIP_ERR_PARAM, "guard_bits must be 0, 1..7 or J2K_HIP_GUARD_AUTO | a floor of 0..7");
+        if (p->dci_profile) throw Error(J2K_HIP_ERR_PARAM, "guard_bits cannot be combined with dci_profile: a digital cinema profile writes two guard bits");
+        c.guard_auto = (gb & J2K_HIP_GUARD_AUTO) != 0;
+        if (const uint32_t count = gb & ~(uint32_t)J2K_HIP_GUARD_AUTO) c.guard = count;
+        const char *over = guard_bits_refusal(c, c.guard);
+        if (over) throw Error(J2K_HIP_ERR_PARAM, std::string("guard_bits: ") + over);
+    }
     return c;
+}
+
+// Why `guard` guard bits cannot be written for these parameters (null: they can): a band would signal more bit-planes than the
+// reader takes in a code-block, or than the Tier-1 pass tables hold.
+const char *guard_bits_refusal(const Coding &c, uint32_t guard)
+{
+    for (uint32_t b = 0; b < 3 * c.numres - 2; ++b) {
+        const int Mb = band_quant(c.prec, c.reversible, c.numres, b, (int)guard).numbps;
+        if (Mb > kMaxBitplanes) return "a sub-band would signal more than the 30 bit-planes the reader accepts in a code-block";
+        if (3 * Mb - 2 > kMaxPasses) return "a sub-band would need more coding passes than the Tier-1 tables hold";
+    }
+    return nullptr;
 }
 
 void refuse_subsampled_tiles(const Coding &cod)
@@ -193,7 +214,7 @@ static const double kNorms97[4][10] = {
     {2.022, 3.989, 8.355, 17.04, 34.27, 68.63, 137.3, 274.6, 549.0, 0},
     {2.080, 3.865, 8.307, 17.18, 34.71, 69.59, 139.3, 278.6, 557.2, 0}};
 
-BandQuant band_quant(uint32_t prec, bool reversible, uint32_t numres, uint32_t bandidx)
+BandQuant band_quant(uint32_t prec, bool reversible, uint32_t numres, uint32_t bandidx, int guard)
 {
     const int resno = bandidx == 0 ? 0 : (int)((bandidx - 1) / 3 + 1);
     const int orient = bandidx == 0 ? 0 : (int)((bandidx - 1) % 3 + 1);
@@ -210,7 +231,7 @@ BandQuant band_quant(uint32_t prec, bool reversible, uint32_t numres, uint32_t b
     BandQuant q;
     q.mant = (n < 0 ? iss >> -n : iss << n) & 0x7ff;
     q.expn = (int)prec + gain - p;
-    q.numbps = q.expn + kGuardBits - 1;
+    q.numbps = q.expn + guard - 1;
     const int log2gain = orient == 0 ? 0 : (orient == 3 ? 2 : 1); // Table E-1
     const int Rb = (int)prec + log2gain;                          // E-4
     q.stepsize = (float)((1.0 + q.mant / 2048.0) * std::pow(2.0, (double)(Rb - q.expn)));
@@ -265,7 +286,7 @@ Geometry build_geometry(const Coding &cod, uint32_t tile_first, uint32_t tile_co
                         B.x0 = ceildivpow2(TC.x0 - ox, nb); B.y0 = ceildivpow2(TC.y0 - oy, nb);
                         B.x1 = ceildivpow2(TC.x1 - ox, nb); B.y1 = ceildivpow2(TC.y1 - oy, nb);
                     }
-                    B.q = band_quant(cod.cprec[c] ? cod.cprec[c] : cod.prec, cod.reversible, cod.numres, (uint32_t)B.bandidx);
+                    B.q = band_quant(cod.cprec[c] ? cod.cprec[c] : cod.prec, cod.reversible, cod.numres, (uint32_t)B.bandidx, (int)cod.guard);
                     g.max_Mb = std::max<uint32_t>(g.max_Mb, (uint32_t)B.q.numbps);
                     B.precs.assign((size_t)R.pw * R.ph, Precinct{});
                 }
@@ -319,6 +340,20 @@ Geometry build_geometry(const Coding &cod, uint32_t tile_first, uint32_t tile_co
         T.num_cblks = (uint32_t)g.cblks.size() - T.first_cblk;
     }
     return g;
+}
+
+Geometry with_guard_bits(const Geometry &g, uint32_t guard)
+{
+    Geometry o = g;
+    const int d = (int)guard - (int)g.cod.guard;
+    o.cod.guard = guard;
+    o.max_Mb = (uint32_t)((int)g.max_Mb + d);
+    for (Tile &T : o.tiles)
+        for (TileComp &TC : T.comps)
+            for (Resolution &R : TC.res)
+                for (uint32_t b = 0; b < R.nbands; ++b) R.bands[b].q.numbps += d;
+    for (Cblk &c : o.cblks) c.Mb = (uint8_t)((int)c.Mb + d);
+    return o;
 }
 
 std::vector<PacketRef> packet_order(const Coding &cod, const Tile &T, uint32_t maxlayers)

@@ -12,8 +12,8 @@ struct BandQuant {
     float stepsize; // Delta_b (E-3); 1.0 for the reversible path
 };
 
-// Quantisation of sub-band `bandidx` (0 = LL, then HL,LH,HH per resolution 1..numres-1).
-BandQuant band_quant(uint32_t prec, bool reversible, uint32_t numres, uint32_t bandidx);
+// Quantisation of sub-band `bandidx` (0 = LL, then HL,LH,HH per resolution 1..numres-1) under `guard` guard bits.
+BandQuant band_quant(uint32_t prec, bool reversible, uint32_t numres, uint32_t bandidx, int guard = kGuardBits);
 
 // One code-block, in Tier-2 packet order (tile, then resolution, component, precinct, band, raster).
 struct Cblk {
@@ -65,6 +65,8 @@ struct Geometry {
 };
 
 Geometry build_geometry(const Coding &cod, uint32_t tile_first, uint32_t tile_count);
+// The same geometry under `guard` guard bits: the partition stands, every band and block signals guard - cod.guard bit-planes more.
+Geometry with_guard_bits(const Geometry &g, uint32_t guard);
 
 // One packet = one quality layer of one precinct of one resolution of one tile-component.
 struct PacketRef { uint32_t layer, res, comp, prec; };

@@ -146,6 +146,7 @@ struct j2k_hip_encoder {
     int last_levels = 0;
     double level_ms[j2k_hip::kMaxLevels] = {};
     j2k_hip_stats stats = {};
+    uint32_t last_guard = 0; // guard bits of the last file written (j2k_hip_encode_get_guard_bits); 0 before any
 
     j2k_hip::DevBuf in, P, Q, Z, blks, jobs, sym, out, meta, passes, cs, plan;
     std::unique_ptr<j2k_hip::Workers> t2_workers; // host threads of the Tier-2 planner (created with the first big frame)

@@ -619,8 +619,27 @@ int j2k_hip_debug_blocks(const j2k_hip_params *params, uint32_t *rows, size_t ca
     });
 }
 
+int j2k_hip_guard_bits_needed(const j2k_hip_params *params, const uint32_t *numbps, size_t nblocks, uint32_t *g)
+{
+    return host_guarded([&] {
+        if (!numbps || !g) throw Error(J2K_HIP_ERR_PARAM, "guard bits needed: an argument is NULL");
+        const Coding cod = normalise(params);
+        const Geometry geo = build_geometry(cod, 0, cod.ntiles());
+        if (nblocks != geo.cblks.size()) throw Error(J2K_HIP_ERR_PARAM, "guard bits needed: the frame has " + std::to_string(geo.cblks.size()) + " code-blocks");
+        std::vector<CblkResult> res(nblocks);
+        for (size_t i = 0; i < nblocks; ++i) res[i] = CblkResult{numbps[i], 0, 0};
+        *g = guard_bits_needed(geo, res);
+    });
+}
+
 int j2k_hip_debug_tier2(const j2k_hip_params *params, const uint32_t *numbps, const uint32_t *npasses, const uint32_t *length,
                         size_t nblocks, int pricer, uint64_t *total_len)
+{
+    return j2k_hip_debug_tier2_guard(params, numbps, npasses, length, nblocks, pricer, total_len, nullptr);
+}
+
+int j2k_hip_debug_tier2_guard(const j2k_hip_params *params, const uint32_t *numbps, const uint32_t *npasses, const uint32_t *length,
+                              size_t nblocks, int pricer, uint64_t *total_len, uint32_t *guard_bits)
 {
     return host_guarded([&] {
         if (!numbps || !npasses || !length) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 hook: an array is NULL");
@@ -630,13 +649,26 @@ int j2k_hip_debug_tier2(const j2k_hip_params *params, const uint32_t *numbps, co
         if (nblocks != g.cblks.size()) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 hook: the frame has " + std::to_string(g.cblks.size()) + " code-blocks");
         std::vector<CblkResult> res(nblocks);
         for (size_t i = 0; i < nblocks; ++i) res[i] = CblkResult{numbps[i], npasses[i], length[i]};
+        auto run = [&](const Geometry &gg) {
+            uint64_t total = 0;
+            if (pricer) {
+                for (const Tile &T : gg.tiles) { TilePricer tp(gg, T, res); total += tp.committed(); }
+            } else {
+                total = plan_codestream(gg, res, true, true).total_len;
+            }
+            return total;
+        };
+        // (an encode's own path: at the guard bits of the parameters, and under J2K_HIP_GUARD_AUTO once more on an excess)
         uint64_t total = 0;
-        if (pricer) {
-            for (const Tile &T : g.tiles) { TilePricer tp(g, T, res); total += tp.committed(); }
-        } else {
-            total = plan_codestream(g, res, true, true).total_len;
+        uint32_t guard = cod.guard;
+        try { total = run(g); }
+        catch (const GuardExcess &) {
+            if (!cod.guard_auto) throw;
+            guard = guard_bits_needed(g, res);
+            total = run(with_guard_bits(g, guard));
         }
         if (total_len) *total_len = total;
+        if (guard_bits) *guard_bits = guard;
     });
 }
 

@@ -105,6 +105,16 @@ void put_numpasses(BitWriter &bw, uint32_t n) // Table B.4
 
 } // namespace
 
+uint32_t guard_bits_needed(const Geometry &geo, const std::vector<CblkResult> &res)
+{
+    int need = (int)geo.cod.guard;
+    const size_t n = std::min(res.size(), geo.cblks.size());
+    for (size_t i = 0; i < n; ++i) // (Mb = exponent + guard - 1)
+        need = std::max(need, (int)res[i].numbps - (int)geo.cblks[i].Mb + (int)geo.cod.guard);
+    if (need > kMaxGuardBits || guard_bits_refusal(geo.cod, (uint32_t)need)) throw GuardExcess();
+    return (uint32_t)need;
+}
+
 std::vector<uint8_t> main_header(const Coding &c)
 {
     std::vector<uint8_t> v;
@@ -123,9 +133,9 @@ std::vector<uint8_t> main_header(const Coding &c)
     const uint32_t nbands = 3 * c.numres - 2;
     o.u16(0xff5c);                                                     // QCD
     o.u16(c.reversible ? 3 + nbands : 3 + 2 * nbands);
-    o.u8((c.reversible ? 0 : 2) + (kGuardBits << 5));
+    o.u8((c.reversible ? 0 : 2) + (c.guard << 5));
     for (uint32_t b = 0; b < nbands; ++b) {
-        const BandQuant q = band_quant(c.prec, c.reversible, c.numres, b);
+        const BandQuant q = band_quant(c.prec, c.reversible, c.numres, b); // (expn and mant: the same under any guard bits)
         if (c.reversible) o.u8((unsigned)q.expn << 3);
         else o.u16(((unsigned)q.expn << 11) + (unsigned)q.mant);
     }
@@ -197,7 +207,7 @@ void for_each_packet(const Coding &cod, const Tile &T, const std::vector<CblkRes
                             Trees &tr = tv[(size_t)pn * R.nbands + b];
                             for (uint32_t k = 0; k < P.cw * P.ch; ++k) {
                                 const int zbp = B.q.numbps - (int)res[P.first_cblk + k].numbps;
-                                if (zbp < 0) throw Error(J2K_HIP_ERR_OVERFLOW, "code-block has more bit-planes than its sub-band signals (guard bits exceeded)");
+                                if (zbp < 0) throw GuardExcess();
                                 tr.imsb.set(k, zbp);
                             }
                         }
@@ -516,7 +526,7 @@ struct TilePricer::Impl {
         for (const Unit &u : units) // the zero-bit-plane trees carry their values from the start
             for (uint32_t k = 0; k < u.ncblk; ++k) {
                 const int zbp = u.zb_numbps - (int)res[u.first_cblk + k].numbps;
-                if (zbp < 0) throw Error(J2K_HIP_ERR_OVERFLOW, "code-block has more bit-planes than its sub-band signals (guard bits exceeded)");
+                if (zbp < 0) throw GuardExcess();
                 set(imsb.data(), u.node0 + k, zbp);
             }
         incl_w = incl; imsb_w = imsb;

@@ -38,6 +38,14 @@ struct Tier2Plan {
     uint64_t total_len = 0;
 };
 
+// Frames beyond their guard bits.  plan_codestream and TilePricer throw GuardExcess where a block has more
+// bit-planes than its band signals (a negative zero-bit-plane count) -- under a strict count that is the call's error; under
+// Coding::guard_auto the caller asks guard_bits_needed for the count the results need and plans them again on
+// with_guard_bits(geo, that count): the Tier-1 results stand, only QCD and the zero-bit-plane counts move.
+// guard_bits_needed: max(geo.cod.guard, max over the blocks of numbps - exponent(band) + 1); throws GuardExcess itself where
+// that is more than Sqcd holds or gives a band more bit-planes than the reader takes (guard_bits_refusal).
+uint32_t guard_bits_needed(const Geometry &geo, const std::vector<CblkResult> &res);
+
 // Main header: SOC, SIZ, COD, QCD [, COM].
 std::vector<uint8_t> main_header(const Coding &cod);
 

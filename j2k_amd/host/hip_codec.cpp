@@ -468,6 +468,7 @@ bool map_frame(HipCodec::Mode mode, unsigned options, const FileInfo &info, cons
         p.color_space = J2K_HIP_CS_UNSPECIFIED;
         p.icc_profile = NULL; p.icc_profile_len = 0;
     }
+    if ((options & HipCodec::AutoGuardBits) && !p.dci_profile) p.guard_bits = J2K_HIP_GUARD_AUTO; // (as many as the frame needs, two at least)
     return true;
 }
 

@@ -37,7 +37,12 @@ class HipCodec : public Codec {
     //   FileInfo.depth says: the transform is the depth conversion).  The real profile (dci_profile 3 / 4) is then reached
     //   for any world depth when the frame fits the container.  No ICC profile is written and the colour space is
     //   unspecified.  Compare takes the same mapping.  With Chroma422 / Chroma420 as well, CinemaXYZ wins on such a frame.
-    enum Options { NoOptions = 0, PromoteAE16 = 1, DemoteAE16 = 2, Chroma422 = 4, Chroma420 = 8, CinemaXYZ = 16 };
+    //   AutoGuardBits (both modes; not under a cinema profile, which is pinned to libopenjp2's bytes): WriteFile writes a frame
+    //   whose coefficients outgrow the bit-planes two guard bits signal -- a lossless frame that libopenjp2 writes wrongly
+    //   and this codec otherwise refuses with "Error writing file" -- with the guard bits it needs
+    //   (j2k_hip_params.guard_bits = J2K_HIP_GUARD_AUTO).  Every other frame is written byte for byte as without the option;
+    //   ReadFile and Compare take the count from the file.
+    enum Options { NoOptions = 0, PromoteAE16 = 1, DemoteAE16 = 2, Chroma422 = 4, Chroma420 = 8, CinemaXYZ = 16, AutoGuardBits = 32 };
 
     // device: HIP device ordinal, or -1 = the host threads that call this codec take the devices in turn
     explicit HipCodec(Mode mode = ReferenceLiteral, int device = -1, unsigned options = NoOptions);
