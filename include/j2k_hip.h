@@ -1008,6 +1008,31 @@ int j2k_hip_debug_cblk_capacities(uint32_t area, uint32_t Mb, uint32_t cblk_styl
 int j2k_hip_debug_blocks(const j2k_hip_params *params, uint32_t *rows, size_t cap, size_t *nblocks);
 int j2k_hip_debug_tier2(const j2k_hip_params *params, const uint32_t *numbps, const uint32_t *npasses, const uint32_t *length,
                         size_t nblocks, int pricer, uint64_t *total_len);
+/* j2k_hip_debug_tier2_plan: the plan itself, not only its length -- what plan_codestream hands the gather kernel.  Inputs as
+ * j2k_hip_debug_tier2, and
+ *   pass_rate    per block and pass, the bytes at the end of the pass (nblocks rows of J2K_HIP_MAX_PASSES words): required
+ *                when `params` carry a code-block style, refused otherwise;
+ *   alloc_np / alloc_len / alloc_off   a layer allocation, entry [block * alloc_layers + layer] (passes, bytes and the bytes'
+ *                offset inside the block's codeword); all three or none, alloc_layers = params->layers;
+ *   nworkers     0: planned serially; n: with n worker threads (tiles of 4096 blocks and more are planned side by side).
+ * params.guard_bits is honoured as by j2k_hip_debug_tier2_guard (plan, excess, re-plan).  Sizes are queried as with
+ * j2k_hip_debug_blocks: a first call with the pointers of `out` NULL fills total_len, guard_bits and the four counts; a second
+ * call with buffers of those capacities fills them (J2K_HIP_ERR_OVERFLOW where one is too small, J2K_HIP_ERR_PARAM where a
+ * piece list is given in part).  A plan is laid into a
+ * codestream by copying blob[src, src + len) to dst for every header piece and the blocks' bytes to cblk_dst[block] (no
+ * allocation: ncblk_dst = nblocks, nbodies = 0) or bytes [off, off + len) of block `cblk` to dst for every body piece. */
+typedef struct j2k_hip_tier2_plan {
+    uint64_t total_len;
+    uint32_t guard_bits;
+    size_t blob_bytes, nheaders, ncblk_dst, nbodies;
+    uint8_t *blob; size_t blob_cap;
+    uint64_t *hdr_dst; uint32_t *hdr_src, *hdr_len; size_t hdr_cap;
+    uint64_t *cblk_dst; size_t cblk_cap;
+    uint64_t *body_dst; uint32_t *body_cblk, *body_off, *body_len; size_t body_cap;
+} j2k_hip_tier2_plan;
+int j2k_hip_debug_tier2_plan(const j2k_hip_params *params, const uint32_t *numbps, const uint32_t *npasses, const uint32_t *length,
+                             size_t nblocks, const uint32_t *pass_rate, const uint32_t *alloc_np, const uint32_t *alloc_len,
+                             const uint32_t *alloc_off, uint32_t alloc_layers, uint32_t nworkers, j2k_hip_tier2_plan *out);
 /* The knob's current value through *value (tests restore what they change). */
 int j2k_hip_debug_get_tune(const char *key, int *value);
 /* Waves per SIMD the fused front end + level-1 DWT kernel reaches by its register count AS BUILT (read from the code object;

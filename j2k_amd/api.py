@@ -107,7 +107,17 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink",
            "j2k_hip_debug_cblk_capacities", "j2k_hip_debug_blocks", "j2k_hip_debug_tier2",
-           "j2k_hip_encode_get_guard_bits", "j2k_hip_guard_bits_needed", "j2k_hip_debug_tier2_guard"]
+           "j2k_hip_encode_get_guard_bits", "j2k_hip_guard_bits_needed", "j2k_hip_debug_tier2_guard", "j2k_hip_debug_tier2_plan"]
+
+class Tier2Plan(C.Structure):
+    """include/j2k_hip.h: j2k_hip_tier2_plan."""
+    _fields_ = [("total_len", C.c_uint64), ("guard_bits", C.c_uint32),
+                ("blob_bytes", C.c_size_t), ("nheaders", C.c_size_t), ("ncblk_dst", C.c_size_t), ("nbodies", C.c_size_t),
+                ("blob", C.c_void_p), ("blob_cap", C.c_size_t),
+                ("hdr_dst", C.c_void_p), ("hdr_src", C.c_void_p), ("hdr_len", C.c_void_p), ("hdr_cap", C.c_size_t),
+                ("cblk_dst", C.c_void_p), ("cblk_cap", C.c_size_t),
+                ("body_dst", C.c_void_p), ("body_cblk", C.c_void_p), ("body_off", C.c_void_p), ("body_len", C.c_void_p), ("body_cap", C.c_size_t)]
+
 
 class IdwtRegion(C.Structure):
     """include/j2k_hip.h: j2k_hip_idwt_region."""
@@ -299,6 +309,9 @@ def load_library():
         L.j2k_hip_encode_get_guard_bits.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
         L.j2k_hip_guard_bits_needed.argtypes = [C.POINTER(Params), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
         L.j2k_hip_debug_tier2_guard.argtypes = L.j2k_hip_debug_tier2.argtypes + [C.POINTER(C.c_uint32)]
+    if hasattr(L, "j2k_hip_debug_tier2_plan"):
+        L.j2k_hip_debug_tier2_plan.argtypes = [C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Tier2Plan)]
     _lib = L
     return L
 
@@ -522,6 +535,87 @@ def host_tier2(params: Params, numbps, npasses, length, pricer: bool = False, wi
     if rc != 0:
         raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
     return (total.value, guard.value) if with_guard else total.value
+
+
+MAX_PASSES = 96  # J2K_HIP_MAX_PASSES: the row length of the per-pass tables
+
+
+def host_tier2_plan(params: Params, numbps, npasses, length, rates=None, alloc=None, workers: int = 0) -> dict:
+    """Host Tier-2's plan of per-block results in frame_blocks order (j2k_hip_debug_tier2_plan; no device needed).  rates:
+    (n, MAX_PASSES) bytes at the end of every pass, required under a code-block style and refused without one; alloc: (np, len,
+    off), each (n, layers), a layer allocation; workers: 0 plans serially, n with n threads.  params.guard_bits is honoured as by
+    host_tier2.  Returns dict(total_len, guard_bits, blob, headers = (dst, src, len) arrays, cblk_dst (no allocation) or None,
+    bodies = (dst, cblk, off, len) arrays (with one) or None, length = the blocks' lengths as given, which assemble() needs
+    beside cblk_dst); assemble() lays it out."""
+    L = load_library()
+    a = [np.ascontiguousarray(v, dtype=np.uint32) for v in (numbps, npasses, length)]
+    assert a[0].shape == a[1].shape == a[2].shape and a[0].ndim == 1
+    n = a[0].size
+    ptr = lambda v: v.ctypes.data if v is not None and v.size else None
+    r = None
+    if rates is not None:
+        r = np.ascontiguousarray(rates, dtype=np.uint32)
+        assert r.shape == (n, MAX_PASSES)
+    al, layers = [None, None, None], 0
+    if alloc is not None:
+        al = [np.ascontiguousarray(v, dtype=np.uint32) for v in alloc]
+        assert al[0].ndim == 2 and al[0].shape[0] == n and al[0].shape == al[1].shape == al[2].shape
+        layers = al[0].shape[1]
+    out = Tier2Plan()
+
+    def call():
+        rc = L.j2k_hip_debug_tier2_plan(C.byref(params), a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, n, ptr(r), ptr(al[0]), ptr(al[1]),
+                                        ptr(al[2]), layers, workers, C.byref(out))
+        if rc != 0:
+            raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
+
+    call()  # sizes
+    blob = np.zeros(max(1, out.blob_bytes), np.uint8)
+    hd, hs, hl = np.zeros(max(1, out.nheaders), np.uint64), np.zeros(max(1, out.nheaders), np.uint32), np.zeros(max(1, out.nheaders), np.uint32)
+    cd = np.zeros(max(1, out.ncblk_dst), np.uint64)
+    bd = np.zeros(max(1, out.nbodies), np.uint64)
+    bc, bo, bl = (np.zeros(max(1, out.nbodies), np.uint32) for _ in range(3))
+    out.blob, out.blob_cap = blob.ctypes.data, blob.size
+    out.hdr_dst, out.hdr_src, out.hdr_len, out.hdr_cap = hd.ctypes.data, hs.ctypes.data, hl.ctypes.data, hd.size
+    out.cblk_dst, out.cblk_cap = cd.ctypes.data, cd.size
+    out.body_dst, out.body_cblk, out.body_off, out.body_len, out.body_cap = bd.ctypes.data, bc.ctypes.data, bo.ctypes.data, bl.ctypes.data, bd.size
+    call()
+    nh, nbd = out.nheaders, out.nbodies
+    return dict(total_len=int(out.total_len), guard_bits=int(out.guard_bits), blob=blob[:out.blob_bytes],
+                headers=(hd[:nh], hs[:nh], hl[:nh]),
+                cblk_dst=cd[:out.ncblk_dst] if alloc is None else None,
+                bodies=(bd[:nbd], bc[:nbd], bo[:nbd], bl[:nbd]) if alloc is not None else None,
+                length=a[2])
+
+
+def assemble(plan: dict, block_bytes) -> bytes:
+    """The codestream of a host_tier2_plan: the blob's pieces and the blocks' bytes (block_bytes[i]: bytes or uint8 array of
+    block i, frame_blocks order) laid where the plan puts them.  Every byte of the stream must be written exactly once."""
+    total = plan["total_len"]
+    out = np.zeros(total, np.uint8)
+    seen = np.zeros(total, np.uint8)
+
+    def put(dst, src):
+        out[dst:dst + len(src)] = src
+        seen[dst:dst + len(src)] += 1
+
+    blob = plan["blob"]
+    for d, s, ln in zip(*plan["headers"]):
+        assert int(d) + int(ln) <= total and int(s) + int(ln) <= blob.size
+        put(int(d), blob[int(s):int(s) + int(ln)])
+    blocks = [np.frombuffer(bytes(b), np.uint8) for b in block_bytes]
+    if plan["bodies"] is None:
+        for i, d in enumerate(plan["cblk_dst"]):
+            ln = int(plan["length"][i])
+            assert blocks[i].size == ln and int(d) + ln <= total
+            put(int(d), blocks[i])
+    else:
+        for d, c, o, ln in zip(*plan["bodies"]):
+            assert int(o) + int(ln) <= blocks[int(c)].size and int(d) + int(ln) <= total
+            put(int(d), blocks[int(c)][int(o):int(o) + int(ln)])
+    if not np.all(seen == 1):
+        raise AssertionError("Tier-2 plan: its pieces do not tile the codestream")
+    return out.tobytes()
 
 
 def guard_bits_needed(params: Params, numbps) -> int:

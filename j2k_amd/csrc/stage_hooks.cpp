@@ -5,6 +5,7 @@
 // The decode path's hooks are in decoder.cpp.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -669,6 +670,93 @@ int j2k_hip_debug_tier2_guard(const j2k_hip_params *params, const uint32_t *numb
         }
         if (total_len) *total_len = total;
         if (guard_bits) *guard_bits = guard;
+    });
+}
+
+int j2k_hip_debug_tier2_plan(const j2k_hip_params *params, const uint32_t *numbps, const uint32_t *npasses, const uint32_t *length,
+                             size_t nblocks, const uint32_t *pass_rate, const uint32_t *alloc_np, const uint32_t *alloc_len,
+                             const uint32_t *alloc_off, uint32_t alloc_layers, uint32_t nworkers, j2k_hip_tier2_plan *out)
+{
+    return host_guarded([&] {
+        if (!numbps || !npasses || !length || !out) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: an array is NULL");
+        const Coding cod = normalise(params);
+        if (cod.cblk_style && !pass_rate) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: a code-block style needs the per-pass byte counts");
+        if (!cod.cblk_style && pass_rate) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: per-pass byte counts without a code-block style");
+        const bool with_alloc = alloc_np || alloc_len || alloc_off;
+        if (with_alloc && !(alloc_np && alloc_len && alloc_off)) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: a layer allocation is np, len and off");
+        if (with_alloc && alloc_layers != cod.layers) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: the allocation's layers are not the parameters'");
+        if (nworkers > 64) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: more than 64 workers");
+        const Geometry g = build_geometry(cod, 0, cod.ntiles());
+        if (nblocks != g.cblks.size()) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: the frame has " + std::to_string(g.cblks.size()) + " code-blocks");
+        std::vector<CblkResult> res(nblocks);
+        for (size_t i = 0; i < nblocks; ++i) {
+            res[i] = CblkResult{numbps[i], npasses[i], length[i]};
+            if (npasses[i] > (uint32_t)kMaxPasses) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: more passes than the pass tables hold");
+            if (pass_rate) {
+                const uint32_t *r = pass_rate + i * (size_t)kMaxPasses;
+                for (uint32_t p = 0; p < npasses[i]; ++p)
+                    if (r[p] > length[i] || (p && r[p] < r[p - 1])) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: per-pass byte counts must not decrease nor pass the length");
+                res[i].rates = r;
+            }
+        }
+        LayerAlloc alloc;
+        if (with_alloc) {
+            const size_t n = nblocks * (size_t)alloc_layers;
+            alloc.layers = alloc_layers;
+            alloc.np.assign(alloc_np, alloc_np + n); alloc.len.assign(alloc_len, alloc_len + n); alloc.off.assign(alloc_off, alloc_off + n);
+            for (size_t i = 0; i < nblocks; ++i) {
+                uint64_t passes = 0;
+                for (uint32_t l = 0; l < alloc_layers; ++l) {
+                    const size_t k = i * alloc_layers + l;
+                    passes += alloc.np[k];
+                    if (alloc.np[k] && (alloc.off[k] > length[i] || alloc.len[k] > length[i] - alloc.off[k]))
+                        throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: a layer's bytes lie outside the block's");
+                }
+                if (passes > npasses[i]) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: the layers hold more passes than the block has");
+            }
+        }
+        std::unique_ptr<Workers> workers;
+        if (nworkers) workers.reset(new Workers(nworkers));
+        auto run = [&](const Geometry &gg) { return plan_codestream(gg, res, true, true, with_alloc ? &alloc : nullptr, workers.get()); };
+        // (an encode's own path, as j2k_hip_debug_tier2_guard walks it)
+        Tier2Plan plan;
+        uint32_t guard = cod.guard;
+        try { plan = run(g); }
+        catch (const GuardExcess &) {
+            if (!cod.guard_auto) throw;
+            guard = guard_bits_needed(g, res);
+            plan = run(with_guard_bits(g, guard));
+        }
+        out->total_len = plan.total_len;
+        out->guard_bits = guard;
+        out->blob_bytes = plan.blob.size();
+        out->nheaders = plan.hdr_segs.size();
+        out->ncblk_dst = plan.cblk_dst.size();
+        out->nbodies = plan.body_segs.size();
+        if (out->blob) {
+            if (out->blob_cap < plan.blob.size()) throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-2 plan hook: blob buffer too small");
+            if (!plan.blob.empty()) std::memcpy(out->blob, plan.blob.data(), plan.blob.size());
+        }
+        if (out->hdr_dst || out->hdr_src || out->hdr_len) {
+            if (!(out->hdr_dst && out->hdr_src && out->hdr_len)) throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: header pieces are hdr_dst, hdr_src and hdr_len");
+            if (out->hdr_cap < plan.hdr_segs.size()) throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-2 plan hook: header piece arrays too small");
+            for (size_t i = 0; i < plan.hdr_segs.size(); ++i) {
+                out->hdr_dst[i] = plan.hdr_segs[i].dst; out->hdr_src[i] = plan.hdr_segs[i].src; out->hdr_len[i] = plan.hdr_segs[i].len;
+            }
+        }
+        if (out->cblk_dst) {
+            if (out->cblk_cap < plan.cblk_dst.size()) throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-2 plan hook: cblk_dst array too small");
+            std::copy(plan.cblk_dst.begin(), plan.cblk_dst.end(), out->cblk_dst);
+        }
+        if (out->body_dst || out->body_cblk || out->body_off || out->body_len) {
+            if (!(out->body_dst && out->body_cblk && out->body_off && out->body_len))
+                throw Error(J2K_HIP_ERR_PARAM, "Tier-2 plan hook: body pieces are body_dst, body_cblk, body_off and body_len");
+            if (out->body_cap < plan.body_segs.size()) throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-2 plan hook: body piece arrays too small");
+            for (size_t i = 0; i < plan.body_segs.size(); ++i) {
+                const BodySeg &b = plan.body_segs[i];
+                out->body_dst[i] = b.dst; out->body_cblk[i] = b.cblk; out->body_off[i] = b.off; out->body_len[i] = b.len;
+            }
+        }
     });
 }
 

@@ -148,6 +148,14 @@ const char *j2ko_decode_error(void);
  * termall only); hdr = {code-block style, reversible, components, tiles}.  Returns the number of blocks or -1. */
 long j2ko_file_blocks(const uint8_t *file, size_t len, int32_t *meta, size_t cap_blocks, uint32_t *segs, size_t cap_segs, uint8_t *bytes,
                       size_t cap_bytes, int hdr[4]);
+/* The same, and what each packet header announced: pieces = 4 words per length field read -- block (index into meta), layer,
+ * bytes, passes -- block after block, inside a block in the order read; one piece per layer a block contributes to, under
+ * bypass / termall one per codeword segment the layer's passes fall into.  *npieces receives their number. */
+long j2ko_file_block_pieces(const uint8_t *file, size_t len, int32_t *meta, size_t cap_blocks, uint32_t *segs, size_t cap_segs, uint8_t *bytes,
+                            size_t cap_bytes, int hdr[4], uint32_t *pieces, size_t cap_pieces, size_t *npieces);
+/* Of the file read last (j2ko_decode, j2ko_file_blocks, j2ko_file_block_pieces): out[0] = the packet headers read, out[1] =
+ * those whose last bit was the last bit of a byte 0xFF, by the reader's own bit position (B.10.1: one more byte follows). */
+void j2ko_packet_stats(long out[2]);
 /* Header only (GetFileInfo, :222-426): info = {width, height, ncomp, prec, reversible, mct, numres, is_jp2, enumcs,
  * icc offset in the file, icc length, alpha channel mask}. */
 int j2ko_decode_info(const uint8_t *file, size_t len, int info[12]);

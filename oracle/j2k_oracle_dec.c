@@ -594,7 +594,20 @@ typedef struct {
      * passes each segment takes, in order */
     int nseg;
     uint32_t seg_bytes[128], seg_np[128], seg_max[128];
+    /* what the packet headers announced, one entry per length field read: layer, bytes, passes */
+    uint32_t *pieces; int npieces, cap_pieces;
 } dcblk_t;
+static int cblk_piece(dcblk_t *cb, int layer, uint32_t bytes, int passes)
+{
+    if (cb->npieces == cb->cap_pieces) {
+        cb->cap_pieces = cb->cap_pieces * 2 + 8;
+        cb->pieces = (uint32_t *)realloc(cb->pieces, sizeof(uint32_t) * 3 * (size_t)cb->cap_pieces);
+        if (!cb->pieces) return -1;
+    }
+    uint32_t *e = cb->pieces + 3 * cb->npieces++;
+    e[0] = (uint32_t)layer; e[1] = bytes; e[2] = (uint32_t)passes;
+    return 0;
+}
 typedef struct { int cw, ch; dcblk_t *cblks; ttree_t incl, imsb; } dprec_t;
 typedef struct { int orient, x0, y0, x1, y1, numbps; float stepsize; dprec_t *precs; } dband_t;
 typedef struct { int x0, y0, x1, y1, pw, ph, nbands, ppx, ppy; dband_t bands[3]; } dres_t;
@@ -797,7 +810,7 @@ static void free_tilecomp(const dhdr_t *H, dres_t *res)
             dband_t *B = &res[r].bands[b];
             for (int pn = 0; pn < res[r].pw * res[r].ph; pn++) {
                 dprec_t *P = &B->precs[pn];
-                for (int k = 0; k < P->cw * P->ch; k++) free(P->cblks[k].data);
+                for (int k = 0; k < P->cw * P->ch; k++) { free(P->cblks[k].data); free(P->cblks[k].pieces); }
                 free(P->cblks); free(P->incl.nodes); free(P->imsb.nodes);
             }
             free(B->precs);
@@ -813,6 +826,11 @@ static int get_numpasses(bior_t *b)
     if ((n = bior_read(b, 5)) != 31) return 6 + (int)n;
     return 37 + (int)bior_read(b, 7);
 }
+
+/* What the packet headers of the file read last were, by the reader's own bit position: their number, and how many had their
+ * last bit in the last bit of a byte 0xFF -- B.10.1 then wants one more byte behind it, which bior_align takes. */
+static long g_packets_read, g_headers_ending_on_ff;
+void j2ko_packet_stats(long out[2]) { out[0] = g_packets_read; out[1] = g_headers_ending_on_ff; }
 
 /* one packet (B.10): header, then the code-block contributions; returns the new read position or NULL */
 static const uint8_t *read_packet(const dhdr_t *H, dres_t *R, int pn, int layer, const uint8_t *p, const uint8_t *end)
@@ -845,7 +863,7 @@ static const uint8_t *read_packet(const dhdr_t *H, dres_t *R, int pn, int layer,
                 const int np = get_numpasses(&bio);
                 while (bior_bit(&bio)) cb->lenbits++;
                 size_t l = 0;
-                if (!multiseg) l = bior_read(&bio, cb->lenbits + flog2((unsigned)np));
+                if (!multiseg) { l = bior_read(&bio, cb->lenbits + flog2((unsigned)np)); if (cblk_piece(cb, layer, (uint32_t)l, np)) return NULL; }
                 else { /* one length per codeword segment the new passes fall into (B.10.7.2) */
                     int left = np;
                     while (left > 0) {
@@ -866,6 +884,7 @@ static const uint8_t *read_packet(const dhdr_t *H, dres_t *R, int pn, int layer,
                         const uint32_t l1 = bior_read(&bio, cb->lenbits + flog2((unsigned)take));
                         cb->seg_bytes[k] += l1; cb->seg_np[k] += (uint32_t)take;
                         left -= take; l += l1;
+                        if (cblk_piece(cb, layer, l1, take)) return NULL;
                     }
                 }
                 if (ntodo >= 3 * 4096) return NULL;
@@ -873,6 +892,8 @@ static const uint8_t *read_packet(const dhdr_t *H, dres_t *R, int pn, int layer,
                 if (bio.overrun) return NULL;
             }
         }
+    g_packets_read++;
+    if (bio.ct == 0 && (bio.buf & 0xff) == 0xff) g_headers_ending_on_ff++; /* every bit of a 0xFF byte was header */
     bior_align(&bio);
     if (bio.overrun) return NULL;
     p = bio.p;
@@ -1000,6 +1021,7 @@ typedef struct {
     int32_t *meta; size_t nblk, cap_blk;
     uint32_t *segs; size_t nseg, cap_seg;
     uint8_t *bytes; size_t nbytes, cap_bytes;
+    uint32_t *pieces; size_t npieces, cap_pieces; /* optional: block (index into meta), layer, bytes, passes */
     int overflow;
 } blkdump_t;
 
@@ -1041,6 +1063,11 @@ static int decode_tile(const dhdr_t *H, int tileno, const uint8_t *data, size_t 
                             if (dump->nblk >= dump->cap_blk || dump->nseg + (size_t)cb->nseg > dump->cap_seg || dump->nbytes + cb->len > dump->cap_bytes) {
                                 dump->overflow = 1;
                                 continue;
+                            }
+                            if (dump->pieces && dump->npieces + (size_t)cb->npieces > dump->cap_pieces) { dump->overflow = 1; continue; }
+                            for (int i = 0; dump->pieces && i < cb->npieces; i++) {
+                                uint32_t *e = dump->pieces + 4 * dump->npieces++;
+                                e[0] = (uint32_t)dump->nblk; e[1] = cb->pieces[3 * i]; e[2] = cb->pieces[3 * i + 1]; e[3] = cb->pieces[3 * i + 2];
                             }
                             int32_t *m = dump->meta + 16 * dump->nblk++;
                             const float hs = H->reversible ? 1.0f : step;
@@ -1103,6 +1130,7 @@ static int decode_impl(const uint8_t *file, size_t flen, int reduce, int32_t *ou
     dims[0] = ow; dims[1] = oh; dims[2] = H.ncomp; dims[3] = H.prec;
     if (!dump && (size_t)ow * (size_t)oh * (size_t)H.ncomp > cap_samples) FAIL("output capacity too small");
     const int ntiles = H.ntx * H.nty;
+    g_packets_read = g_headers_ending_on_ff = 0;
     if (hdr) { hdr[0] = H.cblksty; hdr[1] = H.reversible; hdr[2] = H.ncomp; hdr[3] = ntiles; }
     uint8_t **tdata = (uint8_t **)calloc((size_t)ntiles, sizeof(uint8_t *));
     size_t *tlen = (size_t *)calloc((size_t)ntiles, sizeof(size_t));
@@ -1157,6 +1185,26 @@ long j2ko_file_blocks(const uint8_t *file, size_t flen, int32_t *meta, size_t ca
     d.meta = meta; d.cap_blk = cap_blocks; d.segs = segs; d.cap_seg = cap_segs; d.bytes = bytes; d.cap_bytes = cap_bytes;
     if (decode_impl(file, flen, 0, NULL, 0, dims, &d, hdr)) return -1;
     if (d.overflow) FAIL("j2ko_file_blocks: a capacity is too small");
+    return (long)d.nblk;
+}
+
+/* j2ko_file_blocks, and per block and layer what that layer's packet header announced: pieces = 4 words per length field the
+ * reader took, in the order of the blocks and inside a block in the order read -- block (index into meta), layer, bytes,
+ * passes.  Without bypass / termall a layer's contribution is one piece; with them one per codeword segment the layer's passes
+ * fall into (B.10.7.2).  *npieces receives their number.  This is the reader's own parse written down: a block's pieces sum to
+ * its totals and their bytes, in order, are its bytes (tests/test_tier2_plan_refs.py). */
+long j2ko_file_block_pieces(const uint8_t *file, size_t flen, int32_t *meta, size_t cap_blocks, uint32_t *segs, size_t cap_segs, uint8_t *bytes,
+                            size_t cap_bytes, int hdr[4], uint32_t *pieces, size_t cap_pieces, size_t *npieces)
+{
+    blkdump_t d;
+    int dims[4];
+    memset(&d, 0, sizeof d);
+    d.meta = meta; d.cap_blk = cap_blocks; d.segs = segs; d.cap_seg = cap_segs; d.bytes = bytes; d.cap_bytes = cap_bytes;
+    d.pieces = pieces; d.cap_pieces = cap_pieces;
+    if (!pieces || !npieces) FAIL("j2ko_file_block_pieces: no piece array");
+    if (decode_impl(file, flen, 0, NULL, 0, dims, &d, hdr)) return -1;
+    if (d.overflow) FAIL("j2ko_file_block_pieces: a capacity is too small");
+    *npieces = d.npieces;
     return (long)d.nblk;
 }
 

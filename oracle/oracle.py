@@ -125,6 +125,10 @@ class Oracle:
         L.j2ko_file_blocks.restype = C.c_long
         L.j2ko_file_blocks.argtypes = [C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int32), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t,
                                        C.POINTER(C.c_uint8), C.c_size_t, C.POINTER(C.c_int32)]
+        L.j2ko_file_block_pieces.restype = C.c_long
+        L.j2ko_file_block_pieces.argtypes = L.j2ko_file_blocks.argtypes + [C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_size_t)]
+        L.j2ko_packet_stats.restype = None
+        L.j2ko_packet_stats.argtypes = [C.POINTER(C.c_long)]
         L.j2ko_idwt53.restype = None
         L.j2ko_idwt53.argtypes = L.j2ko_dwt53.argtypes
         L.j2ko_idwt97.restype = None
@@ -183,27 +187,46 @@ class Oracle:
                                               sg.ctypes.data_as(C.POINTER(C.c_uint32)), len(segs or ()), _i32p(out), C.byref(below))
         return (out, below.value) if want_below else out
 
-    def file_blocks(self, data: bytes) -> dict:
+    def file_blocks(self, data: bytes, layers: bool = False) -> dict:
         """Every code-block of a file that holds passes, as the oracle's Tier-2 found it (j2ko_file_blocks): dict(style,
         reversible, blocks = [dict(tile, comp, res, orient, rect = (x, y, w, h) in the tile-component's plane, numbps,
-        npasses, half_step, segs = [(bytes, passes), ...] under bypass / termall, data)])."""
+        npasses, half_step, segs = [(bytes, passes), ...] under bypass / termall, data)]).
+        layers: every block also has pieces = [(layer, bytes, passes), ...], one per length field its packet headers held,
+        in the order read (j2ko_file_block_pieces), and the dict holds packets = the packet headers read and headers_ending_on_ff =
+        those whose last bit was the last bit of a 0xFF byte, by the reader's bit position (j2ko_packet_stats)."""
         buf = np.frombuffer(data, dtype=np.uint8)
-        cap_b, cap_s = 1 << 16, 1 << 20
+        cap_b, cap_s, cap_p = 1 << 16, 1 << 20, 1 << 20
         meta = np.zeros((cap_b, 16), dtype=np.int32)
         segs = np.zeros((cap_s, 2), dtype=np.uint32)
         raw = np.zeros(len(data) + 16, dtype=np.uint8)
         hdr = (C.c_int32 * 4)()
-        n = self.L.j2ko_file_blocks(_u8p(buf), len(data), _i32p(meta), cap_b, segs.ctypes.data_as(C.POINTER(C.c_uint32)), cap_s,
-                                    _u8p(raw), raw.size, hdr)
+        u32p = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        if layers:
+            pieces = np.zeros((cap_p, 4), dtype=np.uint32)
+            npc = C.c_size_t()
+            n = self.L.j2ko_file_block_pieces(_u8p(buf), len(data), _i32p(meta), cap_b, u32p(segs), cap_s, _u8p(raw), raw.size, hdr,
+                                              u32p(pieces), cap_p, C.byref(npc))
+        else:
+            n = self.L.j2ko_file_blocks(_u8p(buf), len(data), _i32p(meta), cap_b, u32p(segs), cap_s, _u8p(raw), raw.size, hdr)
         if n < 0:
             raise RuntimeError("oracle decode failed: " + self.L.j2ko_decode_error().decode())
         blocks = []
-        for m in meta[:n]:
-            tile, comp, res, orient, x, y, w, h, nb, npass, s0, ns, off, ln, hs, _ = (int(v) for v in m)
+        for m in meta[:n].tolist():
+            tile, comp, res, orient, x, y, w, h, nb, npass, s0, ns, off, ln, hs, _ = m
             blocks.append(dict(tile=tile, comp=comp, res=res, orient=orient, rect=(x, y, w, h), w=w, h=h, numbps=nb, npasses=npass,
                                half_step=float(np.array([hs], dtype=np.int32).view(np.float32)[0]),
                                segs=[(int(a), int(b)) for a, b in segs[s0:s0 + ns]], data=raw[off:off + ln].tobytes()))
-        return dict(style=int(hdr[0]), reversible=bool(hdr[1]), ncomp=int(hdr[2]), ntiles=int(hdr[3]), blocks=blocks)
+        if layers:
+            for b in blocks:
+                b["pieces"] = []
+            for blk, lay, nbytes, npass in pieces[:npc.value].tolist():
+                blocks[blk]["pieces"].append((lay, nbytes, npass))
+        out = dict(style=int(hdr[0]), reversible=bool(hdr[1]), ncomp=int(hdr[2]), ntiles=int(hdr[3]), blocks=blocks)
+        if layers:
+            st = (C.c_long * 2)()
+            self.L.j2ko_packet_stats(st)
+            out.update(packets=int(st[0]), headers_ending_on_ff=int(st[1]))
+        return out
 
     def decode_output(self, comps, precs, reversible: bool, mct: bool) -> list:
         """The tail of a tile's decode (j2ko_decode_output): comps = one 2-D plane per component, int32 (reversible) or

@@ -41,12 +41,15 @@ static void synth_tables(const Geometry &g, uint32_t seed, std::vector<CblkResul
     uint32_t s = seed;
     for (size_t i = 0; i < nb; ++i) {
         const Cblk &c = g.cblks[i];
-        const uint32_t bps = lcg(s) % (c.Mb + 1u);
+        // the two extremes among them: every seventh block has all the bit-planes of its band (the largest pass count the band
+        // allows), every fifth adds no byte over a stretch of passes, every eleventh has passes and not one byte
+        const uint32_t bps = i % 7 == 3 ? c.Mb : lcg(s) % (c.Mb + 1u);
         res[i].numbps = bps;
         res[i].npasses = bps ? 3 * bps - 2 : 0;
         uint32_t acc = 0;
         for (uint32_t k = 0; k < res[i].npasses; ++k) {
-            acc += lcg(s) % (1 + (uint32_t)c.w * c.h / 8);
+            const uint32_t more = lcg(s) % (1 + (uint32_t)c.w * c.h / 8);
+            if (!(i % 11 == 5 || (i % 5 == 2 && k % 8 < 5))) acc += more;
             rate[i * kMaxPasses + k] = acc;
             nmse[i * kMaxPasses + k] = (int32_t)(lcg(s) % 100000);
         }
