@@ -705,6 +705,7 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
     t1_arena_args(e, tt, ta);
     ta.mq_prio = tn.mq_prio ? 3 : 0;
     ta.sparse = tn.t1_sparse;
+    ta.mq_window = tn.mq_window;
     ta.style = cod.cblk_style;
 #ifdef J2K_MQ_TIMES
     { // diagnostic build: where the two waves of the coder spend their cycles (previous frame's totals, at every encode)
@@ -1172,6 +1173,7 @@ bool encode_begin_banded(j2k_hip_encoder *e, const Coding &cod, const j2k_hip_pl
     t1_arena_args(e, tt, ta);
     ta.mq_prio = tn.mq_prio ? 3 : 0;
     ta.sparse = tn.t1_sparse;
+    ta.mq_window = tn.mq_window;
     ta.want_rates = 0; // (a band-pipelined call never runs under rate control: no per-pass byte counts)
     ta.gate_groups = e->gate_groups.as<T1Args::GateGroup>(); ta.gate_group_of = e->gate_group_of.as<unsigned>();
     ta.gate_ready = gate_ready; ta.gate_done = gate_done; ta.gate_abort = gate_abort;

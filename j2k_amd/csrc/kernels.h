@@ -48,6 +48,10 @@ struct Tuning {
     // debug only (tests, A/B): the modeller's sample-wise path for sparse significance / cleanup passes.  0 = chosen per pass
     // half by its counts, -1 = never, 1 = whenever the half fits the stage, however dense.  Never changes a byte.
     int t1_sparse = 0;
+    // debug only (tests, A/B): the plain two-wave coder's consumer (t1_mq2_kernel<false>).  0 = groups of four decisions on the wide
+    // code register (t1_mq_window.h), a group that reports a hazard coded again per decision; -1 = every group per decision, the
+    // consumer as the rate-control instantiation has it; 2 = every group sent back (both state conversions run).  Never changes a byte.
+    int mq_window = 0;
 };
 Tuning &tuning();
 int tune(const char *key, int value); // 0 = ok, 1 = unknown key
@@ -223,6 +227,7 @@ struct T1Args {
     // Code-block style of the frame (COD SPcod, cblk_style.h; 0 = none).  t1_model: with bypass, the sign decisions of raw passes
     // carry the sign itself.  launch_t1_mq: a style sends the blocks to the styled coder (t1_mq_styled.hip).
     unsigned style;
+    int mq_window;                      // t1_mq2 without want_rates: the consumer's code register (the knob mq_window).  (Last: no other member moves.)
 };
 void launch_t1_model(const T1Args &a, hipStream_t s);
 // blocks [first, nblks): the two-wave coder, or under a style the styled one

@@ -75,6 +75,7 @@ static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uin
         ta.want_dist = pass_dist != nullptr; // the distortion sums cost LDS and issue slots: only on request
         ta.want_rates = pass_rate || pass_dist; // the coder's per-pass byte counts: whenever the pass tables are read back
         ta.sparse = tuning().t1_sparse;
+        ta.mq_window = tuning().mq_window;
         ta.style = cblk_style;
 #ifdef J2K_T1_COUNTERS
         t1_counters(ta);

@@ -43,6 +43,7 @@
 #include "kernels.h"
 #include "t1_common.h"
 #include "cblk_style.h"
+#include "t1_mq_window.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -1087,6 +1088,12 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
     unsigned *pass_rate = a.pass_rate + (size_t)(live ? b : 0) * kDevMaxPasses;
     unsigned char *ostage_b = reinterpret_cast<unsigned char *>(ostage);
     unsigned C = 0, CT = 12, B = 0;
+    // Without RATES the state carried from group to group is the wide register of t1_mq_window.h -- (C, CT, B) as one number --
+    // unless the knob mq_window says otherwise: -1 = every group per decision on (C, CT, B), as under RATES; 2 = every group
+    // accumulated, then sent back and coded per decision, through both conversions.  No byte depends on it.
+    bool window = false, window_again = false;
+    if constexpr (!RATES) { window = a.mq_window >= 0; window_again = a.mq_window == 2; }
+    MqWide wide = mq_wide_from(C, CT, B);
     int flushed = 0;
     bool overflow = false;
     // The lane's stage: its data bytes start at dbase, and the byte at dbase is number `flushed` of the codeword.  `pos` is
@@ -1182,6 +1189,31 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
                 if constexpr (RATES) {
                     if (ends_here && __any(rel > 4 * g && rel <= 4 * g + 4)) four(std::true_type(), e, g);
                     else four(std::false_type(), e, g);
+                } else if (window) {
+                    // The group on the wide register (t1_mq_window.h): four additions and shifts without a test, then as many
+                    // peel rounds as the busiest lane has bytes -- one BYTEOUT's worth of selects per round instead of per
+                    // decision.  If some lane reports that its group is not exact that way (a carry above a 0xFF, a byte that
+                    // may have rolled over, a register wider than 63 bits), the whole wave codes the group per decision from its
+                    // starting state: the peel's bytes lie behind `pos` and are written over.
+                    const MqWide wide0 = wide;
+                    const unsigned pos0 = pos;
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) mq_wide_add(wide, e[jj]);
+                    bool again = window_again || mq_wide_is_wide(wide) || mq_wide_has_carry(wide);
+                    if (!__any(again)) {
+                        while (__any(mq_wide_due(wide))) {
+                            const bool due = mq_wide_due(wide);
+                            const unsigned byte = mq_wide_peel(wide, due, again);
+                            ostage_b[pos] = (unsigned char)byte;
+                            pos += due ? 1u : 0u;
+                        }
+                    }
+                    if (__any(again)) {
+                        pos = pos0;
+                        mq_wide_to(wide0, C, CT, B);
+                        four(std::false_type(), e, g);
+                        wide = mq_wide_from(C, CT, B);
+                    }
                 } else four(std::false_type(), e, g);
             }
             // Codeword bytes leave the stage in 16-byte units, every lane's at once: when some lane has 64 waiting, all lanes send
@@ -1190,6 +1222,9 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
             // left -- fewer than 16 bytes and the candidate's slot: four words -- to the front of its stage and pulls `pos` back.
             // A chunk adds fewer than 48 bytes to a lane, so fewer than 64 + 48 = 112 ever wait: the candidate's slot is at most
             // data byte 111 of the lane's kRing = 128, and the move reads no further than byte 6 * 16 + 15.
+            // (Per decision: a shift of at most 15 and 7 or 8 shifts to a byte, three BYTEOUTs -- 12 a group.  On the wide
+            // register a group peels at most five -- it starts below 35 bits, is peeled only if it stayed within 63, and a round
+            // takes 7 or 8 off -- and a group that is sent back starts again at the `pos` it began with: 12 bounds both, 48 a chunk.)
             const int waiting = (int)(pos - dbase); // (nothing yet: -1)
             if (__any(waiting >= 64)) {
                 const int units = waiting >> 4; // (-1 -> -1)
@@ -1223,6 +1258,9 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
 #ifdef J2K_MQ_TIMES
     if (lane == 0 && a.dbg) { atomicAdd(a.dbg + 2, (unsigned long long)tw_); atomicAdd(a.dbg + 3, (unsigned long long)tb_); }
 #endif
+    if constexpr (!RATES) {
+        if (window) mq_wide_to(wide, C, CT, B); // FLUSH runs on (C, CT, B)
+    }
     const bool fin = live && npasses;
     const unsigned A = finalA[lane]; // written by the producer before the last barrier
     if (fin) {

@@ -34,6 +34,7 @@ const Knob kKnobs[] = {
     {"decseq_group", "J2K_DECSEQ_GROUP", &Tuning::decseq_group},
     {"bands", "J2K_BANDS", &Tuning::bands},
     {"t1_sparse", "J2K_T1_SPARSE", &Tuning::t1_sparse},
+    {"mq_window", "J2K_MQ_WINDOW", &Tuning::mq_window},
 };
 
 Tuning g_tuning;

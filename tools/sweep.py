@@ -80,7 +80,7 @@ def set_knobs(kn):
 
 
 DEFAULTS = dict(dwt_xcd=1, fused_ppc=0, fused_wpb=0, dwt_ppc=0, dwt_min_waves=2048, dwt_pairs=2,
-                level_events=0, mq_wait_us=1500, mq_yield=2, mq_prio=1, groups=2, t1_sparse=0)
+                level_events=0, mq_wait_us=1500, mq_yield=2, mq_prio=1, groups=2, t1_sparse=0, mq_window=0)
 
 
 def dwt():
@@ -120,7 +120,8 @@ def live():
     p = params()
     planes = api.planes_from_layout(d, lay, 3)
     ref = None
-    variants = [dict(), dict(mq_yield=0), dict(), dict(t1_sparse=-1), dict(t1_sparse=1)]  # (t1_sparse: the modeller's two ways of writing a pass half)
+    # (t1_sparse: the modeller's two ways of writing a pass half; mq_window: the plain coder's consumer per decision / every group sent back)
+    variants = [dict(), dict(mq_yield=0), dict(), dict(t1_sparse=-1), dict(t1_sparse=1), dict(mq_window=-1), dict(mq_window=2)]
     if os.environ.get("SWEEP_LIVE"):  # an explicit list of knob settings (JSON), e.g. '[{}, {"mq_yield": 0}]'
         import json
         variants = json.loads(os.environ["SWEEP_LIVE"])
