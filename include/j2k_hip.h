@@ -825,6 +825,34 @@ int j2k_hip_stage_t1_styled(j2k_hip_encoder *enc, int reversible, void *d_coef, 
                             uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
                             void *data, size_t data_cap, uint32_t *pass_rate, uint32_t cblk_style);
 
+/* j2k_hip_stage_t1_styled with the caller's slots: the same launches under the same tuning knobs (modeller, coder -- the
+ * two-wave coder with cblk_style = 0, its pass-rate instantiation when pass_rate is given, the styled coder otherwise -- and
+ * the rate fix-up under a style), but block i gets sym_cap[i] bytes for its decisions and out_cap[i] for its codeword in
+ * place of what the frame's rule (j2k_hip_debug_cblk_capacities) would give, and a block that does not fit does not fail
+ * the call.  For the tests that hold the kernels' capacity checks to their reports.
+ * In: sym_cap[i], out_cap[i]: multiples of 16, at least 16, at most the rule's value for the block's area at Mb = 30 under
+ * cblk_style; guard_bytes: a multiple of 16.  Anything else is J2K_HIP_ERR_PARAM before any launch.
+ * Layout of both arenas: guard, slot 0, guard, slot 1, .., slot nblocks-1, guard -- slot i of an arena begins
+ * guard_bytes + sum over j < i of (cap[j] + guard_bytes) bytes in.  Before the launches every byte of both arenas, guards and
+ * slots alike, is set to J2K_HIP_SLOT_FILL.
+ * Out (host): *err = the kernels' error word: 0, or 2 = a block's decisions did not fit sym_cap (the modeller reports that
+ * block with no passes, no decisions, and the coder leaves its codeword slot alone), or 3 = a codeword did not fit out_cap
+ * (its length[i] is the length it would have had; the bytes that fit are in the slot); with both kinds in one call either.
+ * The call itself returns J2K_HIP_OK then.  numbps, npasses, nsym (decisions) and length per block; pass_rate (NULL, or
+ * nblocks rows of J2K_HIP_MAX_PASSES, as j2k_hip_stage_t1_styled's -- a block whose codeword did not fit gets the coder's
+ * counts without the fix-ups that look at bytes); sym_arena / out_arena receive the arenas whole (a buffer smaller than the
+ * layout: J2K_HIP_ERR_OVERFLOW before any launch).
+ * A block fits exactly: round_up(decisions, 16) bytes of sym_cap and round_up(length, 16) bytes of out_cap suffice, and the
+ * kernels write no byte outside [0, round_up(decisions, 16)) and [0, round_up(length, 4)) of a slot that holds its block.
+ * J2K_HIP_ABI_VERSION is still 9: a function was added, none changed. */
+#define J2K_HIP_SLOT_FILL 0xA5
+int j2k_hip_stage_t1_slots(j2k_hip_encoder *enc, int reversible, void *d_coef, uint32_t stride,
+                           uint32_t nblocks, const uint32_t *bx, const uint32_t *by, const uint32_t *bw,
+                           const uint32_t *bh, const uint32_t *orient, const float *stepsize, uint32_t cblk_style,
+                           const uint32_t *sym_cap, const uint32_t *out_cap, uint32_t guard_bytes, uint32_t *err,
+                           uint32_t *numbps, uint32_t *npasses, uint32_t *nsym, uint32_t *length, uint32_t *pass_rate,
+                           void *sym_arena, size_t sym_arena_cap, void *out_arena, size_t out_arena_cap);
+
 /* The rate control's kernels alone (rate_prepare_kernel, rate_ahead_kernel, rate_scan_kernel), on Tier-1 tables the caller
  * supplies, driven through the objects an encode drives them with.  All arrays are host memory.
  * In, per block i < nblocks (>= 1): weight[i] (the block's weight without the bit-plane), comp[i] (0..3), numbps[i] (<= 31),

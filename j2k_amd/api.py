@@ -101,7 +101,7 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_encode_tiles_distributed", "j2k_hip_multi_last_error",
            "j2k_hip_encode_to_buffer", "j2k_hip_encode_device", "j2k_hip_encode_sequence_device", "j2k_hip_encode_tiles_device",
            "j2k_hip_main_header", "j2k_hip_file_header", "j2k_hip_xyz_tables", "j2k_hip_stage_frontend", "j2k_hip_stage_dwt", "j2k_hip_stage_dwt_regions", "j2k_hip_stage_t1", "j2k_hip_stage_t1_passes",
-           "j2k_hip_stage_t1_styled", "j2k_hip_stage_transform",
+           "j2k_hip_stage_t1_styled", "j2k_hip_stage_t1_slots", "j2k_hip_stage_transform",
            "j2k_hip_stage_rate", "j2k_hip_stage_gather", "j2k_hip_stage_pack_offsets",
            "j2k_hip_stage_idwt", "j2k_hip_stage_idwt_window", "j2k_hip_stage_t1_decode", "j2k_hip_stage_t1_decode_styled", "j2k_hip_stage_decode_output",
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
@@ -257,6 +257,9 @@ def load_library():
                                    C.POINTER(C.c_float), U32P, U32P, U32P, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t]
     L.j2k_hip_stage_t1_passes.argtypes = L.j2k_hip_stage_t1.argtypes + [U32P, C.POINTER(C.c_int32)]
     L.j2k_hip_stage_t1_styled.argtypes = L.j2k_hip_stage_t1.argtypes + [U32P, C.c_uint32]
+    L.j2k_hip_stage_t1_slots.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, U32P, U32P, U32P, U32P, U32P,
+                                         C.POINTER(C.c_float), C.c_uint32, U32P, U32P, C.c_uint32, U32P, U32P, U32P, U32P, U32P, U32P,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
     L.j2k_hip_stage_rate.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 9 + [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                      C.c_void_p, C.POINTER(RateScan), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.j2k_hip_stage_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
@@ -1343,6 +1346,45 @@ class Encoder:
                 o["rates"] = list(rates[i * MP:i * MP + o["npasses"]])
                 o["nmsedec"] = list(dist[i * MP:i * MP + o["npasses"]])
         return out
+
+    def stage_t1_slots(self, coef: np.ndarray, rects, orients, stepsizes, reversible: bool, style: int, sym_cap, out_cap,
+                       guard_bytes: int, want_passes: bool = False):
+        """j2k_hip_stage_t1_slots: stage_t1 with the caller's capacities per block (bytes of decisions, bytes of codeword) and
+        guard stripes of guard_bytes around every slot; a block that does not fit does not raise.  Returns a dict: err (the
+        kernels' error word), numbps / npasses / nsym / length (uint32 arrays), rates ((n, 96) uint32, with want_passes), sym
+        and out (the arenas whole, uint8), sym_off / out_off (where each block's slot begins: computed here, from the layout
+        the header states) and fill (the byte both arenas are filled with before the launches)."""
+        dt = np.int32 if reversible else np.float32
+        coef = np.ascontiguousarray(coef, dtype=dt)
+        H, W = coef.shape
+        nb = len(rects)
+        U = lambda v: (C.c_uint32 * max(nb, 1))(*v)
+        bx, by, bw, bh = (U([r[i] for r in rects]) for i in range(4))
+        ori = U(orients)
+        ss = (C.c_float * max(nb, 1))(*stepsizes)
+        sc, oc = U([int(v) for v in sym_cap]), U([int(v) for v in out_cap])
+        sym_off = guard_bytes + np.concatenate([[0], np.cumsum([int(v) + guard_bytes for v in sym_cap])]).astype(np.int64)
+        out_off = guard_bytes + np.concatenate([[0], np.cumsum([int(v) + guard_bytes for v in out_cap])]).astype(np.int64)
+        sym = np.zeros(int(sym_off[-1]), dtype=np.uint8)
+        out = np.zeros(int(out_off[-1]), dtype=np.uint8)
+        numbps, npasses, nsym, length = (np.zeros(max(nb, 1), dtype=np.uint32) for _ in range(4))
+        P = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        MP = 96
+        rates = np.zeros((max(nb, 1), MP), dtype=np.uint32) if want_passes else None
+        err = C.c_uint32(0xffffffff)
+        d = self.upload(coef)
+        try:
+            self._check(self.L.j2k_hip_stage_t1_slots(self.h, int(reversible), d, W, nb, bx, by, bw, bh, ori, ss, C.c_uint32(style),
+                                                      sc, oc, guard_bytes, C.byref(err), P(numbps), P(npasses), P(nsym), P(length),
+                                                      P(rates) if want_passes else None, sym.ctypes.data, sym.size,
+                                                      out.ctypes.data, out.size))
+        finally:
+            self.free(d)
+        res = dict(err=err.value, numbps=numbps[:nb], npasses=npasses[:nb], nsym=nsym[:nb], length=length[:nb], sym=sym, out=out,
+                   sym_off=sym_off[:nb], out_off=out_off[:nb], fill=0xA5)
+        if want_passes:
+            res["rates"] = rates[:nb]
+        return res
 
     def stage_rate(self, weight, comp, numbps, npasses, pass_rate, pass_dist, first=0, count=0, done=None, ahead=None, scans=()):
         """j2k_hip_stage_rate.  Tables per block (pass_rate / pass_dist: (n, 96)); scans: (thresh, mode, slot) with mode one

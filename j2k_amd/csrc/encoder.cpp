@@ -129,15 +129,27 @@ bool same_coding(const Coding &a, const Coding &b)
 // Decision-stream and codeword capacities of a code-block of `area` samples with up to Mb bit-planes under code-block style
 // `style`: one rule for the frames (prepare_geometry) and for the Tier-1 stage hooks.  A frame passes the band's own Mb; the
 // hooks know no band and pass 30, so a hook's capacities are a frame's or larger (two to three times at the usual depths):
-// the hooks show that the rule holds the codewords of Mb = 30, not that a frame's smaller Mb does.
-// A frame's block can come with Mb + 1 bit-planes (a frame beyond its guard bits): the slots of Mb hold its
-// decisions and codeword all the same (tests/test_guard_bits_refs.py, on the oracle's decision streams), so such a frame ends
-// in Tier-2's J2K_HIP_ERR_OVERFLOW and not in a Tier-1 capacity error -- or, under J2K_HIP_GUARD_AUTO, is planned again with
-// more guard bits from the very slots it was coded into.  A fixed guard-bit count above two raises Mb and the slots with it.
+// the hooks show that the rule holds the codewords of Mb = 30, not that a frame's smaller Mb does.  That is
+// tests/test_t1_capacity_refs.py's (the rule against the oracle's decisions and codewords for Mb = 1 .. 12, blocks of Mb and
+// of Mb + 1 bit-planes) and tests/test_t1_capacity.py's, through j2k_hip_stage_t1_slots: a block fits a slot exactly -- its
+// decisions rounded up to 16 bytes, its codeword rounded up to 16 bytes -- and one that does not is reported (error word
+// 2: the modeller, 3: a coder), never stored past its slot.
+// The most decisions a w x h block of p bit-planes can have: every sample takes one zero-coding or refinement decision per
+// plane (or shares a run-length decision) and turns significant once, one sign: (p + 1) area.  A run-length column that
+// breaks costs at most two decisions more than the four zero-coding decisions it stands for; the sample that broke it is
+// significant from then on, which keeps its own column and the columns beside it out of run-length mode for good: at most
+// every other column of a full stripe breaks, once -- 2 ceil(w / 2) floor(h / 4) <= area / 4 + 16 more.  The bound is met
+// (the family run_breaks of the test: (p + 1.25) area for 64 x 64).
+// A frame's block can come with Mb + 1 bit-planes (a frame beyond its guard bits), and the slots of Mb must
+// hold its decisions and codeword all the same, so that such a frame ends in Tier-2's J2K_HIP_ERR_OVERFLOW and not in a
+// Tier-1 capacity error -- or, under J2K_HIP_GUARD_AUTO, is planned again with more guard bits from the very slots it was
+// coded into.  (Mb + 2.25) area + 16 is within the first term below from Mb = 3 on and above it for Mb = 1 and 2 (1- and
+// 2-bit frames at one or two guard bits): the second term is there for those, and changes no capacity of Mb >= 3.
+// A fixed guard-bit count above two raises Mb and the slots with it.
 CblkCaps j2k_hip::cblk_capacities(size_t area, uint32_t Mb, uint32_t style)
 {
-    // <= 1.5 decisions per sample and bit-plane (ZC/MR + run-length overhead) + one sign each
-    const size_t symcap = round_up(area * 3 * Mb / 2 + area + 64, 1024);
+    // <= 1.5 decisions per sample and bit-plane (ZC/MR + run-length overhead) + one sign each; a block of Mb + 1 planes
+    const size_t symcap = round_up(std::max(area * 3 * Mb / 2 + area + 64, (Mb + 2) * area + area / 4 + 16), 1024);
     // Under a code-block style every terminated pass adds to the codeword: a FLUSH at most two bytes beyond what the open
     // segment would have needed anyway, the predictable form at most four, the padding of a raw segment one, and the
     // four segmentation symbols of a cleanup pass under two.  8 bytes for each of the 3 Mb - 2 passes cover them all;

@@ -17,11 +17,25 @@
 
 using namespace j2k_hip;
 
-// the three Tier-1 stage hooks are one function: pass_rate / pass_dist on request, a code-block style or none
+// What j2k_hip_stage_t1_slots adds to the Tier-1 stage hooks: the caller's capacities, guard stripes between the slots, the
+// error word instead of a failure, and both arenas whole.
+struct T1Slots {
+    const uint32_t *sym_cap, *out_cap;
+    uint32_t guard_bytes;
+    uint32_t *err, *nsym;
+    void *sym_arena; size_t sym_arena_cap;
+    void *out_arena; size_t out_arena_cap;
+};
+constexpr int kSlotFill = 0xA5; // what an arena of j2k_hip_stage_t1_slots holds wherever no kernel wrote (J2K_HIP_SLOT_FILL)
+static_assert(kSlotFill == J2K_HIP_SLOT_FILL, "the header names the fill");
+
+// the Tier-1 stage hooks are one function: pass_rate / pass_dist on request, a code-block style or none, and the slots by the
+// frame's rule (at Mb = 30, back to back) or as the caller lays them out (slots)
 static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
                            const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
                            const float *stepsize, uint32_t *numbps, uint32_t *npasses, uint32_t *length, uint64_t *offsets,
-                           void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist, uint32_t cblk_style)
+                           void *data, size_t data_cap, uint32_t *pass_rate, int32_t *pass_dist, uint32_t cblk_style,
+                           const T1Slots *slots = nullptr)
 {
     if (!e) return J2K_HIP_ERR_PARAM;
     return guarded(e, [&] {
@@ -30,24 +44,36 @@ static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uin
         // the styles a frame refuses (geometry.cpp)
         if (cblk_style & kStyleVcausal) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: vertically causal contexts (bit 8) are not written");
         if (cblk_style & ~(uint32_t)(kStylesEncoded | kStyleVcausal)) throw Error(J2K_HIP_ERR_PARAM, "cblk_style: unknown code-block style bits");
+        if (slots) {
+            if (!slots->sym_cap || !slots->out_cap || !slots->err || !slots->nsym || !slots->sym_arena || !slots->out_arena || !numbps || !npasses || !length)
+                throw Error(J2K_HIP_ERR_PARAM, "Tier-1 slots: an array is NULL");
+            if (slots->guard_bytes % 16) throw Error(J2K_HIP_ERR_PARAM, "Tier-1 slots: guard_bytes must be a multiple of 16");
+        }
         HIP_CHECK(hipSetDevice(e->device));
         hipStream_t s = e->stream;
+        const size_t guard = slots ? slots->guard_bytes : 0;
         const size_t nb = nblocks;
         std::vector<CblkDev> blks(nb);
-        size_t sym_off = 0, out_off = 0;
+        size_t sym_off = guard, out_off = guard; // (a guard stripe in front of every slot and behind the last)
         for (size_t i = 0; i < nb; ++i) {
             if (bw[i] == 0 || bh[i] == 0 || bw[i] > 64 || bh[i] > 64 || orient[i] > 3) throw Error(J2K_HIP_ERR_PARAM, "bad code-block rectangle");
             CblkDev d{};
             d.coef_off = (unsigned long long)by[i] * stride + bx[i];
             const size_t area = (size_t)bw[i] * bh[i];
             const CblkCaps caps = cblk_capacities(area, 30, cblk_style); // (Mb = 30: no band is known here; a frame's are smaller)
-            const size_t symcap = caps.sym, outcap = caps.out;
+            size_t symcap = caps.sym, outcap = caps.out;
+            if (slots) {
+                symcap = slots->sym_cap[i]; outcap = slots->out_cap[i];
+                if (symcap % 16 || outcap % 16 || symcap < 16 || outcap < 16 || symcap > caps.sym || outcap > caps.out)
+                    throw Error(J2K_HIP_ERR_PARAM, "Tier-1 slots: a capacity must be a multiple of 16, at least 16 and at most the rule's at Mb = 30");
+            }
             d.sym_off = sym_off; d.sym_cap = (unsigned)symcap; d.out_off = out_off; d.out_cap = (unsigned)outcap;
             d.stepsize = stepsize ? stepsize[i] : 1.0f;
             d.w = (unsigned short)bw[i]; d.h = (unsigned short)bh[i]; d.orient = (unsigned char)orient[i]; d.Mb = 30;
-            sym_off += symcap; out_off += outcap;
+            sym_off += symcap + guard; out_off += outcap + guard;
             blks[i] = d;
         }
+        if (slots && (sym_off > slots->sym_arena_cap || out_off > slots->out_arena_cap)) throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 slots: an arena buffer is too small");
         {
             // The modeller rewrites every block of d_coef in place (scaled magnitudes, transposed bit-planes): two blocks that
             // share a sample would read each other's scratch.  Sweep over the blocks sorted by their top row.
@@ -81,16 +107,26 @@ static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uin
         t1_counters(ta);
 #endif
         HIP_CHECK(hipMemsetAsync(ta.err, 0, sizeof(uint32_t), s));
+        if (slots) { // guards and slots alike: a byte that no kernel wrote comes back as the fill
+            HIP_CHECK(hipMemsetAsync(e->sym.p, kSlotFill, sym_off, s));
+            HIP_CHECK(hipMemsetAsync(e->out.p, kSlotFill, out_off, s));
+        }
         launch_t1_model(ta, s);
         launch_t1_mq(ta, s);
         if (cblk_style) launch_t1_rate_fixup(ta, s); // as a styled frame has them: on the device, behind the styled coder
         std::vector<uint32_t> hm(tt.meta_words());
         HIP_CHECK(hipMemcpyAsync(hm.data(), e->meta.p, hm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (slots) {
+            HIP_CHECK(hipMemcpyAsync(slots->sym_arena, e->sym.p, sym_off, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(slots->out_arena, e->out.p, out_off, hipMemcpyDeviceToHost, s));
+        }
         HIP_CHECK(hipStreamSynchronize(s));
-        if (*tt.err(hm.data())) throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 kernel reported error " + std::to_string(*tt.err(hm.data())));
+        if (slots) *slots->err = *tt.err(hm.data()); // (the caller's to judge: a block that does not fit is what this hook is for)
+        else if (*tt.err(hm.data())) throw Error(J2K_HIP_ERR_OVERFLOW, "Tier-1 kernel reported error " + std::to_string(*tt.err(hm.data())));
         size_t pos = 0;
         for (size_t i = 0; i < nb; ++i) {
             numbps[i] = tt.numbps(hm.data())[i]; npasses[i] = tt.npasses(hm.data())[i]; length[i] = tt.len(hm.data())[i];
+            if (slots) { slots->nsym[i] = tt.nsym(hm.data())[i]; continue; } // (the codewords are in the arena)
             offsets[i] = pos;
             if (pos + length[i] > data_cap) throw Error(J2K_HIP_ERR_OVERFLOW, "data buffer too small");
             if (length[i]) HIP_CHECK(hipMemcpy(static_cast<uint8_t *>(data) + pos, e->out.as<uint8_t>() + blks[i].out_off, length[i], hipMemcpyDeviceToHost));
@@ -103,12 +139,12 @@ static int stage_t1_blocks(j2k_hip_encoder *e, int reversible, void *d_coef, uin
                 const uint32_t np = npasses[i];
                 uint32_t *rate = tt.pass_rate(hp.data()) + tt.row(i);
                 const uint32_t *nmsedec = tt.pass_nmsedec(hp.data()) + tt.row(i);
-                if (!cblk_style) {
+                if (!cblk_style && !(slots && length[i] > blks[i].out_cap)) { // (a codeword that did not fit has no bytes to look at)
                     // the reference's fix-ups of the per-pass byte counts: an estimate never exceeds what
                     // follows it, and a pass never ends on 0xFF  (under a style the kernel above has applied them)
                     uint32_t last = length[i];
                     for (uint32_t p = np; p > 0;) { --p; if (rate[p] > last) rate[p] = last; else last = rate[p]; }
-                    const uint8_t *bytes = static_cast<const uint8_t *>(data) + offsets[i];
+                    const uint8_t *bytes = slots ? static_cast<const uint8_t *>(slots->out_arena) + blks[i].out_off : static_cast<const uint8_t *>(data) + offsets[i];
                     for (uint32_t p = 0; p < np; ++p)
                         if (rate[p] > 0 && bytes[rate[p] - 1] == 0xff) --rate[p];
                 }
@@ -375,6 +411,17 @@ int j2k_hip_stage_t1_styled(j2k_hip_encoder *e, int reversible, void *d_coef, ui
 {
     return stage_t1_blocks(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses, length,
                            offsets, data, data_cap, pass_rate, nullptr, cblk_style);
+}
+
+int j2k_hip_stage_t1_slots(j2k_hip_encoder *e, int reversible, void *d_coef, uint32_t stride, uint32_t nblocks,
+                           const uint32_t *bx, const uint32_t *by, const uint32_t *bw, const uint32_t *bh, const uint32_t *orient,
+                           const float *stepsize, uint32_t cblk_style, const uint32_t *sym_cap, const uint32_t *out_cap,
+                           uint32_t guard_bytes, uint32_t *err, uint32_t *numbps, uint32_t *npasses, uint32_t *nsym, uint32_t *length,
+                           uint32_t *pass_rate, void *sym_arena, size_t sym_arena_cap, void *out_arena, size_t out_arena_cap)
+{
+    const T1Slots slots{sym_cap, out_cap, guard_bytes, err, nsym, sym_arena, sym_arena_cap, out_arena, out_arena_cap};
+    return stage_t1_blocks(e, reversible, d_coef, stride, nblocks, bx, by, bw, bh, orient, stepsize, numbps, npasses, length,
+                           nullptr, nullptr, 0, pass_rate, nullptr, cblk_style, &slots);
 }
 
 // The rate control's kernels alone (rate.hip), on tables the caller supplies, through the objects an encode drives them with:
