@@ -48,9 +48,11 @@ struct Tuning {
     // debug only (tests, A/B): the modeller's sample-wise path for sparse significance / cleanup passes.  0 = chosen per pass
     // half by its counts, -1 = never, 1 = whenever the half fits the stage, however dense.  Never changes a byte.
     int t1_sparse = 0;
-    // debug only (tests, A/B): the plain two-wave coder's consumer (t1_mq2_kernel<false>).  0 = groups of four decisions on the wide
-    // code register (t1_mq_window.h), a group that reports a hazard coded again per decision; -1 = every group per decision, the
-    // consumer as the rate-control instantiation has it; 2 = every group sent back (both state conversions run).  Never changes a byte.
+    // debug only (tests, A/B): the plain two-wave coder's consumer (t1_mq2_kernel<false>).  0 = groups of four decisions, summed by
+    // the producer, on the wide code register (t1_mq_window.h), a group that reports a hazard coded again per decision; -1 = every
+    // group per decision, the consumer as the rate-control instantiation has it; 2 = every group peeled, then sent back (both state
+    // conversions run); 3 = every lane reports every group long (sent back before the peel).  -1, 2 and 3 unpack the group's
+    // addends and shifts at every group.  Never changes a byte.
     int mq_window = 0;
 };
 Tuning &tuning();

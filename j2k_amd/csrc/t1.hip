@@ -918,7 +918,7 @@ __device__ __forceinline__ unsigned ctx_word2(unsigned qe, unsigned idx, unsigne
 //   stage 2 (code register C, counter CT, pending byte B): += addend, << n, BYTEOUTs, pass rates
 // Stage 1 never needs C/CT/B, so a workgroup runs them as a producer wave and a consumer wave on
 // different SIMDs, 64 blocks each (lane = block), joined by a double-buffered LDS queue of
-// {addend | n << 16} words that is handed over once per 16 decisions (one barrier).  The serial
+// {addend | n << 16} words (in a plain frame: of groups of four, summed) that is handed over once per 16 decisions (one barrier).  The serial
 // chain per decision is cut roughly in half.
 // Staged codeword bytes per lane of the two-wave coder.  (As a ring of 256 -- the ring index a byte of the count -- it coded a
 // frame alone 1 % sooner, but its 8 KiB more of LDS per workgroup cost 3 % with frames in flight (8020 against 8280 Mpixel/s
@@ -938,7 +938,8 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
     // One 32-bit word per look-up -- the producer knows which of the two it wants before it asks -- instead of the pair:
     // half the LDS bytes of the gather, whose bank conflicts were a third of this kernel's LDS-active cycles (profiles/r2_t1_pmc.txt)
     __shared__ unsigned trans[256];
-    __shared__ uint4 queue[2][4][64]; // [buffer][decision / 4][lane]
+    // [buffer][decision / 4][lane]; without RATES the same 16 bytes per lane and group as two halves of eight, [buffer][decision / 4][half][lane]
+    __shared__ uint4 queue[2][4][64];
     __shared__ __attribute__((aligned(16))) unsigned ostage[(kRing / 4 + 1) * 64]; // per lane one pad word, then kRing bytes: stride kRing + 4 B (an odd number of banks), conflict-free byte-out stores
     __shared__ unsigned finalA[64];   // the producer's interval register after the last decision (FLUSH needs it)
     const int lane = threadIdx.x & 63;
@@ -1019,14 +1020,15 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
                 // One decision: the context's word, the transition it may take (asked for as soon as the word is there),
                 // the interval.  Both table addresses come from byte permutes of values formed once per four symbols: the
                 // context word's is the context number above lane * 4 (both fit a byte), the transition entry's the state
-                // word's low bits xor the decision's bit at bit 9 -- the tables' own offsets ride in the instructions -- and
-                // what goes to the consumer is {addend | shift << 16} as before.
+                // word's low bits xor the decision's bit at bit 9 -- the tables' own offsets ride in the instructions.
                 unsigned char *const ctx_b = reinterpret_cast<unsigned char *>(ctxs);
                 const unsigned char *const trans_b = reinterpret_cast<const unsigned char *>(trans);
                 const unsigned lane4 = (unsigned)lane * 4u;
                 // c4: the four symbols' context numbers, one byte each; b4: the symbols (context << 1 | bit < 128) shifted up by
                 // one: a symbol's byte, moved to byte 1, has its bit at bit 9 and nothing else under the mask; jj: which of the four
-                auto decide = [&](unsigned c4, unsigned b4, auto jj_) -> unsigned {
+                // What goes to the consumer under RATES is {addend | shift << 16}, the value returned; otherwise the group
+                // is summed (below) from q, the decision's addend still in the high half, and nn, its shift.
+                auto decide = [&](unsigned c4, unsigned b4, auto jj_, unsigned &q, unsigned &nn) -> unsigned {
                     constexpr unsigned jj = decltype(jj_)::value;
                     unsigned *const cp = reinterpret_cast<unsigned *>(ctx_b + __builtin_amdgcn_perm(c4, lane4, 0x0c0c0400u + (jj << 8)));
                     const unsigned st = *cp;
@@ -1041,29 +1043,68 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
                     *cp = renorm ? tr : st;
                     const unsigned n = (unsigned)__builtin_clz(A);
                     A <<= n;
-                    return __builtin_amdgcn_alignbit(n, use_a1 ? qe : 0u, 16);
+                    if constexpr (RATES) return __builtin_amdgcn_alignbit(n, use_a1 ? qe : 0u, 16);
+                    q = use_a1 ? qe : 0u;
+                    nn = n;
+                    return 0u;
+                };
+                // Without RATES the group goes over summed (t1_mq_window.h): {G, shifts} in one 8-byte half of the lane's 16 bytes
+                // -- all the consumer reads unless the group is coded again -- and the addends in the other; the halves of the
+                // 64 lanes lie together, so that either is read at eight bytes a lane without a bank conflict.
+                auto send = [&](const int g, const unsigned (&q)[4], const unsigned (&n)[4]) {
+                    unsigned G = 0, N = 0, shifts = 0;
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        mq_group_add(G, N, q[jj] >> 16, n[jj]);
+                        shifts = mq_group_add_shift(shifts, n[jj], (unsigned)jj);
+                    }
+                    uint2 *const half = reinterpret_cast<uint2 *>(queue) + ((c & 1) * 4 + g) * 128 + lane;
+                    half[0] = make_uint2(G, shifts);
+                    half[64] = make_uint2(mq_group_pack_addends_high(q[0], q[1]), mq_group_pack_addends_high(q[2], q[3]));
                 };
                 if (__all(rem == 16)) { // every lane has a full chunk: no per-decision test for the lane's end
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         const unsigned c4 = (words[g] >> 1) & 0x1f1f1f1fu, b4 = words[g] << 1;
-                        unsigned e[4];
-                        e[0] = decide(c4, b4, std::integral_constant<unsigned, 0>());
-                        e[1] = decide(c4, b4, std::integral_constant<unsigned, 1>());
-                        e[2] = decide(c4, b4, std::integral_constant<unsigned, 2>());
-                        e[3] = decide(c4, b4, std::integral_constant<unsigned, 3>());
-                        queue[c & 1][g][lane] = make_uint4(e[0], e[1], e[2], e[3]);
+                        unsigned e[4], q[4], n[4];
+                        e[0] = decide(c4, b4, std::integral_constant<unsigned, 0>(), q[0], n[0]);
+                        e[1] = decide(c4, b4, std::integral_constant<unsigned, 1>(), q[1], n[1]);
+                        e[2] = decide(c4, b4, std::integral_constant<unsigned, 2>(), q[2], n[2]);
+                        e[3] = decide(c4, b4, std::integral_constant<unsigned, 3>(), q[3], n[3]);
+                        if constexpr (RATES) queue[c & 1][g][lane] = make_uint4(e[0], e[1], e[2], e[3]);
+                        else send(g, q, n);
                     }
                 } else
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const unsigned c4 = (words[g] >> 1) & 0x1f1f1f1fu, b4 = words[g] << 1;
-                    unsigned e[4] = {0, 0, 0, 0};
-                    if (4 * g + 0 < rem) e[0] = decide(c4, b4, std::integral_constant<unsigned, 0>());
-                    if (4 * g + 1 < rem) e[1] = decide(c4, b4, std::integral_constant<unsigned, 1>());
-                    if (4 * g + 2 < rem) e[2] = decide(c4, b4, std::integral_constant<unsigned, 2>());
-                    if (4 * g + 3 < rem) e[3] = decide(c4, b4, std::integral_constant<unsigned, 3>());
-                    queue[c & 1][g][lane] = make_uint4(e[0], e[1], e[2], e[3]);
+                    if constexpr (RATES) {
+                        unsigned e[4] = {0, 0, 0, 0}, q, n;
+                        if (4 * g + 0 < rem) e[0] = decide(c4, b4, std::integral_constant<unsigned, 0>(), q, n);
+                        if (4 * g + 1 < rem) e[1] = decide(c4, b4, std::integral_constant<unsigned, 1>(), q, n);
+                        if (4 * g + 2 < rem) e[2] = decide(c4, b4, std::integral_constant<unsigned, 2>(), q, n);
+                        if (4 * g + 3 < rem) e[3] = decide(c4, b4, std::integral_constant<unsigned, 3>(), q, n);
+                        queue[c & 1][g][lane] = make_uint4(e[0], e[1], e[2], e[3]);
+                    } else {
+                        // (the four words summed in place, each decision's share under the decision's own mask: four zeros to
+                        //  start from instead of eight, and a decision past the lane's end leaves every field as it is)
+                        unsigned G = 0, N = 0, shifts = 0, a[2] = {0, 0};
+                        auto one = [&](auto jj_) {
+                            constexpr unsigned jj = decltype(jj_)::value;
+                            unsigned q, n;
+                            decide(c4, b4, jj_, q, n);
+                            mq_group_add(G, N, q >> 16, n);
+                            shifts = mq_group_add_shift(shifts, n, jj);
+                            a[jj >> 1] = (jj & 1u) ? mq_group_pack_addends(a[jj >> 1], q >> 16) : q >> 16;
+                        };
+                        if (4 * g + 0 < rem) one(std::integral_constant<unsigned, 0>());
+                        if (4 * g + 1 < rem) one(std::integral_constant<unsigned, 1>());
+                        if (4 * g + 2 < rem) one(std::integral_constant<unsigned, 2>());
+                        if (4 * g + 3 < rem) one(std::integral_constant<unsigned, 3>());
+                        uint2 *const half = reinterpret_cast<uint2 *>(queue) + ((c & 1) * 4 + g) * 128 + lane;
+                        half[0] = make_uint2(G, shifts);
+                        half[64] = make_uint2(a[0], a[1]);
+                    }
                 }
             } else {
                 finalA[lane] = A >> 16; // last iteration: nothing left to produce
@@ -1090,9 +1131,10 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
     unsigned C = 0, CT = 12, B = 0;
     // Without RATES the state carried from group to group is the wide register of t1_mq_window.h -- (C, CT, B) as one number --
     // unless the knob mq_window says otherwise: -1 = every group per decision on (C, CT, B), as under RATES; 2 = every group
-    // accumulated, then sent back and coded per decision, through both conversions.  No byte depends on it.
-    bool window = false, window_again = false;
-    if constexpr (!RATES) { window = a.mq_window >= 0; window_again = a.mq_window == 2; }
+    // accumulated and peeled, then sent back and coded per decision, through both conversions; 3 = every lane reports every
+    // group long: sent back before anything is peeled.  No byte depends on it.
+    bool window = false, window_again = false, window_long = false;
+    if constexpr (!RATES) { window = a.mq_window >= 0; window_again = a.mq_window == 2; window_long = a.mq_window == 3; }
     MqWide wide = mq_wide_from(C, CT, B);
     int flushed = 0;
     bool overflow = false;
@@ -1184,37 +1226,61 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
             if constexpr (RATES) ends_here = __any(rel <= 16);
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const uint4 q = queue[(c - 1) & 1][g][lane];
-                const unsigned e[4] = {q.x, q.y, q.z, q.w};
                 if constexpr (RATES) {
+                    const uint4 q = queue[(c - 1) & 1][g][lane];
+                    const unsigned e[4] = {q.x, q.y, q.z, q.w};
                     if (ends_here && __any(rel > 4 * g && rel <= 4 * g + 4)) four(std::true_type(), e, g);
                     else four(std::false_type(), e, g);
-                } else if (window) {
-                    // The group on the wide register (t1_mq_window.h): four additions and shifts without a test, then as many
-                    // peel rounds as the busiest lane has bytes -- one BYTEOUT's worth of selects per round instead of per
-                    // decision.  If some lane reports that its group is not exact that way (a carry above a 0xFF, a byte that
-                    // may have rolled over, a register wider than 63 bits), the whole wave codes the group per decision from its
-                    // starting state: the peel's bytes lie behind `pos` and are written over.
+                } else {
+                    // The group as the producer summed it (t1_mq_window.h): V = (V << N) + G, then as many peel rounds as the
+                    // busiest lane has bytes -- one BYTEOUT's worth of selects per round instead of per decision.  The wave codes
+                    // the group per decision from its starting state -- the peel's bytes lie behind `pos` and are written over --
+                    // if some lane reports that it is not exact that way: its shifts sum to more than 15 (G is not whole), a
+                    // carry above a 0xFF, or a byte that reads 0x00 and whose top boundary a carry crossed.  Only then are the
+                    // four {addend, shift} read and unpacked.
+                    const uint2 *const half = reinterpret_cast<const uint2 *>(queue) + (((c - 1) & 1) * 4 + g) * 128 + lane;
+                    uint2 q = half[0];
+                    asm("" : "+v"(q.x), "+v"(q.y)); // (one 8-byte load: left to itself the compiler reads the two words apart, G only where it is used, and two 4-byte reads at 8 bytes a lane meet in the banks)
+                    bool again = true; // (wave-uniform from here on)
                     const MqWide wide0 = wide;
                     const unsigned pos0 = pos;
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) mq_wide_add(wide, e[jj]);
-                    bool again = window_again || mq_wide_is_wide(wide) || mq_wide_has_carry(wide);
-                    if (!__any(again)) {
-                        while (__any(mq_wide_due(wide))) {
-                            const bool due = mq_wide_due(wide);
-                            const unsigned byte = mq_wide_peel(wide, due, again);
-                            ostage_b[pos] = (unsigned char)byte;
-                            pos += due ? 1u : 0u;
+                    if (window) {
+                        const unsigned N = mq_group_N(q.y);
+                        mq_wide_add_group(wide, q.x, N);
+                        again = __any(window_long || mq_group_is_long(N) || mq_wide_has_carry(wide));
+                        if (!again) {
+                            const unsigned long long V_after = wide.V;
+                            unsigned zpos = kMqNoZero;
+                            // (a group that is not long ends below 50 bits and a round takes 7 or 8 off: three rounds at most, so
+                            //  plain tests instead of a loop, whose carried registers cost a copy each on every round)
+                            static_assert(kMqExactMax + kMqGroupMaxN - 3u * 7u < kMqWideDue, "three peel rounds must do");
+                            auto round = [&]() {
+                                const bool due = mq_wide_due(wide);
+                                const unsigned byte = mq_wide_peel_mark(wide, due, zpos);
+                                ostage_b[pos] = (unsigned char)byte;
+                                pos += due ? 1u : 0u;
+                            };
+                            if (__any(mq_wide_due(wide))) {
+                                round();
+                                if (__any(mq_wide_due(wide))) {
+                                    round();
+                                    if (__any(mq_wide_due(wide))) round();
+                                }
+                            }
+                            again = window_again;
+                            if (__any(zpos != kMqNoZero)) again = __any(window_again || mq_group_rolled(V_after, wide0.V, N, zpos));
                         }
                     }
-                    if (__any(again)) {
-                        pos = pos0;
-                        mq_wide_to(wide0, C, CT, B);
+                    if (again) {
+                        const uint2 r = half[64];
+                        unsigned e[4];
+#pragma unroll
+                        for (unsigned jj = 0; jj < 4; ++jj) e[jj] = mq_group_decision(q.y, r.x, r.y, jj);
+                        if (window) { pos = pos0; mq_wide_to(wide0, C, CT, B); }
                         four(std::false_type(), e, g);
-                        wide = mq_wide_from(C, CT, B);
+                        if (window) wide = mq_wide_from(C, CT, B);
                     }
-                } else four(std::false_type(), e, g);
+                }
             }
             // Codeword bytes leave the stage in 16-byte units, every lane's at once: when some lane has 64 waiting, all lanes send
             // the whole units they have.  (Each lane on its own -- 64 bytes whenever it had them -- ran this code in five chunks
@@ -1223,8 +1289,9 @@ __global__ __launch_bounds__(128) void t1_mq2_kernel(T1Args a)
             // A chunk adds fewer than 48 bytes to a lane, so fewer than 64 + 48 = 112 ever wait: the candidate's slot is at most
             // data byte 111 of the lane's kRing = 128, and the move reads no further than byte 6 * 16 + 15.
             // (Per decision: a shift of at most 15 and 7 or 8 shifts to a byte, three BYTEOUTs -- 12 a group.  On the wide
-            // register a group peels at most five -- it starts below 35 bits, is peeled only if it stayed within 63, and a round
-            // takes 7 or 8 off -- and a group that is sent back starts again at the `pos` it began with: 12 bounds both, 48 a chunk.)
+            // register a group peels at most three -- it starts below 35 bits, is peeled only if its shifts sum to 15 at most, and
+            // a round takes 7 or 8 off -- and a group that is sent back starts again at the `pos` it began with: 12 bounds both,
+            // 48 a chunk.)
             const int waiting = (int)(pos - dbase); // (nothing yet: -1)
             if (__any(waiting >= 64)) {
                 const int units = waiting >> 4; // (-1 -> -1)

@@ -120,8 +120,8 @@ def live():
     p = params()
     planes = api.planes_from_layout(d, lay, 3)
     ref = None
-    # (t1_sparse: the modeller's two ways of writing a pass half; mq_window: the plain coder's consumer per decision / every group sent back)
-    variants = [dict(), dict(mq_yield=0), dict(), dict(t1_sparse=-1), dict(t1_sparse=1), dict(mq_window=-1), dict(mq_window=2)]
+    # (t1_sparse: the modeller's two ways of writing a pass half; mq_window: the plain coder's consumer per decision / every group sent back / every group long)
+    variants = [dict(), dict(mq_yield=0), dict(), dict(t1_sparse=-1), dict(t1_sparse=1), dict(mq_window=-1), dict(mq_window=2), dict(mq_window=3)]
     if os.environ.get("SWEEP_LIVE"):  # an explicit list of knob settings (JSON), e.g. '[{}, {"mq_yield": 0}]'
         import json
         variants = json.loads(os.environ["SWEEP_LIVE"])
