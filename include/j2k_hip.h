@@ -229,6 +229,23 @@ typedef struct j2k_hip_params {
      * sizeof(j2k_hip_params) of this header, or the size the struct had before the field (it ended behind rgb_to_xyz), which
      * reads as guard_bits 0. */
     uint32_t guard_bits;
+    /* ---- quality layers at given rate-distortion slopes (excludes layer_rates, layer_psnr, dci_profile and cblk_style:
+     * J2K_HIP_ERR_PARAM, the text naming layer_slopes).  `layers` thresholds, one per quality layer: layer l of every tile is
+     * opj_tcd_makelayer(l, layer_slopes[l], final) over the tile's code-blocks -- a block gives the layer the passes whose
+     * weighted distortion decrease per byte reaches the threshold (OpenJPEG's units and arithmetic, IEEE doubles).  A negative
+     * entry takes everything that is left; entries need not be ordered.  A NaN or an infinite entry is J2K_HIP_ERR_PARAM.
+     * There is no search and no byte budget: blocks are cut independently, in one launch on the device behind the coder for
+     * all tiles (and all frames of j2k_hip_encode_sequence_device), and the per-pass tables are not copied to the host.  One
+     * threshold for every frame of a sequence gives constant quality: the bytes follow the content.
+     * j2k_hip_encode_get_layer_slopes reports the thresholds a layer_rates / layer_psnr search ended at; a file written with
+     * them is that search's file, byte for byte.  Combines with what layer_rates combines with (tiles, precincts, every
+     * progression, comp_sub_* / rgb_to_sycc, rgb_to_xyz, guard_bits) on every entry point that writes a file, the tile-sharded
+     * ones included; the band-pipelined host call stays off as under every rate control.  NULL: every byte, launch, copy and
+     * statistic is what it was without the field.
+     * J2K_HIP_ABI_VERSION is still 9: the field was appended and functions were added, none changed.  struct_size is the guard:
+     * sizeof(j2k_hip_params) of this header, the size before this field (offsetof layer_slopes: guard_bits and the padding
+     * behind it) or the size before guard_bits; the two older sizes read as layer_slopes NULL. */
+    const double *layer_slopes;
 } j2k_hip_params;
 
 #define J2K_HIP_GUARD_AUTO 0x100u /* OR-ed with the floor, 0 .. 7 (0 = 2) */
@@ -373,6 +390,15 @@ int j2k_hip_encode_sequence_device(j2k_hip_encoder *enc, const j2k_hip_params *p
  * takes; J2K_HIP_ERR_PARAM where nblocks is not the frame's number of code-blocks. */
 int j2k_hip_encode_get_guard_bits(const j2k_hip_encoder *enc, uint32_t *g);
 int j2k_hip_guard_bits_needed(const j2k_hip_params *params, const uint32_t *numbps, size_t nblocks, uint32_t *g);
+
+/* The rate-distortion slope thresholds the layers of tile `tile` (raster index, Isot) of the handle's last file were laid out
+ * at (j2k_hip_params.layer_slopes): after a layer_rates, layer_psnr or dci_profile file the thresholds its search ended at,
+ * -1 where a layer took everything that was left; after a layer_slopes file the thresholds it was given.  Of a sequence call:
+ * its last frame's; of a tile-range call: the tiles of the range.  *n (optional) = the number of layers; out (optional)
+ * receives min(cap, layers) entries.  Feeding them back as layer_slopes, tile by tile, writes the same tile bytes; a
+ * single-tile file is reproduced byte for byte.  J2K_HIP_ERR_PARAM before any such file (a file without rate control has no
+ * thresholds) or for a tile the last file does not have; a failed call leaves the record alone. */
+int j2k_hip_encode_get_layer_slopes(const j2k_hip_encoder *enc, uint32_t tile, double *out, uint32_t cap, uint32_t *n);
 
 /* --- tile-sharded encode (multi-GPU) -----------------------------------------------
  * Encode only tiles [tile_first, tile_first+tile_count) of the image (raster tile index, Isot).
@@ -881,6 +907,23 @@ int j2k_hip_stage_rate(j2k_hip_encoder *enc, uint32_t nblocks, const double *wei
                        double *disto, float *reach, double *bounds, uint32_t first, uint32_t count, const uint8_t *done,
                        const double *ahead, uint32_t K, uint64_t *body, const j2k_hip_rate_scan *scans, uint32_t nscans,
                        j2k_hip_rate_taken *taken, uint32_t *bytes, uint64_t *sums);
+
+/* rate_layers_kernel alone (j2k_hip_params.layer_slopes): ONE launch over Tier-1 tables the caller supplies, as an encode
+ * queues it behind the coder.  In: the per-block arrays and rows of j2k_hip_stage_rate (all host memory; weight is looked up
+ * at i % nweights, as the frames of a sequence share one frame's weights: 1 <= nweights <= nblocks), and slopes[layers],
+ * 1 <= layers <= 100, finite.  Out, per block i and layer l at [i * layers + l]: passes[] = the block's passes in layers 0..l
+ * (opj_tcd_makelayer at slopes[l] on top of the layers before), bytes[] = pass_rate[i][passes - 1], 0 without passes.
+ * Both out arrays have (nblocks + J2K_HIP_RATE_LAYERS_SPARE) * layers entries: the device arrays are filled with 0xA5 first and
+ * come back whole, so the spare entries show what the launch's idle lanes wrote (nothing).  rate_back / dist_back (optional,
+ * nblocks rows of J2K_HIP_MAX_PASSES) receive the pass tables as they lie on the device after the launch: the kernel writes
+ * neither, so a row's entries at and beyond npasses come back as the caller filled them.
+ * Refused with J2K_HIP_ERR_PARAM: what j2k_hip_stage_rate refuses of the tables, layers out of range, a slope that is not
+ * finite, an encode pending on the handle.  The handle's cached geometry is dropped. */
+#define J2K_HIP_RATE_LAYERS_SPARE 64
+int j2k_hip_stage_rate_layers(j2k_hip_encoder *enc, uint32_t nblocks, const double *weight, uint32_t nweights,
+                              const uint32_t *numbps, const uint32_t *npasses, const uint32_t *pass_rate,
+                              const int32_t *pass_dist, const double *slopes, uint32_t layers, uint8_t *passes,
+                              uint32_t *bytes, uint32_t *rate_back, int32_t *dist_back);
 
 /* The codestream assembly alone: ONE launch of gather_kernel over three lists of pieces, its arguments filled as an encode
  * and a decode fill them.  dst (host, dst_bytes) goes up as it is, receives the pieces and comes back; `src` (host) is the

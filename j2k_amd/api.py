@@ -43,7 +43,8 @@ class Params(C.Structure):
                 ("dci_profile", C.c_uint32), ("max_cs_size", C.c_uint32), ("max_comp_size", C.c_uint32),
                 ("cblk_style", C.c_uint32),
                 ("comp_sub_x", C.c_uint32 * 4), ("comp_sub_y", C.c_uint32 * 4), ("rgb_to_sycc", C.c_uint32),
-                ("rgb_to_xyz", C.c_uint32), ("guard_bits", C.c_uint32)]
+                ("rgb_to_xyz", C.c_uint32), ("guard_bits", C.c_uint32),
+                ("layer_slopes", C.POINTER(C.c_double))]
 
 
 GUARD_AUTO = 0x100  # J2K_HIP_GUARD_AUTO: OR-ed with a floor of 0..7 (0 = 2)
@@ -107,7 +108,8 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_get_stats", "j2k_hip_get_dwt_level_ms", "j2k_hip_malloc", "j2k_hip_free",
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink",
            "j2k_hip_debug_cblk_capacities", "j2k_hip_debug_blocks", "j2k_hip_debug_tier2",
-           "j2k_hip_encode_get_guard_bits", "j2k_hip_guard_bits_needed", "j2k_hip_debug_tier2_guard", "j2k_hip_debug_tier2_plan"]
+           "j2k_hip_encode_get_guard_bits", "j2k_hip_guard_bits_needed", "j2k_hip_debug_tier2_guard", "j2k_hip_debug_tier2_plan",
+           "j2k_hip_encode_get_layer_slopes", "j2k_hip_stage_rate_layers"]
 
 class Tier2Plan(C.Structure):
     """include/j2k_hip.h: j2k_hip_tier2_plan."""
@@ -315,6 +317,9 @@ def load_library():
     if hasattr(L, "j2k_hip_debug_tier2_plan"):
         L.j2k_hip_debug_tier2_plan.argtypes = [C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(Tier2Plan)]
+    if hasattr(L, "j2k_hip_encode_get_layer_slopes"):
+        L.j2k_hip_encode_get_layer_slopes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.j2k_hip_stage_rate_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32] + [C.c_void_p] * 4
     _lib = L
     return L
 
@@ -400,13 +405,14 @@ def make_params(width, height, channels, depth, reversible=True, ycc=False, laye
                 num_resolutions=6, cblk=(64, 64), promote=False, comment="", jp2=False, color_space=0,
                 alpha_channel=-1, alpha_premultiplied=False, icc=None, rates=None, psnr=None, progression=0,
                 pixel_aspect=None, dpi=0.0, precincts=None, dci_profile=0, max_cs_size=0, max_comp_size=0, cblk_style=0,
-                sub=None, rgb_to_sycc=False, rgb_to_xyz=0, guard_bits=0):
+                sub=None, rgb_to_sycc=False, rgb_to_xyz=0, guard_bits=0, slopes=None):
     """comment: None -> library default COM, "" -> no COM segment.  jp2/color_space/alpha_channel/icc describe
     the JP2 file wrapper (color_space in OPJ_COLOR_SPACE numbering: 1 sRGB, 2 grey, 3 sYCC).
     sub = [(dx, dy), ...]: the sub-sampling factors of the components (SIZ XRsiz / YRsiz), one pair per channel; rgb_to_sycc:
     the planes are R, G, B[, A] of the full image and the library makes Y, Cb, Cr[, A] at those factors.  rgb_to_xyz: channels
     0..2 are R'G'B' (1 sRGB, 2 Rec.709 under a 2.4 power, 3 linear Rec.709) and the library makes cinema X'Y'Z' codes of them.
-    guard_bits: 0 = two, strictly; 1..7 = that many, strictly; GUARD_AUTO | floor = as many as the frame needs, the floor at least."""
+    guard_bits: 0 = two, strictly; 1..7 = that many, strictly; GUARD_AUTO | floor = as many as the frame needs, the floor at least.
+    slopes: one rate-distortion slope threshold per layer (layer_slopes; negative = everything that is left); sets the layer count."""
     p = Params()
     p.struct_size = C.sizeof(Params)
     p.width, p.height, p.channels, p.depth = width, height, channels, depth
@@ -439,6 +445,10 @@ def make_params(width, height, channels, depth, reversible=True, ycc=False, laye
         p.layers = len(psnr)
         p._psnr_keepalive = (C.c_float * len(psnr))(*psnr)
         p.layer_psnr = C.cast(p._psnr_keepalive, C.POINTER(C.c_float))
+    if slopes is not None:  # one slope threshold per layer, exact doubles (what Encoder.layer_slopes reports of a search)
+        p.layers = len(slopes)
+        p._slopes_keepalive = (C.c_double * len(slopes))(*slopes)
+        p.layer_slopes = C.cast(p._slopes_keepalive, C.POINTER(C.c_double))
     if icc:
         p._icc_keepalive = C.create_string_buffer(bytes(icc), len(icc))  # borrowed by the C side for each call
         p.icc_profile, p.icc_profile_len = C.cast(p._icc_keepalive, C.c_void_p), len(icc)
@@ -1164,6 +1174,15 @@ class Encoder:
         self._check(self.L.j2k_hip_encode_get_guard_bits(self.h, C.byref(g)))
         return g.value
 
+    def layer_slopes(self, tile: int = 0) -> list:
+        """The slope thresholds the layers of tile `tile` of the last file this handle wrote were laid out at
+        (j2k_hip_encode_get_layer_slopes): what a rates / psnr search ended at (-1: everything left), or the slopes given."""
+        n = C.c_uint32()
+        self._check(self.L.j2k_hip_encode_get_layer_slopes(self.h, tile, None, 0, C.byref(n)))
+        out = (C.c_double * max(n.value, 1))()
+        self._check(self.L.j2k_hip_encode_get_layer_slopes(self.h, tile, out, n.value, C.byref(n)))
+        return [out[i] for i in range(n.value)]
+
     def dwt_time(self, first: int, count: int, repeat: int = 20) -> float:
         """Mean device time (ms) of the DWT launches of levels [first, first+count) of the last encode, replayed back to back."""
         ms = C.c_double()
@@ -1424,6 +1443,27 @@ class Encoder:
         if ns:
             out.update(taken=taken[:ns, :count], bytes=nbytes[:ns, :count], sums=sums)
         return out
+
+    def stage_rate_layers(self, weight, numbps, npasses, pass_rate, pass_dist, slopes):
+        """j2k_hip_stage_rate_layers: rate_layers_kernel on tables per block (pass_rate / pass_dist: (n, 96); weight: one per
+        block, or fewer -- block i takes weight[i % len(weight)]).  Returns a dict: passes (n, L) uint8 and bytes (n, L) uint32,
+        cumulative over the layers; spare_passes / spare_bytes: the entries behind the last block's as they came back (the
+        device arrays were filled with 0xA5); rate_back / dist_back: the pass tables as they lie on the device afterwards."""
+        MP, SPARE = 96, 64
+        n, nl = len(npasses), len(slopes)
+        weight = np.ascontiguousarray(weight, dtype=np.float64)
+        numbps = np.ascontiguousarray(numbps, dtype=np.uint32)
+        npasses = np.ascontiguousarray(npasses, dtype=np.uint32)
+        pass_rate = np.ascontiguousarray(pass_rate, dtype=np.uint32).reshape(n, MP)
+        pass_dist = np.ascontiguousarray(pass_dist, dtype=np.int32).reshape(n, MP)
+        sl = np.ascontiguousarray(slopes, dtype=np.float64)
+        assert numbps.size == n
+        passes, nbytes = np.zeros((n + SPARE, max(nl, 1)), np.uint8), np.zeros((n + SPARE, max(nl, 1)), np.uint32)
+        rate_back, dist_back = np.zeros((n, MP), np.uint32), np.zeros((n, MP), np.int32)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self._check(self.L.j2k_hip_stage_rate_layers(self.h, n, ptr(weight), weight.size, ptr(numbps), ptr(npasses), ptr(pass_rate), ptr(pass_dist),
+                                                     ptr(sl), nl, ptr(passes), ptr(nbytes), ptr(rate_back), ptr(dist_back)))
+        return dict(passes=passes[:n], bytes=nbytes[:n], spare_passes=passes[n:], spare_bytes=nbytes[n:], rate_back=rate_back, dist_back=dist_back)
 
     def stage_gather(self, src, dst, blocks=(), headers=(), segments=(), blob=None) -> np.ndarray:
         """j2k_hip_stage_gather: src / dst (/ blob, default: src) uint8 arrays, the piece lists [(dst, src, len)].  Returns

@@ -36,12 +36,19 @@ struct GuardExcess : Error {
 
 // struct_size of j2k_hip_params before guard_bits was appended: such a caller passes guard_bits 0
 constexpr size_t kParamsSizeBeforeGuardBits = offsetof(j2k_hip_params, guard_bits);
-inline bool params_size_ok(const j2k_hip_params *p) { return p->struct_size == sizeof(j2k_hip_params) || p->struct_size == kParamsSizeBeforeGuardBits; }
+// ... and before layer_slopes was: guard_bits and the padding behind it (the struct is pointer-aligned), layer_slopes NULL
+constexpr size_t kParamsSizeBeforeLayerSlopes = offsetof(j2k_hip_params, layer_slopes);
+inline bool params_size_ok(const j2k_hip_params *p)
+{
+    return p->struct_size == sizeof(j2k_hip_params) || p->struct_size == kParamsSizeBeforeLayerSlopes || p->struct_size == kParamsSizeBeforeGuardBits;
+}
+inline bool params_has_guard_bits(const j2k_hip_params *p) { return p->struct_size >= kParamsSizeBeforeLayerSlopes; }
+inline const double *params_layer_slopes(const j2k_hip_params *p) { return p->struct_size == sizeof(j2k_hip_params) ? p->layer_slopes : nullptr; }
 // the caller's struct widened to this library's layout (what lies beyond its struct_size is not read)
 inline j2k_hip_params widened(const j2k_hip_params *p)
 {
     j2k_hip_params q = {};
-    std::memcpy(&q, p, p->struct_size == kParamsSizeBeforeGuardBits ? kParamsSizeBeforeGuardBits : sizeof q);
+    std::memcpy(&q, p, p->struct_size); // (one of the three sizes params_size_ok takes)
     q.struct_size = sizeof q;
     return q;
 }
@@ -88,8 +95,10 @@ struct Coding {
     bool has_comment = false;
     std::vector<float> rates;      // rate control: one compression ratio per layer (empty = no target)
     std::vector<float> psnr;       // fixed quality: one PSNR target (dB) per layer (empty = none); excludes rates
+    std::vector<double> slopes;    // given slope thresholds: one per layer (empty = none; negative: everything left); excludes both
     bool rate_control() const
     {
+        if (!slopes.empty()) return true;
         for (float r : rates) if (r > 1.0f) return true;
         for (float q : psnr) if (q > 0.0f) return true;
         return false;

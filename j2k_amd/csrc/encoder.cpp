@@ -788,15 +788,40 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
         T1Args tf = ta;
         tf.first = 0; tf.nblks = (int)nb;
         launch_t1_rate_fixup(tf, s);
-        e->h_passes.ensure(tt.h_passes_bytes());
+        if (cod.slopes.empty() || tn.rate_dev < 0) e->h_passes.ensure(tt.h_passes_bytes()); // (given slopes on the device: the tables do not come down)
         // The allocation's per-block work right here, behind the coder (rate.hip): distortions, slope ranges, bounds.  Byte
         // budgets only (fixed quality sums distortions in OpenJPEG's block order on the host), one frame per call.
         const int dev_min = tn.rate_dev == 0 ? 8192 : tn.rate_dev;
         // (the cinema profiles' caps per component keep the bound walk and the summed candidates out: twice the device rounds, each
         //  behind whatever else is on the chip -- with other frames in flight their allocation is the faster one on the host's threads)
-        pd.rc_device = dev_min > 0 && cod.psnr.empty() && F == 1 && nb >= (size_t)dev_min && (!cod.max_comp_size || dev.inflight.load() <= 1);
+        pd.rc_device = dev_min > 0 && cod.slopes.empty() && cod.psnr.empty() && F == 1 && nb >= (size_t)dev_min && (!cod.max_comp_size || dev.inflight.load() <= 1);
         pd.rc_tables_pending = false;
-        if (!(pd.rc_device && tn.overlap))
+        // Layers at given slopes: nothing to search, so the whole allocation is one launch here, over the blocks of every tile and
+        // frame of the call, and what comes down is a pass count and a byte count per block and layer -- the pass tables stay
+        // where they are.  At every size; rate_dev = -1 leaves the same walk to the host, over the tables.
+        pd.rc_layers = !cod.slopes.empty() && tn.rate_dev >= 0;
+        if (pd.rc_layers) {
+            const size_t nl = nb * cod.layers, counts = round_up(nl, 256);
+            e->rc_weight.ensure(nb1 * sizeof(double) + nb1);
+            e->rc_layers.ensure(counts + nl * sizeof(uint32_t));
+            e->h_rc_layers.ensure(std::max(counts + nl * sizeof(uint32_t), nb1 * sizeof(double) + nb1));
+            if (!e->rc_weight_valid) { // once per geometry, in the layout the bisection's kernels take them in (rate_device.h)
+                const std::vector<double> w = rate_block_weights(g);
+                std::memcpy(e->h_rc_layers.p, w.data(), nb1 * sizeof(double));
+                unsigned char *hc = e->h_rc_layers.as<unsigned char>() + nb1 * sizeof(double);
+                for (size_t i = 0; i < nb1; ++i) hc[i] = (unsigned char)std::min<uint32_t>(g.cblks[i].comp, 3u);
+                HIP_CHECK(hipMemcpyAsync(e->rc_weight.p, e->h_rc_layers.p, nb1 * sizeof(double) + nb1, hipMemcpyHostToDevice, s));
+                e->rc_weight_valid = true;
+            }
+            RateLayersArgs la = {};
+            la.nblks = (unsigned)nb; la.layers = cod.layers; la.nweights = (unsigned)nb1;
+            la.weight = e->rc_weight.as<double>();
+            la.numbps = tt.numbps(meta); la.npasses = tt.npasses(meta);
+            la.pass_nmsedec = reinterpret_cast<const int *>(tt.pass_nmsedec(e->passes.as<uint32_t>())); la.pass_rate = tt.pass_rate(e->passes.as<uint32_t>());
+            la.passes = e->rc_layers.as<unsigned char>(); la.bytes = reinterpret_cast<unsigned *>(e->rc_layers.as<unsigned char>() + counts);
+            launch_rate_layers(la, cod.slopes.data(), s);
+            HIP_CHECK(hipMemcpyAsync(e->h_rc_layers.p, e->rc_layers.p, counts + nl * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        } else if (!(pd.rc_device && tn.overlap))
             HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_nmsedec, tt.h_passes_bytes(), hipMemcpyDeviceToHost, s));
         if (pd.rc_device) {
             const RateArgs ra = rate_args(e, tt);
@@ -889,6 +914,7 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
     size_t plan_total = 0, cs_total = 0;
     const size_t nbd = rate_control ? 0 : nb1; // per-block destinations or per-layer pieces
     uint32_t guard = cod.guard; // of the frame planned last
+    std::vector<double> last_slopes; // ... and its layers' thresholds (rate control)
     {
         Range r("j2k_hip tier2 host");
         for (size_t f = 0; f < F; ++f) {
@@ -899,9 +925,14 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
                 for (size_t i = 0; i < nb1; ++i) res[i].rates = e->h_passes.as<uint32_t>() + tt.row(b0 + i);
             // the frame's plan under the guard bits of `gg`: the layer allocation (its header bits hold the zero-bit-plane
             // counts), then the codestream
+            std::vector<double> frame_slopes; // the thresholds the frame's layers were laid out at, per tile
             auto plan_frame = [&](const Geometry &gg) -> Tier2Plan {
                 LayerAlloc alloc;
-                if (rate_control) {
+                if (pd.rc_layers) { // given slopes, cut on the device: the counts of this frame's blocks (they do not depend on the guard bits)
+                    const size_t nl = nb * cod.layers;
+                    const uint8_t *hl = e->h_rc_layers.as<uint8_t>();
+                    alloc = layers_from_counts(gg, hl + b0 * cod.layers, reinterpret_cast<const uint32_t *>(hl + round_up(nl, 256)) + b0 * cod.layers, cod.slopes.data());
+                } else if (rate_control) {
                     const uint32_t *hp = e->h_passes.as<uint32_t>(); // [nmsedec | rate]
                     const uint32_t *h_rate = tt.h_rate(hp) + tt.row(b0), *h_nmsedec = hp + tt.row(b0);
 #ifdef J2K_ALLOC_DUMP
@@ -926,12 +957,16 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
                         }
                     }
 #endif
+                    if (!cod.slopes.empty()) alloc = allocate_layers_slopes(gg, res, h_rate, reinterpret_cast<const int32_t *>(h_nmsedec), cod.slopes.data());
+                    else {
                     std::unique_ptr<HipRateDevice> rdev;
                     if (pd.rc_device) rdev.reset(new HipRateDevice(e, tt));
                     const unsigned at = std::max(1u, std::min((unsigned)std::max(1, tuning().alloc_threads), std::thread::hardware_concurrency()));
                     if (nb1 >= 4096 && !(e->alloc_workers && e->alloc_workers->size() == at)) e->alloc_workers.reset(new Workers(at));
                     alloc = allocate_layers(gg, res, h_rate, reinterpret_cast<const int32_t *>(h_nmsedec), lead, at, rdev.get(), e->alloc_workers.get());
+                    }
                 }
+                if (rate_control) frame_slopes = alloc.slopes;
                 if (pd.rc_tables_pending) { HIP_CHECK(hipEventSynchronize(e->rc_tables)); pd.rc_tables_pending = false; } // (never read: still ours to wait for)
                 // big frames: a few host threads write the packet headers of the (resolution, component) pairs side by side
                 if (nb1 >= 4096 && !e->t2_workers) e->t2_workers.reset(new Workers(plan_threads()));
@@ -946,6 +981,7 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
                 guard = guard_bits_needed(g, res);
                 plans[f] = plan_frame(with_guard_bits(g, guard));
             }
+            if (f == F - 1) last_slopes.swap(frame_slopes);
             lays[f] = GatherPlan(plans[f].blob.size(), plans[f].hdr_segs.size(), nbd, plans[f].body_segs.size());
             plan_off[f] = plan_total;
             plan_total += lays[f].total;
@@ -1017,6 +1053,7 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
     std::vector<EncodeOut> outs(F);
     for (size_t f = 0; f < F; ++f) { outs[f].d_cs = e->cs.as<uint8_t>() + cs_off[f]; outs[f].len = (size_t)plans[f].total_len; }
     if (framed) e->last_guard = guard;
+    e->last_slopes.swap(last_slopes); e->last_slopes_first = e->geo_first; e->last_slopes_layers = cod.layers;
     return outs;
 }
 
@@ -1455,6 +1492,7 @@ void encode_end_banded(j2k_hip_encoder *e, j2k_hip_write_fn write, void *user)
     st.ms_after_upload = t_end - pd.t_uploaded;
     st.ms_total = t_end - pd.t_begin;
     e->last_guard = guard;
+    e->last_slopes.clear(); // (no rate control on this path: the file has no thresholds)
 }
 
 std::vector<EncodeOut> encode_impl(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes,
@@ -1937,6 +1975,16 @@ int j2k_hip_encode_get_guard_bits(const j2k_hip_encoder *e, uint32_t *g)
 {
     if (!e || !g) return J2K_HIP_ERR_PARAM;
     *g = e->last_guard;
+    return J2K_HIP_OK;
+}
+
+int j2k_hip_encode_get_layer_slopes(const j2k_hip_encoder *e, uint32_t tile, double *out, uint32_t cap, uint32_t *n)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    const uint32_t L = e->last_slopes_layers;
+    if (e->last_slopes.empty() || !L || tile < e->last_slopes_first || (size_t)(tile - e->last_slopes_first) >= e->last_slopes.size() / L) return J2K_HIP_ERR_PARAM;
+    if (n) *n = L;
+    for (uint32_t l = 0; out && l < L && l < cap; ++l) out[l] = e->last_slopes[(size_t)(tile - e->last_slopes_first) * L + l];
     return J2K_HIP_OK;
 }
 

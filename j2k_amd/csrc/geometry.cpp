@@ -109,6 +109,17 @@ Coding normalise(const j2k_hip_params *p)
         for (float q : c.psnr)
             if (!(q >= 0.0f) || q > 1000.0f) throw Error(J2K_HIP_ERR_PARAM, "layer_psnr must be finite and >= 0");
     }
+    // layers at given slope thresholds: no search, so nothing to accept but the numbers themselves
+    if (const double *sl = params_layer_slopes(p)) {
+        if (p->dci_profile) throw Error(J2K_HIP_ERR_PARAM, "layer_slopes cannot be combined with dci_profile: a digital cinema profile sets its own rate (max_cs_size, max_comp_size)");
+        if (p->layer_rates) throw Error(J2K_HIP_ERR_PARAM, "layer_rates and layer_slopes exclude each other");
+        if (p->layer_psnr) throw Error(J2K_HIP_ERR_PARAM, "layer_psnr and layer_slopes exclude each other");
+        if (p->cblk_style) throw Error(J2K_HIP_ERR_PARAM, "cblk_style cannot be combined with layer_slopes: rate control does not price codeword segments");
+        if (c.layers > 100) throw Error(J2K_HIP_ERR_PARAM, "layer_slopes: rate control supports at most 100 layers");
+        c.slopes.assign(sl, sl + c.layers);
+        for (double v : c.slopes)
+            if (!std::isfinite(v)) throw Error(J2K_HIP_ERR_PARAM, "layer_slopes must be finite (a negative threshold takes everything that is left)");
+    }
     // code-block style: everything but vertically causal contexts, and not under a layer allocation
     if (p->cblk_style) {
         if (p->cblk_style & kStyleVcausal)
@@ -175,7 +186,7 @@ Coding normalise(const j2k_hip_params *p)
     if (!(p->dpi >= 0.0f) || p->dpi > 1e6f) throw Error(J2K_HIP_ERR_PARAM, "dpi must be finite and >= 0");
     c.dpi = p->dpi;
     // guard bits: a fixed count, or a floor under J2K_HIP_GUARD_AUTO (a caller of the layout before the field: 0)
-    if (const uint32_t gb = p->struct_size == sizeof(j2k_hip_params) ? p->guard_bits : 0u) {
+    if (const uint32_t gb = params_has_guard_bits(p) ? p->guard_bits : 0u) {
         if ((gb & ~(uint32_t)J2K_HIP_GUARD_AUTO) > (uint32_t)kMaxGuardBits)
             throw Error(J2K_HIP_ERR_PARAM, "guard_bits must be 0, 1..7 or J2K_HIP_GUARD_AUTO | a floor of 0..7");
         if (p->dci_profile) throw Error(J2K_HIP_ERR_PARAM, "guard_bits cannot be combined with dci_profile: a digital cinema profile writes two guard bits");

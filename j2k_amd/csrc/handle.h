@@ -110,6 +110,7 @@ struct Pending {
     size_t F = 1, nb1 = 0;
     bool framed = true, rate_control = false;
     bool rc_device = false;   // rate control: the per-block work was queued on the device behind the coder (rate.hip)
+    bool rc_layers = false;   // layers at given slopes: rate_layers_kernel was queued behind the coder, its counts are on their way to h_rc_layers
     bool rc_tables_pending = false; // ... and the pass tables are coming down on a side stream: wait for rc_tables before reading h_passes
     double dwt_bytes = 0;
     uint32_t *meta = nullptr;
@@ -157,6 +158,13 @@ struct j2k_hip_encoder {
     j2k_hip::DevBuf rc_weight, rc_disto, rc_reach, rc_bounds, rc_small;
     j2k_hip::PinnedBuf h_rc_bounds, h_rc_small;
     bool rc_weight_valid = false;
+    // layers at given slopes (rate_layers_kernel): per block and layer a pass count and a byte count, [nb * L] bytes then [nb * L] words
+    j2k_hip::DevBuf rc_layers;
+    j2k_hip::PinnedBuf h_rc_layers;
+    // the thresholds the layers of the last file's tiles were laid out at (j2k_hip_encode_get_layer_slopes): [tile][layer] of
+    // tiles [last_slopes_first, ..); empty before any file under rate control
+    std::vector<double> last_slopes;
+    uint32_t last_slopes_first = 0, last_slopes_layers = 0;
 
     // cached geometry (host + device images)
     bool geo_valid = false;

@@ -271,6 +271,19 @@ struct RateArgs {
 void launch_rate_prepare(const RateArgs &a, hipStream_t s);
 void launch_rate_ahead(const RateArgs &a, unsigned first, unsigned count, unsigned K, hipStream_t s);
 void launch_rate_scan(const RateArgs &a, unsigned first, unsigned count, double thresh, hipStream_t s);
+// Layers at given slope thresholds (rate_layers_kernel): one launch over every block of the call, all tiles and frames.
+constexpr unsigned kRateMaxLayers = 100;
+struct RateSlopes { double v[kRateMaxLayers]; }; // the thresholds, as kernel arguments
+struct RateLayersArgs {
+    unsigned nblks, layers, nweights;   // weight is read at id % nweights: the frames of a sequence share one frame's weights
+    const double *weight;               // per block of a frame (rate_block_weights)
+    const unsigned *numbps, *npasses;   // Tier-1 results
+    const int *pass_nmsedec;            // [nblks][kDevMaxPasses]
+    const unsigned *pass_rate;          // [nblks][kDevMaxPasses], after the fix-ups
+    unsigned char *passes;              // [nblks][layers] out: passes in layers 0..l
+    unsigned *bytes;                    // [nblks][layers] out: pass_rate[passes - 1], 0 without passes
+};
+void launch_rate_layers(const RateLayersArgs &a, const double *slopes, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Decode path.  Tier-1 decoding: one wavefront per code-block runs the MQ decoder and the bit

@@ -12,6 +12,7 @@
 //   rate_scan_kernel     opj_tcd_makelayer's scan of every block at one threshold: pass counts and decisions
 // The host (rate_control.cpp) keeps the bisection's control flow and the exact pricing of candidates.
 // All three are bound by latency of strided reads of 50 000 short rows; together they take tens of microseconds.
+//   rate_layers_kernel   no search at all: every layer of every block at thresholds the caller gives (layer_slopes)
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -84,6 +85,35 @@ __global__ void __launch_bounds__(64) rate_scan_kernel(RateArgs a, unsigned firs
     }
     __syncthreads();
     if (threadIdx.x < kRateSums && part[threadIdx.x]) atomicAdd(a.scan_sums + threadIdx.x, part[threadIdx.x]);
+}
+
+// Layers at given slope thresholds (j2k_hip_params.layer_slopes): per block the whole of opj_tcd_makelayer for layers 0..L-1,
+// `done` carried from layer to layer in a register.  A thread per block as above; the block's distortions live in the thread's
+// private memory (the lanes' rows interleave there, so the L walks over them are coalesced) and are never written out.  No
+// `steepest` shortcut: it never changes a pass count (rate_block_choose), and without it nothing of rate_prepare_kernel is needed.
+// The thresholds are kernel arguments (uniform reads).  Out, [id * L + l]: passes in layers 0..l, and the bytes up to the last of them.
+__global__ void __launch_bounds__(64) rate_layers_kernel(RateLayersArgs a, RateSlopes sl)
+{
+    const unsigned id = blockIdx.x * 64u + threadIdx.x;
+    if (id >= a.nblks) return;
+    const unsigned np = min(a.npasses[id], (unsigned)kDevMaxPasses);
+    const unsigned *rate = a.pass_rate + (size_t)id * kDevMaxPasses;
+    double disto[kDevMaxPasses];
+    rate_block_disto(a.weight[id % a.nweights], a.numbps[id], np, a.pass_nmsedec + (size_t)id * kDevMaxPasses, disto, nullptr);
+    unsigned done = 0;
+    for (unsigned l = 0; l < a.layers; ++l) {
+        done = rate_block_choose(rate, disto, np, done, 0.0, false, sl.v[l], nullptr);
+        a.passes[(size_t)id * a.layers + l] = (unsigned char)done;
+        a.bytes[(size_t)id * a.layers + l] = done ? rate[done - 1] : 0u;
+    }
+}
+
+void launch_rate_layers(const RateLayersArgs &a, const double *slopes, hipStream_t s)
+{
+    if (!a.nblks || !a.layers || a.layers > kRateMaxLayers) return;
+    RateSlopes sl = {};
+    for (unsigned l = 0; l < a.layers; ++l) sl.v[l] = slopes[l];
+    hipLaunchKernelGGL(rate_layers_kernel, dim3((a.nblks + 63) / 64), dim3(64), 0, s, a, sl);
 }
 
 void launch_rate_prepare(const RateArgs &a, hipStream_t s)

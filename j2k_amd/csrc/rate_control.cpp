@@ -108,6 +108,9 @@ LayerAlloc allocate(const Geometry &geo, const std::vector<CblkResult> &res, con
     LayerAlloc al;
     al.layers = L;
     al.np.assign(nb * L, 0); al.len.assign(nb * L, 0); al.off.assign(nb * L, 0);
+    al.slopes.assign(geo.tiles.size() * L, -1.0);
+    // the threshold a tile's layer is finally laid out at (tiles may run side by side: each writes its own entries)
+    auto note = [&](const Tile &T, uint32_t layno, double good) { al.slopes[(size_t)(&T - geo.tiles.data()) * L + layno] = good; };
 
     PHASE(whole, "whole call");
     // worker threads for large tiles (created once per call, not per loop)
@@ -466,6 +469,7 @@ LayerAlloc allocate(const Geometry &geo, const std::vector<CblkResult> &res, con
                     }
                     good = stable == 0 ? thresh : stable;
                 } else good = -1;
+                note(T, layno, good);
                 make_layer(T, layno, good, false);
                 const double dl = layer_disto(layno); // before `done` moves on
                 make_layer(T, layno, good, true);
@@ -672,6 +676,7 @@ LayerAlloc allocate(const Geometry &geo, const std::vector<CblkResult> &res, con
                     stable = thresh;
                 }
                 good = stable == 0 ? thresh : stable;
+                note(T, layno, good);
                 if (light) leave_light(); // (every candidate was decided by its sums: the ends are still on the device)
                 // The layer is the candidate laid out at `good`, and the bisection has usually been there: the last one that
                 // fitted (or, if none did, the last one of all).  Its pass counts are final as they stand -- the blocks that were
@@ -690,7 +695,7 @@ LayerAlloc allocate(const Geometry &geo, const std::vector<CblkResult> &res, con
                     if (layno + 1 < L) { PHASE(commit, "commit"); pricer.commit(al, layno); }
                     continue;
                 }
-            } else good = -1; // everything that is left
+            } else { good = -1; note(T, layno, good); } // everything that is left
             need_tables();
             { PHASE(final, "final layer"); make_layer(T, layno, good, true); }
             if (layno + 1 < L && !plain) { PHASE(commit, "commit"); pricer.commit(al, layno); }
@@ -804,6 +809,54 @@ LayerAlloc allocate_layers_plain(const Geometry &geo, const std::vector<CblkResu
                                  const int32_t *pass_nmsedec, size_t main_header_len)
 {
     return allocate(geo, res, pass_rate, pass_nmsedec, main_header_len, true, 1);
+}
+
+void rate_block_layers(double weight, uint32_t numbps, uint32_t np, const uint32_t *rate, const int32_t *nmsedec, const double *slopes, uint32_t L,
+                       uint8_t *passes, uint32_t *bytes)
+{
+    double disto[kRatePasses];
+    rate_block_disto(weight, numbps, np, nmsedec, disto, nullptr);
+    uint32_t done = 0;
+    for (uint32_t l = 0; l < L; ++l) {
+        done = rate_block_choose(rate, disto, np, done, 0.0, false, slopes[l], nullptr);
+        passes[l] = (uint8_t)done;
+        bytes[l] = done ? rate[done - 1] : 0u;
+    }
+}
+
+LayerAlloc layers_from_counts(const Geometry &geo, const uint8_t *passes, const uint32_t *bytes, const double *slopes)
+{
+    const uint32_t L = geo.cod.layers;
+    const size_t nb = geo.cblks.size();
+    LayerAlloc al;
+    al.layers = L;
+    al.np.assign(nb * L, 0); al.len.assign(nb * L, 0); al.off.assign(nb * L, 0);
+    for (size_t id = 0; id < nb; ++id) {
+        uint32_t done = 0, before = 0; // passes in the layers before, and the bytes up to the last of them
+        for (uint32_t l = 0; l < L; ++l) {
+            const size_t k = id * L + l;
+            const uint32_t n = passes[k];
+            al.np[k] = n - done;
+            if (n != done) { al.len[k] = bytes[k] - before; al.off[k] = before; before = bytes[k]; }
+            done = n;
+        }
+    }
+    al.slopes.resize(geo.tiles.size() * L);
+    for (size_t t = 0; t < geo.tiles.size(); ++t) std::copy(slopes, slopes + L, al.slopes.begin() + t * L);
+    return al;
+}
+
+LayerAlloc allocate_layers_slopes(const Geometry &geo, const std::vector<CblkResult> &res, const uint32_t *pass_rate,
+                                  const int32_t *pass_nmsedec, const double *slopes)
+{
+    const uint32_t L = geo.cod.layers;
+    const size_t nb = geo.cblks.size();
+    std::vector<uint8_t> passes(nb * L);
+    std::vector<uint32_t> bytes(nb * L);
+    for (size_t id = 0; id < nb; ++id)
+        rate_block_layers(block_weight(geo.cod, geo.cblks[id]), res[id].numbps, res[id].npasses, pass_rate + id * kMaxPasses, pass_nmsedec + id * kMaxPasses,
+                          slopes, L, passes.data() + id * L, bytes.data() + id * L);
+    return layers_from_counts(geo, passes.data(), bytes.data(), slopes);
 }
 
 } // namespace j2k_hip

@@ -74,4 +74,16 @@ std::unique_ptr<RateDevice> make_host_rate_device(const Geometry &geo, const std
 LayerAlloc allocate_layers_plain(const Geometry &geo, const std::vector<CblkResult> &res, const uint32_t *pass_rate,
                                  const int32_t *pass_nmsedec, size_t main_header_len);
 
+// Layers at given slope thresholds (j2k_hip_params.layer_slopes): layer l of every tile is opj_tcd_makelayer(l, slopes[l], final)
+// over its blocks.  No bisection, no budget, no pricing: blocks are independent.
+// rate_block_layers: one block -- passes[l] = its passes in layers 0..l, bytes[l] = rate[passes[l] - 1] (0 without passes); the
+// walk rate_layers_kernel (rate.hip) does per thread, through the same functions of rate_block.h.
+void rate_block_layers(double weight, uint32_t numbps, uint32_t np, const uint32_t *rate, const int32_t *nmsedec, const double *slopes, uint32_t L,
+                       uint8_t *passes, uint32_t *bytes);
+// the allocation those per-block counts stand for ([id * L + l], the frame's blocks), filled as the bisection's assign() fills it
+LayerAlloc layers_from_counts(const Geometry &geo, const uint8_t *passes, const uint32_t *bytes, const double *slopes);
+// the host path: rate_block_layers over downloaded pass tables, then layers_from_counts
+LayerAlloc allocate_layers_slopes(const Geometry &geo, const std::vector<CblkResult> &res, const uint32_t *pass_rate,
+                                  const int32_t *pass_nmsedec, const double *slopes);
+
 } // namespace j2k_hip

@@ -532,6 +532,62 @@ int j2k_hip_stage_rate(j2k_hip_encoder *e, uint32_t nblocks, const double *weigh
     });
 }
 
+// rate_layers_kernel alone, on tables the caller supplies: they go where T1Tables puts a frame's, the launch is the one
+// encode_begin queues behind the coder (launch_rate_layers over a RateLayersArgs), the counts come back as encode_end reads them.
+int j2k_hip_stage_rate_layers(j2k_hip_encoder *e, uint32_t nblocks, const double *weight, uint32_t nweights, const uint32_t *numbps,
+                              const uint32_t *npasses, const uint32_t *pass_rate, const int32_t *pass_dist, const double *slopes,
+                              uint32_t layers, uint8_t *passes, uint32_t *bytes, uint32_t *rate_back, int32_t *dist_back)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        const size_t nb = nblocks, L = layers;
+        if (!nb || !weight || !numbps || !npasses || !pass_rate || !pass_dist || !slopes || !passes || !bytes)
+            throw Error(J2K_HIP_ERR_PARAM, "rate layers stage: no blocks, or a table is NULL");
+        if (!nweights || nweights > nb) throw Error(J2K_HIP_ERR_PARAM, "rate layers stage: nweights must be 1..nblocks");
+        if (!L || L > kRateMaxLayers) throw Error(J2K_HIP_ERR_PARAM, "rate layers stage: layers must be 1..100");
+        for (size_t l = 0; l < L; ++l)
+            if (!std::isfinite(slopes[l])) throw Error(J2K_HIP_ERR_PARAM, "rate layers stage: a slope is not finite");
+        for (size_t i = 0; i < nb; ++i) {
+            if (numbps[i] > 31) throw Error(J2K_HIP_ERR_PARAM, "rate layers stage: more than 31 bit-planes");
+            if (npasses[i] > (uint32_t)kDevMaxPasses || (npasses[i] && npasses[i] + 2 > 3 * numbps[i]))
+                throw Error(J2K_HIP_ERR_PARAM, "rate layers stage: more passes than the bit-planes hold");
+        }
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        invalidate_cached_tables(e); // tables of the handle's last frame are overwritten
+        const T1Tables tt(nb);
+        const size_t rows = tt.row(nb);
+        e->meta.ensure(tt.meta_bytes());
+        e->passes.ensure(tt.passes_bytes());
+        uint32_t *meta = e->meta.as<uint32_t>();
+        uint32_t *pn = e->passes.as<uint32_t>();
+        HIP_CHECK(hipMemcpyAsync(tt.numbps(meta), numbps, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.npasses(meta), npasses, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.pass_nmsedec(pn), pass_dist, rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.pass_rate(pn), pass_rate, rows * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        e->rc_weight.ensure((size_t)nweights * sizeof(double));
+        HIP_CHECK(hipMemcpyAsync(e->rc_weight.p, weight, (size_t)nweights * sizeof(double), hipMemcpyHostToDevice, s));
+        // (filled first: what the launch leaves alone -- the spare entries behind the last block's -- comes back as 0xA5 bytes)
+        const size_t nl = (nb + J2K_HIP_RATE_LAYERS_SPARE) * L, counts = round_up(nl, 256);
+        e->rc_layers.ensure(counts + nl * sizeof(uint32_t));
+        HIP_CHECK(hipMemsetAsync(e->rc_layers.p, 0xA5, counts + nl * sizeof(uint32_t), s));
+        RateLayersArgs la = {};
+        la.nblks = (unsigned)nb; la.layers = (unsigned)L; la.nweights = nweights;
+        la.weight = e->rc_weight.as<double>();
+        la.numbps = tt.numbps(meta); la.npasses = tt.npasses(meta);
+        la.pass_nmsedec = reinterpret_cast<const int *>(tt.pass_nmsedec(pn)); la.pass_rate = tt.pass_rate(pn);
+        la.passes = e->rc_layers.as<unsigned char>(); la.bytes = reinterpret_cast<unsigned *>(e->rc_layers.as<unsigned char>() + counts);
+        launch_rate_layers(la, slopes, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(passes, la.passes, nl, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(bytes, la.bytes, nl * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (rate_back) HIP_CHECK(hipMemcpyAsync(rate_back, tt.pass_rate(pn), rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (dist_back) HIP_CHECK(hipMemcpyAsync(dist_back, tt.pass_nmsedec(pn), rows * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 // One launch_gather over pieces the caller supplies: the plan is laid out and its GatherArgs filled by the GatherPlan an encode
 // uses (table_layout.h) -- encode_end's table order by construction -- with block pieces as a CblkDev table, the blocks' lengths
 // in the `len` column of T1Tables and cblk_dst, as a frame has them, and segments alone as the decoder has them.

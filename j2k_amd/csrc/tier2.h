@@ -28,6 +28,9 @@ struct BodySeg { uint64_t dst; uint32_t cblk; uint32_t off; uint32_t len; }; // 
 struct LayerAlloc {
     uint32_t layers = 0;
     std::vector<uint32_t> np, len, off;
+    // the slope threshold every tile's final layers were laid out at, [tile (its place in geo.tiles) * layers + l]: what a
+    // bisection ended at (`good`), -1 where a layer took everything left, or the thresholds given (allocate_layers_slopes)
+    std::vector<double> slopes;
 };
 
 struct Tier2Plan {

@@ -45,7 +45,7 @@ size_t sink_write(void *user, const void *buf, size_t n)
 
 } // namespace
 
-HipCodec::HipCodec(Mode mode, int device, unsigned options) : _mode(mode), _device(device), _options(options), _fallback(NULL), _read_layers(0), _read_xyz(0), _read_xyz_profile_only(true) {}
+HipCodec::HipCodec(Mode mode, int device, unsigned options) : _mode(mode), _device(device), _options(options), _fallback(NULL), _read_layers(0), _read_xyz(0), _read_xyz_profile_only(true), _quality_layers(0) {}
 HipCodec::~HipCodec() {}
 
 const char *HipCodec::LastError() { return t_enc.error.c_str(); }
@@ -344,7 +344,8 @@ namespace {
 // that define the source samples and the geometry, and none of the coding fields).  rates: room for the layer targets that
 // p.layer_rates may point to.  false: FileInfo and Buffer do not agree.
 bool map_frame(HipCodec::Mode mode, unsigned options, const FileInfo &info, const Buffer &buffer, j2k_hip_params &p,
-               j2k_hip_plane planes[J2K_CODEC_MAX_CHANNELS], float rates[J2K_CODEC_MAX_LAYERS])
+               j2k_hip_plane planes[J2K_CODEC_MAX_CHANNELS], float rates[J2K_CODEC_MAX_LAYERS], const double *quality_slopes = NULL,
+               unsigned quality_layers = 0)
 {
     bool ok = info.channels == buffer.channels && buffer.channels >= 1 && buffer.channels <= J2K_CODEC_MAX_CHANNELS;
     if (!ok) return false;
@@ -422,8 +423,14 @@ bool map_frame(HipCodec::Mode mode, unsigned options, const FileInfo &info, cons
         }
     }
     // settings.method == QUALITY: `quality` (1..100) has no defined meaning in the reference (its WriteFile never
-    // reads it, and OpenJPEG's own quality mode takes PSNR values in dB): left unmapped on purpose; a host that has a
-    // PSNR in mind uses j2k_hip_params.layer_psnr directly.
+    // reads it, and OpenJPEG's own quality mode takes PSNR values in dB): no formula is invented for it.  A host gives the
+    // method its meaning with HipCodec::SetQualitySlopes -- one rate-distortion slope threshold per layer
+    // (j2k_hip_params.layer_slopes): the layers are cut at those thresholds, no search, the bytes follow the content.
+    // Without slopes the method stays unmapped; a host that has a PSNR in mind uses j2k_hip_params.layer_psnr directly.
+    if (mode == HipCodec::HonourSettings && method == QUALITY && quality_layers > 0) {
+        p.layers = quality_layers;
+        p.layer_slopes = quality_slopes;
+    }
     if (mode == HipCodec::HonourSettings && method == SIZE && info.settings.fileSize > 0) {
         // settings.fileSize (KiB) as a rate target -- the reference stores it (aftereffects/j2k.cpp:793-830) but
         // its WriteFile never hands it to OpenJPEG (:707).  Expressed the way OpenJPEG takes targets: one
@@ -481,7 +488,7 @@ void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &b
     j2k_hip_params p;
     j2k_hip_plane planes[J2K_CODEC_MAX_CHANNELS];
     float rates[J2K_CODEC_MAX_LAYERS];
-    if (!map_frame(_mode, _options, info, buffer, p, planes, rates)) { t_enc.error = "inconsistent FileInfo/Buffer"; throw Exception("Error writing file"); }
+    if (!map_frame(_mode, _options, info, buffer, p, planes, rates, _quality_slopes, _quality_layers)) { t_enc.error = "inconsistent FileInfo/Buffer"; throw Exception("Error writing file"); }
 
     if (!thread_handle(_device)) throw Exception("Error writing file"); // reference: :756-757 (no CPU fallback)
     int rc = j2k_hip_encode(t_enc.h, &p, planes, sink_write, &file);

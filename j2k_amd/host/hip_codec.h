@@ -115,6 +115,20 @@ class HipCodec : public Codec {
     // file cut down to those layers, what libopenjp2 does for opj_dparameters_t::cp_layer (include/j2k_hip.h:
     // j2k_hip_decode_set_max_layers).  Tier-1, the longest stage of a read, shrinks with the coding passes that remain.  A file
     // handed to the fallback codec is read in full: the Codec interface has no such parameter.
+    // Quality by rate-distortion slope (settings.method == QUALITY under HonourSettings): WriteFile writes n quality layers, layer
+    // l holding of every code-block the coding passes whose distortion decrease per byte reaches slopes[l] (OpenJPEG's units;
+    // a negative entry: everything that is left) -- include/j2k_hip.h: j2k_hip_params.layer_slopes.  One threshold held over a
+    // shot gives constant quality: the bytes follow the content.  What number stands for which `quality` is the host's choice
+    // (pick a slope on one frame with Compare, or take the ones a SIZE encode ended at: j2k_hip_encode_get_layer_slopes); this
+    // codec does not invent a formula.  n = 0 (the initial state): QUALITY stays unmapped, the frame is written as without the
+    // method.  At most J2K_CODEC_MAX_LAYERS entries are taken; the other methods ignore them.  The values are copied.
+    void SetQualitySlopes(const double *slopes, unsigned n)
+    {
+        _quality_layers = slopes == NULL ? 0u : (n > J2K_CODEC_MAX_LAYERS ? (unsigned)J2K_CODEC_MAX_LAYERS : n);
+        for (unsigned l = 0; l < _quality_layers; l++) _quality_slopes[l] = slopes[l];
+    }
+    unsigned QualityLayers() const { return _quality_layers; }
+
     void SetReadLayers(unsigned layers) { _read_layers = layers; }
     unsigned ReadLayers() const { return _read_layers; }
 
@@ -140,6 +154,8 @@ class HipCodec : public Codec {
     unsigned _read_layers;
     unsigned _read_xyz;
     bool _read_xyz_profile_only;
+    double _quality_slopes[J2K_CODEC_MAX_LAYERS];
+    unsigned _quality_layers;
 };
 
 } // namespace j2k

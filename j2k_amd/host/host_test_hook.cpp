@@ -399,6 +399,19 @@ long write_frame(const unsigned char *frame, unsigned width, unsigned height, lo
     if (const char *ch = std::getenv("J2K_HOST_TEST_CHROMA")) // test knob: 422 | 420 -> HipCodec::Chroma422 / Chroma420
         options |= std::atoi(ch) == 420 ? HipCodec::Chroma420 : (std::atoi(ch) == 422 ? HipCodec::Chroma422 : 0u);
     HipCodec hip(honour ? HipCodec::HonourSettings : HipCodec::ReferenceLiteral, -1, options);
+    if (const char *q = std::getenv("J2K_HOST_TEST_QUALITY")) { // test knob: settings.method = QUALITY; value = the slopes for
+        info.settings.method = QUALITY;                          // SetQualitySlopes, comma-separated (hex floats keep every bit), or "" for none
+        double slopes[J2K_CODEC_MAX_LAYERS + 1];
+        unsigned n = 0;
+        for (const char *s = q; *s && n <= J2K_CODEC_MAX_LAYERS;) {
+            char *end = NULL;
+            const double v = std::strtod(s, &end);
+            if (end == s) break;
+            slopes[n++] = v;
+            s = *end == ',' ? end + 1 : end;
+        }
+        if (n) hip.SetQualitySlopes(slopes, n);
+    }
     Codec *codec = &hip; // through the interface, as RGBAoutputFile does (j2k_rgba_file.cpp:812)
     try {
         codec->WriteFile(file, info, buf, NULL);
