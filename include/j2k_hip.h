@@ -400,6 +400,65 @@ int j2k_hip_guard_bits_needed(const j2k_hip_params *params, const uint32_t *numb
  * thresholds) or for a tile the last file does not have; a failed call leaves the record alone. */
 int j2k_hip_encode_get_layer_slopes(const j2k_hip_encoder *enc, uint32_t tile, double *out, uint32_t cap, uint32_t *n);
 
+/* --- a sequence to a byte budget: one slope threshold per shot, found on the device -----------------
+ * The candidates are a fixed public grid, T(k) = ldexp(m[k mod 16], floor(k / 16)) for J2K_HIP_SLOPE_K_MIN <= k <=
+ * J2K_HIP_SLOPE_K_MAX with m[j] = the double nearest 2^(j / 16) (mod and floor towards minus infinity), and
+ * J2K_HIP_SLOPE_ALL for the threshold -1: everything that is left.  The integer order of the indices is the order of the
+ * candidates, finest first.  j2k_hip_slope_grid: *t = T(k), -1.0 for J2K_HIP_SLOPE_ALL; J2K_HIP_ERR_PARAM outside the range.
+ *
+ * len_f(c) = the length of the file j2k_hip_encode_device writes of frame f under `params` with layers = 1 and
+ * layer_slopes = { T(c) }.  total_bytes limits all files of the call together, frame_max_bytes any one of them; 0 = no limit.
+ *   cap_f: J2K_HIP_SLOPE_ALL without frame_max_bytes; else len_f(cap_f) <= frame_max_bytes, and cap_f is J2K_HIP_SLOPE_ALL or
+ *          len_f(cap_f - 1) > frame_max_bytes.
+ *   c*:    with c_f(c) = max(c, cap_f): sum over f of len_f(c_f(c*)) <= total_bytes, and c* is J2K_HIP_SLOPE_ALL or the sum at
+ *          c* - 1 is above total_bytes (without total_bytes: c* = J2K_HIP_SLOPE_ALL).
+ * Frame f of the call is the file at c_f(c*), byte for byte.  File length is not a monotone function of the threshold, so such
+ * boundaries need not be unique: any index with the property may be returned, the same one for the same input.
+ * Where even J2K_HIP_SLOPE_K_MAX does not fit: J2K_HIP_ERR_OVERFLOW, the text naming the field (total_bytes / frame_max_bytes)
+ * and the length at the coarsest candidate; nothing is written -- no output pointer, no length -- and the handle takes its next call.
+ * Overflow goes by the search's walk: from where it stands it moves to coarser candidates until one fits and reports overflow
+ * once J2K_HIP_SLOPE_K_MAX itself does not; as lengths need not fall with the index, that may be reported although some finer
+ * index would have fitted by a few header bytes.  A successful call leaves no file above frame_max_bytes: a frame that exceeds it
+ * at the shared index takes the next boundary at or above that index as its cap.
+ * The search always runs on the device; the tuning knob rate_dev = -1 leaves the cut of the final layers to the host, over the
+ * downloaded pass tables, as for layer_slopes -- the same files.
+ *
+ * j2k_hip_encode_sequence_budget_check (host only, no handle; text through j2k_hip_last_error(NULL)) refuses with
+ * J2K_HIP_ERR_PARAM, the text naming the field, what the call refuses before any device work: layers other than 0 or 1;
+ * layer_rates, layer_psnr, layer_slopes, dci_profile or cblk_style set; J2K_HIP_GUARD_AUTO (a re-plan would move the lengths the
+ * search priced; a fixed count is fine); a struct_size that is not the struct's; flags other than 0; nframes == 0.
+ * j2k_hip_encode_sequence_budget_device: the frames are resident, as for j2k_hip_encode_sequence_device, whose outputs these
+ * are; frame_index (optional, nframes entries) receives c_f(c*), result (optional; struct_size set by the caller) what the
+ * search did: curve_launches = launches of rate_curve_kernel, exact_plans = whole-frame plans beyond the one every frame needs.
+ * Afterwards j2k_hip_encode_get_layer_slopes reports the last frame's threshold.
+ * J2K_HIP_ABI_VERSION is still 9: functions and structs were added, none changed. */
+#define J2K_HIP_SLOPE_K_MIN (-2048)
+#define J2K_HIP_SLOPE_K_MAX 2047
+#define J2K_HIP_SLOPE_ALL (-2049)
+typedef struct j2k_hip_budget {
+    uint32_t struct_size; /* sizeof(j2k_hip_budget) */
+    uint32_t flags;       /* 0 */
+    uint64_t total_bytes, frame_max_bytes;
+} j2k_hip_budget;
+typedef struct j2k_hip_budget_result {
+    uint32_t struct_size; /* sizeof(j2k_hip_budget_result) */
+    int32_t shared_index; /* c* */
+    uint64_t total_bytes; /* of the files written */
+    uint32_t capped_frames, curve_launches, exact_plans, reserved;
+} j2k_hip_budget_result;
+int j2k_hip_slope_grid(int32_t k, double *t);
+int j2k_hip_encode_sequence_budget_check(const j2k_hip_params *params, uint32_t nframes, const j2k_hip_budget *budget);
+int j2k_hip_encode_sequence_budget_device(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes,
+                                          uint32_t nframes, const j2k_hip_budget *budget, const void **d_codestreams,
+                                          size_t *lens, int32_t *frame_index, j2k_hip_budget_result *result);
+/* The same from host frames (planes = nframes consecutive sets of channel views in host memory), the files handed to one sink
+ * per frame, users[f] with `write`, each front to back, frame 0 first.  No sink sees a byte before every frame's plan is final:
+ * a budget that cannot be met, and every other refusal, leaves all of them untouched.  The handle keeps one input arena per
+ * host frame of the largest such call it has served (nframes frames' worth of device memory) until j2k_hip_destroy. */
+int j2k_hip_encode_sequence_budget(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes,
+                                   uint32_t nframes, const j2k_hip_budget *budget, j2k_hip_write_fn write, void *const *users,
+                                   int32_t *frame_index, j2k_hip_budget_result *result);
+
 /* --- tile-sharded encode (multi-GPU) -----------------------------------------------
  * Encode only tiles [tile_first, tile_first+tile_count) of the image (raster tile index, Isot).
  * Emits the tile-parts (SOT..data) of those tiles, in order, without main header or EOC, into the
@@ -924,6 +983,20 @@ int j2k_hip_stage_rate_layers(j2k_hip_encoder *enc, uint32_t nblocks, const doub
                               const uint32_t *numbps, const uint32_t *npasses, const uint32_t *pass_rate,
                               const int32_t *pass_dist, const double *slopes, uint32_t layers, uint8_t *passes,
                               uint32_t *bytes, uint32_t *rate_back, int32_t *dist_back);
+
+/* rate_curve_kernel alone (j2k_hip_encode_sequence_budget_device): ONE launch over the tables of j2k_hip_stage_rate_layers, read
+ * as nframes frames of nblocks / nframes blocks each.  Candidate j < K is the grid index min(base + j * step,
+ * J2K_HIP_SLOPE_K_MAX); frame f is evaluated at max(candidate, cap[f]).  Out: sums[(f * K + j) * 2] = the body bytes of frame f's
+ * blocks cut at T(that index), [.. + 1] = their header bits (rate_block_header_bits), followed by J2K_HIP_RATE_LAYERS_SPARE
+ * entries that keep the 0xA5 fill; rate_back / dist_back as for j2k_hip_stage_rate_layers.
+ * Refused with J2K_HIP_ERR_PARAM: what that hook refuses of the tables, K outside 1..64, step == 0, nframes == 0 or not a divisor
+ * of nblocks, nweights other than 1..nblocks (block i takes weight[i % nweights]), base or a cap outside J2K_HIP_SLOPE_ALL..J2K_HIP_SLOPE_K_MAX, an encode
+ * pending on the handle.  The handle's cached geometry is dropped. */
+#define J2K_HIP_RATE_CURVE_MAX 64
+int j2k_hip_stage_rate_curve(j2k_hip_encoder *enc, uint32_t nblocks, const double *weight, uint32_t nweights,
+                             const uint32_t *numbps, const uint32_t *npasses, const uint32_t *pass_rate,
+                             const int32_t *pass_dist, uint32_t nframes, const int32_t *cap, int32_t base, uint32_t step,
+                             uint32_t K, uint64_t *sums, uint32_t *rate_back, int32_t *dist_back);
 
 /* The codestream assembly alone: ONE launch of gather_kernel over three lists of pieces, its arguments filled as an encode
  * and a decode fill them.  dst (host, dst_bytes) goes up as it is, receives the pieces and comes back; `src` (host) is the

@@ -109,7 +109,27 @@ EXPORTS = ["j2k_hip_abi_version", "j2k_hip_create", "j2k_hip_destroy", "j2k_hip_
            "j2k_hip_memcpy_h2d", "j2k_hip_memcpy_d2h", "j2k_hip_synchronize", "j2k_hip_debug_copy_sink", "j2k_hip_debug_count_sink",
            "j2k_hip_debug_cblk_capacities", "j2k_hip_debug_blocks", "j2k_hip_debug_tier2",
            "j2k_hip_encode_get_guard_bits", "j2k_hip_guard_bits_needed", "j2k_hip_debug_tier2_guard", "j2k_hip_debug_tier2_plan",
-           "j2k_hip_encode_get_layer_slopes", "j2k_hip_stage_rate_layers"]
+           "j2k_hip_encode_get_layer_slopes", "j2k_hip_stage_rate_layers",
+           "j2k_hip_slope_grid", "j2k_hip_encode_sequence_budget_check", "j2k_hip_encode_sequence_budget_device",
+           "j2k_hip_encode_sequence_budget",
+           "j2k_hip_stage_rate_curve"]
+
+SLOPE_K_MIN, SLOPE_K_MAX, SLOPE_ALL = -2048, 2047, -2049  # include/j2k_hip.h: the public grid of slope thresholds
+
+
+class Budget(C.Structure):
+    """include/j2k_hip.h: j2k_hip_budget."""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("total_bytes", C.c_uint64), ("frame_max_bytes", C.c_uint64)]
+
+
+class BudgetResult(C.Structure):
+    """include/j2k_hip.h: j2k_hip_budget_result."""
+    _fields_ = [("struct_size", C.c_uint32), ("shared_index", C.c_int32), ("total_bytes", C.c_uint64), ("capped_frames", C.c_uint32),
+                ("curve_launches", C.c_uint32), ("exact_plans", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def make_budget(total_bytes: int = 0, frame_max_bytes: int = 0) -> Budget:
+    return Budget(C.sizeof(Budget), 0, total_bytes, frame_max_bytes)
 
 class Tier2Plan(C.Structure):
     """include/j2k_hip.h: j2k_hip_tier2_plan."""
@@ -320,6 +340,15 @@ def load_library():
     if hasattr(L, "j2k_hip_encode_get_layer_slopes"):
         L.j2k_hip_encode_get_layer_slopes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.j2k_hip_stage_rate_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32] + [C.c_void_p] * 4
+    if hasattr(L, "j2k_hip_slope_grid"):
+        L.j2k_hip_slope_grid.argtypes = [C.c_int32, C.POINTER(C.c_double)]
+        L.j2k_hip_encode_sequence_budget_check.argtypes = [C.POINTER(Params), C.c_uint32, C.POINTER(Budget)]
+        L.j2k_hip_encode_sequence_budget_device.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.POINTER(Budget), C.c_void_p, C.c_void_p,
+                                                            C.c_void_p, C.POINTER(BudgetResult)]
+        L.j2k_hip_encode_sequence_budget.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.POINTER(Budget), WRITE_FN, C.POINTER(C.c_void_p),
+                                                     C.c_void_p, C.POINTER(BudgetResult)]
+        L.j2k_hip_stage_rate_curve.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_uint32, C.c_void_p, C.c_int32,
+                                               C.c_uint32, C.c_uint32] + [C.c_void_p] * 3
     _lib = L
     return L
 
@@ -453,6 +482,26 @@ def make_params(width, height, channels, depth, reversible=True, ycc=False, laye
         p._icc_keepalive = C.create_string_buffer(bytes(icc), len(icc))  # borrowed by the C side for each call
         p.icc_profile, p.icc_profile_len = C.cast(p._icc_keepalive, C.c_void_p), len(icc)
     return p
+
+
+def slope_grid(k: int) -> float:
+    """j2k_hip_slope_grid: threshold k of the public grid, -1.0 for SLOPE_ALL; refused outside SLOPE_ALL..SLOPE_K_MAX."""
+    L = load_library()
+    t = C.c_double()
+    if not -(1 << 31) <= k < (1 << 31):
+        raise J2kHipError(1, "slope grid index outside the range")
+    rc = L.j2k_hip_slope_grid(k, C.byref(t))
+    if rc != 0:
+        raise J2kHipError(rc, "slope grid index outside the range")
+    return t.value
+
+
+def sequence_budget_check(params: Params, nframes: int, budget: Budget) -> None:
+    """j2k_hip_encode_sequence_budget_check: raises what Encoder.encode_sequence_budget_device would refuse before any device work."""
+    L = load_library()
+    rc = L.j2k_hip_encode_sequence_budget_check(C.byref(params), nframes, C.byref(budget))
+    if rc != 0:
+        raise J2kHipError(rc, L.j2k_hip_last_error(None).decode())
 
 
 def main_header(params: Params) -> bytes:
@@ -885,6 +934,51 @@ class Encoder:
         ptrs, lens = (C.c_void_p * nf)(), (C.c_size_t * nf)()
         self._check(self.L.j2k_hip_encode_sequence_device(self.h, C.byref(params), arr, nf, ptrs, lens))
         return [(ptrs[f], lens[f], self.d2h(ptrs[f], lens[f]).tobytes() if download else None) for f in range(nf)]
+
+    def encode_sequence_budget_device(self, d_frames: list, layout: dict, params: Params, total_bytes: int = 0, frame_max_bytes: int = 0,
+                                      budget: Budget | None = None, outputs=None, download: bool = True):
+        """j2k_hip_encode_sequence_budget_device: the frames of one shot (device pointers, same layout) to a byte budget ->
+        (files [bytes], frame_index [int], result dict).  outputs = (ptrs, lens, index) ctypes arrays to pass instead of fresh ones."""
+        nf, nc = len(d_frames), params.channels
+        arr = (Plane * (nf * nc))()
+        for f, d in enumerate(d_frames):
+            one = planes_from_layout(d, layout, nc)
+            for c in range(nc):
+                arr[f * nc + c] = one[c]
+        ptrs, lens, index = outputs if outputs else ((C.c_void_p * nf)(), (C.c_size_t * nf)(), (C.c_int32 * nf)())
+        b = budget if budget is not None else make_budget(total_bytes, frame_max_bytes)
+        res = BudgetResult(struct_size=C.sizeof(BudgetResult))
+        self._check(self.L.j2k_hip_encode_sequence_budget_device(self.h, C.byref(params), arr, nf, C.byref(b), ptrs, lens, index, C.byref(res)))
+        files = [self.d2h(ptrs[f], lens[f]).tobytes() if download else int(lens[f]) for f in range(nf)]  # (not downloaded: the lengths)
+        return files, [int(v) for v in index], {k: int(getattr(res, k)) for k, _ in BudgetResult._fields_ if k not in ("struct_size", "reserved")}
+
+    def encode_sequence_budget(self, frames: list, layout: dict, params: Params, total_bytes: int = 0, frame_max_bytes: int = 0,
+                               budget: Budget | None = None, capacity: int | None = None, fill: int = 0):
+        """j2k_hip_encode_sequence_budget: the same from host frames (AE-layout buffers), every file into a copy sink of its own ->
+        (files [bytes], frame_index [int], result dict, sinks [(buffer, bytes written)]).  The sinks' buffers (capacity bytes
+        each, filled with `fill` first) come back too, so that a failed call can be shown to have written nothing: on failure the
+        J2kHipError carries them as .sinks."""
+        nf, nc = len(frames), params.channels
+        arr = (Plane * (nf * nc))()
+        for f, fr in enumerate(frames):
+            one = planes_from_layout(fr.ctypes.data, layout, nc)
+            for c in range(nc):
+                arr[f * nc + c] = one[c]
+        cap = capacity if capacity is not None else max(int(fr.nbytes) for fr in frames) * 2 + (1 << 20)
+        bufs = [np.full(cap, fill, np.uint8) for _ in range(nf)]
+        sinks = [CopySink(b.ctypes.data, cap, 0) for b in bufs]
+        users = (C.c_void_p * nf)(*[C.cast(C.pointer(sk), C.c_void_p) for sk in sinks])
+        index = (C.c_int32 * nf)(*([fill] * nf))
+        b = budget if budget is not None else make_budget(total_bytes, frame_max_bytes)
+        res = BudgetResult(struct_size=C.sizeof(BudgetResult))
+        try:
+            self._check(self.L.j2k_hip_encode_sequence_budget(self.h, C.byref(params), arr, nf, C.byref(b), native_sink(self.L), users, index, C.byref(res)))
+        except J2kHipError as x:
+            x.sinks = [(bufs[f], int(sinks[f].pos)) for f in range(nf)]
+            x.index = [int(v) for v in index]
+            raise
+        files = [bufs[f][:sinks[f].pos].tobytes() for f in range(nf)]
+        return files, [int(v) for v in index], {k: int(getattr(res, k)) for k, _ in BudgetResult._fields_ if k not in ("struct_size", "reserved")}
 
     def encode_tiles_device(self, d_frame: int, layout: dict, params: Params, tile_first: int, tile_count: int):
         planes = planes_from_layout(d_frame, layout, params.channels)
@@ -1464,6 +1558,27 @@ class Encoder:
         self._check(self.L.j2k_hip_stage_rate_layers(self.h, n, ptr(weight), weight.size, ptr(numbps), ptr(npasses), ptr(pass_rate), ptr(pass_dist),
                                                      ptr(sl), nl, ptr(passes), ptr(nbytes), ptr(rate_back), ptr(dist_back)))
         return dict(passes=passes[:n], bytes=nbytes[:n], spare_passes=passes[n:], spare_bytes=nbytes[n:], rate_back=rate_back, dist_back=dist_back)
+
+    def stage_rate_curve(self, weight, numbps, npasses, pass_rate, pass_dist, nframes, cap, base, step, K):
+        """j2k_hip_stage_rate_curve: rate_curve_kernel on tables per block, read as nframes frames.  Returns a dict: sums
+        (nframes, K, 2) uint64 = body bytes and header bits per frame and candidate; spare: the entries behind them as they came
+        back (filled with 0xA5 first); rate_back / dist_back: the pass tables as they lie on the device afterwards."""
+        MP, SPARE = 96, 64
+        n = len(npasses)
+        weight = np.ascontiguousarray(weight, dtype=np.float64)
+        numbps = np.ascontiguousarray(numbps, dtype=np.uint32)
+        npasses = np.ascontiguousarray(npasses, dtype=np.uint32)
+        pass_rate = np.ascontiguousarray(pass_rate, dtype=np.uint32).reshape(n, MP)
+        pass_dist = np.ascontiguousarray(pass_dist, dtype=np.int32).reshape(n, MP)
+        cap = np.ascontiguousarray(cap, dtype=np.int32)
+        assert numbps.size == n and cap.size == nframes
+        nf, k = max(int(nframes), 0), max(int(K), 0)
+        sums = np.zeros(nf * min(k, 64) * 2 + SPARE, np.uint64)
+        rate_back, dist_back = np.zeros((n, MP), np.uint32), np.zeros((n, MP), np.int32)
+        ptr = lambda a: a.ctypes.data if a.size else None
+        self._check(self.L.j2k_hip_stage_rate_curve(self.h, n, ptr(weight), weight.size, ptr(numbps), ptr(npasses), ptr(pass_rate), ptr(pass_dist),
+                                                    nframes, ptr(cap), base, step, K, ptr(sums), ptr(rate_back), ptr(dist_back)))
+        return dict(sums=sums[:nf * k * 2].reshape(nf, k, 2), spare=sums[nf * k * 2:], rate_back=rate_back, dist_back=dist_back)
 
     def stage_gather(self, src, dst, blocks=(), headers=(), segments=(), blob=None) -> np.ndarray:
         """j2k_hip_stage_gather: src / dst (/ blob, default: src) uint8 arrays, the piece lists [(dst, src, len)].  Returns

@@ -46,6 +46,7 @@
 #include "bands.h"
 #include "cblk_style.h"
 #include "handle.h"
+#include "rate_budget.h"
 #include "rate_device.h"
 #include "xyz_tables.h"
 
@@ -571,7 +572,7 @@ namespace {
 // share every launch of the context modeller and of the MQ coder, so their coder chains run side by side
 // instead of one after the other -- what a sequence of small frames needs.
 void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes,
-                  bool planes_on_device, uint32_t tile_first, uint32_t tile_count, bool framed, uint32_t nframes = 1)
+                  bool planes_on_device, uint32_t tile_first, uint32_t tile_count, bool framed, uint32_t nframes = 1, bool budget = false)
 {
     Pending &pd = e->pend;
     if (pd.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
@@ -799,7 +800,9 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
         // Layers at given slopes: nothing to search, so the whole allocation is one launch here, over the blocks of every tile and
         // frame of the call, and what comes down is a pass count and a byte count per block and layer -- the pass tables stay
         // where they are.  At every size; rate_dev = -1 leaves the same walk to the host, over the tables.
-        pd.rc_layers = !cod.slopes.empty() && tn.rate_dev >= 0;
+        // (a call to a byte budget searches on the device's counts whatever rate_dev says; under rate_dev = -1 the tables come down
+        //  as well, for the host's cut of the final layers)
+        pd.rc_layers = !cod.slopes.empty() && (tn.rate_dev >= 0 || budget);
         if (pd.rc_layers) {
             const size_t nl = nb * cod.layers, counts = round_up(nl, 256);
             e->rc_weight.ensure(nb1 * sizeof(double) + nb1);
@@ -819,8 +822,12 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
             la.numbps = tt.numbps(meta); la.npasses = tt.npasses(meta);
             la.pass_nmsedec = reinterpret_cast<const int *>(tt.pass_nmsedec(e->passes.as<uint32_t>())); la.pass_rate = tt.pass_rate(e->passes.as<uint32_t>());
             la.passes = e->rc_layers.as<unsigned char>(); la.bytes = reinterpret_cast<unsigned *>(e->rc_layers.as<unsigned char>() + counts);
-            launch_rate_layers(la, cod.slopes.data(), s);
-            HIP_CHECK(hipMemcpyAsync(e->h_rc_layers.p, e->rc_layers.p, counts + nl * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            if (!budget) { // (a budget call cuts at the indices its search visits: encode_end launches)
+                launch_rate_layers(la, cod.slopes.data(), s);
+                HIP_CHECK(hipMemcpyAsync(e->h_rc_layers.p, e->rc_layers.p, counts + nl * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            }
+            pd.budget_host_cut = budget && tn.rate_dev < 0;
+            if (pd.budget_host_cut) HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_nmsedec, tt.h_passes_bytes(), hipMemcpyDeviceToHost, s));
         } else if (!(pd.rc_device && tn.overlap))
             HIP_CHECK(hipMemcpyAsync(e->h_passes.p, ta.pass_nmsedec, tt.h_passes_bytes(), hipMemcpyDeviceToHost, s));
         if (pd.rc_device) {
@@ -874,7 +881,13 @@ void encode_begin(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hi
 }
 
 // Second half: waits for the Tier-1 results, plans the codestream on the host (Tier-2), assembles it in HBM.
-std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
+// A sequence to a byte budget (j2k_hip_encode_sequence_budget_device): the limits in, what the search ended at out.
+struct BudgetCall {
+    uint64_t total = 0, frame_max = 0;
+    BudgetOutcome out;
+};
+
+std::vector<EncodeOut> encode_end(j2k_hip_encoder *e, BudgetCall *bc = nullptr)
 {
     Pending &pd = e->pend;
     if (!pd.active) throw Error(J2K_HIP_ERR_PARAM, "no encode in progress on this handle");
@@ -917,6 +930,137 @@ std::vector<EncodeOut> encode_end(j2k_hip_encoder *e)
     std::vector<double> last_slopes; // ... and its layers' thresholds (rate control)
     {
         Range r("j2k_hip tier2 host");
+        if (bc) {
+            // The frames' cuts are searched for (rate_budget.h): the curve is a launch over the pass tables of all frames, which
+            // are in HBM; an exact price is the cut of a frame at one threshold (rate_layers_kernel over its blocks, the counts
+            // to pinned memory) and its plan.  The plans at the indices the search ends at are the files.
+            if (!pd.rc_layers) throw Error(J2K_HIP_ERR_PARAM, "internal: a budget call without the device's counts");
+            const size_t counts = round_up(nb * cod.layers, 256);
+            struct Planned { int32_t index; Tier2Plan plan; std::vector<double> slopes; };
+            std::vector<std::vector<Planned>> kept(F); // per frame its last plans (the search ends among them)
+            RateLayersArgs la0 = {};
+            la0.layers = 1; la0.nweights = (unsigned)nb1;
+            la0.weight = e->rc_weight.as<double>();
+            la0.numbps = tt.numbps(meta); la0.npasses = tt.npasses(meta);
+            la0.pass_nmsedec = reinterpret_cast<const int *>(tt.pass_nmsedec(e->passes.as<uint32_t>())); la0.pass_rate = tt.pass_rate(e->passes.as<uint32_t>());
+            la0.passes = e->rc_layers.as<unsigned char>(); la0.bytes = reinterpret_cast<unsigned *>(e->rc_layers.as<unsigned char>() + counts);
+            uint8_t *hl = e->h_rc_layers.as<uint8_t>();
+            struct Pricer : BudgetPricer {
+                std::function<void(const uint32_t *, const int32_t *, uint32_t, uint64_t *)> fn;
+                void lengths(const uint32_t *fr, const int32_t *ix, uint32_t n, uint64_t *len) override { fn(fr, ix, n, len); }
+            } pricer;
+            auto cut = [&](size_t f0, size_t f1, int32_t index) { // frames [f0, f1) at one threshold: one launch, their counts down
+                RateLayersArgs la = la0;
+                const size_t b0 = f0 * nb1, n = (f1 - f0) * nb1;
+                la.nblks = (unsigned)n;
+                la.numbps += b0; la.npasses += b0; la.pass_nmsedec += tt.row(b0); la.pass_rate += tt.row(b0);
+                la.passes += b0; la.bytes += b0;
+                const double t = rate_slope_grid(index);
+                launch_rate_layers(la, &t, s);
+                HIP_CHECK(hipGetLastError());
+                HIP_CHECK(hipMemcpyAsync(hl + b0, la.passes, n, hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipMemcpyAsync(hl + counts + b0 * sizeof(uint32_t), la.bytes, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            };
+            auto plan_at = [&](size_t f, int32_t index) -> uint64_t {
+                std::vector<CblkResult> res(nb1);
+                const size_t b0 = f * nb1;
+                for (size_t i = 0; i < nb1; ++i) res[i] = CblkResult{tt.numbps(hm)[b0 + i], tt.npasses(hm)[b0 + i], tt.len(hm)[b0 + i]};
+                const double t = rate_slope_grid(index);
+                LayerAlloc alloc = layers_from_counts(g, hl + b0, reinterpret_cast<const uint32_t *>(hl + counts) + b0, &t);
+                if (nb1 >= 4096 && !e->t2_workers) e->t2_workers.reset(new Workers(plan_threads()));
+                Planned p{index, plan_codestream(g, res, framed, framed, &alloc, e->t2_workers.get()), alloc.slopes};
+                const uint64_t len = p.plan.total_len;
+                if (kept[f].size() >= 3) kept[f].erase(kept[f].begin());
+                kept[f].push_back(std::move(p));
+                return len;
+            };
+            pricer.fn = [&](const uint32_t *fr, const int32_t *ix, uint32_t n, uint64_t *len) {
+                uint32_t i = 0;
+                while (i < n) { // a piece of the list in which no frame comes twice (its counts have one place)
+                    uint32_t j = i;
+                    std::vector<bool> seen(F, false);
+                    while (j < n && fr[j] < F && !seen[fr[j]]) seen[fr[j++]] = true;
+                    if (j == i) throw Error(J2K_HIP_ERR_PARAM, "internal: budget search asked for a frame the call does not have");
+                    for (uint32_t a = i; a < j;) { // runs of neighbouring frames at one index share a launch
+                        uint32_t b = a + 1;
+                        while (b < j && fr[b] == fr[b - 1] + 1 && ix[b] == ix[a]) ++b;
+                        cut(fr[a], (size_t)fr[b - 1] + 1, ix[a]);
+                        a = b;
+                    }
+                    HIP_CHECK(hipStreamSynchronize(s));
+                    for (uint32_t a = i; a < j; ++a) len[a] = plan_at(fr[a], ix[a]);
+                    i = j;
+                }
+            };
+            struct Curve : BudgetCurve {
+                j2k_hip_encoder *e; hipStream_t s; RateCurveArgs a; size_t F; uint64_t fixed;
+                void curve(int32_t base, uint32_t step, uint32_t K, const int32_t *cap, uint64_t *sums) override
+                {
+                    const size_t nsums = F * K * 2 * sizeof(uint64_t);
+                    e->rc_small.ensure(nsums + F * sizeof(int32_t));
+                    e->h_rc_small.ensure(nsums + F * sizeof(int32_t));
+                    uint8_t *d = e->rc_small.as<uint8_t>(), *h = e->h_rc_small.as<uint8_t>();
+                    std::memcpy(h + nsums, cap, F * sizeof(int32_t));
+                    HIP_CHECK(hipMemcpyAsync(d + nsums, h + nsums, F * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                    HIP_CHECK(hipMemsetAsync(d, 0, nsums, s));
+                    RateCurveArgs c = a;
+                    c.base = base; c.step = step; c.K = K;
+                    c.cap = reinterpret_cast<const int *>(d + nsums); c.sums = reinterpret_cast<unsigned long long *>(d);
+                    launch_rate_curve(c, s);
+                    HIP_CHECK(hipGetLastError());
+                    HIP_CHECK(hipMemcpyAsync(h, d, nsums, hipMemcpyDeviceToHost, s));
+                    HIP_CHECK(hipStreamSynchronize(s));
+                    std::memcpy(sums, h, nsums);
+                }
+                uint64_t fixed_bytes(uint32_t) override { return fixed; }
+            } curve;
+            curve.e = e; curve.s = s; curve.F = F;
+            curve.fixed = lead + 14 * g.tiles.size() + 2; // (SOT and SOD per tile, EOC; what the packets cost empty the first real lengths show)
+            curve.a = RateCurveArgs{};
+            curve.a.nblks = (unsigned)nb; curve.a.nb1 = (unsigned)nb1; curve.a.nweights = (unsigned)nb1;
+            curve.a.weight = la0.weight; curve.a.numbps = la0.numbps; curve.a.npasses = la0.npasses;
+            curve.a.pass_nmsedec = la0.pass_nmsedec; curve.a.pass_rate = la0.pass_rate;
+            if (nb1) {
+                BudgetSearch search((uint32_t)F, curve, pricer);
+                bc->out = search.run(bc->total, bc->frame_max);
+            } else
+                throw Error(J2K_HIP_ERR_PARAM, "a byte budget needs code-blocks to cut");
+            const BudgetOutcome &bo = bc->out;
+            if (bo.status == BudgetOutcome::OVER_TOTAL)
+                throw Error(J2K_HIP_ERR_OVERFLOW, "total_bytes: the frames do not fit at the coarsest threshold of the grid, where they take " + std::to_string(bo.smallest) + " bytes together");
+            if (bo.status == BudgetOutcome::OVER_FRAME)
+                throw Error(J2K_HIP_ERR_OVERFLOW, "frame_max_bytes: frame " + std::to_string(bo.over_frame) + " does not fit at the coarsest threshold of the grid, where it takes " + std::to_string(bo.smallest) + " bytes");
+            for (size_t f = 0; f < F; ++f) {
+                auto has = [&] { return std::find_if(kept[f].begin(), kept[f].end(), [&](const Planned &p) { return p.index == bo.index[f]; }); };
+                if (has() == kept[f].end()) { // (the walk moved on by more plans than are kept: once more)
+                    const uint32_t fr = (uint32_t)f;
+                    uint64_t len = 0;
+                    pricer.fn(&fr, &bo.index[f], 1, &len);
+                    ++bc->out.exact_plans;
+                }
+                auto it = has();
+                if (pd.budget_host_cut) {
+                    // rate_dev = -1: the final layers are cut by the host's walk over the downloaded tables (allocate_layers_slopes,
+                    // section 21's host path) and planned from that; the search's plan of the index only told its length
+                    std::vector<CblkResult> res(nb1);
+                    const size_t b0 = f * nb1;
+                    for (size_t i = 0; i < nb1; ++i) res[i] = CblkResult{tt.numbps(hm)[b0 + i], tt.npasses(hm)[b0 + i], tt.len(hm)[b0 + i]};
+                    const uint32_t *hp = e->h_passes.as<uint32_t>();
+                    const double t = rate_slope_grid(bo.index[f]);
+                    LayerAlloc alloc = allocate_layers_slopes(g, res, tt.h_rate(hp) + tt.row(b0), reinterpret_cast<const int32_t *>(hp + tt.row(b0)), &t);
+                    it->plan = plan_codestream(g, res, framed, framed, &alloc, e->t2_workers.get());
+                    it->slopes = alloc.slopes;
+                    if (it->plan.total_len != bo.len[f]) throw Error(J2K_HIP_ERR_PARAM, "internal: the host's cut of a frame differs from the device's");
+                }
+                plans[f] = std::move(it->plan);
+                if (f == F - 1) last_slopes = it->slopes;
+                lays[f] = GatherPlan(plans[f].blob.size(), plans[f].hdr_segs.size(), nbd, plans[f].body_segs.size());
+                plan_off[f] = plan_total;
+                plan_total += lays[f].total;
+                cs_off[f] = cs_total;
+                cs_total += round_up(plans[f].total_len + 64, 256);
+            }
+        } else
         for (size_t f = 0; f < F; ++f) {
             std::vector<CblkResult> res(nb1);
             const size_t b0 = f * nb1; // the frame's first block in the tables
@@ -1717,6 +1861,85 @@ int j2k_hip_encode_sequence_device(j2k_hip_encoder *e, const j2k_hip_params *par
     });
 }
 
+int j2k_hip_slope_grid(int32_t k, double *t)
+{
+    if (!t || k < kSlopeAll || k > kSlopeKMax) return J2K_HIP_ERR_PARAM;
+    *t = rate_slope_grid(k);
+    return J2K_HIP_OK;
+}
+
+} // extern "C"
+
+namespace {
+// What a call to a byte budget refuses of its arguments, before any device work (throws); returns the parameters it encodes
+// under: one layer, cut at a threshold of the search's choosing.
+j2k_hip_params budget_params(const j2k_hip_params *params, uint32_t nframes, const j2k_hip_budget *budget)
+{
+    if (!params || !budget) throw Error(J2K_HIP_ERR_PARAM, "params / budget is NULL");
+    if (!params_size_ok(params)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_params.struct_size does not match this library");
+    if (budget->struct_size != sizeof(j2k_hip_budget)) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_budget.struct_size does not match this library");
+    if (budget->flags) throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_budget.flags must be 0");
+    if (!nframes) throw Error(J2K_HIP_ERR_PARAM, "nframes must not be 0");
+    j2k_hip_params p = widened(params);
+    if (p.layers > 1) throw Error(J2K_HIP_ERR_PARAM, "layers: a byte budget cuts one layer (0 or 1)");
+    if (p.layer_rates) throw Error(J2K_HIP_ERR_PARAM, "layer_rates cannot be combined with a byte budget: the budget sets the cut");
+    if (p.layer_psnr) throw Error(J2K_HIP_ERR_PARAM, "layer_psnr cannot be combined with a byte budget: the budget sets the cut");
+    if (p.layer_slopes) throw Error(J2K_HIP_ERR_PARAM, "layer_slopes cannot be combined with a byte budget: the search chooses the threshold");
+    if (p.dci_profile) throw Error(J2K_HIP_ERR_PARAM, "dci_profile cannot be combined with a byte budget: a digital cinema profile sets its own rate");
+    if (p.cblk_style) throw Error(J2K_HIP_ERR_PARAM, "cblk_style cannot be combined with a byte budget: rate control does not price codeword segments");
+    if (p.guard_bits & J2K_HIP_GUARD_AUTO)
+        throw Error(J2K_HIP_ERR_PARAM, "guard_bits: J2K_HIP_GUARD_AUTO cannot be combined with a byte budget (a re-plan would move the lengths the search priced); give a fixed count");
+    static const double all = -1.0;
+    p.layers = 1;
+    p.layer_slopes = &all;
+    (void)normalise(&p); // whatever else the parameters are refused for
+    return p;
+}
+
+void budget_report(const BudgetCall &bc, uint32_t nframes, int32_t *frame_index, j2k_hip_budget_result *result)
+{
+    for (uint32_t f = 0; frame_index && f < nframes; ++f) frame_index[f] = bc.out.index[f];
+    if (!result) return;
+    result->shared_index = bc.out.shared; result->total_bytes = bc.out.total; result->capped_frames = bc.out.capped;
+    result->curve_launches = bc.out.curve_launches; result->exact_plans = bc.out.exact_plans; result->reserved = 0;
+}
+} // namespace
+
+extern "C" {
+
+int j2k_hip_encode_sequence_budget_check(const j2k_hip_params *params, uint32_t nframes, const j2k_hip_budget *budget)
+{
+    try {
+        (void)budget_params(params, nframes, budget);
+        return J2K_HIP_OK;
+    } catch (const Error &x) {
+        create_error() = x.what();
+        return x.code;
+    } catch (...) {
+        return J2K_HIP_ERR_PARAM;
+    }
+}
+
+int j2k_hip_encode_sequence_budget_device(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes,
+                                          uint32_t nframes, const j2k_hip_budget *budget, const void **d_codestreams, size_t *lens,
+                                          int32_t *frame_index, j2k_hip_budget_result *result)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        const j2k_hip_params p = budget_params(params, nframes, budget);
+        if (!d_codestreams || !lens) throw Error(J2K_HIP_ERR_PARAM, "output arrays are NULL");
+        if (result && result->struct_size != sizeof(j2k_hip_budget_result))
+            throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_budget_result.struct_size does not match this library");
+        BudgetCall bc;
+        bc.total = budget->total_bytes; bc.frame_max = budget->frame_max_bytes;
+        encode_begin(e, &p, planes, true, 0, 0, true, nframes, true);
+        const std::vector<EncodeOut> outs = encode_end(e, &bc);
+        for (uint32_t f = 0; f < nframes; ++f) { d_codestreams[f] = outs[f].d_cs; lens[f] = outs[f].len; }
+        budget_report(bc, nframes, frame_index, result);
+    });
+}
+
 int j2k_hip_encode_to_buffer(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes, void *out,
                              size_t out_cap, size_t *out_len)
 {
@@ -1793,6 +2016,48 @@ int j2k_hip_encode(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_h
         if (e->pend.active && e->pend.banded) { encode_end_banded(e, write, user); return; }
         const EncodeOut o = encode_end(e)[0];
         deliver(e, o, write, user);
+    });
+}
+
+int j2k_hip_encode_sequence_budget(j2k_hip_encoder *e, const j2k_hip_params *params, const j2k_hip_plane *planes, uint32_t nframes,
+                                   const j2k_hip_budget *budget, j2k_hip_write_fn write, void *const *users, int32_t *frame_index,
+                                   j2k_hip_budget_result *result)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        const j2k_hip_params p = budget_params(params, nframes, budget);
+        if (!write || !users) throw Error(J2K_HIP_ERR_PARAM, "write callback / sinks are NULL");
+        if (!planes) throw Error(J2K_HIP_ERR_PARAM, "planes is NULL");
+        if (nframes > 1024) throw Error(J2K_HIP_ERR_PARAM, "number of frames must be 1..1024");
+        if (result && result->struct_size != sizeof(j2k_hip_budget_result))
+            throw Error(J2K_HIP_ERR_PARAM, "j2k_hip_budget_result.struct_size does not match this library");
+        const Coding cod = normalise(&p);
+        HIP_CHECK(hipSetDevice(e->device));
+        // Every frame goes up through upload_planes into an input arena of its own (the handle's, exchanged for the frame's while
+        // the upload is queued), so that all are resident when the one-call path starts.
+        if (e->seq_in.size() < nframes) e->seq_in.resize(nframes);
+        std::vector<j2k_hip_plane> dplanes((size_t)nframes * cod.ncomp);
+        for (uint32_t f = 0; f < nframes; ++f) {
+            if (!e->seq_in[f]) e->seq_in[f].reset(new DevBuf);
+            DevBuf &mine = *e->seq_in[f];
+            struct Exchange {
+                DevBuf &a, &b;
+                Exchange(DevBuf &x, DevBuf &y) : a(x), b(y) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); }
+                ~Exchange() { std::swap(a.p, b.p); std::swap(a.cap, b.cap); }
+            } exchange(e->in, mine);
+            j2k_hip_plane dp[4];
+            for (uint32_t c = 0; c < cod.ncomp; ++c) dp[c] = planes[(size_t)f * cod.ncomp + c];
+            upload_planes(e, cod, planes + (size_t)f * cod.ncomp, 0, (int)cod.height, dp, e->stream);
+            for (uint32_t c = 0; c < cod.ncomp; ++c) dplanes[(size_t)f * cod.ncomp + c] = dp[c];
+        }
+        BudgetCall bc;
+        bc.total = budget->total_bytes; bc.frame_max = budget->frame_max_bytes;
+        encode_begin(e, &p, dplanes.data(), true, 0, 0, true, nframes, true);
+        const std::vector<EncodeOut> outs = encode_end(e, &bc);
+        // every plan is final: the files leave, one sink each, front to back
+        for (uint32_t f = 0; f < nframes; ++f) deliver(e, outs[f], write, users[f]);
+        budget_report(bc, nframes, frame_index, result);
     });
 }
 

@@ -111,6 +111,7 @@ struct Pending {
     bool framed = true, rate_control = false;
     bool rc_device = false;   // rate control: the per-block work was queued on the device behind the coder (rate.hip)
     bool rc_layers = false;   // layers at given slopes: rate_layers_kernel was queued behind the coder, its counts are on their way to h_rc_layers
+    bool budget_host_cut = false; // a call to a byte budget under rate_dev = -1: the pass tables are on their way to h_passes for the final cut
     bool rc_tables_pending = false; // ... and the pass tables are coming down on a side stream: wait for rc_tables before reading h_passes
     double dwt_bytes = 0;
     uint32_t *meta = nullptr;
@@ -150,6 +151,7 @@ struct j2k_hip_encoder {
     uint32_t last_guard = 0; // guard bits of the last file written (j2k_hip_encode_get_guard_bits); 0 before any
 
     j2k_hip::DevBuf in, P, Q, Z, blks, jobs, sym, out, meta, passes, cs, plan;
+    std::vector<std::unique_ptr<j2k_hip::DevBuf>> seq_in; // j2k_hip_encode_sequence_budget: an input arena per host frame of the call
     std::unique_ptr<j2k_hip::Workers> t2_workers; // host threads of the Tier-2 planner (created with the first big frame)
     std::unique_ptr<j2k_hip::Workers> alloc_workers; // host threads of the layer allocation (rate control), kept from frame to frame
     j2k_hip::PinnedBuf h_meta, h_cs, h_plan, h_passes;

@@ -284,6 +284,22 @@ struct RateLayersArgs {
     unsigned *bytes;                    // [nblks][layers] out: pass_rate[passes - 1], 0 without passes
 };
 void launch_rate_layers(const RateLayersArgs &a, const double *slopes, hipStream_t s);
+// The rate curve of a call (rate_curve_kernel; a sequence to a byte budget): body bytes and header bits of
+// every frame at K candidates of the slope grid (rate_block.h: rate_slope_grid), one launch over the blocks of all frames.
+// Candidate j is the grid index min(base + j * step, kSlopeKMax); frame f = id / nb1 is evaluated at max(candidate, cap[f]).
+constexpr unsigned kRateCurveMax = 64;
+struct RateCurveArgs {
+    unsigned nblks, nb1, nweights;      // nb1 blocks per frame; weight is read at id % nweights
+    unsigned K, step;                   // 1 <= K <= kRateCurveMax candidates
+    int base;
+    const double *weight;
+    const unsigned *numbps, *npasses;   // Tier-1 results
+    const int *pass_nmsedec;            // [nblks][kDevMaxPasses]
+    const unsigned *pass_rate;          // [nblks][kDevMaxPasses], after the fix-ups
+    const int *cap;                     // [nblks / nb1] per frame: the finest index it may be cut at
+    unsigned long long *sums;           // [nblks / nb1][K][2] out: body bytes, header bits (added to: zeroed by the caller)
+};
+void launch_rate_curve(const RateCurveArgs &a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
 // Decode path.  Tier-1 decoding: one wavefront per code-block runs the MQ decoder and the bit

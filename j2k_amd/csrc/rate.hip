@@ -13,6 +13,7 @@
 // The host (rate_control.cpp) keeps the bisection's control flow and the exact pricing of candidates.
 // All three are bound by latency of strided reads of 50 000 short rows; together they take tens of microseconds.
 //   rate_layers_kernel   no search at all: every layer of every block at thresholds the caller gives (layer_slopes)
+//   rate_curve_kernel    body bytes and header bits of every frame of a call at up to 64 candidates of the slope grid (a byte budget)
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -106,6 +107,62 @@ __global__ void __launch_bounds__(64) rate_layers_kernel(RateLayersArgs a, RateS
         a.passes[(size_t)id * a.layers + l] = (unsigned char)done;
         a.bytes[(size_t)id * a.layers + l] = done ? rate[done - 1] : 0u;
     }
+}
+
+// The rate curve of a call (a sequence to a byte budget): per frame and candidate of the slope grid the body bytes and the
+// header bits of the frame's blocks cut at that candidate -- what the search prices a threshold with, for every frame at once.
+// A thread per block and a wave per workgroup, as above; the distortions in private memory, written nowhere.  Per candidate
+// the thread cuts its block (rate_block_choose, no shortcut) unless the frame's cap left the index where it was, and the
+// wave folds the lanes' numbers by frame: the lanes' frames ascend, so a segmented scan over the lanes puts a frame's sum into
+// its last lane, which adds it -- one integer atomic per (frame, candidate, workgroup) that has something to add; integer
+// sums do not depend on the order of arrival.  A workgroup holds as many frames as its 64 blocks belong to.
+__global__ void __launch_bounds__(64) rate_curve_kernel(RateCurveArgs a)
+{
+    const unsigned lane = threadIdx.x, id = blockIdx.x * 64u + lane;
+    const bool live = id < a.nblks;
+    const unsigned f = live ? id / a.nb1 : 0xFFFFFFFFu; // (idle lanes: a frame of their own that adds nothing)
+    const unsigned row = live ? id : 0u;
+    const unsigned np = live ? min(a.npasses[row], (unsigned)kDevMaxPasses) : 0u;
+    const unsigned *rate = a.pass_rate + (size_t)row * kDevMaxPasses;
+    double disto[kDevMaxPasses];
+    rate_block_disto(a.weight[row % a.nweights], a.numbps[row], np, a.pass_nmsedec + (size_t)row * kDevMaxPasses, disto, nullptr);
+    const int cap = live ? a.cap[f] : kSlopeKMax;
+    const unsigned next_f = __shfl_down(f, 1);
+    const bool tail = live && (lane == 63u || next_f != f);
+    int at = 0;
+    bool have = false;
+    unsigned long long body = 0;
+    unsigned bits = 0;
+    for (unsigned j = 0; j < a.K; ++j) {
+        const long long c = (long long)a.base + (long long)j * (long long)a.step;
+        int idx = c > (long long)kSlopeKMax ? kSlopeKMax : (int)c;
+        if (idx < cap) idx = cap;
+        if (!have || idx != at) { // (a capped frame's columns repeat: cut once)
+            const unsigned n = rate_block_choose(rate, disto, np, 0, 0.0, false, rate_slope_grid(idx), nullptr);
+            const unsigned bytes = n ? rate[n - 1] : 0u;
+            body = bytes; bits = rate_block_header_bits(n, bytes);
+            at = idx; have = true;
+        }
+        unsigned long long sb = body;
+        unsigned sh = bits;
+        for (unsigned d = 1; d < 64u; d <<= 1) {
+            const unsigned long long ub = __shfl_up(sb, d);
+            const unsigned uh = __shfl_up(sh, d);
+            const unsigned uf = __shfl_up(f, d);
+            if (lane >= d && uf == f) { sb += ub; sh += uh; }
+        }
+        if (tail) {
+            unsigned long long *out = a.sums + ((size_t)f * a.K + j) * 2;
+            if (sb) atomicAdd(out, sb);
+            if (sh) atomicAdd(out + 1, (unsigned long long)sh);
+        }
+    }
+}
+
+void launch_rate_curve(const RateCurveArgs &a, hipStream_t s)
+{
+    if (!a.nblks || !a.nb1 || !a.nweights || !a.K || a.K > kRateCurveMax || !a.step) return;
+    hipLaunchKernelGGL(rate_curve_kernel, dim3((a.nblks + 63) / 64), dim3(64), 0, s, a);
 }
 
 void launch_rate_layers(const RateLayersArgs &a, const double *slopes, hipStream_t s)

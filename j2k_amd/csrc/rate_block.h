@@ -160,6 +160,19 @@ J2K_HD uint32_t rate_block_header_bits(uint32_t n, uint32_t bytes)
     return code + (uint32_t)inc + 1u + (uint32_t)(3 + inc + lnp);
 }
 
+// The public grid of slope thresholds (j2k_hip.h: j2k_hip_slope_grid): T(k) = ldexp(m[k mod 16], floor(k / 16)), m[j] the double
+// nearest 2^(j / 16); kSlopeAll stands for -1, everything that is left.  ldexp is exact, so both sides form the same bits.
+constexpr int kSlopeKMin = -2048, kSlopeKMax = 2047, kSlopeAll = -2049;
+J2K_HD double rate_slope_grid(int k)
+{
+    constexpr double m[16] = {0x1.0000000000000p+0, 0x1.0b5586cf9890fp+0, 0x1.172b83c7d517bp+0, 0x1.2387a6e756238p+0,
+                              0x1.306fe0a31b715p+0, 0x1.3dea64c123422p+0, 0x1.4bfdad5362a27p+0, 0x1.5ab07dd485429p+0,
+                              0x1.6a09e667f3bcdp+0, 0x1.7a11473eb0187p+0, 0x1.8ace5422aa0dbp+0, 0x1.9c49182a3f090p+0,
+                              0x1.ae89f995ad3adp+0, 0x1.c199bdd85529cp+0, 0x1.d5818dcfba487p+0, 0x1.ea4afa2a490dap+0};
+    if (k <= kSlopeAll) return -1.0;
+    return ldexp(m[k & 15], k >> 4); // (two's complement: & 15 and >> 4 are mod and floor for a negative k too)
+}
+
 // The bound on a block's body bytes at the thresholds ahead[0..K) (descending: the candidates of the rounds as long as every
 // one fits): fn(k, change) for every k at which the bound moves, change = bytes(k) - bytes(k - 1).
 template <class Fn> J2K_HD void rate_block_ahead(const uint32_t *rate, const float *reach, uint32_t total, uint32_t done, const double *ahead, uint32_t K, Fn fn)

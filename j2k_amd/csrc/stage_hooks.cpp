@@ -588,6 +588,72 @@ int j2k_hip_stage_rate_layers(j2k_hip_encoder *e, uint32_t nblocks, const double
     });
 }
 
+// rate_curve_kernel alone, on tables the caller supplies, read as nframes frames: the tables go where T1Tables puts a call's, the
+// launch is the one the budget search makes (launch_rate_curve over a RateCurveArgs), the sums come back whole.
+int j2k_hip_stage_rate_curve(j2k_hip_encoder *e, uint32_t nblocks, const double *weight, uint32_t nweights, const uint32_t *numbps,
+                             const uint32_t *npasses, const uint32_t *pass_rate, const int32_t *pass_dist, uint32_t nframes,
+                             const int32_t *cap, int32_t base, uint32_t step, uint32_t K, uint64_t *sums, uint32_t *rate_back,
+                             int32_t *dist_back)
+{
+    if (!e) return J2K_HIP_ERR_PARAM;
+    return guarded(e, [&] {
+        static_assert(J2K_HIP_RATE_CURVE_MAX == kRateCurveMax, "the header's candidate count is the kernel's");
+        static_assert(J2K_HIP_SLOPE_K_MIN == kSlopeKMin && J2K_HIP_SLOPE_K_MAX == kSlopeKMax && J2K_HIP_SLOPE_ALL == kSlopeAll, "one grid");
+        if (e->pend.active) throw Error(J2K_HIP_ERR_PARAM, "the previous j2k_hip_encode_begin on this handle has not been finished");
+        const size_t nb = nblocks, F = nframes;
+        if (!nb || !weight || !numbps || !npasses || !pass_rate || !pass_dist || !cap || !sums)
+            throw Error(J2K_HIP_ERR_PARAM, "rate curve stage: no blocks, or a table is NULL");
+        if (!F || nb % F) throw Error(J2K_HIP_ERR_PARAM, "rate curve stage: nframes must divide nblocks");
+        if (!nweights || nweights > nb) throw Error(J2K_HIP_ERR_PARAM, "rate curve stage: nweights must be 1..nblocks");
+        if (!K || K > kRateCurveMax) throw Error(J2K_HIP_ERR_PARAM, "rate curve stage: K must be 1..64");
+        if (!step) throw Error(J2K_HIP_ERR_PARAM, "rate curve stage: step must not be 0");
+        if (base < kSlopeAll || base > kSlopeKMax) throw Error(J2K_HIP_ERR_PARAM, "rate curve stage: base outside the slope grid");
+        for (size_t f = 0; f < F; ++f)
+            if (cap[f] < kSlopeAll || cap[f] > kSlopeKMax) throw Error(J2K_HIP_ERR_PARAM, "rate curve stage: a cap outside the slope grid");
+        for (size_t i = 0; i < nb; ++i) {
+            if (numbps[i] > 31) throw Error(J2K_HIP_ERR_PARAM, "rate curve stage: more than 31 bit-planes");
+            if (npasses[i] > (uint32_t)kDevMaxPasses || (npasses[i] && npasses[i] + 2 > 3 * numbps[i]))
+                throw Error(J2K_HIP_ERR_PARAM, "rate curve stage: more passes than the bit-planes hold");
+        }
+        HIP_CHECK(hipSetDevice(e->device));
+        hipStream_t s = e->stream;
+        invalidate_cached_tables(e); // tables of the handle's last frame are overwritten
+        const T1Tables tt(nb);
+        const size_t rows = tt.row(nb);
+        e->meta.ensure(tt.meta_bytes());
+        e->passes.ensure(tt.passes_bytes());
+        uint32_t *meta = e->meta.as<uint32_t>();
+        uint32_t *pn = e->passes.as<uint32_t>();
+        HIP_CHECK(hipMemcpyAsync(tt.numbps(meta), numbps, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.npasses(meta), npasses, nb * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.pass_nmsedec(pn), pass_dist, rows * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(tt.pass_rate(pn), pass_rate, rows * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        e->rc_weight.ensure((size_t)nweights * sizeof(double));
+        HIP_CHECK(hipMemcpyAsync(e->rc_weight.p, weight, (size_t)nweights * sizeof(double), hipMemcpyHostToDevice, s));
+        // [sums F x K x 2][spare][caps F]: the spare entries are filled and come back, the sums proper start at zero
+        const size_t nsums = F * K * 2, all = nsums + J2K_HIP_RATE_LAYERS_SPARE, caps_at = round_up(all * sizeof(uint64_t), 256);
+        e->rc_layers.ensure(caps_at + F * sizeof(int32_t));
+        uint8_t *d = e->rc_layers.as<uint8_t>();
+        HIP_CHECK(hipMemsetAsync(d, 0xA5, all * sizeof(uint64_t), s));
+        HIP_CHECK(hipMemsetAsync(d, 0, nsums * sizeof(uint64_t), s));
+        HIP_CHECK(hipMemcpyAsync(d + caps_at, cap, F * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        RateCurveArgs ca = {};
+        ca.nblks = (unsigned)nb; ca.nb1 = (unsigned)(nb / F); ca.nweights = nweights;
+        ca.K = K; ca.step = step; ca.base = base;
+        ca.weight = e->rc_weight.as<double>();
+        ca.numbps = tt.numbps(meta); ca.npasses = tt.npasses(meta);
+        ca.pass_nmsedec = reinterpret_cast<const int *>(tt.pass_nmsedec(pn)); ca.pass_rate = tt.pass_rate(pn);
+        ca.cap = reinterpret_cast<const int *>(d + caps_at);
+        ca.sums = reinterpret_cast<unsigned long long *>(d);
+        launch_rate_curve(ca, s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(sums, d, all * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        if (rate_back) HIP_CHECK(hipMemcpyAsync(rate_back, tt.pass_rate(pn), rows * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        if (dist_back) HIP_CHECK(hipMemcpyAsync(dist_back, tt.pass_nmsedec(pn), rows * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+    });
+}
+
 // One launch_gather over pieces the caller supplies: the plan is laid out and its GatherArgs filled by the GatherPlan an encode
 // uses (table_layout.h) -- encode_end's table order by construction -- with block pieces as a CblkDev table, the blocks' lengths
 // in the `len` column of T1Tables and cblk_dst, as a frame has them, and segments alone as the decoder has them.

@@ -24,6 +24,9 @@ extern "C" int j2k_hip_compare(j2k_hip_encoder *enc, const j2k_hip_params *param
 // quiet read of the code values (apply_read_cinema).
 extern "C" int j2k_hip_decode_set_xyz_to_rgb(j2k_hip_encoder *enc, uint32_t target) __attribute__((weak));
 extern "C" int j2k_hip_read_profile(const void *file, size_t len, uint32_t *rsiz) __attribute__((weak));
+extern "C" int j2k_hip_encode_sequence_budget(j2k_hip_encoder *enc, const j2k_hip_params *params, const j2k_hip_plane *planes, uint32_t nframes,
+                                              const j2k_hip_budget *budget, j2k_hip_write_fn write, void *const *users, int32_t *frame_index,
+                                              j2k_hip_budget_result *result) __attribute__((weak));
 
 namespace j2k {
 namespace {
@@ -508,6 +511,42 @@ void HipCodec::WriteFile(OutputFile &file, const FileInfo &info, const Buffer &b
         }
     }
     if (rc != J2K_HIP_OK) {
+        t_enc.error = j2k_hip_last_error(t_enc.h);
+        throw Exception("Error writing file");
+    }
+    t_enc.error.clear();
+}
+
+void HipCodec::WriteFiles(OutputFile *const *files, const FileInfo &info, const Buffer *buffers, unsigned n, unsigned long long total_bytes,
+                          unsigned long long frame_max_bytes)
+{
+    if (files == NULL || buffers == NULL || n == 0) { t_enc.error = "no frames"; throw Exception("Error writing file"); }
+    if (j2k_hip_encode_sequence_budget == NULL) { t_enc.error = "this libj2k_hip has no j2k_hip_encode_sequence_budget"; throw Exception("Error writing file"); }
+    // The frames' mapping is WriteFile's, without what chooses layers: the budget sets the cut (one layer), so settings.method
+    // and settings.layers are not looked at, and the guard bits stay a fixed count (a re-plan would move the lengths priced).
+    FileInfo plain = info;
+    plain.settings.method = LOSSLESS;
+    plain.settings.layers = 0;
+    const unsigned options = _options & ~(unsigned)AutoGuardBits;
+    j2k_hip_params p, first;
+    float rates[J2K_CODEC_MAX_LAYERS];
+    std::vector<j2k_hip_plane> planes;
+    std::vector<void *> users;
+    for (unsigned f = 0; f < n; f++) {
+        j2k_hip_plane one[J2K_CODEC_MAX_CHANNELS];
+        if (files[f] == NULL || !map_frame(_mode, options, plain, buffers[f], p, one, rates)) { t_enc.error = "inconsistent FileInfo/Buffer"; throw Exception("Error writing file"); }
+        assert(files[f]->Tell() == 0);
+        if (f == 0) first = p;
+        else if (p.channels != first.channels || p.promote_ae16 != first.promote_ae16) { t_enc.error = "the frames' buffers differ"; throw Exception("Error writing file"); }
+        planes.insert(planes.end(), one, one + p.channels);
+        users.push_back(files[f]);
+    }
+    if (!thread_handle(_device)) throw Exception("Error writing file");
+    j2k_hip_budget b = j2k_hip_budget();
+    b.struct_size = sizeof b;
+    b.total_bytes = total_bytes; b.frame_max_bytes = frame_max_bytes;
+    const int rc = j2k_hip_encode_sequence_budget(t_enc.h, &first, planes.data(), n, &b, sink_write, users.data(), NULL, NULL);
+    if (rc != J2K_HIP_OK) { // (a budget that cannot be met, and every refusal, come before any sink saw a byte)
         t_enc.error = j2k_hip_last_error(t_enc.h);
         throw Exception("Error writing file");
     }

@@ -94,6 +94,15 @@ class HipCodec : public Codec {
     // (frames before the damaged one may have been written); LastError() names the frame.
     bool ReadFiles(InputFile *const *files, const Buffer *buffers, unsigned n, unsigned subsample);
 
+    // The frames of a shot to a byte budget in one encode (include/j2k_hip.h: j2k_hip_encode_sequence_budget), the mirror of
+    // ReadFiles: buffers[i] goes to *files[i] under the FileInfo / Buffer mapping of WriteFile, all n files together in at most
+    // total_bytes and none above frame_max_bytes (0: no limit), every frame cut at one rate-distortion slope threshold unless
+    // its own limit asks for a coarser one -- quality as even as the two limits allow.  settings.method and settings.layers
+    // are not looked at (the budget sets the cut, in one layer), and AutoGuardBits does not apply.  Throws "Error writing file"
+    // on failure -- a budget that cannot be met among them, LastError() naming the limit -- with nothing written to any file.
+    void WriteFiles(OutputFile *const *files, const FileInfo &info, const Buffer *buffers, unsigned n, unsigned long long total_bytes,
+                    unsigned long long frame_max_bytes);
+
     // What did a file lose against the frame it was written from?  `info` and `buffer` are what WriteFile was given (the same
     // FileInfo / Buffer -> parameters / planes mapping: PromoteAE16, FLOAT channels and Chroma422 / Chroma420 included); the
     // file is decoded and compared on the GPU (include/j2k_hip.h: j2k_hip_compare), nothing but a few sums comes back.

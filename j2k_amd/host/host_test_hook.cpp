@@ -431,6 +431,62 @@ long write_frame(const unsigned char *frame, unsigned width, unsigned height, lo
 
 extern "C" {
 
+// HipCodec::WriteFiles: n A,R,G,B worlds (frames[f], laid out as for j2k_host_test_write) to a byte budget, HonourSettings with
+// settings.method = SIZE and a file size set (both must be ignored).  File f is copied to out + f * out_stride and its length to
+// lens[f].  Returns 0, or -1 after a j2k::Exception (what() | LastError() in err): lens[f] then holds what file f had received.
+long j2k_host_test_write_files(const unsigned char *const *frames, unsigned n, unsigned width, unsigned height, long rowbytes, int pixel_size,
+                               int channels, int depth, int reversible, int ycc, int tile_size, unsigned options, unsigned long long total_bytes,
+                               unsigned long long frame_max_bytes, unsigned char *out, unsigned long out_stride, unsigned long *lens, char *err,
+                               unsigned long err_cap)
+{
+    using namespace j2k;
+    FileInfo info;
+    info.width = width; info.height = height;
+    info.channels = (unsigned char)channels; info.depth = (unsigned char)depth;
+    info.alpha = channels == 4 ? STRAIGHT : NO_ALPHA;
+    info.settings.order = LRCP;
+    info.settings.method = SIZE; info.settings.fileSize = 1; info.settings.layers = 3;
+    info.settings.reversible = reversible != 0; info.settings.ycc = ycc != 0;
+    info.settings.tileSize = (unsigned short)tile_size;
+    std::vector<Buffer> bufs(n);
+    for (unsigned f = 0; f < n; f++) {
+        Channel argb[4];
+        for (int i = 0; i < 4; i++) {
+            Channel &c = argb[i];
+            c.width = width; c.height = height;
+            c.sampleType = pixel_size == 4 ? FLOAT : (pixel_size == 2 ? USHORT : UCHAR);
+            c.depth = (unsigned char)(pixel_size * 8);
+            c.sgnd = false;
+            c.buf = const_cast<unsigned char *>(frames[f]) + i * pixel_size;
+            c.colbytes = 4 * pixel_size;
+            c.rowbytes = rowbytes;
+        }
+        const Channel *by_name[4] = {&argb[1], &argb[2], &argb[3], &argb[0]}; // RED, GREEN, BLUE, ALPHA
+        bufs[f].channels = info.channels;
+        for (int c = 0; c < channels; c++) bufs[f].channel[c] = *by_name[info.channelMap[c]];
+    }
+    std::vector<MemoryOutputFile> files(n);
+    std::vector<OutputFile *> ptrs;
+    for (unsigned f = 0; f < n; f++) ptrs.push_back(&files[f]);
+    HipCodec hip(HipCodec::HonourSettings, -1, options);
+    long rc = 0;
+    try {
+        hip.WriteFiles(ptrs.data(), info, bufs.data(), n, total_bytes, frame_max_bytes);
+    } catch (const Exception &e) {
+        if (err && err_cap) {
+            std::string m = std::string(e.what()) + " | " + HipCodec::LastError();
+            std::strncpy(err, m.c_str(), err_cap - 1);
+            err[err_cap - 1] = 0;
+        }
+        rc = -1;
+    }
+    for (unsigned f = 0; f < n; f++) {
+        lens[f] = (unsigned long)files[f].data.size();
+        if (out && files[f].data.size() <= out_stride) std::memcpy(out + (size_t)f * out_stride, files[f].data.data(), files[f].data.size());
+    }
+    return rc;
+}
+
 // HipCodec::Compare of `file` against the A,R,G,B world `frame` (as in j2k_host_test_write: HonourSettings, the PROMOTE and
 // CHROMA knobs, FileInfo of width x height x channels at `depth` bits; the coding settings do not matter).  ints_out = 7 values
 // per channel (samples, differing, sumAbs, sumSq, maxAbs, firstX, firstY), dbl_out = 2 (mse, psnr).  Returns 1 = compared,
